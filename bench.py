@@ -14,7 +14,7 @@ sustained.)  Each reconstruction of the batch:
 Multi-GPU: independent realisations per rank (weak scaling, no data-path
 collective) + ONE RCCL all-reduce of the bandpower moments at the end.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 With N > 1 and no torchrun environment the script starts N ranks itself (a child
 ``python -m torch.distributed.run`` started BEFORE this process touches the GPU);
@@ -861,6 +861,10 @@ def measure(args, torch, dist, world, rank, prec):
         elapsed = float(t.item())
     total = int(mom_n.item())
     assert total == args.steps * B * max(world, 1), "moment counter %d != steps x batch x ranks" % total
+    # what a caller of the timed path receives after its last step: the bandpower moments accumulated over the K steps
+    # (all ranks), as --dump-outputs writes them
+    outputs = {"moments_n": mom_n.double().cpu().numpy(), "moments_S": mom_S.double().cpu().numpy(),
+               "moments_C": mom_C.double().cpu().numpy(), "mean_bandpowers": (mom_S / float(total)).double().cpu().numpy()}
     # the timed region really produced the bandpowers: its accumulated sum equals the usage-weighted sum of the per-map
     # bandpowers computed through the fine-grained public calls (same kernels, one map at a time)
     use = map_usage(args.steps * B, len(tmaps), R.pair and not args.trace_steps)
@@ -886,7 +890,7 @@ def measure(args, torch, dist, world, rank, prec):
     res = {"prec": prec, "P": P, "R": R, "tmaps": tmaps, "seed": seed, "total": total, "elapsed": elapsed, "t_issue": t_issue,
            "value": total / elapsed, "ms_per_step": elapsed / args.steps * 1e3, "bandpower_check": {"maps_checked": len(check_maps), "max_rel_dev": dev,
            "how": "accumulated S of the timed one-call path vs the usage-weighted per-map bandpowers of the fine-grained public calls"},
-           "mean_bandpowers": (mom_S / float(total)).cpu().numpy().tolist()}
+           "mean_bandpowers": (mom_S / float(total)).cpu().numpy().tolist(), "outputs": outputs}
     if rank != 0:
         return res
     per, G = per_kernel_table(torch, P, R, args)
@@ -987,6 +991,14 @@ def block_of(args, res, world, dist):
             "roofline": res.get("roofline"), "hbm": res.get("hbm"), "kappa_out": res.get("kappa_out")}
 
 
+def dump_outputs(path, blocks):
+    """--dump-outputs: every array of ``blocks`` ({prefix: {name: ndarray}}) as <path>/<prefix>_<name>.npy, float64"""
+    os.makedirs(path, exist_ok=True)
+    for prefix, arrays in blocks.items():
+        for name, a in arrays.items():
+            np.save(os.path.join(path, "%s_%s.npy" % (prefix, name)), np.asarray(a, dtype=np.float64))
+
+
 def release(res, torch):
     for k in ("R", "P", "tmaps"):
         res.pop(k, None)
@@ -1030,7 +1042,12 @@ def main():
     ap.add_argument("--mc-n", type=int, default=4096)
     ap.add_argument("--mc-sims", type=int, default=1000)
     ap.add_argument("--mc-windowed", action="store_true", help="--config mc with the reference's apodisation taper (oa_mc_run_windowed)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the run, write what each precision's timed path "
+                    "returned after its last step (the bandpower moments n, S, C over all K steps and ranks, and S / n) as "
+                    "DIR/<prec>_<name>.npy in float64; the inputs depend only on the arguments")
     args = ap.parse_args()
+    if args.dump_outputs and args.config != "qe":
+        raise SystemExit("bench.py: --dump-outputs applies to --config qe")
     args.auto_streams = args.streams <= 0
     if args.streams <= 0:
         args.streams = 2 if args.n >= 8192 else 3
@@ -1143,6 +1160,7 @@ def main():
             out["extra"] = extra
         out["hbm"] = hbm
     ref_head = head["R"].bandpowers(0).double().cpu() if rank == 0 else None
+    dumped = {args.prec: head["outputs"]}
     release(head, torch)
     if other:
         sec = measure(args, torch, dist, world, rank, other)
@@ -1152,6 +1170,7 @@ def main():
             blk2["note"] = "the same job, same maps (the GRF draw depends only on (seed, index)), through the %s kernels: its own timed " \
                            "region of K steps, roofline and per-kernel table" % other
             out[other] = blk2
+        dumped[other] = sec["outputs"]
         release(sec, torch)
         SECTIONS.mark("second_block_" + other)
     if rank == 0:
@@ -1173,6 +1192,8 @@ def main():
             out["cpu_baseline"] = cpu_baseline(N, args.res)
             SECTIONS.mark("cpu_baseline")
         out["sections_s"] = SECTIONS.t
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, dumped)
         print(json.dumps(out))
     if world > 1:
         dist.barrier()

@@ -122,3 +122,41 @@ dist.barrier(); dist.destroy_process_group()
                         "127.0.0.1", "--master-port", "29612", f.name], capture_output=True, text=True, timeout=900)
     os.unlink(f.name)
     assert r.returncode == 0 and "MC2 OK" in r.stdout, r.stderr[-2000:]
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs writes the timed path's bandpower moments after exactly --steps timed steps, and two runs with the same
+    arguments (same seeded inputs) write the same arrays."""
+    import json
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "OA_BENCH_BACKEND"):
+        env.pop(k, None)
+    steps, batch = 3, 4
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("run%d" % run)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                            "--batch", str(batch), "--n", "1024", "--res", "2.0", "--also", "f32", "--no-cpu", "--no-extras",
+                            "--preroll", "0.1", "--dump-outputs", str(d)], capture_output=True, text=True, env=env, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == steps and line["ms_per_step"] > 0
+        assert line["config"]["maps_per_step"] == batch and line["f32"]["reconstructions_timed"] == steps * batch
+        dumps.append({p.name: np.load(str(p)) for p in sorted(d.iterdir())})
+    a, b = dumps
+    for prec in ("f64", "f32"):
+        names = ["%s_%s.npy" % (prec, n) for n in ("moments_n", "moments_S", "moments_C", "mean_bandpowers")]
+        assert set(names) <= set(a)
+        assert a["%s_moments_n.npy" % prec].tolist() == [steps * batch]
+        S, n = a["%s_moments_S.npy" % prec], a["%s_moments_n.npy" % prec][0]
+        assert S.shape == (19,) and a["%s_moments_C.npy" % prec].shape == (19, 19) and np.all(S > 0)
+        np.testing.assert_allclose(a["%s_mean_bandpowers.npy" % prec], S / n, rtol=1e-15)
+    assert sum(x.nbytes for x in a.values()) < 64 << 20
+    assert set(a) == set(b)
+    for k in a:
+        assert a[k].dtype == np.float64
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-12, atol=0)
+    # the two precisions computed the same job from the same maps
+    np.testing.assert_allclose(a["f32_mean_bandpowers.npy"], a["f64_mean_bandpowers.npy"], rtol=1e-3)
