@@ -43,7 +43,7 @@ typedef struct oa_plan oa_plan;
 const char* oa_last_error(void);
 /* ABI version = 100 x the build round that last changed a signature in this header; bindings must refuse a library
  * that reports less than the version they were written against (OA_ABI_VERSION) */
-#define OA_ABI_VERSION 402
+#define OA_ABI_VERSION 403
 int oa_version(void);
 /* number of HIP devices visible; <0 on error (no compute) */
 int oa_device_count(void);
@@ -56,7 +56,8 @@ int oa_device_count(void);
  * evaluation on an inner power-of-two plan -- both exact: oa_fft_r2c / oa_fft_c2r / oa_fft_c2c, oa_lens_maps(_hc) and all
  * per-mode / binning / RNG kernels work, `width` / `rband` hints are ignored, and the fused oa_qe_rows /
  * oa_qe_*_cols / oa_fft_cols / oa_fft_pass calls return an error (use the modular oa_qe_legs .. oa_qe_div chain,
- * as orphics_amd/lensing.py:_reconstruct_hc_modular does). */
+ * as orphics_amd/lensing.py:_reconstruct_hc_modular does).  The one-call TT entries (oa_qe_tt, oa_qe_tt_moments(2), oa_mc_run)
+ * also take 2^a 3^b 5^c sides, on a BAND GRID (see oa_plan_band_grid); chirp-z sides have no one-call path. */
 int oa_plan_create(int ny, int nx, int dtype, oa_plan** out);
 int oa_plan_destroy(oa_plan* p);
 long oa_plan_kpitch(const oa_plan* p);
@@ -180,6 +181,22 @@ int oa_plan_set_filters(oa_plan* p, const void* FG, const void* FH, const void* 
  * with the row bands of each call (mrow == 0 switches it off there too). */
 int oa_plan_set_col_grid(oa_plan* p, int mcol);
 int oa_plan_col_grid(const oa_plan* p);
+/* BAND GRID: the one-call TT entries on map sides 2^a 3^b 5^c that are not powers of two (oa_qe_tt from a map or from kX [, kY],
+ * oa_qe_tt_moments, oa_qe_tt_moments2, oa_mc_run incl. OA_OPT_MC_BATCH and the mean-field stack).  The estimator is band-limited
+ * (legs: columns < leg_cols, rows |ky| < leg_rows; kappa: columns < kappa_cols, rows |ky| < kappa_rows), so on ANY My x Mx grid with
+ *     My >= max(2 leg_rows + kappa_rows, 2 kappa_rows),   Mx >= 2 leg_cols + kappa_cols
+ * and the same ell lattice (a mode of signed index ky at row ky mod My) it returns the same kappa modes, up to the factor
+ * (ny nx) / (My Mx) that the plan folds into its copy of Fnorm.  oa_plan_set_filters on such a plan resolves (My, Mx): Mx from
+ * mrow, My from the column-grid policy (oa_plan_set_col_grid): -1 = the smallest power of two >= the bound and >= 128; an explicit
+ * power of two is checked against the bound; 0 (the map's own grid), unbounded filters (0 = all) and a grid not smaller than the map
+ * side are refused with a message naming the reason (the modular chain serves those).  The plan then owns an inner power-of-two plan
+ * of My x Mx points with inner-layout copies of FG, FH, Fnorm and of the bin ids (made by oa_plan_set_filters / oa_plan_set_bins,
+ * which synchronise the device; oa_plan_set_bins keeps the WHOLE N-plane mode counts), and every call runs the fused power-of-two
+ * pipeline there: only the input transform (one mixed-radix row R2C that stores the leg columns, then an ny-point DFT evaluated at the
+ * leg rows), the Monte-Carlo draw (the leg band of oa_grf_hc's N-grid draw, same Philox counters) and the scatter of kappa's band
+ * into the N-grid output / mean-field stack see the map's grid.  oa_qe_pol, oa_qe_mv, oa_qe_tt_splits, oa_mc_run_windowed and
+ * oa_qe_tt_stage stay power-of-two only.  oa_plan_band_grid reports (My, Mx), or (0, 0) when no band grid is bound. */
+int oa_plan_band_grid(const oa_plan* p, int* my, int* mx);
 /* R of the R-SPLIT from-map path this plan's one-call TT entries run (0 = not this geometry; 4: 8192^2 / 4096^2 maps at the reference's
  * band limits, 8: 16384^2 float64, 2: 8192^2 with up to 1280 leg columns -- the T filter to ell = 6000): the row R2C carries the first
  * radix-R butterfly of the column transform (R = ny / column grid) and ONE single-pass column kernel goes from its output to

@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("ORPHICS_AMD_LIB", os.path.join(_HERE, "liborphics_amd
 
 OA_F32 = 0
 OA_F64 = 1
-ABI_VERSION = 402     # include/orphics_amd.h OA_ABI_VERSION: the signatures below are those of this version
+ABI_VERSION = 403     # include/orphics_amd.h OA_ABI_VERSION: the signatures below are those of this version
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
@@ -43,6 +43,7 @@ SIGNATURES = {
     "oa_plan_set_filters": (c_int, [c_void_p] * 4 + [c_int] * 5),
     "oa_plan_set_col_grid": (c_int, [c_void_p, c_int]),
     "oa_plan_col_grid": (c_int, [c_void_p]),
+    "oa_plan_band_grid": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "oa_plan_rsplit": (c_int, [c_void_p]),
     "oa_plan_div_fused": (c_int, [c_void_p]),
     "oa_plan_set_option": (c_int, [c_void_p, c_int, c_int]),

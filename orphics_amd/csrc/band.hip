@@ -1,0 +1,217 @@
+// BAND GRID of the one-call TT entries on map sides 2^a 3^b 5^c (pipeline.hip, include/orphics_amd.h): the estimator is
+// band-limited, so after the input transform everything runs on a small power-of-two (My, Mx) grid through the fused pow2
+// pipeline of an inner plan.  The kernels here move data between the map's N-grid and that inner grid:
+//   * band_map_r2c   : real map -> the leg band of its transform (columns < wl, rows |ky| < rl), written in the inner hc layout.
+//                      Row pass: the mixed-radix packed N/2 R2C of mixed.hip (fft_mixed.hpp) with only the columns < wl stored
+//                      (ny x wl complex instead of ny x (nx/2+1)); column pass: an ny-point DFT evaluated only at the 2 rl - 1 kept
+//                      rows (pruned-output DFT, double accumulation, split over row segments + an ordered sum) into the inner plane;
+//   * band_copy      : band region (rows |ky| < r, columns < w) of one grid's hc-layout plane -> the other grid's (filters, bin ids,
+//                      Fourier-space legs N -> inner; kappa_hat inner -> N), optionally scaled;
+//   * band_stack_add : the mean-field stack update of oa_mc_run (f64 interleaved N-grid accumulator += inner kappa_hat planes).
+// A mode of signed index ky sits at row ky mod ny on one grid and ky mod My on the other; the columns are the same.
+#include <algorithm>
+#include "fft_launch.hpp"
+#include "fft_mixed.hpp"
+
+namespace oa {
+
+// band row i of 0 .. 2 r - 2 -> signed ky (0 .. r - 1, then -(r - 1) .. -1) -> row of a grid of m rows
+OA_HD int band_row(int i, int r, int m) { return i < r ? i : i - (2 * r - 1) + m; }
+
+// one map row per workgroup: packed N/2-point mixed-radix transform + untangle (mr_row_body, MR_R2C), store of columns < w only
+template <typename T>
+struct BandRowArgs {
+    const T* in;
+    cx<T>* out;
+    long in_pitch;                   // reals per map row
+    int w, N;                        // stored columns; packed transform length nx / 2
+    MrFactors f;
+    const cx<T>* tw;                 // W_N^e
+    const cx<T>* tw2;                // W_2N^e (untangle)
+};
+template <typename T>
+__global__ __launch_bounds__(256) void band_row_kernel(BandRowArgs<T> a) {
+    const T* __restrict__ in = a.in;
+    cx<T>* __restrict__ out = a.out;
+    const long in_pitch = a.in_pitch;
+    const int w = a.w, N = a.N;
+    const cx<T>* __restrict__ tw = a.tw;
+    const cx<T>* __restrict__ tw2 = a.tw2;
+    GpuCtx c{oa_dyn_smem};
+    cx<T>* b0 = reinterpret_cast<cx<T>*>(c.smem());
+    cx<T>* b1 = b0 + N + 1;
+    const int tid = threadIdx.x, NT = blockDim.x;
+    const long row = blockIdx.x;
+    const cx<T>* src = reinterpret_cast<const cx<T>*>(in + row * in_pitch);
+    for (int n = tid; n < N; n += NT) b0[n] = src[n];
+    c.sync();
+    const cx<T>* r = mr_transform<T>(c, b0, b1, N, a.f, 0, tw, tid, NT);
+    cx<T>* dst = out + row * w;
+    for (int k = tid; k < w; k += NT) {
+        const cx<T> Zk = r[k == N ? 0 : k], Zm = conj(r[k == 0 ? 0 : N - k]);
+        const cx<T> E = (Zk + Zm) * (T)0.5, O = mul_mi(Zk - Zm) * (T)0.5;
+        dst[k] = E + tw2[k] * O;
+    }
+}
+
+// pruned-output column DFT: out[ky, x] = sum_y rows[y, x] W_ny^(ky y) for |ky| < rl, x < w; a workgroup owns 16 columns x 16 output
+// rows x one SEGMENT of yseg rows and walks it in chunks of 32 (operands and twiddles staged in LDS as doubles; accumulation in double
+// for both precisions); its partial sums go to part[seg][k][x], which band_cols_sum adds in segment order (deterministic).  With one
+// segment per tile the 1200^2 leg band is 28 workgroups of 1200 rows each (~100 us); segments give the chip a few hundred.
+constexpr int BC_TX = 16, BC_TK = 16, BC_YC = 32, BC_TARGET_WG = 512;
+static int band_cols_segments(int ny, int w, int rl, int* yseg) {
+    const long tiles = (long)((w + BC_TX - 1) / BC_TX) * ((2 * rl - 1 + BC_TK - 1) / BC_TK);
+    long nseg = std::max(1L, std::min((long)((ny + BC_YC - 1) / BC_YC), BC_TARGET_WG / tiles));
+    int ys = (int)((ny + nseg - 1) / nseg);
+    ys = (ys + BC_YC - 1) / BC_YC * BC_YC;
+    *yseg = ys;
+    return (ny + ys - 1) / ys;
+}
+size_t band_map_scratch_bytes(const oa_plan* p, int wl, int rl) {
+    int ys = 0;
+    const int nseg = band_cols_segments(p->ny, wl, rl, &ys);
+    return (size_t)p->ny * wl * 2 * (p->dtype == OA_F32 ? 4 : 8) + (size_t)nseg * (2 * rl - 1) * wl * sizeof(double2);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void band_cols_kernel(const cx<T>* __restrict__ rows, int ny, int w, int rl, const cx<T>* __restrict__ tw,
+                                                        double2* __restrict__ part, int yseg) {
+    __shared__ double2 A[BC_YC][BC_TX];
+    __shared__ double2 W[BC_TK][BC_YC];
+    const int tid = threadIdx.x, tx = tid & (BC_TX - 1), tk = tid / BC_TX;
+    const int x0 = blockIdx.x * BC_TX, k0 = blockIdx.y * BC_TK;
+    const int nk = 2 * rl - 1;
+    double ar = 0.0, ai = 0.0;
+    const int ybeg = blockIdx.z * yseg, yend = std::min(ny, ybeg + yseg);
+    for (int y0 = ybeg; y0 < yend; y0 += BC_YC) {
+        for (int e = tid; e < BC_YC * BC_TX; e += 256) {
+            const int yy = e / BC_TX, cc = e % BC_TX, y = y0 + yy, x = x0 + cc;
+            double2 v = make_double2(0.0, 0.0);
+            if (y < ny && x < w) { const cx<T> s = rows[(long)y * w + x]; v = make_double2((double)s.x, (double)s.y); }
+            A[yy][cc] = v;
+        }
+        for (int e = tid; e < BC_TK * BC_YC; e += 256) {
+            const int kk = e / BC_YC, yy = e % BC_YC, y = y0 + yy, ki = k0 + kk;
+            double2 v = make_double2(0.0, 0.0);
+            if (y < ny && ki < nk) {
+                const int kmod = band_row(ki, rl, ny);                                   // ky mod ny
+                const cx<T> t = tw[(int)(((long)kmod * y) % ny)];
+                v = make_double2((double)t.x, (double)t.y);
+            }
+            W[kk][yy] = v;
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int yy = 0; yy < BC_YC; ++yy) {
+            const double2 a = A[yy][tx], t = W[tk][yy];
+            ar = fma(a.x, t.x, fma(-a.y, t.y, ar));
+            ai = fma(a.x, t.y, fma(a.y, t.x, ai));
+        }
+        __syncthreads();
+    }
+    const int x = x0 + tx, ki = k0 + tk;
+    if (x < w && ki < nk) part[((long)blockIdx.z * nk + ki) * w + x] = make_double2(ar, ai);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void band_cols_sum(const double2* __restrict__ part, int nseg, int w, int rl, cx<T>* __restrict__ out, int my,
+                                                     long okp) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, ki = blockIdx.y, nk = 2 * rl - 1;
+    if (x >= w) return;
+    double ar = 0.0, ai = 0.0;
+    for (int s = 0; s < nseg; ++s) { const double2 v = part[((long)s * nk + ki) * w + x]; ar += v.x; ai += v.y; }
+    out[(long)band_row(ki, rl, my) * okp + x] = mk<T>((T)ar, (T)ai);
+}
+
+template <typename T>
+static int map_r2c_t(oa_plan* p, const void* map, void* rowbuf, int wl, int rl, void* dst, int dny, long dkp, hipStream_t st) {
+    const int N = p->nx / 2;
+    int rc = 0;
+    BandRowArgs<T> a{(const T*)map, (cx<T>*)rowbuf, (long)p->nx, wl, N, mixed_factor(N), (const cx<T>*)p->mr_twxh, (const cx<T>*)p->mr_twx};
+    launch_go(rc, st, band_row_kernel<T>, dim3(p->ny), 256, 2 * ((size_t)N + 1) * sizeof(cx<T>), a);
+    if (rc) return rc;
+    int yseg = 0;
+    const int nseg = band_cols_segments(p->ny, wl, rl, &yseg);
+    double2* part = reinterpret_cast<double2*>((char*)rowbuf + (size_t)p->ny * wl * sizeof(cx<T>));     // (band_map_scratch_bytes)
+    dim3 grid((wl + BC_TX - 1) / BC_TX, (2 * rl - 1 + BC_TK - 1) / BC_TK, nseg);
+    hipLaunchKernelGGL(band_cols_kernel<T>, grid, dim3(256), 0, st, (const cx<T>*)rowbuf, p->ny, wl, rl, (const cx<T>*)p->mr_twy, part, yseg);
+    OA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(band_cols_sum<T>, dim3((wl + 255) / 256, 2 * rl - 1), dim3(256), 0, st, (const double2*)part, nseg, wl, rl, (cx<T>*)dst, dny, dkp);
+    OA_LAUNCH_CHECK();
+    return 0;
+}
+int band_map_r2c(oa_plan* p, const void* map, void* rowbuf, int wl, int rl, void* dst, int dny, long dkp, hipStream_t st) {
+    OA_REQUIRE(p->mixed && wl >= 1 && wl <= p->nx / 2 && rl >= 1 && 2 * rl - 1 <= std::min(p->ny, dny), "band input transform: bad band");
+    return p->dtype == OA_F32 ? map_r2c_t<float>(p, map, rowbuf, wl, rl, dst, dny, dkp, st)
+                              : map_r2c_t<double>(p, map, rowbuf, wl, rl, dst, dny, dkp, st);
+}
+
+template <typename E> OA_D E band_scaled(E v, double) { return v; }
+OA_D float band_scaled(float v, double s) { return (float)((double)v * s); }
+OA_D double band_scaled(double v, double s) { return v * s; }
+template <typename E>
+__global__ __launch_bounds__(256) void band_copy_kernel(const E* __restrict__ src, long spitch, int sny, E* __restrict__ dst, long dpitch, int dny,
+                                                        int w, int r, double scale) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= w) return;
+    const int i = blockIdx.y;
+    dst[(long)band_row(i, r, dny) * dpitch + x] = band_scaled(src[(long)band_row(i, r, sny) * spitch + x], scale);
+}
+// kind: 0 f32, 1 f64, 2 int32 (real planes), 3 complex f32, 4 complex f64; scale applies to the real float kinds only
+int band_copy(int kind, const void* src, long spitch, int sny, void* dst, long dpitch, int dny, int w, int r, double scale, hipStream_t st) {
+    OA_REQUIRE(w >= 1 && r >= 1 && 2 * r - 1 <= std::min(sny, dny), "band copy: bad band");
+    dim3 grid((w + 255) / 256, 2 * r - 1);
+    switch (kind) {
+        case 0: hipLaunchKernelGGL(band_copy_kernel<float>, grid, dim3(256), 0, st, (const float*)src, spitch, sny, (float*)dst, dpitch, dny, w, r, scale); break;
+        case 1: hipLaunchKernelGGL(band_copy_kernel<double>, grid, dim3(256), 0, st, (const double*)src, spitch, sny, (double*)dst, dpitch, dny, w, r, scale); break;
+        case 2: hipLaunchKernelGGL(band_copy_kernel<int32_t>, grid, dim3(256), 0, st, (const int32_t*)src, spitch, sny, (int32_t*)dst, dpitch, dny, w, r, scale); break;
+        case 3: hipLaunchKernelGGL(band_copy_kernel<cx<float>>, grid, dim3(256), 0, st, (const cx<float>*)src, spitch, sny, (cx<float>*)dst, dpitch, dny, w, r, scale); break;
+        case 4: hipLaunchKernelGGL(band_copy_kernel<cx<double>>, grid, dim3(256), 0, st, (const cx<double>*)src, spitch, sny, (cx<double>*)dst, dpitch, dny, w, r, scale); break;
+        default: return fail("band copy: bad kind");
+    }
+    OA_LAUNCH_CHECK();
+    return 0;
+}
+
+// zero every element of an (ny, kp) hc plane outside kappa's band (columns < w of the rows |ky| < r), element by element: on these sides
+// kp = nx / 2 + 16 may be odd, so rows are not 16-byte units (pipeline.hip's zero_complement assumes they are)
+template <typename T>
+__global__ __launch_bounds__(256) void band_zero_kernel(cx<T>* __restrict__ out, int ny, long kp, int w, int r) {
+    const int y = blockIdx.y;
+    const bool band = y < r || y > ny - r;
+    for (long x = (band ? w : 0) + blockIdx.x * (long)blockDim.x + threadIdx.x; x < kp; x += (long)gridDim.x * blockDim.x)
+        out[(long)y * kp + x] = mk<T>((T)0, (T)0);
+}
+int band_zero_outside(int dtype, void* out, int ny, long kp, int w, int r, hipStream_t st) {
+    OA_REQUIRE(w >= 1 && w <= kp && r >= 1 && 2 * r - 1 <= ny, "band zero: bad band");
+    dim3 grid((unsigned)std::min<long>(4, (kp + 255) / 256), ny);
+    if (dtype == OA_F32) hipLaunchKernelGGL(band_zero_kernel<float>, grid, dim3(256), 0, st, (cx<float>*)out, ny, kp, w, r);
+    else hipLaunchKernelGGL(band_zero_kernel<double>, grid, dim3(256), 0, st, (cx<double>*)out, ny, kp, w, r);
+    OA_LAUNCH_CHECK();
+    return 0;
+}
+
+// acc (N grid, interleaved re / im doubles, apitch complex elements per row) += the nbatch inner planes (sstride complex elements apart), in
+// plane order -- the order of stack_add_region
+template <typename T>
+__global__ __launch_bounds__(256) void band_stack_kernel(const T* __restrict__ src, long spitch, int sny, int nbatch, long sstride,
+                                                         double* __restrict__ acc, long apitch, int any, int w, int r) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;      // real-valued element within the row (2 per complex column)
+    if (c >= 2 * w) return;
+    const int i = blockIdx.y;
+    const long si = 2 * (long)band_row(i, r, sny) * spitch + c, ai = 2 * (long)band_row(i, r, any) * apitch + c;
+    double a = acc[ai];
+    for (int b = 0; b < nbatch; ++b) a += (double)src[si + 2 * b * sstride];
+    acc[ai] = a;
+}
+int band_stack_add(int dtype, const void* src, long spitch, int sny, int nbatch, long sstride, double* acc, long apitch, int any, int w, int r,
+                   hipStream_t st) {
+    OA_REQUIRE(w >= 1 && r >= 1 && 2 * r - 1 <= std::min(sny, any), "band stack: bad band");
+    dim3 grid((2 * w + 255) / 256, 2 * r - 1);
+    if (dtype == OA_F32)
+        hipLaunchKernelGGL(band_stack_kernel<float>, grid, dim3(256), 0, st, (const float*)src, spitch, sny, nbatch, sstride, acc, apitch, any, w, r);
+    else
+        hipLaunchKernelGGL(band_stack_kernel<double>, grid, dim3(256), 0, st, (const double*)src, spitch, sny, nbatch, sstride, acc, apitch, any, w, r);
+    OA_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace oa

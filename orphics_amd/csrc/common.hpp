@@ -174,6 +174,17 @@ int qe_cols_div_w(oa_plan* p, const void* pa, const void* pb, const void* Fn, vo
 int qe_tt_pair_w(oa_plan* p, const void* map0, const void* map1, const void* FG, const void* FH, const void* Fn, void* c0, void* c1,
                  void* c2, void* g0, void* g1, void* out0, void* out1, int wl, int wk, int rl, int rk, int mrow, int my, long pl, long pk,
                  hipStream_t st, DivBinFuse* fuse = nullptr, const void* fgh = nullptr);
+// BAND GRID of the one-call TT entries on map sides 2^a 3^b 5^c (band.hip, pipeline.hip): N-grid <-> inner power-of-two grid
+// rowbuf: band_map_scratch_bytes(p, wl, rl) bytes (row pass + the column pass's per-segment partial sums)
+int band_map_r2c(oa_plan* p, const void* map, void* rowbuf, int wl, int rl, void* dst, int dny, long dkp, hipStream_t st);
+size_t band_map_scratch_bytes(const oa_plan* p, int wl, int rl);
+int band_copy(int kind, const void* src, long spitch, int sny, void* dst, long dpitch, int dny, int w, int r, double scale, hipStream_t st);
+int band_zero_outside(int dtype, void* out, int ny, long kp, int w, int r, hipStream_t st);
+int band_stack_add(int dtype, const void* src, long spitch, int sny, int nbatch, long sstride, double* acc, long apitch, int any, int w, int r,
+                   hipStream_t st);
+// the leg band of oa_grf_hc's N-grid draw (same Philox counters) into the hc layout of an (my, okp) grid, nreal planes zstride elements apart
+int grf_band_inner(oa_plan* p, uint64_t seed, uint64_t stream_id, int nreal, const void* covsqrt_hc, void* out, int my, long okp, long zstride,
+                   int width, int rband, hipStream_t stream);
 }
 #define OA_NEED_POW2(p, what) \
     OA_REQUIRE((p)->pow2, what ": needs power-of-two map sides (other sizes: oa_fft_r2c / oa_fft_c2r / oa_fft_c2c and the modular oa_qe_legs / oa_mul_real / oa_qe_div calls)")

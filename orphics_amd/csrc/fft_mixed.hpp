@@ -11,8 +11,9 @@
 //     (the autosort form of fft_kernels.hpp with a run-time radix list); factors from the W_N table (L1/L2-resident);
 //   * real rows as packed N/2-point transforms with the (un)tangle of fft_kernels.hpp (N even: every map side is);
 //   * inverse transforms as the forward transform of the swapped data, IDFT(x) = swap(DFT(swap(x))).
-// Sides with another prime factor keep the chirp-z path.  The fused estimator kernels remain power-of-two; on these sides the
-// estimators run the modular calls (oa_qe_legs / oa_mul_real / oa_qe_div) over these transforms.
+// Sides with another prime factor keep the chirp-z path.  The fused estimator kernels remain power-of-two; on these sides the one-call
+// TT entries run them on a power-of-two band grid (band.hip), the other estimators the modular calls (oa_qe_legs / oa_mul_real /
+// oa_qe_div) over these transforms.
 #pragma once
 #include "cx.hpp"
 

@@ -65,6 +65,14 @@ struct Pipeline {
     bool opt_mv_chain = true;         // oa_qe_mv: estimator chains (pieces summed in real space inside one row-stage launch)
     bool opt_divbin = true;           // moment entries: radial binning + moments in the tail of the single-pass divergence launch
     bool opt_win_fused = true;        // oa_mc_run_windowed: C2R x window -> R2C as one row pass (the real map stays in LDS)
+    // BAND GRID (map sides 2^a 3^b 5^c, p->mixed; include/orphics_amd.h): the one-call TT entries run on an inner power-of-two plan of
+    // (bmy, bmx) points that holds inner-layout copies of the filters and bin ids; made by oa_plan_set_filters / oa_plan_set_col_grid
+    oa_plan* band = nullptr;
+    int bmy = 0, bmx = 0;
+    void* bplanes = nullptr;          // inner layout: FG, FH, Fnorm (real planes), then the two input-transform planes kX, kY (hc)
+    int32_t* bids = nullptr;          // inner-layout bin ids (-1 outside kappa's band)
+    void* brows = nullptr;            // band input transform: row pass (ny x leg_cols complex) + column-pass partial sums
+    size_t brows_bytes = 0;
 };
 
 static size_t plane_bytes(const oa_plan* p) { return (size_t)p->ny * p->kp * 2 * (p->dtype == OA_F32 ? 4 : 8); }
@@ -91,6 +99,10 @@ void pipeline_release(oa_plan* p) {
     if (q->fn_t) (void)hipFree(q->fn_t);
     if (q->fb_t) (void)hipFree(q->fb_t);
     if (q->ids_t) (void)hipFree(q->ids_t);
+    if (q->band) (void)oa_plan_destroy(q->band);
+    if (q->bplanes) (void)hipFree(q->bplanes);
+    if (q->bids) (void)hipFree(q->bids);
+    if (q->brows) (void)hipFree(q->brows);
     delete q;
     p->pipe = nullptr;
 }
@@ -169,19 +181,50 @@ static int resolve_col_grid(oa_plan* p, Pipeline* q) { return resolve_my(p, q->m
 using namespace oa;
 
 static int ensure_div_tables(oa_plan* p, oa::Pipeline* q, hipStream_t st);
+// BAND GRID (map sides 2^a 3^b 5^c), defined below the Monte-Carlo helpers
+namespace oa {
+static int band_grid_rule(const oa_plan* p, int mrow, int mcol, int wl, int wk, int rl, int rk, int* my, int* mx);
+static int mixed_bind(oa_plan* p, Pipeline* q);
+static int mixed_bins(oa_plan* p, Pipeline* q, hipStream_t st);
+static int mixed_qe_tt(oa_plan* p, Pipeline* q, const void* map, const void* kX, const void* kY, void* out, int zero_outside, hipStream_t st);
+static int mixed_moments(oa_plan* p, Pipeline* q, const void* map, int64_t* n, double* S, double* C, hipStream_t st);
+static int mixed_mc_run(oa_plan* p, Pipeline* q, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, int64_t* n, double* S,
+                        double* C, double* meanfield_acc, hipStream_t st);
+static void band_options(Pipeline* q);
+}  // namespace oa
+#define OA_NOT_MIXED(p, what) \
+    OA_REQUIRE(!(p)->mixed, what ": not available on map sides that are not powers of two (one-call TT entries there: oa_qe_tt, oa_qe_tt_moments(2), oa_mc_run)")
 
 extern "C" {
 
 int oa_plan_set_col_grid(oa_plan* p, int mcol) {
     OA_REQUIRE(p, "oa_plan_set_col_grid: NULL plan");
-    OA_NEED_POW2(p, "oa_plan_set_col_grid");
+    OA_REQUIRE(p->pow2 || p->mixed, "oa_plan_set_col_grid: map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path");
     OA_REQUIRE(mcol <= 0 || is_pow2(mcol), "oa_plan_set_col_grid: mcol must be -1 (auto), 0 (off) or a power of two");
     Pipeline* q = pipe_of(p);
     q->mcol = mcol;
+    if (p->mixed) {                                // the band grid's rows: re-resolved, the inner plan remade only if they change
+        if (!q->FG) return 0;
+        int my = 0, mx = 0;
+        int rc = band_grid_rule(p, q->mrow, q->mcol, q->wl, q->wk, q->rl, q->rk, &my, &mx);
+        if (!rc && q->band && my == q->bmy && mx == q->bmx) return 0;
+        if (!rc) rc = mixed_bind(p, q);
+        if (rc) q->FG = nullptr;                   // nothing is bound after a refused grid
+        return rc;
+    }
     return q->FG ? resolve_col_grid(p, q) : 0;     // oa_qe_pol resolves it per call from its own row bands
 }
 
 int oa_plan_col_grid(const oa_plan* p) { return (p && p->pipe) ? ((Pipeline*)p->pipe)->my : 0; }
+
+int oa_plan_band_grid(const oa_plan* p, int* my, int* mx) {
+    OA_REQUIRE(p && my && mx, "oa_plan_band_grid: NULL argument");
+    const Pipeline* q = (const Pipeline*)p->pipe;
+    const bool bound = q && q->FG && q->band;
+    *my = bound ? q->bmy : 0;
+    *mx = bound ? q->bmx : 0;
+    return 0;
+}
 
 int oa_plan_set_option(oa_plan* p, int option, int value) {
     OA_REQUIRE(p, "oa_plan_set_option: NULL plan");
@@ -198,6 +241,17 @@ int oa_plan_set_option(oa_plan* p, int option, int value) {
         default: return fail("oa_plan_set_option: unknown option");
     }
 }
+}  // extern "C"
+namespace oa {
+// the band plan runs the one-call launches of a mixed plan: it follows the options set on the outer plan
+static void band_options(Pipeline* q) {
+    if (!q->band || !q->band->pipe) return;
+    Pipeline* b = (Pipeline*)q->band->pipe;
+    b->opt_mc_batch = q->opt_mc_batch; b->opt_mv_batch = q->opt_mv_batch; b->opt_mv_rowbatch = q->opt_mv_rowbatch;
+    b->opt_mv_chain = q->opt_mv_chain; b->opt_divbin = q->opt_divbin; b->opt_win_fused = q->opt_win_fused;
+}
+}  // namespace oa
+extern "C" {
 int oa_plan_rsplit(const oa_plan* p) {
     if (!p || !p->pipe) return 0;
     const Pipeline* q = (const Pipeline*)p->pipe;
@@ -207,6 +261,7 @@ int oa_plan_rsplit(const oa_plan* p) {
 int oa_plan_div_fused(const oa_plan* p) {
     if (!p || !p->pipe) return 0;
     const Pipeline* q = (const Pipeline*)p->pipe;
+    if (p->mixed) { band_options((Pipeline*)q); return (q->FG && q->ids && q->band) ? oa_plan_div_fused(q->band) : 0; }
     if (!q->FG || !q->ids || !q->opt_divbin) return 0;
     const int rows = q->my ? q->my : p->ny;            // rows of the grid the divergence runs on
     const bool sp = p->dtype == OA_F32 ? Fft2dPlan<float>::single_pass_div() : Fft2dPlan<double>::single_pass_div();
@@ -219,14 +274,20 @@ int oa_plan_div_fused(const oa_plan* p) {
 int oa_plan_set_filters(oa_plan* p, const void* FG, const void* FH, const void* Fnorm, int leg_cols, int kappa_cols,
                         int leg_rows, int kappa_rows, int mrow) {
     OA_REQUIRE(p && FG && FH && Fnorm, "oa_plan_set_filters: NULL argument");
-    OA_NEED_POW2(p, "oa_plan_set_filters");
+    OA_REQUIRE(p->pow2 || p->mixed, "oa_plan_set_filters: map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no "
+               "one-call path (use the modular oa_qe_legs / oa_mul_real / oa_qe_div calls)");
     OA_REQUIRE(p->have_laxes, "oa_plan_set_filters: call oa_plan_set_laxes first");
     Pipeline* q = pipe_of(p);
     q->FG = FG; q->FH = FH; q->Fn = Fnorm;
     ++q->bind_gen;                             // the tile-major copy of Fnorm is repacked by the next call that uses it
     q->wl = leg_cols; q->wk = kappa_cols; q->rl = leg_rows; q->rk = kappa_rows; q->mrow = mrow;
     q->mcol = mrow == 0 ? 0 : -1;             // the map's own grid in x means the map's own grid in y too
-    if (int rc = ensure_work(p, q)) return rc;
+    if (int rc = ensure_work(p, q)) { if (p->mixed) q->FG = nullptr; return rc; }
+    if (p->mixed) {                            // BAND GRID: inner plan + inner-layout copies of the filters (and of the bins, if bound)
+        int rc = mixed_bind(p, q);
+        if (rc) q->FG = nullptr;
+        return rc;
+    }
     return resolve_col_grid(p, q);
 }
 
@@ -253,6 +314,7 @@ int oa_plan_set_bins(oa_plan* p, const int32_t* ids_hc, int nids, double norm, v
     // mode counts per bin over the WHOLE plane (the per-call binning visits only kappa's active region)
     if (int rc = oa_bin_power(p->dtype, q->c[0], q->c[0], norm, ids_hc, nullptr, (long)p->ny * p->kp, nids, p->kp, p->nx / 2, q->sums,
                               q->counts_full, nullptr, q->bin_scratch, 0, 0, stream)) return rc;
+    if (p->mixed) return (q->FG && q->band) ? mixed_bins(p, q, (hipStream_t)stream) : 0;     // (else: when the filters are bound)
     return ensure_div_tables(p, q, (hipStream_t)stream);
 }
 
@@ -318,6 +380,11 @@ static int qe_tt_impl(oa_plan* p, const void* real_map, const void* kX, const vo
                       void* stream, DivBinFuse* fuse, int rows_done = 0);
 int oa_qe_tt(oa_plan* p, const void* real_map, const void* kX, const void* kY, void* out_kappa_hc, int zero_outside,
              void* stream) {
+    if (p && p->mixed) {
+        OA_REQUIRE(p->pipe && ((Pipeline*)p->pipe)->FG, "oa_qe_tt: call oa_plan_set_filters first");
+        OA_REQUIRE((real_map != nullptr) != (kX != nullptr), "oa_qe_tt: pass either a real map or the Fourier-space leg(s)");
+        return mixed_qe_tt(p, (Pipeline*)p->pipe, real_map, kX, kY, out_kappa_hc, zero_outside, (hipStream_t)stream);
+    }
     return qe_tt_impl(p, real_map, kX, kY, out_kappa_hc, zero_outside, stream, nullptr);
 }
 // rows_done: the row-transformed map already sits on the plan's scratch plane (qe_windowed_rows_w): column stages only, multi-pass
@@ -463,6 +530,7 @@ int oa_qe_tt_moments(oa_plan* p, const void* real_map, int64_t* n, double* S, do
     OA_REQUIRE(p && p->pipe && ((Pipeline*)p->pipe)->FG && ((Pipeline*)p->pipe)->ids, "oa_qe_tt_moments: call oa_plan_set_filters and oa_plan_set_bins first");
     OA_REQUIRE(real_map && n && S && C, "oa_qe_tt_moments: NULL argument");
     Pipeline* q = (Pipeline*)p->pipe;
+    if (p->mixed) return mixed_moments(p, q, real_map, n, S, C, (hipStream_t)stream);
     if (int rc = ensure_div_tables(p, q, (hipStream_t)stream)) return rc;
     DivBinFuse f = make_fuse(p, q, n, S, C, 0);
     if (int rc = qe_tt_impl(p, real_map, nullptr, nullptr, nullptr, 0, stream, divbin_enabled(q) ? &f : nullptr)) return rc;
@@ -663,6 +731,7 @@ int oa_qe_mv(oa_plan* p, int nest, const int* host_npieces, const double* host_s
 int oa_qe_tt_splits(oa_plan* p, int nsplits, const void* const* host_kmaps, void* const* host_out, int zero_outside, void* stream) {
     OA_REQUIRE(p && p->pipe && ((Pipeline*)p->pipe)->FG, "oa_qe_tt_splits: call oa_plan_set_filters first");
     OA_REQUIRE(nsplits >= 1 && nsplits <= 64 && host_kmaps && host_out, "oa_qe_tt_splits: bad argument");
+    OA_NOT_MIXED(p, "oa_qe_tt_splits");
     Pipeline* q = (Pipeline*)p->pipe;
     hipStream_t st = (hipStream_t)stream;
     const long pl = work_pitch(p, q->wl), pk = work_pitch(p, q->wk);
@@ -712,6 +781,10 @@ int oa_qe_tt_moments2(oa_plan* p, const void* real_map0, const void* real_map1, 
     OA_REQUIRE(p && p->pipe && ((Pipeline*)p->pipe)->FG && ((Pipeline*)p->pipe)->ids, "oa_qe_tt_moments2: call oa_plan_set_filters and oa_plan_set_bins first");
     OA_REQUIRE(real_map0 && real_map1 && n && S && C, "oa_qe_tt_moments2: NULL argument");
     Pipeline* q = (Pipeline*)p->pipe;
+    if (p->mixed) {                            // two steps on the band grid, map order
+        if (int rc = mixed_moments(p, q, real_map0, n, S, C, (hipStream_t)stream)) return rc;
+        return mixed_moments(p, q, real_map1, n, S, C, (hipStream_t)stream);
+    }
     const long pl = work_pitch(p, q->wl), pk = work_pitch(p, q->wk);
     // second kappa plane: the plan-owned input-transform plane (unused on the from-map path); only kappa's active region of
     // it is ever read back (binning)
@@ -740,6 +813,7 @@ int oa_qe_tt_moments2(oa_plan* p, const void* real_map0, const void* real_map1, 
  * moment accumulation (into plan-owned dummies).  Stages read what the previous ones left in the work planes. */
 int oa_qe_tt_stage(oa_plan* p, int stage, const void* real_map, void* stream) {
     OA_REQUIRE(p && p->pipe && ((Pipeline*)p->pipe)->FG, "oa_qe_tt_stage: call oa_plan_set_filters first");
+    OA_NOT_MIXED(p, "oa_qe_tt_stage");
     Pipeline* q = (Pipeline*)p->pipe;
     const long pl = work_pitch(p, q->wl), pk = work_pitch(p, q->wk);
     hipStream_t st = (hipStream_t)stream;
@@ -791,7 +865,8 @@ static size_t mc_pool_bytes(const oa_plan* p, const Pipeline* q, int B) {
  * stage, divergence, binned power + moments in realisation order, mean-field stack -- each ONE launch for the batch (oa_mc_run and,
  * behind its windowed front end, oa_mc_run_windowed).  *fallback = 1: this geometry's row stage takes one map per launch (nothing
  * was launched). */
-static int mc_batch_tail(oa_plan* p, Pipeline* q, int B, int64_t* n, double* S, double* C, double* meanfield_acc, hipStream_t st, int* fallback) {
+static int mc_batch_tail(oa_plan* p, Pipeline* q, int B, int64_t* n, double* S, double* C, double* meanfield_acc, hipStream_t st, int* fallback,
+                         bool keep_kappa = false) {     // keep_kappa: the kappa planes are stored (c[0] ...) even without a stack here
     *fallback = 0;
     const long pl = work_pitch(p, q->wl), pk = work_pitch(p, q->wk);
     const size_t es = 2 * (p->dtype == OA_F32 ? 4 : 8), pb = plane_bytes(p);
@@ -822,7 +897,7 @@ static int mc_batch_tail(oa_plan* p, Pipeline* q, int B, int64_t* n, double* S, 
     if (rc < 0) { *fallback = 1; return 0; }          // this geometry's row stage takes one map per launch: one-by-one loop
     if (rc) return rc;
     if ((rc = ensure_div_tables(p, q, st))) return rc;
-    DivBinFuse f = make_fuse(p, q, n, S, C, meanfield_acc ? 1 : 0);
+    DivBinFuse f = make_fuse(p, q, n, S, C, (meanfield_acc || keep_kappa) ? 1 : 0);
     if ((rc = qe_cols_div_batch_w(p, prod, prod + lbk, q->Fn, q->c[0], tmp, B, (long)(2 * lbk / es), 0, (long)(pb / es), q->wk, q->rk, pk, st, my,
                                   divbin_enabled(q) ? &f : nullptr)))
         return rc;
@@ -831,6 +906,169 @@ static int mc_batch_tail(oa_plan* p, Pipeline* q, int B, int64_t* n, double* S, 
     if (!f.done && (rc = bin_power_moments(p->dtype, q->c[0], q->norm, q->ids, (long)p->ny * p->kp, q->nids, p->kp, p->nx / 2, q->sums, q->counts_tmp,
                                 q->bin_scratch, q->wk, q->rk, q->ticket, q->counts_full, n, S, C, st, B, (long)(pb / es)))) return rc;
     if (meanfield_acc && (rc = stack_add_region(p->dtype, q->c[0], meanfield_acc, p->ny, p->kp, q->wk, q->rk, st, B, (long)(2 * pb / es)))) return rc;
+    return 0;
+}
+
+/* ---- BAND GRID: the one-call TT entries on map sides 2^a 3^b 5^c (include/orphics_amd.h) ---------------------------------------
+ * Legs confined to columns < wl and rows |ky| < rl, kappa to columns < wk and rows |ky| < rk: on any (My, Mx) grid with
+ * My >= max(2 rl + rk, 2 rk), Mx >= 2 wl + wk the estimator returns the same kappa modes as on the map's own (ny, nx) grid (same
+ * ell lattice; a mode of signed index ky at row ky mod My), times (ny nx) / (My Mx): each inverse transform carries its own grid's
+ * 1 / Npix and the forward transform sums over its own grid.  That factor is folded into the inner copy of Fnorm.  With My, Mx
+ * powers of two the inner computation IS the fused pipeline of a power-of-two plan fed with Fourier-space legs; only the input
+ * transform (band_map_r2c), the GRF draw and the kappa scatter see the map's grid. */
+constexpr int BAND_MIN = 128;                  // smallest inner side (the fused estimator kernels are exercised from 128 points up)
+static int band_side(int mreq, long need, int side, const char* axis, int* out) {
+    *out = 0;
+    int m = mreq;
+    if (m < 0) { m = BAND_MIN; while (m < need) m <<= 1; }
+    else if (!is_pow2(m)) return fail(std::string("oa_plan_set_filters: band grid ") + axis + " must be a power of two");
+    else if (m < need) return fail(std::string("oa_plan_set_filters: band grid ") + axis + " of " + std::to_string(m) + " points < " +
+                                   std::to_string(need) + " would alias the leg products into the kept kappa modes");
+    if (m >= side)
+        return fail(std::string("oa_plan_set_filters: band too wide for the map: the band grid needs ") + std::to_string(m) + " points in " + axis +
+                    " (alias-free bound " + std::to_string(need) + "), not fewer than the map's " + std::to_string(side) +
+                    " -- no one-call path on this geometry (use the modular chain)");
+    *out = m;
+    return 0;
+}
+static int band_grid_rule(const oa_plan* p, int mrow, int mcol, int wl, int wk, int rl, int rk, int* my, int* mx) {
+    *my = *mx = 0;
+    if (mrow == 0 || mcol == 0)
+        return fail("oa_plan_set_filters: sides that are not powers of two have no fused path on the map's own grid (mrow = 0 / column grid 0): "
+                    "the one-call entries run on a band grid (mrow, column grid -1 or a power of two)");
+    if (wl <= 0 || wk <= 0 || rl <= 0 || rk <= 0)
+        return fail("oa_plan_set_filters: sides that are not powers of two need band-limited filters (leg / kappa columns and rows > 0; "
+                    "0 = all has no band grid)");
+    if (int rc = band_side(mrow, 2L * wl + wk, p->nx, "x", mx)) return rc;
+    return band_side(mcol, std::max(2L * rl + rk, 2L * rk), p->ny, "y", my);
+}
+static size_t band_real_bytes(const oa_plan* b) { return (size_t)b->ny * b->kp * (b->dtype == OA_F32 ? 4 : 8); }
+// (re)make the band plan for the bound filters, copy the filters (and the bins) into its layout and bind them there.  Set-up call:
+// synchronises the device (the caller's planes may have been written on any stream)
+static int mixed_bind(oa_plan* p, Pipeline* q) {
+    int my = 0, mx = 0;
+    if (int rc = band_grid_rule(p, q->mrow, q->mcol, q->wl, q->wk, q->rl, q->rk, &my, &mx)) return rc;
+    OA_HIP(hipDeviceSynchronize());
+    if (!q->band || q->bmy != my || q->bmx != mx) {
+        if (q->band) { (void)oa_plan_destroy(q->band); q->band = nullptr; }
+        if (q->bplanes) { (void)hipFree(q->bplanes); q->bplanes = nullptr; }
+        if (q->bids) { (void)hipFree(q->bids); q->bids = nullptr; }
+        q->bmy = q->bmx = 0;
+        if (int rc = oa_plan_create(my, mx, p->dtype, &q->band)) return rc;
+        std::vector<double> ly(p->ny), lx(p->nx), bly(my), blx(mx);
+        OA_HIP(hipMemcpy(ly.data(), p->ly64, p->ny * sizeof(double), hipMemcpyDeviceToHost));
+        OA_HIP(hipMemcpy(lx.data(), p->lx64, p->nx * sizeof(double), hipMemcpyDeviceToHost));
+        for (int i = 0; i < my; ++i) bly[i] = ly[i < my / 2 ? i : i - my + p->ny];    // the N grid's ell at the same signed index
+        for (int i = 0; i < mx; ++i) blx[i] = lx[i < mx / 2 ? i : i - mx + p->nx];
+        if (int rc = oa_plan_set_laxes(q->band, bly.data(), blx.data())) return rc;
+        OA_HIP(hipMalloc(&q->bplanes, 3 * band_real_bytes(q->band) + 2 * plane_bytes(q->band)));
+        OA_HIP(hipMalloc((void**)&q->bids, (size_t)my * q->band->kp * sizeof(int32_t)));
+        q->bmy = my; q->bmx = mx;
+        band_options(q);
+    }
+    oa_plan* b = q->band;
+    const size_t rb = band_real_bytes(b);
+    const size_t sb = band_map_scratch_bytes(p, q->wl, q->rl);
+    if (q->brows_bytes < sb) {
+        if (q->brows) { (void)hipFree(q->brows); q->brows = nullptr; q->brows_bytes = 0; }
+        OA_HIP(hipMalloc(&q->brows, sb));
+        q->brows_bytes = sb;
+    }
+    char* f = (char*)q->bplanes;
+    OA_HIP(hipMemset(f, 0, 3 * rb + 2 * plane_bytes(b)));          // zero outside the bands (the input planes: only their band is written)
+    const int kind = p->dtype == OA_F32 ? 0 : 1;
+    const double fscale = (double)b->ny * b->nx / ((double)p->ny * p->nx);
+    int rc = band_copy(kind, q->FG, p->kp, p->ny, f, b->kp, my, q->wl, q->rl, 1.0, nullptr);
+    if (!rc) rc = band_copy(kind, q->FH, p->kp, p->ny, f + rb, b->kp, my, q->wl, q->rl, 1.0, nullptr);
+    if (!rc) rc = band_copy(kind, q->Fn, p->kp, p->ny, f + 2 * rb, b->kp, my, q->wk, q->rk, fscale, nullptr);
+    if (rc) return rc;
+    OA_HIP(hipDeviceSynchronize());
+    if (int rc2 = oa_plan_set_filters(b, f, f + rb, f + 2 * rb, q->wl, q->wk, q->rl, q->rk, -1)) return rc2;
+    if (q->ids) {
+        if (int rc2 = mixed_bins(p, q, nullptr)) return rc2;
+        OA_HIP(hipDeviceSynchronize());
+    }
+    return 0;
+}
+// the bound bin ids in the band plan's layout; the band plan's mode counts are replaced by the WHOLE N-plane ones (a bandpower divides
+// by the full grid's count).  Also takes the band plan's Monte-Carlo planes now (set-up time), zero-filled
+static int mixed_bins(oa_plan* p, Pipeline* q, hipStream_t st) {
+    oa_plan* b = q->band;
+    OA_HIP(hipMemsetAsync(q->bids, 0xFF, (size_t)b->ny * b->kp * sizeof(int32_t), st));
+    if (int rc = band_copy(2, q->ids, p->kp, p->ny, q->bids, b->kp, b->ny, q->wk, q->rk, 1.0, st)) return rc;
+    if (int rc = oa_plan_set_bins(b, q->bids, q->nids, q->norm, st)) return rc;
+    Pipeline* qb = (Pipeline*)b->pipe;
+    OA_HIP(hipMemcpyAsync(qb->counts_full, q->counts_full, q->nids * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    if (!qb->mc_src) {
+        if (int rc = ensure_mc_src(b, qb)) return rc;
+        OA_HIP(hipMemset(qb->mc_src, 0, (size_t)MC_BATCH_MAX * plane_bytes(b)));
+    }
+    return ensure_pool(qb, mc_pool_bytes(b, qb, MC_BATCH_MAX));
+}
+static void* band_in(const Pipeline* q, int which) { return (char*)q->bplanes + 3 * band_real_bytes(q->band) + which * plane_bytes(q->band); }
+static int band_cx_kind(const oa_plan* p) { return p->dtype == OA_F32 ? 3 : 4; }
+
+// oa_qe_tt: input band -> band plan's fused pipeline (kappa on its plan-owned plane) -> scatter into the N-grid output
+static int mixed_qe_tt(oa_plan* p, Pipeline* q, const void* map, const void* kX, const void* kY, void* out, int zero_outside, hipStream_t st) {
+    oa_plan* b = q->band;
+    void* bx = band_in(q, 0);
+    void* by = nullptr;
+    int rc;
+    if (map) rc = band_map_r2c(p, map, q->brows, q->wl, q->rl, bx, b->ny, b->kp, st);
+    else {
+        rc = band_copy(band_cx_kind(p), kX, p->kp, p->ny, bx, b->kp, b->ny, q->wl, q->rl, 1.0, st);
+        if (!rc && kY && kY != kX) { by = band_in(q, 1); rc = band_copy(band_cx_kind(p), kY, p->kp, p->ny, by, b->kp, b->ny, q->wl, q->rl, 1.0, st); }
+    }
+    if (rc) return rc;
+    if ((rc = qe_tt_impl(b, nullptr, bx, by, nullptr, 0, st, nullptr))) return rc;
+    void* o = out ? out : q->kk;
+    if (out && zero_outside && (rc = band_zero_outside(p->dtype, o, p->ny, p->kp, q->wk, q->rk, st))) return rc;
+    return band_copy(band_cx_kind(p), ((Pipeline*)b->pipe)->kk, b->kp, b->ny, o, p->kp, p->ny, q->wk, q->rk, 1.0, st);
+}
+// one Monte-Carlo step of a real map: input band, then oa_qe_tt_moments' sequence on the band plan (its bins carry the N-plane counts)
+static int mixed_moments(oa_plan* p, Pipeline* q, const void* map, int64_t* n, double* S, double* C, hipStream_t st) {
+    oa_plan* b = q->band;
+    Pipeline* qb = (Pipeline*)b->pipe;
+    band_options(q);
+    void* bx = band_in(q, 0);
+    if (int rc = band_map_r2c(p, map, q->brows, q->wl, q->rl, bx, b->ny, b->kp, st)) return rc;
+    if (int rc = ensure_div_tables(b, qb, st)) return rc;
+    DivBinFuse f = make_fuse(b, qb, n, S, C, 0);
+    if (int rc = qe_tt_impl(b, nullptr, bx, nullptr, nullptr, 0, st, divbin_enabled(qb) ? &f : nullptr)) return rc;
+    if (f.done) return 0;
+    return bandpower_moments(b, qb, n, S, C, st);
+}
+// oa_mc_run: the leg band of each realisation's N-grid draw straight into the band plan's layout, then oa_mc_run's batched launches there;
+// the mean-field stack is updated in the N-grid layout from the batch's kappa planes
+static int mixed_mc_run(oa_plan* p, Pipeline* q, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, int64_t* n, double* S,
+                        double* C, double* meanfield_acc, hipStream_t st) {
+    oa_plan* b = q->band;
+    Pipeline* qb = (Pipeline*)b->pipe;
+    band_options(q);
+    const int BMAX = std::max(1, std::min(MC_BATCH_MAX, qb->opt_mc_batch));
+    const long pbe = (long)(plane_bytes(b) / (2 * (b->dtype == OA_F32 ? 4 : 8)));     // complex elements per band plane
+    long i = sim_lo;
+    bool batched = true;
+    while (batched && i < sim_hi) {
+        const int B = (int)std::min<long>(BMAX, sim_hi - i);
+        if (int rc = ensure_mc_src(b, qb)) return rc;                            // (taken by oa_plan_set_bins: no allocation here)
+        if (int rc = ensure_pool(qb, mc_pool_bytes(b, qb, B))) return rc;
+        int rc = grf_band_inner(p, base_seed, (uint64_t)i, B, covsqrt_hc, qb->mc_src, b->ny, b->kp, pbe, q->wl, q->rl, st);
+        if (rc) return rc;
+        int fallback = 0;
+        if ((rc = mc_batch_tail(b, qb, B, n, S, C, nullptr, st, &fallback, meanfield_acc != nullptr))) return rc;
+        if (fallback) { batched = false; break; }
+        if (meanfield_acc && (rc = band_stack_add(p->dtype, qb->c[0], b->kp, b->ny, B, pbe, meanfield_acc, p->kp, p->ny, q->wk, q->rk, st))) return rc;
+        i += B;
+    }
+    void* bx = band_in(q, 0);
+    for (; i < sim_hi; ++i) {
+        int rc = grf_band_inner(p, base_seed, (uint64_t)i, 1, covsqrt_hc, bx, b->ny, b->kp, 0, q->wl, q->rl, st);
+        if (rc) return rc;
+        if ((rc = qe_tt_impl(b, nullptr, bx, nullptr, nullptr, 0, st, nullptr))) return rc;
+        if ((rc = bandpower_moments(b, qb, n, S, C, st))) return rc;
+        if (meanfield_acc && (rc = band_stack_add(p->dtype, qb->kk, b->kp, b->ny, 1, 0, meanfield_acc, p->kp, p->ny, q->wk, q->rk, st))) return rc;
+    }
     return 0;
 }
 }  // namespace oa
@@ -843,6 +1081,7 @@ int oa_mc_run(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const vo
     OA_REQUIRE(covsqrt_hc && n && S && C && sim_hi >= sim_lo, "oa_mc_run: bad argument");
     Pipeline* q = (Pipeline*)p->pipe;
     hipStream_t st = (hipStream_t)stream;
+    if (p->mixed) return mixed_mc_run(p, q, base_seed, sim_lo, sim_hi, covsqrt_hc, n, S, C, meanfield_acc, st);
     long i = sim_lo;
     // BATCHES of realisations: at 4096^2 a realisation is ~60 MB of traffic behind ~10 launches, i.e. launch latency; with B
     // realisations per launch (grid z) the column and row stages fill the chip.  Same kernels on the same operands in the same

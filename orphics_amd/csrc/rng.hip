@@ -1,5 +1,6 @@
 // K8: on-device Gaussian random fields (Philox4x32-10 counter RNG + Box-Muller)
 // K9: device-side moment accumulation for Monte-Carlo ensembles.
+#include <algorithm>
 #include "common.hpp"
 
 namespace oa {
@@ -94,6 +95,57 @@ __global__ __launch_bounds__(256) void grf_hc_kernel(uint64_t seed, uint64_t sid
         const T s = cs ? cs[i] : (T)1;
         out[i] = mk<T>(re * s, im * s);
     }
+}
+
+// BAND GRID draw of oa_mc_run on map sides 2^a 3^b 5^c (pipeline.hip): the leg band (columns < 2 wpairs, rows y < rband or
+// y > ny - rband) of grf_hc_kernel's N-grid draw -- same Philox counters, same self-conjugate edge rules, amplitude from the N-grid
+// covsqrt -- written into the hc layout of the inner (my, okp) grid, row ky mod my instead of ky mod ny
+template <typename T>
+__global__ __launch_bounds__(256) void grf_band_inner_kernel(uint64_t seed, uint64_t sid, const T* __restrict__ cs, cx<T>* __restrict__ out,
+                                                             int ny, int nx, long kp, int wpairs, int rband, int my, long okp, long zstride) {
+    sid += blockIdx.z;
+    out += (long)blockIdx.z * zstride;
+    const int nxh = nx / 2;
+    const int npair = nxh / 2 + 1;
+    const int pr = blockIdx.x * blockDim.x + threadIdx.x;
+    int y = blockIdx.y, yo = y;
+    if (y >= rband) { y += ny - (2 * rband - 1); yo += my - (2 * rband - 1); }
+    if (pr >= wpairs) return;
+    const T rs2 = (T)0.70710678118654752440;
+    float n[4];
+    int cur_ys = -1;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int x = 2 * pr + j;
+        if (x > nxh) break;
+        const bool edgecol = (x == 0 || x == nxh);
+        int ys = y;
+        bool cj = false;
+        if (edgecol && y > ny / 2) { ys = ny - y; cj = true; }
+        if (ys != cur_ys) { normals4(seed, sid, (uint64_t)ys * (uint64_t)npair + (uint64_t)pr, n); cur_ys = ys; }
+        T re = (T)n[2 * j], im = (T)n[2 * j + 1];
+        if (edgecol && (ys == 0 || ys == ny / 2)) { im = (T)0; }
+        else { re *= rs2; im *= rs2; }
+        if (cj) im = -im;
+        const T s = cs ? cs[(long)y * kp + x] : (T)1;
+        out[(long)yo * okp + x] = mk<T>(re * s, im * s);
+    }
+}
+int grf_band_inner(oa_plan* p, uint64_t seed, uint64_t stream_id, int nreal, const void* covsqrt_hc, void* out, int my, long okp, long zstride,
+                   int width, int rband, hipStream_t stream) {
+    OA_REQUIRE(p && out && nreal >= 1 && width >= 1 && rband >= 1 && 2 * rband - 1 <= std::min(p->ny, my) && 2 * ((width + 1) / 2) <= okp,
+               "band draw: bad argument");
+    const int wpairs = (width + 1) / 2;
+    const int bs = wpairs >= 256 ? 256 : 64;
+    dim3 grid((wpairs + bs - 1) / bs, 2 * rband - 1, nreal);
+    if (p->dtype == OA_F32)
+        hipLaunchKernelGGL(grf_band_inner_kernel<float>, grid, dim3(bs), 0, stream, seed, stream_id, (const float*)covsqrt_hc, (cx<float>*)out,
+                           p->ny, p->nx, p->kp, wpairs, rband, my, okp, zstride);
+    else
+        hipLaunchKernelGGL(grf_band_inner_kernel<double>, grid, dim3(bs), 0, stream, seed, stream_id, (const double*)covsqrt_hc, (cx<double>*)out,
+                           p->ny, p->nx, p->kp, wpairs, rband, my, okp, zstride);
+    OA_LAUNCH_CHECK();
+    return 0;
 }
 
 // MapGen.get_map in one pass (maps.py:1579-1587): up to three white fields of streams (seed, sid0 + j) -- the counters and the

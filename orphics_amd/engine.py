@@ -161,6 +161,32 @@ def dev_bin_power(k1, k2, norm, ids, nids, herm_pitch=0, herm_nxh=-1, active_col
     return sums, counts
 
 
+BAND_MIN = 128      # smallest side of a band grid (pipeline.hip BAND_MIN)
+
+
+def band_grid(ny, nx, leg_cols, kappa_cols, leg_rows, kappa_rows, mrow=-1, mcol=-1):
+    """(My, Mx) of the BAND GRID the one-call TT entries run on for map sides 2^a 3^b 5^c that are not powers of two
+    (include/orphics_amd.h, oa_plan_band_grid), or None where ``oa_plan_set_filters`` refuses: the C rule, host-side, so that a
+    caller picks the modular chain without a failing call.  Mx from ``mrow``, My from the column-grid policy ``mcol``: -1 = the
+    smallest power of two >= the alias-free bound (max(2 leg_rows + kappa_rows, 2 kappa_rows) rows, 2 leg_cols + kappa_cols
+    columns) and >= 128; a power of two must reach the bound; 0 (the map's own grid), unbounded filters (0) and a grid not smaller
+    than the map side have no band grid."""
+    if mrow == 0 or mcol == 0 or min(leg_cols, kappa_cols, leg_rows, kappa_rows) <= 0:
+        return None
+
+    def side(m, need, n):
+        if m < 0:
+            m = BAND_MIN
+            while m < need:
+                m <<= 1
+        elif m & (m - 1) or m < need:
+            return None
+        return m if m < n else None
+    mx = side(int(mrow), 2 * leg_cols + kappa_cols, int(nx))
+    my = side(int(mcol), max(2 * leg_rows + kappa_rows, 2 * kappa_rows), int(ny))
+    return None if mx is None or my is None else (my, mx)
+
+
 class Engine(object):
     _cache = {}
 
@@ -456,6 +482,18 @@ class Engine(object):
     def copy_options_to(self, other):
         for name, value in getattr(self, "_options", {}).items():
             other.set_option(name, value)
+
+    def band_grid(self, leg_cols, kappa_cols, leg_rows, kappa_rows, mrow=-1, mcol=-1):
+        """:func:`band_grid` for this plan's sides (None on power-of-two and chirp-z plans: no band grid there)."""
+        if not self.mixed:
+            return None
+        return band_grid(self.ny, self.nx, leg_cols, kappa_cols, leg_rows, kappa_rows, mrow, mcol)
+
+    def plan_band_grid(self):
+        """(My, Mx) the plan resolved for its bound TT filters (``oa_plan_band_grid``); (0, 0) = none bound."""
+        my, mx = ctypes.c_int(0), ctypes.c_int(0)
+        check(self.lib.oa_plan_band_grid(self.plan, ctypes.byref(my), ctypes.byref(mx)))
+        return my.value, mx.value
 
     def release_pools(self):
         """free the plan-owned pools of the multi-map entries (oa_lens_maps, oa_qe_mv, oa_qe_tt_splits, oa_mc_run)"""

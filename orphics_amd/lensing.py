@@ -157,6 +157,23 @@ class Estimator(object):
         rb = int(np.minimum(y, Ny - y).max()) + 1
         return 0 if 2 * rb - 1 >= Ny else rb
 
+    def one_call(self):
+        """True when the one-call TT entries (``oa_qe_tt``, ``tt_moments``, ``oa_mc_run``) serve this estimator: power-of-two
+        sides, or sides 2^a 3^b 5^c whose band grid resolves (``Engine.band_grid``: band-limited filters, a row / column grid
+        policy other than the map's own grid, and a grid smaller than the map)."""
+        e = self.eng
+        if e.pow2:
+            return True
+        (wl, wk), (rl, rk) = self._W["TT"], self._R["TT"]
+        return e.band_grid(wl, wk, rl, rk, self.mrow, self.mcol) is not None
+
+    @property
+    def band_grid(self):
+        """(My, Mx) of the band grid the one-call TT path runs on (sides 2^a 3^b 5^c), (0, 0) on power-of-two plans."""
+        if self.eng.pow2:
+            return (0, 0)
+        return self._bind().plan_band_grid()
+
     @property
     def col_grid(self):
         """Rows the one-call TT path runs its inverse-column / row / forward-column stages on (0 = the map's ny)."""
@@ -417,7 +434,7 @@ class Estimator(object):
         ``kappa_cols`` columns of the result are computed; the remaining columns of ``out`` are zero-filled (on
         every call, unless ``out`` came from :meth:`new_output`)."""
         e = self.eng
-        if fused and e.pow2:
+        if fused and self.one_call():
             e._chk(kX, "hc")
             if kY is not None and kY is not kX:
                 e._chk(kY, "hc")
@@ -441,8 +458,8 @@ class Estimator(object):
         transform is consumed inside the fused leg kernel and never written.  Same result as
         ``reconstruct_tt_hc(eng.rfft(tmap))``."""
         e = self.eng
-        if not e.pow2:                       # chirp-z sizes: modular chain of public calls
-            return self.reconstruct_tt_hc(e.rfft(tmap), out=out)
+        if not self.one_call():              # no one-call path on this geometry: modular chain of public calls
+            return self.reconstruct_tt_hc(e.rfft(tmap), out=out, fused=False)
         e._chk(tmap, "real")
         return self._qe_tt(tmap, None, None, out)
 

@@ -66,6 +66,10 @@ class GaussianN0MonteCarlo(object):
         qest.bind_bins(self.ids, self.nids, self.norm)
         self.window = None
         self.window_moments = (1.0, 1.0)
+        if window is not None and not e.pow2:
+            from ._lib import OrphicsAmdError
+            raise OrphicsAmdError("GaussianN0MonteCarlo: a window needs power-of-two map sides (oa_mc_run_windowed); %dx%d runs "
+                                  "oa_mc_run on its band grid without a window only" % (e.ny, e.nx))
         if window is not None:
             w = np.asarray(window, dtype=np.float64)
             if w.shape != (e.ny, e.nx):

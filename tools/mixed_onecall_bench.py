@@ -1,0 +1,92 @@
+"""Timing of the one-call TT path on map sides 2^a 3^b 5^c (BAND GRID, include/orphics_amd.h oa_plan_band_grid) against the
+modular chain on the same plan, on the reference notebooks' patches (tutorials/tt_verification.ipynb: 1200^2 at 0.5'; mapwork.ipynb:
+2400^2), both precisions.  One JSON line per (side, precision):
+    onecall_ms / modular_ms : qe_TT per map (kappa_from_map("TT") from a real device map), median of --reps timed blocks of --iters
+    mc_sims_per_s           : GaussianN0MonteCarlo.run_local (oa_mc_run, bandpower moments, no mean field)
+    map_bytes               : bytes of the real map the band input transform reads
+--only-onecall N: run N one-call reconstructions per geometry and nothing else (the workload for
+    rocprofv3 --kernel-trace --stats -- python tools/mixed_onecall_bench.py --only-onecall 200)."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def setup(n, res, prec):
+    from orphics_amd import cosmology, lensing, maps
+    from orphics_amd.geometry import FlatGeometry
+    shape = (n, n)
+    g = FlatGeometry.from_res(shape, res)
+    th = cosmology.default_theory()
+    ml = g.modlmap()
+    beam = maps.gauss_beam(ml, 1.5)
+    noise = np.full(shape, cosmology.white_noise_power(1.0))
+    tmask = maps.mask_kspace(shape, g, lmin=300, lmax=2000)
+    kmask = maps.mask_kspace(shape, g, lmin=20, lmax=3500)
+    cl = th.lCl("TT", ml)
+    q = lensing.qest(shape, g, th, noise2d=noise, beam2d=beam, kmask=tmask, kmask_K=kmask, unlensed_equals_lensed=True, dtype=prec)
+    rng = np.random.default_rng(1)
+    tmap = np.fft.ifft2(np.fft.fft2(rng.standard_normal(shape)) * np.sqrt((cl * beam ** 2 + noise) / g.pixarea)).real
+    return q, tmap, (cl * beam ** 2 + noise)[:, :n // 2 + 1]
+
+
+def timed(fn, iters, reps):
+    import torch
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(iters):
+            fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b) / iters)
+    return float(np.median(out))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sides", default="1200,2400")
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--sims", type=int, default=600)
+    ap.add_argument("--only-onecall", type=int, default=0)
+    args = ap.parse_args()
+    import torch
+    from orphics_amd import mc
+    torch.cuda.set_device(0)
+    for n in [int(s) for s in args.sides.split(",")]:
+        for prec in ("f32", "f64"):
+            q, tmap, tot_h = setup(n, 0.5, prec)
+            e = q.eng
+            tm = e.to_real(tmap)
+            out = q.new_output()
+            if args.only_onecall:
+                for _ in range(args.only_onecall):
+                    q.reconstruct_tt_from_map(tm, out=out)
+                torch.cuda.synchronize()
+                continue
+            one = timed(lambda: q.reconstruct_tt_from_map(tm, out=out), args.iters, args.reps)
+            kbuf = e.hc()
+            mod = timed(lambda: q.reconstruct_tt_hc(e.rfft(tm, out=kbuf), out=out, fused=False), args.iters, args.reps)
+            drv = mc.GaussianN0MonteCarlo(q, tot_h, np.linspace(100, 3000, 12), base_seed=3)
+            drv.run_local(range(12))
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            drv.run_local(range(100, 100 + args.sims))
+            b.record()
+            b.synchronize()
+            sims = args.sims / (a.elapsed_time(b) / 1e3)
+            print(json.dumps(dict(side=n, prec=prec, band_grid=list(q.band_grid), onecall_ms=round(one, 4), modular_ms=round(mod, 4),
+                                  speedup=round(mod / one, 2), mc_sims_per_s=round(sims, 1), map_bytes=n * n * e.rdt.itemsize)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
