@@ -184,8 +184,8 @@ int oa_plan_col_grid(const oa_plan* p);
 /* BAND GRID: the one-call TT entries on map sides 2^a 3^b 5^c that are not powers of two (oa_qe_tt from a map or from kX [, kY],
  * oa_qe_tt_moments, oa_qe_tt_moments2, oa_mc_run incl. OA_OPT_MC_BATCH and the mean-field stack).  The estimator is band-limited
  * (legs: columns < leg_cols, rows |ky| < leg_rows; kappa: columns < kappa_cols, rows |ky| < kappa_rows), so on ANY My x Mx grid with
- *     My >= max(2 leg_rows + kappa_rows, 2 kappa_rows),   Mx >= 2 leg_cols + kappa_cols
- * and the same ell lattice (a mode of signed index ky at row ky mod My) it returns the same kappa modes, up to the factor
+ *     My >= max(2 leg_rows + kappa_rows, 2 kappa_rows),   Mx >= max(2 leg_cols + kappa_cols, 2 kappa_cols)
+ * (Mx >= 2 kappa_cols: kappa's columns fit the inner plane's Mx / 2 + 1) and the same ell lattice (a mode of signed index ky at row ky mod My) it returns the same kappa modes, up to the factor
  * (ny nx) / (My Mx) that the plan folds into its copy of Fnorm.  oa_plan_set_filters on such a plan resolves (My, Mx): Mx from
  * mrow, My from the column-grid policy (oa_plan_set_col_grid): -1 = the smallest power of two >= the bound and >= 128; an explicit
  * power of two is checked against the bound; 0 (the map's own grid), unbounded filters (0 = all) and a grid not smaller than the map

@@ -158,6 +158,7 @@ __global__ __launch_bounds__(256) void band_copy_kernel(const E* __restrict__ sr
 // kind: 0 f32, 1 f64, 2 int32 (real planes), 3 complex f32, 4 complex f64; scale applies to the real float kinds only
 int band_copy(int kind, const void* src, long spitch, int sny, void* dst, long dpitch, int dny, int w, int r, double scale, hipStream_t st) {
     OA_REQUIRE(w >= 1 && r >= 1 && 2 * r - 1 <= std::min(sny, dny), "band copy: bad band");
+    OA_REQUIRE(w <= spitch && w <= dpitch, "band copy: band wider than a plane's row pitch");
     dim3 grid((w + 255) / 256, 2 * r - 1);
     switch (kind) {
         case 0: hipLaunchKernelGGL(band_copy_kernel<float>, grid, dim3(256), 0, st, (const float*)src, spitch, sny, (float*)dst, dpitch, dny, w, r, scale); break;
@@ -205,6 +206,7 @@ __global__ __launch_bounds__(256) void band_stack_kernel(const T* __restrict__ s
 int band_stack_add(int dtype, const void* src, long spitch, int sny, int nbatch, long sstride, double* acc, long apitch, int any, int w, int r,
                    hipStream_t st) {
     OA_REQUIRE(w >= 1 && r >= 1 && 2 * r - 1 <= std::min(sny, any), "band stack: bad band");
+    OA_REQUIRE(w <= spitch && w <= apitch, "band stack: band wider than a plane's row pitch");
     dim3 grid((2 * w + 255) / 256, 2 * r - 1);
     if (dtype == OA_F32)
         hipLaunchKernelGGL(band_stack_kernel<float>, grid, dim3(256), 0, st, (const float*)src, spitch, sny, nbatch, sstride, acc, apitch, any, w, r);

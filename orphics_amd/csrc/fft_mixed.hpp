@@ -6,7 +6,8 @@
 // (czt.hip): two complex 4096^2 transforms + four elementwise passes per transform of a 1200^2 real map.  Here they are ordinary
 // mixed-radix Stockham transforms staged in LDS:
 //   * one sequence (row passes) or a tile of C adjacent columns (column passes) per workgroup, ping-pong between two LDS buffers,
-//     one workgroup barrier per stage; radices 4, 2, 3, 5 chosen on the host (mixed_factor);
+//     one workgroup barrier per stage; radices 4, 2, 3, 5 chosen on the host (mixed_factor); where two buffers exceed the LDS (float64
+//     sides above 5120) the stages run in place in one buffer (mr_transform_ip);
 //   * stage of radix R after sub-length Ns:  v_t = in[j + t N/R] W_N^(k t N/(Ns R)),  k = j mod Ns;  out[(j - k) R + k + t Ns] = DFT_R(v)_t
 //     (the autosort form of fft_kernels.hpp with a run-time radix list); factors from the W_N table (L1/L2-resident);
 //   * real rows as packed N/2-point transforms with the (un)tangle of fft_kernels.hpp (N even: every map side is);
@@ -118,6 +119,79 @@ OA_HD cx<T>* mr_transform(Ctx& ctx, cx<T>* buf0, cx<T>* buf1, int N, const MrFac
     return A;
 }
 
+// IN-PLACE form, for transforms whose two [N][C] buffers do not fit the LDS (float64 columns of ny > 5120, complex rows of nx >= 5120):
+// one buffer of N C values; per stage each thread loads the R inputs of ALL its butterflies into registers, barrier, twiddles + DFT_R,
+// stores to the autosort positions, barrier.  Butterflies per thread are bounded at compile time (mr_ip_nb): with 1024 threads that
+// covers N <= 8192 (at most 10 complex values in registers); the host checks it (mr_ip_fits) before a launch.
+template <int R> constexpr int mr_ip_nb() { return R == 2 ? 4 : (R == 3 ? 3 : 2); }
+inline bool mr_ip_fits(const MrFactors& f, int N, int logC, int NT) {
+    for (int s = 0; s < f.n; ++s) {
+        const int R = f.r[s], nb = R == 2 ? mr_ip_nb<2>() : (R == 3 ? mr_ip_nb<3>() : (R == 4 ? mr_ip_nb<4>() : mr_ip_nb<5>()));
+        if ((long)(N / R) << logC > (long)nb * NT) return false;
+    }
+    return true;
+}
+template <typename T, int R, class Ctx>
+OA_HD void mr_stage_ip(Ctx& ctx, cx<T>* A, int N, int Ns, int logC, const cx<T>* tw, int tid, int NT) {
+    constexpr int NB = mr_ip_nb<R>();
+    const int nb = N / R, step = N / (Ns * R), total = nb << logC, cm = (1 << logC) - 1;
+    cx<T> v[NB][R];
+#pragma unroll
+    for (int q = 0; q < NB; ++q) {
+        const int i = tid + q * NT, c = i & cm, j = i >> logC;
+        if (i < total) {
+#pragma unroll
+            for (int t = 0; t < R; ++t) v[q][t] = A[((j + t * nb) << logC) + c];
+        }
+    }
+    ctx.sync();
+#pragma unroll
+    for (int q = 0; q < NB; ++q) {
+        const int i = tid + q * NT, c = i & cm, j = i >> logC, k = j % Ns;
+        if (i < total) {
+            if (Ns > 1) {
+#pragma unroll
+                for (int t = 1; t < R; ++t) v[q][t] = v[q][t] * tw[k * t * step];
+            }
+            MrDft<T, R>::run(v[q]);
+            const int j0 = (j - k) * R + k;
+#pragma unroll
+            for (int t = 0; t < R; ++t) A[((j0 + t * Ns) << logC) + c] = v[q][t];
+        }
+    }
+}
+template <typename T, class Ctx>
+OA_HD cx<T>* mr_transform_ip(Ctx& ctx, cx<T>* buf, int N, const MrFactors& f, int logC, const cx<T>* tw, int tid, int NT) {
+    int Ns = 1;
+    for (int s = 0; s < f.n; ++s) {
+        switch (f.r[s]) {
+            case 2: mr_stage_ip<T, 2>(ctx, buf, N, Ns, logC, tw, tid, NT); break;
+            case 3: mr_stage_ip<T, 3>(ctx, buf, N, Ns, logC, tw, tid, NT); break;
+            case 4: mr_stage_ip<T, 4>(ctx, buf, N, Ns, logC, tw, tid, NT); break;
+            default: mr_stage_ip<T, 5>(ctx, buf, N, Ns, logC, tw, tid, NT); break;
+        }
+        ctx.sync();
+        Ns *= f.r[s];
+    }
+    return buf;
+}
+// the two-buffer form (IP = false) or the in-place one
+template <typename T, bool IP, class Ctx>
+OA_HD cx<T>* mr_run(Ctx& ctx, cx<T>* buf0, cx<T>* buf1, int N, const MrFactors& f, int logC, const cx<T>* tw, int tid, int NT) {
+    if constexpr (IP) return mr_transform_ip<T>(ctx, buf0, N, f, logC, tw, tid, NT);
+    else return mr_transform<T>(ctx, buf0, buf1, N, f, logC, tw, tid, NT);
+}
+
+// LDS of the two-buffer forms: one row of N complex values per workgroup, a [N][C] column tile per workgroup
+template <typename T> inline size_t mr_row_lds(int N) { return 2 * ((size_t)N + 1) * sizeof(cx<T>); }
+template <typename T> inline size_t mr_col_lds(int N, int logC) { return 2 * ((size_t)N << logC) * sizeof(cx<T>); }
+// columns per tile: the largest power of two (<= 16) whose two [N][C] buffers fit 96 KB
+template <typename T> inline int mr_col_logc(int N) {
+    int lc = 0;
+    while (lc < 4 && mr_col_lds<T>(N, lc + 1) <= 96 * 1024) ++lc;
+    return lc;
+}
+
 enum MrMode { MR_C2C_F = 0, MR_C2C_I = 1, MR_R2C = 2, MR_C2R = 3 };
 
 template <typename T>
@@ -139,11 +213,11 @@ struct MrRowArgs {
     long out_zoff;
 };
 
-// one row per workgroup
-template <typename T, class Ctx>
+// one row per workgroup; IP: the in-place stages (one buffer of N values)
+template <typename T, bool IP = false, class Ctx>
 OA_HD void mr_row_body(Ctx& ctx, const MrRowArgs<T>& a) {
     cx<T>* b0 = reinterpret_cast<cx<T>*>(ctx.smem());
-    cx<T>* b1 = b0 + a.N + 1;
+    cx<T>* b1 = IP ? b0 : b0 + a.N + 1;
     const int tid = ctx.tid(), NT = ctx.nthreads(), N = a.N;
     const long row = ctx.bid_x();
     if (a.mode == MR_C2C_F || a.mode == MR_C2C_I) {
@@ -152,7 +226,7 @@ OA_HD void mr_row_body(Ctx& ctx, const MrRowArgs<T>& a) {
         cx<T>* dst = reinterpret_cast<cx<T>*>(a.out) + row * a.out_pitch;
         for (int n = tid; n < N; n += NT) b0[n] = inv ? swp(src[n]) : src[n];
         ctx.sync();
-        const cx<T>* r = mr_transform<T>(ctx, b0, b1, N, a.f, 0, a.tw, tid, NT);
+        const cx<T>* r = mr_run<T, IP>(ctx, b0, b1, N, a.f, 0, a.tw, tid, NT);
         for (int n = tid; n < N; n += NT) { const cx<T> v = r[n] * a.scale; dst[n] = inv ? swp(v) : v; }
     } else if (a.mode == MR_R2C) {
         // packed: z[n] = x[2 n] + i x[2 n + 1]; X[k] = E[k] + W_2N^k O[k], E = (Z[k] + conj Z[N - k]) / 2, O = (Z[k] - conj Z[N - k]) / 2i
@@ -160,7 +234,7 @@ OA_HD void mr_row_body(Ctx& ctx, const MrRowArgs<T>& a) {
         cx<T>* dst = reinterpret_cast<cx<T>*>(a.out) + row * a.out_pitch;
         for (int n = tid; n < N; n += NT) b0[n] = src[n];
         ctx.sync();
-        const cx<T>* r = mr_transform<T>(ctx, b0, b1, N, a.f, 0, a.tw, tid, NT);
+        const cx<T>* r = mr_run<T, IP>(ctx, b0, b1, N, a.f, 0, a.tw, tid, NT);
         for (int k = tid; k <= N; k += NT) {
             const cx<T> Zk = r[k == N ? 0 : k], Zm = conj(r[k == 0 ? 0 : N - k]);
             const cx<T> E = (Zk + Zm) * (T)0.5, O = mul_mi(Zk - Zm) * (T)0.5;
@@ -192,7 +266,7 @@ OA_HD void mr_row_body(Ctx& ctx, const MrRowArgs<T>& a) {
             b0[k] = swp(z);
         }
         ctx.sync();
-        const cx<T>* r = mr_transform<T>(ctx, b0, b1, N, a.f, 0, a.tw, tid, NT);
+        const cx<T>* r = mr_run<T, IP>(ctx, b0, b1, N, a.f, 0, a.tw, tid, NT);
         for (int n = tid; n < N; n += NT) dst[n] = swp(r[n]) * a.scale;
     }
 }
@@ -211,12 +285,12 @@ struct MrColArgs {
     int dpow;
 };
 
-// a tile of C adjacent columns per workgroup, transformed along y
-template <typename T, class Ctx>
+// a tile of C adjacent columns per workgroup, transformed along y; IP: the in-place stages (one [N][C] buffer)
+template <typename T, bool IP = false, class Ctx>
 OA_HD void mr_col_body(Ctx& ctx, const MrColArgs<T>& a) {
     cx<T>* b0 = reinterpret_cast<cx<T>*>(ctx.smem());
     const int C = 1 << a.logC, N = a.N;
-    cx<T>* b1 = b0 + (long)N * C;
+    cx<T>* b1 = IP ? b0 : b0 + (long)N * C;
     const int tid = ctx.tid(), NT = ctx.nthreads();
     const int c0 = ctx.bid_x() << a.logC;
     int ncols = a.width - c0;
@@ -235,7 +309,7 @@ OA_HD void mr_col_body(Ctx& ctx, const MrColArgs<T>& a) {
         b0[i] = inv ? swp(v) : v;
     }
     ctx.sync();
-    const cx<T>* r = mr_transform<T>(ctx, b0, b1, N, a.f, a.logC, a.tw, tid, NT);
+    const cx<T>* r = mr_run<T, IP>(ctx, b0, b1, N, a.f, a.logC, a.tw, tid, NT);
     for (int i = tid; i < N * C; i += NT) {
         const int c = i & (C - 1), n = i >> a.logC;
         if (c < ncols) { const cx<T> v = r[i] * a.scale; a.out[(long)n * a.out_pitch + c0 + c] = inv ? swp(v) : v; }

@@ -18,6 +18,18 @@ __global__ __launch_bounds__(256) void mr_col_kernel(MrColArgs<T> a) {
     GpuCtx c{oa_dyn_smem};
     mr_col_body<T>(c, a);
 }
+// the in-place forms (fft_mixed.hpp mr_transform_ip): only for transforms whose two LDS buffers exceed LDS_MAX
+constexpr int MR_IP_NT = 1024;
+template <typename T>
+__global__ __launch_bounds__(MR_IP_NT) void mr_row_ip_kernel(MrRowArgs<T> a) {
+    GpuCtx c{oa_dyn_smem};
+    mr_row_body<T, true>(c, a);
+}
+template <typename T>
+__global__ __launch_bounds__(MR_IP_NT) void mr_col_ip_kernel(MrColArgs<T> a) {
+    GpuCtx c{oa_dyn_smem};
+    mr_col_body<T, true>(c, a);
+}
 
 bool mixed_sides_ok(int ny, int nx) { return ny % 2 == 0 && nx % 2 == 0 && mixed_ok(ny) && mixed_ok(nx) && mixed_ok(nx / 2); }
 
@@ -54,14 +66,10 @@ static int rows(oa_plan* p, int mode, const void* in, long ipitch, void* out, lo
     a.tw = (const cx<T>*)tw; a.tw2 = (const cx<T>*)p->mr_twx; a.scale = (T)scale; a.mode = mode;
     a.dlx = dlx; a.dpow0 = dpow0; a.dcol_b = dcol_b; a.out_zoff = out_zoff;
     int rc = 0;
-    launch_go(rc, st, mr_row_kernel<T>, dim3(p->ny, nz), 256, 2 * ((size_t)N + 1) * sizeof(cx<T>), a);
+    if (mr_row_lds<T>(N) <= LDS_MAX) launch_go(rc, st, mr_row_kernel<T>, dim3(p->ny, nz), 256, mr_row_lds<T>(N), a);
+    else if (mr_ip_fits(a.f, N, 0, MR_IP_NT)) launch_go(rc, st, mr_row_ip_kernel<T>, dim3(p->ny, nz), MR_IP_NT, (size_t)N * sizeof(cx<T>), a);
+    else rc = fail("fft: transform size exceeds the LDS / workgroup budget for this dtype");
     return rc;
-}
-// columns per tile: the largest power of two whose two [N][C] buffers fit 96 KB
-template <typename T> static int col_logc(int N) {
-    int lc = 0;
-    while (lc < 4 && 2 * ((size_t)N << (lc + 1)) * sizeof(cx<T>) <= 96 * 1024) ++lc;
-    return lc;
 }
 template <typename T>
 static int cols(oa_plan* p, const void* in, long ipitch, void* out, long opitch, int width, bool inverse, double scale, hipStream_t st,
@@ -69,10 +77,13 @@ static int cols(oa_plan* p, const void* in, long ipitch, void* out, long opitch,
     MrColArgs<T> a{};
     a.dly = dly; a.dpow = dpow;
     a.in = (const cx<T>*)in; a.out = (cx<T>*)out; a.in_pitch = ipitch; a.out_pitch = opitch; a.N = p->ny; a.width = width;
-    a.logC = col_logc<T>(p->ny); a.f = mixed_factor(p->ny); a.tw = (const cx<T>*)p->mr_twy; a.scale = (T)scale; a.inverse = inverse ? 1 : 0;
+    a.logC = mr_col_logc<T>(p->ny); a.f = mixed_factor(p->ny); a.tw = (const cx<T>*)p->mr_twy; a.scale = (T)scale; a.inverse = inverse ? 1 : 0;
     const int C = 1 << a.logC;
     int rc = 0;
-    launch_go(rc, st, mr_col_kernel<T>, dim3((width + C - 1) / C), 256, 2 * ((size_t)p->ny << a.logC) * sizeof(cx<T>), a);
+    if (mr_col_lds<T>(p->ny, a.logC) <= LDS_MAX) launch_go(rc, st, mr_col_kernel<T>, dim3((width + C - 1) / C), 256, mr_col_lds<T>(p->ny, a.logC), a);
+    else if (a.logC == 0 && mr_ip_fits(a.f, p->ny, 0, MR_IP_NT))
+        launch_go(rc, st, mr_col_ip_kernel<T>, dim3(width), MR_IP_NT, (size_t)p->ny * sizeof(cx<T>), a);
+    else rc = fail("fft: transform size exceeds the LDS / workgroup budget for this dtype");
     return rc;
 }
 

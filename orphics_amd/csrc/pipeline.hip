@@ -277,6 +277,11 @@ int oa_plan_set_filters(oa_plan* p, const void* FG, const void* FH, const void* 
     OA_REQUIRE(p->pow2 || p->mixed, "oa_plan_set_filters: map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no "
                "one-call path (use the modular oa_qe_legs / oa_mul_real / oa_qe_div calls)");
     OA_REQUIRE(p->have_laxes, "oa_plan_set_filters: call oa_plan_set_laxes first");
+    if (p->pow2) {                             // a band wider than the plane would run the column / row loops past the hc planes
+        const int hw = p->nx / 2 + 1;
+        OA_REQUIRE(leg_cols <= hw && kappa_cols <= hw, "oa_plan_set_filters: leg / kappa columns beyond the hc plane (> nx / 2 + 1)");
+        OA_REQUIRE(2L * leg_rows - 1 <= p->ny && 2L * kappa_rows - 1 <= p->ny, "oa_plan_set_filters: leg / kappa rows beyond the plane (2 rows - 1 > ny)");
+    }
     Pipeline* q = pipe_of(p);
     q->FG = FG; q->FH = FH; q->Fn = Fnorm;
     ++q->bind_gen;                             // the tile-major copy of Fnorm is repacked by the next call that uses it
@@ -911,10 +916,11 @@ static int mc_batch_tail(oa_plan* p, Pipeline* q, int B, int64_t* n, double* S, 
 
 /* ---- BAND GRID: the one-call TT entries on map sides 2^a 3^b 5^c (include/orphics_amd.h) ---------------------------------------
  * Legs confined to columns < wl and rows |ky| < rl, kappa to columns < wk and rows |ky| < rk: on any (My, Mx) grid with
- * My >= max(2 rl + rk, 2 rk), Mx >= 2 wl + wk the estimator returns the same kappa modes as on the map's own (ny, nx) grid (same
- * ell lattice; a mode of signed index ky at row ky mod My), times (ny nx) / (My Mx): each inverse transform carries its own grid's
- * 1 / Npix and the forward transform sums over its own grid.  That factor is folded into the inner copy of Fnorm.  With My, Mx
- * powers of two the inner computation IS the fused pipeline of a power-of-two plan fed with Fourier-space legs; only the input
+ * My >= max(2 rl + rk, 2 rk), Mx >= max(2 wl + wk, 2 wk) the estimator returns the same kappa modes as on the map's own (ny, nx) grid
+ * (same ell lattice; a mode of signed index ky at row ky mod My), times (ny nx) / (My Mx): each inverse transform carries its own grid's
+ * 1 / Npix and the forward transform sums over its own grid.  That factor is folded into the inner copy of Fnorm.  Mx >= 2 wk keeps
+ * kappa's wk columns inside the inner plane's Mx / 2 + 1 (its Fnorm, bin ids and kappa_hat are stored there, as on a power-of-two
+ * plan).  With My, Mx powers of two the inner computation IS the fused pipeline of a power-of-two plan fed with Fourier-space legs; only the input
  * transform (band_map_r2c), the GRF draw and the kappa scatter see the map's grid. */
 constexpr int BAND_MIN = 128;                  // smallest inner side (the fused estimator kernels are exercised from 128 points up)
 static int band_side(int mreq, long need, int side, const char* axis, int* out) {
@@ -939,7 +945,7 @@ static int band_grid_rule(const oa_plan* p, int mrow, int mcol, int wl, int wk, 
     if (wl <= 0 || wk <= 0 || rl <= 0 || rk <= 0)
         return fail("oa_plan_set_filters: sides that are not powers of two need band-limited filters (leg / kappa columns and rows > 0; "
                     "0 = all has no band grid)");
-    if (int rc = band_side(mrow, 2L * wl + wk, p->nx, "x", mx)) return rc;
+    if (int rc = band_side(mrow, std::max(2L * wl + wk, 2L * wk), p->nx, "x", mx)) return rc;
     return band_side(mcol, std::max(2L * rl + rk, 2L * rk), p->ny, "y", my);
 }
 static size_t band_real_bytes(const oa_plan* b) { return (size_t)b->ny * b->kp * (b->dtype == OA_F32 ? 4 : 8); }

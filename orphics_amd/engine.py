@@ -168,8 +168,8 @@ def band_grid(ny, nx, leg_cols, kappa_cols, leg_rows, kappa_rows, mrow=-1, mcol=
     """(My, Mx) of the BAND GRID the one-call TT entries run on for map sides 2^a 3^b 5^c that are not powers of two
     (include/orphics_amd.h, oa_plan_band_grid), or None where ``oa_plan_set_filters`` refuses: the C rule, host-side, so that a
     caller picks the modular chain without a failing call.  Mx from ``mrow``, My from the column-grid policy ``mcol``: -1 = the
-    smallest power of two >= the alias-free bound (max(2 leg_rows + kappa_rows, 2 kappa_rows) rows, 2 leg_cols + kappa_cols
-    columns) and >= 128; a power of two must reach the bound; 0 (the map's own grid), unbounded filters (0) and a grid not smaller
+    smallest power of two >= the alias-free bound (max(2 leg_rows + kappa_rows, 2 kappa_rows) rows, max(2 leg_cols + kappa_cols,
+    2 kappa_cols) columns: kappa's columns must also fit the inner plane's Mx/2 + 1) and >= 128; a power of two must reach the bound; 0 (the map's own grid), unbounded filters (0) and a grid not smaller
     than the map side have no band grid."""
     if mrow == 0 or mcol == 0 or min(leg_cols, kappa_cols, leg_rows, kappa_rows) <= 0:
         return None
@@ -182,7 +182,7 @@ def band_grid(ny, nx, leg_cols, kappa_cols, leg_rows, kappa_rows, mrow=-1, mcol=
         elif m & (m - 1) or m < need:
             return None
         return m if m < n else None
-    mx = side(int(mrow), 2 * leg_cols + kappa_cols, int(nx))
+    mx = side(int(mrow), max(2 * leg_cols + kappa_cols, 2 * kappa_cols), int(nx))
     my = side(int(mcol), max(2 * leg_rows + kappa_rows, 2 * kappa_rows), int(ny))
     return None if mx is None or my is None else (my, mx)
 

@@ -390,9 +390,16 @@ static int do_lens_derivs(int ny, int nx, const cx<T>* k0, const T* lxd, const T
     return 0;
 }
 // ---- mixed-radix passes (fft_mixed.hpp): sides 2^a 3^b 5^c.  what = 0: r2c (real (ny, nx) -> hc (ny, nx/2 + 1), contiguous),
-// 1: c2r (the inverse, unnormalised), 2 / 3: c2c forward / inverse on a full (ny, nx) complex plane
+// 1: c2r (the inverse, unnormalised), 2 / 3: c2c forward / inverse on a full (ny, nx) complex plane.  ip = 0: the library's launches
+// (mixed.hip: 256 threads, mr_col_logc columns per tile); ip = 1: the in-place bodies (mr_transform_ip) forced on, with the fewest
+// threads (a multiple of 64) for which mr_ip_fits holds, so that threads carry several butterflies per stage
+static int ip_threads(const MrFactors& f, int N, int logC) {
+    int nt = 64;
+    while (nt < 1024 && !mr_ip_fits(f, N, logC, nt)) nt += 64;
+    return mr_ip_fits(f, N, logC, nt) ? nt : 0;
+}
 template <typename T>
-static int do_mixed(int ny, int nx, int what, const void* in, void* out) {
+static int do_mixed(int ny, int nx, int what, const void* in, void* out, bool ip = false) {
     if (!mixed_ok(ny) || !mixed_ok(nx) || !mixed_ok(nx / 2) || (nx & 1)) return 1;
     auto tab = [](int N, int extra) {
         std::vector<cx<T>> t((size_t)N + extra);
@@ -403,16 +410,24 @@ static int do_mixed(int ny, int nx, int what, const void* in, void* out) {
     const auto twx = tab(nx, 1), twxh = tab(nx / 2, 0), twy = tab(ny, 0);
     const long kp = nx / 2 + 1;
     EmuLauncher q;
-    auto rows = [&](int mode, const void* i, long ip, void* o, long op, int N, const cx<T>* tw) {
+    int rc = 0;
+    auto rows = [&](int mode, const void* i, long ipitch, void* o, long op, int N, const cx<T>* tw) {
         MrRowArgs<T> a{};
-        a.in = i; a.out = o; a.in_pitch = ip; a.out_pitch = op; a.N = N; a.f = mixed_factor(N); a.tw = tw; a.tw2 = twx.data(); a.scale = (T)1; a.mode = mode;
-        q.run(ny, 1, 64, 2 * ((size_t)N + 1) * sizeof(cx<T>), [&](EmuCtx& c) { mr_row_body<T>(c, a); });
+        a.in = i; a.out = o; a.in_pitch = ipitch; a.out_pitch = op; a.N = N; a.f = mixed_factor(N); a.tw = tw; a.tw2 = twx.data(); a.scale = (T)1; a.mode = mode;
+        if (!ip) { q.run(ny, 1, 256, mr_row_lds<T>(N), [&](EmuCtx& c) { mr_row_body<T>(c, a); }); return; }
+        const int nt = ip_threads(a.f, N, 0);
+        if (!nt) { rc = 2; return; }
+        q.run(ny, 1, nt, (size_t)N * sizeof(cx<T>), [&](EmuCtx& c) { mr_row_body<T, true>(c, a); });
     };
-    auto cols = [&](const cx<T>* i, long ip, cx<T>* o, long op, int width, bool inv) {
+    auto cols = [&](const cx<T>* i, long ipitch, cx<T>* o, long op, int width, bool inv) {
         MrColArgs<T> a{};
-        a.in = i; a.out = o; a.in_pitch = ip; a.out_pitch = op; a.N = ny; a.width = width; a.logC = 2; a.f = mixed_factor(ny); a.tw = twy.data(); a.scale = (T)1;
-        a.inverse = inv ? 1 : 0;
-        q.run((width + 3) / 4, 1, 64, 2 * ((size_t)ny << 2) * sizeof(cx<T>), [&](EmuCtx& c) { mr_col_body<T>(c, a); });
+        a.in = i; a.out = o; a.in_pitch = ipitch; a.out_pitch = op; a.N = ny; a.width = width; a.logC = mr_col_logc<T>(ny); a.f = mixed_factor(ny); a.tw = twy.data();
+        a.scale = (T)1; a.inverse = inv ? 1 : 0;
+        const int C = 1 << a.logC;
+        if (!ip) { q.run((width + C - 1) / C, 1, 256, mr_col_lds<T>(ny, a.logC), [&](EmuCtx& c) { mr_col_body<T>(c, a); }); return; }
+        const int nt = ip_threads(a.f, ny, a.logC);
+        if (!nt) { rc = 2; return; }
+        q.run((width + C - 1) / C, 1, nt, ((size_t)ny << a.logC) * sizeof(cx<T>), [&](EmuCtx& c) { mr_col_body<T, true>(c, a); });
     };
     if (what == 0) { rows(MR_R2C, in, nx, out, kp, nx / 2, twxh.data()); cols((const cx<T>*)out, kp, (cx<T>*)out, kp, (int)kp, false); }
     else if (what == 1) {
@@ -420,12 +435,14 @@ static int do_mixed(int ny, int nx, int what, const void* in, void* out) {
         cols((const cx<T>*)in, kp, tmp.data(), kp, (int)kp, true);
         rows(MR_C2R, tmp.data(), kp, out, nx, nx / 2, twxh.data());
     } else { rows(what == 3 ? MR_C2C_I : MR_C2C_F, in, nx, out, nx, nx, twx.data()); cols((const cx<T>*)out, nx, (cx<T>*)out, nx, nx, what == 3); }
-    return 0;
+    return rc;
 }
 
 extern "C" {
 int emu_mixed_f64(int ny, int nx, int what, const void* in, void* out) { return do_mixed<double>(ny, nx, what, in, out); }
 int emu_mixed_f32(int ny, int nx, int what, const void* in, void* out) { return do_mixed<float>(ny, nx, what, in, out); }
+int emu_mixed_ip_f64(int ny, int nx, int what, const void* in, void* out) { return do_mixed<double>(ny, nx, what, in, out, true); }
+int emu_mixed_ip_f32(int ny, int nx, int what, const void* in, void* out) { return do_mixed<float>(ny, nx, what, in, out, true); }
 int emu_lens_derivs_f64(int ny, int nx, const void* k0, const double* lxd, const double* lyd, double* out, int nd, int separable) { return do_lens_derivs<double>(ny, nx, (const cx<double>*)k0, lxd, lyd, out, nd, separable); }
 int emu_rows_win_f64(int ny, int nx, const void* in, const double* w, void* out, long opitch, double s, int wcols) { return do_rows_win<double>(ny, nx, (const cx<double>*)in, w, (cx<double>*)out, opitch, s, wcols); }
 int emu_rows_win_f32(int ny, int nx, const void* in, const float* w, void* out, long opitch, double s, int wcols) { return do_rows_win<float>(ny, nx, (const cx<float>*)in, w, (cx<float>*)out, opitch, s, wcols); }

@@ -817,13 +817,29 @@ def test_c2r_drops_the_non_hermitian_part_of_the_self_conjugate_columns(emu):
     assert np.abs(back[:, 0] - herm0).max() < 1e-12 * np.abs(herm0).max()      # kx = 0 holds ITS OWN Hermitian part only
 
 
-@pytest.mark.parametrize("ny,nx", [(12, 20), (30, 50), (60, 36), (40, 600), (150, 24), (16, 1200), (90, 120)])
+# (54, 250), (486, 162): 2 3^3 / 2 5^3 and 2 3^5 / 2 3^4 -- a single radix-2 stage next to 3- or 5-only stages, nx/2 odd (125, 81)
+@pytest.mark.parametrize("ny,nx", [(12, 20), (30, 50), (60, 36), (40, 600), (150, 24), (16, 1200), (90, 120), (54, 250), (486, 162),
+                                   (250, 54)])
 @pytest.mark.parametrize("prec", ["f64", "f32"])
 def test_mixed_radix_passes_match_numpy(emu, ny, nx, prec):
     """fft_mixed.hpp (sides 2^a 3^b 5^c that are not powers of two -- the reference notebooks' 600 / 1200 / 2400-pixel patches): the
-    radix-2/3/4/5 Stockham stages, the packed real-row transform with its (un)tangle and the column tiles, against numpy.fft."""
+    radix-2/3/4/5 Stockham stages, the packed real-row transform with its (un)tangle and the column tiles, against numpy.fft, with the
+    library's launches (256 threads, mr_col_logc columns per tile)."""
+    _mixed_matches_numpy(emu.emu_mixed_f64 if prec == "f64" else emu.emu_mixed_f32, ny, nx, prec)
+
+
+# the IN-PLACE stages (mr_transform_ip: the library takes them where two LDS buffers do not fit, float64 sides > 5120) forced on at
+# small sides, with the fewest threads that hold every butterfly (several butterflies per thread and stage): (54, 250) / (250, 54)
+# radix 2 + 3s / 5s and tiles of 16 columns; (486, 162) five radix-3 stages; (96, 40) radix 4, 2, 3 / 4, 2, 5
+@pytest.mark.parametrize("ny,nx", [(54, 250), (250, 54), (486, 162), (96, 40)])
+@pytest.mark.parametrize("prec", ["f64", "f32"])
+def test_mixed_radix_inplace_stages_match_numpy(emu, ny, nx, prec):
+    """The in-place mixed-radix body, all four modes (R2C, C2R, C2C forward and inverse) in both precisions, against numpy.fft."""
+    _mixed_matches_numpy(emu.emu_mixed_ip_f64 if prec == "f64" else emu.emu_mixed_ip_f32, ny, nx, prec)
+
+
+def _mixed_matches_numpy(fn, ny, nx, prec):
     rdt, cdt, tol = (np.float64, np.complex128, 1e-12) if prec == "f64" else (np.float32, np.complex64, 3e-6)
-    fn = emu.emu_mixed_f64 if prec == "f64" else emu.emu_mixed_f32
     rng = np.random.default_rng(ny * 131 + nx)
     x = rng.standard_normal((ny, nx)).astype(rdt)
     k = np.zeros((ny, nx // 2 + 1), dtype=cdt)

@@ -1140,7 +1140,10 @@ def test_lens_many_hc_equals_lens_many_of_the_inverse_transforms(prec, tol, orde
         sims.lenser.lens_many_hc(unl, alpha)
 
 
-@pytest.mark.parametrize("shape", [(120, 150), (96, 160)])
+# (5400, 600): a float64 column transform of 5400 points takes the in-place stages (two [N][C] buffers would exceed the LDS).  Only
+# float64 there: float32 runs the same two-buffer kernels as at the other shapes (its 5400-point transforms pass test_mixed_sides_gpu),
+# and on this 180-degree patch the fifth-order Taylens in float32 is 5.4e-4 of max |T| from the NumPy one (measured)
+@pytest.mark.parametrize("shape", [(120, 150), (96, 160), (5400, 600)])
 def test_flat_lensing_op_on_mixed_radix_sides(shape):
     """oa_lens_maps / oa_lens_maps_hc on sides 2^a 3^b 5^c (the notebooks' patches; csrc/mixed.hip lens_derivs_t: per y-derivative
     order one inverse column transform with (i ly)^b at its load, one row launch that takes every (i lx)^a at its load): the lensed map
@@ -1154,6 +1157,8 @@ def test_flat_lensing_op_on_mixed_radix_sides(shape):
     kap = np.fft.ifft2(np.fft.fft2(rng.standard_normal(shape)) * 1.5 / (1 + (ml / 200.) ** 2)).real
     T = np.fft.ifft2(np.fft.fft2(rng.standard_normal(shape)) / (1 + (ml / 400.) ** 2)).real
     for prec, tol in (("f64", 1e-10), ("f32", 3e-5)):
+        if prec == "f32" and shape == (5400, 600):
+            continue
         L = lensing.FlatLenser(shape, g, dtype=prec)
         e = L.eng
         assert e.mixed and not e.pow2

@@ -111,3 +111,52 @@ def test_band_grid_rule_on_notebook_supports():
     wl, rl = _band(tmask)
     wk, rk = _band(kmask)
     assert 2 * rl + rk > 256 and band_grid(480, 600, wl, wk, rl, rk) is None
+
+
+def test_band_grid_rule_keeps_kappa_inside_the_inner_plane():
+    """Wherever engine.band_grid returns a grid, it is alias-free AND holds kappa's columns: Mx >= 2 wl + wk, Mx >= 2 wk (so
+    Mx // 2 + 1 >= wk: the inner copies of Fnorm / the bin ids and the inner kappa_hat fit the inner hc plane), My >= max(2 rl + rk,
+    2 rk), both powers of two below the side.  Swept over band widths and explicit grids on the notebook sides."""
+    from orphics_amd.engine import BAND_MIN, band_grid
+    widths = (1, 15, 16, 17, 20, 56, 84, 98, 150, 300, 700)
+    grids = (-1, 128, 256, 512, 1024, 2048)
+    n = 0
+    for ny, nx in ((1200, 1200), (2400, 2400), (600, 750), (750, 600)):
+        for wl in widths:
+            for wk in widths:
+                for mrow in grids:
+                    for rl, rk, mcol in ((wl, wk, -1), (wk, wl, -1), (wl, wk, 512), (17, 300, -1)):
+                        got = band_grid(ny, nx, wl, wk, rl, rk, mrow, mcol)
+                        if got is None:
+                            continue
+                        my, mx = got
+                        n += 1
+                        assert mx >= 2 * wl + wk and mx >= 2 * wk and mx // 2 + 1 >= wk, (ny, nx, wl, wk, mrow, got)
+                        assert my >= 2 * rl + rk and my >= 2 * rk, (ny, nx, rl, rk, mcol, got)
+                        for m, side in ((my, ny), (mx, nx)):
+                            assert m >= BAND_MIN and m & (m - 1) == 0 and m < side
+                        if mrow > 0:
+                            assert mx == mrow
+                        if mcol > 0:
+                            assert my == mcol
+    assert n > 500
+    # the narrow-leg / wide-kappa filters of the 1200^2 patch at 0.5' with T 100-700, kappa 20-3000 (wl = 20, wk = 84): 2 wl + wk = 124
+    # alone would give Mx = 128, whose 65 hc columns cannot hold 84 kappa columns
+    assert band_grid(1200, 1200, 20, 84, 20, 84) == (256, 256)
+    assert band_grid(1200, 1200, 20, 84, 20, 84, mrow=128) is None
+
+
+@pytest.mark.parametrize("shape,res,tl,kl,bands,grid", [((1200, 1200), 0.5, (100, 700), (20, 3000), (20, 84), (256, 256)),
+                                                       ((2400, 2400), 0.5, (300, 1900), (20, 5400), (106, 300), (1024, 1024))])
+def test_band_grid_rule_on_wide_kappa_bands(shape, res, tl, kl, bands, grid):
+    """The two geometries whose kappa band is wider than the hc plane of the smallest alias-free grid (the power of two >= 2 wl + wk
+    has fewer than wk columns): the grid the rule picks holds kappa's columns."""
+    from orphics_amd.engine import band_grid
+    g, cl, beam, noise, tmask, kmask = _notebook(shape, res, tl=tl, kl=kl)
+    wl, rl = _band(tmask)
+    wk, rk = _band(kmask)
+    assert (wl, wk) == bands
+    alias_only = max(128, 1 << (2 * wl + wk - 1).bit_length())
+    assert alias_only // 2 + 1 < wk
+    my, mx = band_grid(shape[0], shape[1], wl, wk, rl, rk)
+    assert (my, mx) == grid and mx // 2 + 1 >= wk
