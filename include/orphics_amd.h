@@ -178,7 +178,16 @@ int oa_plan_set_filters(oa_plan* p, const void* FG, const void* FH, const void* 
  * power of two, or none if that is >= ny or the filters have no row band) unless mrow == 0, which selects 0 (the map's
  * own rows, as for the row grid).  oa_plan_set_col_grid overrides: -1 auto, 0 off, > 0 explicit (checked against the
  * bound); oa_plan_col_grid returns the grid resolved for the TT filters (0 = ny).  oa_qe_pol follows the same policy
- * with the row bands of each call (mrow == 0 switches it off there too). */
+ * with the row bands of each call (mrow == 0 switches it off there too).
+ * FROM-MAP GRID.  The bound does not ask for a power of two.  Where the from-map entries (oa_qe_tt from a real map, oa_qe_tt_moments,
+ * oa_qe_tt_moments2, oa_qe_tt_stage) run the R = 4 R-SPLIT path (oa_plan_rsplit) and three quarters of the column grid still satisfy
+ * the bound, their coarse side -- the inverse column transforms of the legs, the row stage, the forward column transforms of the
+ * products -- runs on 3 mcol / 4 rows: 8192-row maps on 1536 = 3 x 512 rows (the reference's TT band limits need 2 x 380 + 664 = 1424),
+ * 4096-row maps on 768.  The row pass and the forward side of the column stage are unchanged (mcol-point transforms of the R planes);
+ * only the kept bins are re-indexed.  A plan then carries two grids: `mcol` for every other entry (Fourier-space legs, oa_qe_pol,
+ * oa_qe_mv, oa_qe_tt_splits, oa_mc_run*), unchanged bit for bit, and the from-map grid, which is what oa_plan_col_grid, oa_plan_rsplit
+ * and oa_plan_div_fused report.  Chosen with mcol = -1; an explicit power of two keeps every entry on that grid; an explicit 3 x 2^k
+ * asks for it (the other entries then run on 4/3 of it) and is refused below the bound or where the geometry has no such path. */
 int oa_plan_set_col_grid(oa_plan* p, int mcol);
 int oa_plan_col_grid(const oa_plan* p);
 /* BAND GRID: the one-call TT entries on map sides 2^a 3^b 5^c that are not powers of two (oa_qe_tt from a map or from kX [, kY],
@@ -204,7 +213,7 @@ int oa_plan_band_grid(const oa_plan* p, int* my, int* mx);
  * Same arithmetic up to the order of the column butterflies; results agree with the multi-pass path to rounding. */
 int oa_plan_rsplit(const oa_plan* p);
 /* 1 when this plan's one-call moment entries (oa_qe_tt_moments, oa_qe_tt_moments2, oa_mc_run) bin |kappa_hat|^2 and update
- * n, S, C in the tail of the single-pass divergence launch (coarse grids of 1024 / 2048 / 4096 rows, bins bound) instead of two more
+ * n, S, C in the tail of the single-pass divergence launch (coarse grids of 1024 / 2048 / 4096 rows and from-map grids of 768 / 1536, bins bound) instead of two more
  * launches over the kappa plane; 0: the separate histogram launches.  Same per-mode arithmetic either way; the order of the
  * float64 sums differs (bandpowers agree to ~1e-15).  When fused, these entries do not write the plan-owned kappa plane
  * (oa_plan_kappa) unless the mean-field stack of oa_mc_run needs it; oa_qe_tt always does.  oa_plan_set_option(p, OA_OPT_DIV_BIN, 0)

@@ -91,6 +91,7 @@ struct oa_plan {
     void* rq8c[5];                           // per-thread constants of the fused row stage's grids of 1024, 1536, 2048, 4096, 8192 points (fft_rowqe8.hpp: RQ8_NGRIDS)
     void* tw_y_small[16];                    // COLUMN GRID: cx<T>[my] = W_my^k for my = 2^i (made on first use, kept: estimators
                                              // with different row bands may alternate on one plan)
+    void* tw_y_m3[16];                       // ... and for the 3 x 2^i grids of the from-map R-split path (slot i)
 };
 
 namespace oa {

@@ -74,6 +74,18 @@ __global__ __launch_bounds__((sizeof(T) == 8 ? 512 : 1024), (sizeof(T) == 8 ? 2 
     col_fband_body<T, SEQF, LR, LOGC>(c, a);
 }
 
+// ... with the coarse side on 3 My / 4 rows (col_fband3_body: 1536 of 2048, 768 of 1024)
+template <typename T, class SEQF, int LOGC>
+__global__ __launch_bounds__((sizeof(T) == 8 ? 512 : 1024)) void col_fband3_pack_kernel(ColFBandArgs<T> a, cx<T>* out) {
+    GpuCtx c{nullptr};
+    col_fband3_pack_body<T, SEQF, LOGC>(c, a, out);
+}
+template <typename T, class SEQF, int LOGC>
+__global__ __launch_bounds__((sizeof(T) == 8 ? 512 : 1024), (sizeof(T) == 8 ? 2 : 4)) void col_fband3_kernel(ColFBandArgs<T> a) {
+    GpuCtx c{oa_dyn_smem};
+    col_fband3_body<T, SEQF, LOGC>(c, a);
+}
+
 // 16384-point rows: two waves per row (even / odd packed samples), one workgroup of 128 threads per row in flight
 __global__ __launch_bounds__(128, 1) void row_r2c_w64x2_kernel(RowW64Args a) {
     GpuCtx c{oa_dyn_smem};
@@ -173,6 +185,18 @@ template <typename T, class SEQ, int LOGC>
 __global__ __launch_bounds__((sizeof(T) == 8 ? 512 : 1024), (sizeof(T) == 8 ? 2 : 4)) void col_div_sp_bin_kernel(ColDivArgs<T> a, DivBinFuse f) {
     GpuCtx c{oa_dyn_smem};
     col_div_body<T, SEQ, GpuCtx, LOGC, DivBinTail<T>>(c, a, DivBinTail<T>{f});
+}
+
+// the same two on column grids of 6 x 2^LOGQ rows (col_div3_body: 1536, 768): 96 KB tiles, six thread groups of Q C / 16 threads
+template <typename T, int LOGQ, int LOGC>
+__global__ __launch_bounds__((sizeof(T) == 8 ? 384 : 768), (sizeof(T) == 8 ? 2 : 3)) void col_div3_sp_kernel(ColDivArgs<T> a) {
+    GpuCtx c{oa_dyn_smem};
+    col_div3_body<T, LOGQ, LOGC>(c, a);
+}
+template <typename T, int LOGQ, int LOGC>
+__global__ __launch_bounds__((sizeof(T) == 8 ? 384 : 768), (sizeof(T) == 8 ? 2 : 3)) void col_div3_sp_bin_kernel(ColDivArgs<T> a, DivBinFuse f) {
+    GpuCtx c{oa_dyn_smem};
+    col_div3_body<T, LOGQ, LOGC, GpuCtx, DivBinTail<T>>(c, a, DivBinTail<T>{f});
 }
 
 template <typename T, class SEQ>
@@ -385,6 +409,25 @@ struct HipLauncher {
         });
         if (!ok) rc = fail("fft: unsupported R-split column stage");
     }
+    // 3 x 2^k coarse grids (R = 4): logMy = 11 -> 1536 rows, 10 -> 768 rows
+    template <typename T>
+    void col_fband3(int gx, int gz, size_t smem, int logMy, const ColFBandArgs<T>& a) {
+        if (rc) return;
+        constexpr int nt = sizeof(T) == 4 ? 1024 : 512, lc11 = sizeof(T) == 4 ? 3 : 2;
+        if (logMy == 11) go(col_fband3_kernel<T, Seq<16, 16, 8>, lc11>, dim3(gx, 4, gz), nt, smem, a);
+        else if (logMy == 10) go(col_fband3_kernel<T, Seq<16, 8, 8>, lc11 + 1>, dim3(gx, 4, gz), nt, smem, a);
+        else rc = fail("fft: unsupported 3 x 2^k R-split column stage");
+    }
+    template <typename T>
+    void col_fband3_pack(int gx, int logMy, const ColFBandArgs<T>& a, cx<T>* out) {
+        if (rc) return;
+        constexpr int nt = sizeof(T) == 4 ? 1024 : 512, lc11 = sizeof(T) == 4 ? 3 : 2;
+        if (logMy == 11) hipLaunchKernelGGL((col_fband3_pack_kernel<T, Seq<16, 16, 8>, lc11>), dim3(gx, 4), dim3(nt), 0, st, a, out);
+        else if (logMy == 10) hipLaunchKernelGGL((col_fband3_pack_kernel<T, Seq<16, 8, 8>, lc11 + 1>), dim3(gx, 4), dim3(nt), 0, st, a, out);
+        else { rc = fail("fft: unsupported 3 x 2^k R-split column stage"); return; }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = fail(std::string("fft launch: ") + hipGetErrorString(e));
+    }
     template <typename T>
     void row_qe(int grid, int nt, size_t smem, const RowQeArgs<T>& a) {
         // rows of 16384 / 32768 points: put the short radix FIRST so that the reversed (inverse) sequence starts with
@@ -514,6 +557,22 @@ struct HipLauncher {
         if (logL == 10) { go(col_div_sp_kernel<T, Seq<16, 16, 4>, lc10 - 1>, dim3(gx, 1, gz), nt, smem, a); return true; }
         return false;
     }
+    // single pass on 1536 / 768 rows (col_div3_body); the tail's histogram rows live in the column tile, as above
+    template <typename T>
+    void col_div3(int gx, size_t smem, int rows, const ColDivArgs<T>& a, int gz = 1) {
+        if (rc) return;
+        constexpr int lc = sizeof(T) == 4 ? 3 : 2;
+        if (rows != 1536 && rows != 768) { rc = fail("fft: unsupported 3 x 2^k divergence grid"); return; }
+        const int nt = a.NT;
+        if (fuse && !a.accumulate && (long)gx * gz * fuse->nids <= fuse->part_cap &&
+            (size_t)(nt / 64) * fuse->nids * sizeof(double) <= ((size_t)rows << a.logC) * sizeof(cx<T>)) {
+            if (rows == 1536) go_fused(col_div3_sp_bin_kernel<T, 8, lc>, gx, gz, nt, smem, a);
+            else go_fused(col_div3_sp_bin_kernel<T, 7, lc + 1>, gx, gz, nt, smem, a);
+            return;
+        }
+        if (rows == 1536) go(col_div3_sp_kernel<T, 8, lc>, dim3(gx, 1, gz), nt, smem, a);
+        else go(col_div3_sp_kernel<T, 7, lc + 1>, dim3(gx, 1, gz), nt, smem, a);
+    }
     template <typename T>
     void col_deriv(int gx, int gy, int nt, size_t smem, const ColDerivArgs<T>& a, int nz) {
         const bool ok = dispatch_seq(a.logL, [&](auto seq) {
@@ -553,13 +612,21 @@ static Fft2dPlan<T> coarse_view(const oa_plan* p, int my) {
     Fft2dPlan<T> f = view<T>(p);
     if (my > 0 && my < p->ny && is_pow2(my) && p->tw_y_small[ilog2(my)]) {
         f.ny = my; f.logNy = ilog2(my); f.tw_y = (const cx<T>*)p->tw_y_small[ilog2(my)]; f.ny_full = p->ny;
+    } else if (my > 0 && my < p->ny && is_m3(my) && p->tw_y_m3[ilog2(my / 3)]) {
+        // 3 x 2^k rows (from-map R-split path): only the members written for it read this view (legs_fband3, rows_qe, cols_div3)
+        f.ny = my; f.logNy = -1; f.tw_y = (const cx<T>*)p->tw_y_m3[ilog2(my / 3)]; f.ny_full = p->ny;
     }
     return f;
 }
+// is `my` a 3 x 2^k grid whose tables exist on this plan?
+static bool m3_ready(const oa_plan* p, int my) { return my > 0 && my < p->ny && is_m3(my) && p->tw_y_m3[ilog2(my / 3)] && p->tw_y_small[ilog2(m3_pow2(my))]; }
 int plan_ensure_col_grid(oa_plan* p, int my) {
     if (my <= 0 || my >= p->ny) return 0;
+    if (is_m3(my) && my >= 96) {               // W_my and the table of the power-of-two grid whose forward side it keeps
+        if (int rc = plan_ensure_col_grid(p, m3_pow2(my))) return rc;
+    } else
     if (!is_pow2(my) || my < 32) return fail("column grid must be a power of two >= 32");
-    void*& slot = p->tw_y_small[ilog2(my)];
+    void*& slot = is_m3(my) ? p->tw_y_m3[ilog2(my / 3)] : p->tw_y_small[ilog2(my)];
     if (slot) return 0;                       // tables are kept: no allocation / synchronisation after the first use of a grid
     if (p->dtype == OA_F32) {
         auto t = make_twiddles<float>(my);
@@ -643,6 +710,13 @@ template <typename T>
 static int rsplit_lr(const oa_plan* p, int my, int width, int wout, int mrow) {
     auto f = view<T>(p);
     const int w = f.clampw(width), wo = f.clampw(wout);
+    if (is_m3(my)) {                             // 3 x 2^k coarse grid: R = 4, the 8-point row stage on R-LAYOUT planes
+        if (!m3_ready(p, my) || !Fft2dPlan<T>::has_rsplit3(p->logNy, p->logNx, my, w)) return 0;
+        if (mrow < 0) { mrow = Fft2dPlan<T>::row_grid_min(p->nx, w, wo); if (2L * w + wo > mrow) mrow = 0; }
+        const auto cv = coarse_view<T>(p, my);
+        const int M = mrow > 0 && mrow < p->nx ? mrow : p->nx;
+        return (mrow > 0 && cv.rows_qe_is_pair(w, wo, mrow) && cv.rq8_ready(M) && rq8_covers(M, w, wo)) ? 2 : 0;
+    }
     if (!(my > 0 && my < p->ny && is_pow2(my) && p->tw_y_small[ilog2(my)]) || !Fft2dPlan<T>::has_rsplit(p->logNy, p->logNx, my, w)) return 0;
     if (mrow < 0) { mrow = Fft2dPlan<T>::row_grid_min(p->nx, w, wo); if (2L * w + wo > mrow) mrow = 0; }
     const auto cv = coarse_view<T>(p, my);
@@ -679,6 +753,14 @@ static int map_legs_cols_impl(oa_plan* p, const void* map, const void* FG, const
     if (lr > 0) {
         // R-SPLIT: the row pass carries the first radix-R butterfly of the column transform; ONE column kernel to the leg planes
         const auto cv = coarse_view<T>(p, my);
+        if (is_m3(my)) {                         // coarse side on 3 x 2^k rows; the row pass and the forward side stay on ny / 4
+            const int myf = m3_pow2(my);
+            const long kplane3 = (long)myf * pw;
+            if (stages & 1) f.rows_rsplit(q, map, tA, pw, kplane3, w, myf);
+            if (stages & 4) f.legs_fband3(q, cv, (const cx<T>*)p->tw_y_small[ilog2(myf)], tA, kplane3, pw, (const T*)FG, (const T*)FH, (const T*)p->lxd,
+                                          (const T*)p->lyd, (cx<T>*)gx, (cx<T>*)gy, (cx<T>*)h, width, rband, pout > 0 ? pout : p->kp, 1, 0, 0, (const cx<T>*)fgh);
+            return q.rc;
+        }
         const long kplane = (long)my * pw;
         if (stages & 1) f.rows_rsplit(q, map, tA, pw, kplane, w, my);
         if (stages & 4) f.legs_fband(q, cv, tA, kplane, pw, (const T*)FG, (const T*)FH, (const T*)p->lxd, (const T*)p->lyd, (cx<T>*)gx, (cx<T>*)gy,
@@ -724,6 +806,12 @@ static int cols_div_impl(oa_plan* p, const void* pa, const void* pb, const void*
     q.fuse = fuse;
     cx<T>* tA = (cx<T>*)p->scratch;
     cx<T>* tB = tA + (size_t)p->ny * p->kp;
+    if (is_m3(my)) {
+        if (!m3_ready(p, my)) return fail("fft: 3 x 2^k column grid without its tables");
+        coarse_view<T>(p, my).cols_div3(q, (const cx<T>*)pa, (const cx<T>*)pb, (const T*)Fn, (const T*)p->lxd, (const T*)p->lyd, (cx<T>*)out, accumulate,
+                                        width, rband, pin);
+        return q.rc;
+    }
     coarse_view<T>(p, my).cols_div(q, (const cx<T>*)pa, (const cx<T>*)pb, (const T*)Fn, (const T*)p->lxd, (const T*)p->lyd,
                                    (cx<T>*)out, tA, tB, accumulate, width, rband, pin);
     return q.rc;
@@ -754,6 +842,9 @@ static int qe_tt_pair_impl(oa_plan* p, const void* map0, const void* map1, const
                            int my, long pl, long pk, hipStream_t st, DivBinFuse* fuse, const void* fgh) {
     auto f = view<T>(p);
     const int lr = rsplit_lr<T>(p, my, wl, wk, mrow);
+    const bool m3 = is_m3(my);
+    if (m3 && !(lr && m3_ready(p, my))) return -1;
+    if (!m3)
     if (!(my > 0 && my < p->ny && is_pow2(my) && p->tw_y_small[ilog2(my)]) || !(lr || Fft2dPlan<T>::has_fwdlegs_cg(p->logNy, my))) return -1;
     const auto cv = coarse_view<T>(p, my);
     const int wi = f.clampw(wl), wo = f.clampw(wk);
@@ -770,13 +861,20 @@ static int qe_tt_pair_impl(oa_plan* p, const void* map0, const void* map1, const
     const double s = 1.0 / ((double)p->ny * p->nx), sy = (double)p->ny / my;
     if (lr) {
         // R-SPLIT: two row passes, then ONE column launch, ONE row-stage launch and ONE divergence launch for both maps
-        const long kplane = (long)my * pl;
-        f.rows_rsplit(q, map0, tA, pl, kplane, wi, my);
-        f.rows_rsplit(q, map1, tA + ms, pl, kplane, wi, my);
+        const int myf = m3 ? m3_pow2(my) : my;                 // rows of the row pass's planes
+        const long kplane = (long)myf * pl;
+        f.rows_rsplit(q, map0, tA, pl, kplane, wi, myf);
+        f.rows_rsplit(q, map1, tA + ms, pl, kplane, wi, myf);
+        if (m3) f.legs_fband3(q, cv, (const cx<T>*)p->tw_y_small[ilog2(myf)], tA, kplane, pl, (const T*)FG, (const T*)FH, (const T*)p->lxd, (const T*)p->lyd,
+                              (cx<T>*)c0, (cx<T>*)c1, (cx<T>*)c2, wl, rl, pl, 2, ms, cms, (const cx<T>*)fgh);
+        else
         f.legs_fband(q, cv, tA, kplane, pl, (const T*)FG, (const T*)FH, (const T*)p->lxd, (const T*)p->lyd, (cx<T>*)c0, (cx<T>*)c1, (cx<T>*)c2, wl, rl,
                      pl, 2, ms, cms, (const cx<T>*)fgh);
         cv.rows_qe(q, (const cx<T>*)c0, (const cx<T>*)c1, (const cx<T>*)c2, (cx<T>*)g0, (cx<T>*)g1, (T)(s * s * sy), 0, wi, wo, mrow, pl, pk, 2, cms, gms,
                    -1, nullptr, lr);
+        if (m3) cv.cols_div3(q, (const cx<T>*)g0, (const cx<T>*)g1, (const T*)Fn, (const T*)p->lxd, (const T*)p->lyd, (cx<T>*)out0, 0, wk, rk, pk, 2, gms,
+                             (long)((cx<T>*)out1 - (cx<T>*)out0));
+        else
         cv.cols_div(q, (const cx<T>*)g0, (const cx<T>*)g1, (const T*)Fn, (const T*)p->lxd, (const T*)p->lyd, (cx<T>*)out0, tA, tB, 0, wk, rk, pk, 2,
                     gms, gms, (long)((cx<T>*)out1 - (cx<T>*)out0));
         return q.rc;
@@ -806,11 +904,20 @@ static int fband_pack_impl(oa_plan* p, const void* FG, const void* FH, void* out
     HipLauncher q{st};
     auto f = view<T>(p);
     const auto cv = coarse_view<T>(p, my);
+    if (is_m3(my)) {
+        if (!m3_ready(p, my)) return fail("fft: 3 x 2^k column grid without its tables");
+        f.legs_fband3(q, cv, (const cx<T>*)p->tw_y_small[ilog2(m3_pow2(my))], nullptr, 0, 0, (const T*)FG, (const T*)FH, (const T*)p->lxd, (const T*)p->lyd,
+                      nullptr, nullptr, nullptr, width, rband, 0, 1, 0, 0, nullptr, (cx<T>*)out);
+        return q.rc;
+    }
     f.legs_fband(q, cv, nullptr, 0, 0, (const T*)FG, (const T*)FH, (const T*)p->lxd, (const T*)p->lyd, nullptr, nullptr, nullptr, width, rband, 0, 1, 0, 0,
                  nullptr, (cx<T>*)out);
     return q.rc;
 }
 long qe_fband_table_entries(const oa_plan* p, int width, int my) {
+    if (is_m3(my))
+        return p->dtype == OA_F32 ? view<float>(p).fband3_table_entries(coarse_view<float>(p, my), width)
+                                  : view<double>(p).fband3_table_entries(coarse_view<double>(p, my), width);
     return p->dtype == OA_F32 ? view<float>(p).fband_table_entries(coarse_view<float>(p, my), width)
                               : view<double>(p).fband_table_entries(coarse_view<double>(p, my), width);
 }
@@ -900,6 +1007,7 @@ static int lens_derivs_impl(oa_plan* p, int nmaps, const void* real_in, long in_
     return q.rc;
 }
 int div_tile_logc(const oa_plan* p, int rows) {
+    if (is_m3(rows)) return p->dtype == OA_F32 ? Fft2dPlan<float>::div3_logc(rows) : Fft2dPlan<double>::div3_logc(rows);
     const int lt = p->dtype == OA_F32 ? Fft2dPlan<float>::div_lt() : Fft2dPlan<double>::div_lt();
     return lt - ilog2(rows);
 }

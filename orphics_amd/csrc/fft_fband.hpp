@@ -24,6 +24,7 @@
 // (k1 = 0) or taken from the forward transform's two-level table at the store (k1 = 1: 2048 entries would not fit next to the tile).
 #pragma once
 #include "fft_kernels.hpp"
+#include "fft_mixed.hpp"
 #ifndef FB_STAMP
 #define FB_STAMP(i)           // (tools/probes/fband_probe.hip records the cycle counter at the phase boundaries)
 #endif
@@ -47,6 +48,7 @@ struct ColFBandArgs {
     const cx<T>* tw;            // W_My^k
     int ny_full, rband;         // rband > 0: the filters vanish on rows rband <= y <= ny_full - rband (not read)
     long in_moff, out_moff;     // several maps per launch (grid z = map)
+    const cx<T>* tw3 = nullptr; // col_fband3_body: W_(3 My / 4)^k, the 3 x 2^k coarse grid's table
 };
 
 // R = 2: ColStore with the factor W_My^(k1 y_lo) taken from the forward transform's two-level LDS table (a global table read between the
@@ -219,6 +221,157 @@ OA_HD void col_fband_pack_body(Ctx& ctx, const ColFBandArgs<T>& a, cx<T>* out) {
             if (live) { const long fi = (long)yf * a.fpitch + (c0 + c); f = mk<T>(a.FG[fi], a.FH[fi]); }
             o[(KQ * u + q) * NT] = f;
         }
+    }
+}
+
+// ===========================================================================
+// The same stage with the COARSE side on 3 My / 4 rows (R = 4; include/orphics_amd.h, COLUMN GRID: any grid of
+// max(2 leg_rows + kappa_rows, 2 kappa_rows) rows is alias-free, and 1536 = 3 x 512 holds the 1424 rows that 8192^2 TT needs).
+// The forward side is col_fband_body's: My-point transform per k1, last radix 8, Ns = My / 8 = 2 Q.  The coarse spectrum per k1 has
+// Mq' = 3 Q points: k2' = k2 (k2 < 3 Q / 2), k2' = k2 - (My - Mq') (k2 >= My - 3 Q / 2).  Of a last-stage butterfly (bins j + t Ns)
+// t = 0 is kept for j < 3 Q / 2 and t = 7 for j >= Q / 2 (at k2' = j + Q); the others lie beyond any admissible leg band.  Thread
+// (m, c), m < Q, owns j = m and j = m + Q: exactly the bins k2' = m, m + Q, m + 2 Q -- the inputs of ONE radix-3 butterfly of the
+// inverse, decimation in frequency (y_lo = 3 y' + q):
+//     x[3 y' + q] = sum_(m < Q) W_Q^(-m y') { W_Mq'^(-m q) sum_t X'[m + Q t] W_3^(-t q) }
+// The braces are formed in registers behind the filters and go to LDS region (leg, q); nine Q-point transforms (three legs x three q,
+// Q C / 16 threads each; the seven other thread groups keep the barriers company on the idle regions of the tile) finish the
+// inverse, and the store puts W_(4 Mq')^(-k1 y_lo) on row 4 y_lo + k1 of the R-LAYOUT plane of 4 Mq' rows.  Against the 4 Q-point
+// inverse: three kept bins per thread instead of four, two LDS stages instead of three.
+// ===========================================================================
+template <typename T>
+struct FBand3Store {
+    cx<T>* base;
+    unsigned kstride;
+    int ncols;
+    const cx<T>* ti;            // LDS: W_(4 Mq')^(k1 y_lo), y_lo < Mq'
+    int q;
+    template <typename U> OA_HD void put(int k, int c, cx<U> v) const {
+        if (c >= ncols) return;
+        const int y = 3 * k + q;
+        base[(unsigned)y * kstride + (unsigned)c] = swp(v * ti[y]);
+    }
+};
+
+// the forward bin k2 (of My = 16 Q) behind kept entry e < 3 (k2' = m + e Q) of thread row m < Q
+template <int Q>
+OA_HD int fband3_bin(int m, int e) {
+    constexpr int Ns = 2 * Q, RL = 8;
+    if (e == 0) return m;                                    // butterfly j = m, t = 0
+    if (e == 2) return m + Q + (RL - 1) * Ns;                // butterfly j = m + Q, t = 7
+    return 2 * m >= Q ? m + (RL - 1) * Ns : m + Q;           // j = m, t = 7 (m >= Q / 2) or j = m + Q, t = 0
+}
+
+template <typename T, class SEQF, int LOGC, class Ctx>
+OA_HD void col_fband3_body(Ctx& ctx, const ColFBandArgs<T>& a) {
+    cx<T>* s = reinterpret_cast<cx<T>*>(ctx.smem());
+    constexpr int logL = seq_total_log<SEQF>();
+    constexpr int R = 4;
+    constexpr int RL = SEQF::get(SEQF::n - 1), NB = EPT / RL;
+    static_assert(RL == 8 && NB == 2, "col_fband3: the last forward radix is 8");
+    constexpr int logQ = logL - 4, Q = 1 << logQ, Mq = 3 * Q;
+    constexpr int C = 1 << LOGC;
+    constexpr int NT = (1 << (logL + LOGC)) / EPT;          // = Q C: thread <-> (m, c)
+    constexpr int NTS = (Q << LOGC) / EPT;                   // threads per Q-point inverse transform (16 groups, 9 at work)
+    const int tid = ctx.tid();
+    int tile = ctx.bid_x();
+    if ((sizeof(cx<T>) << LOGC) < 128) {                     // as col_fband_body: tiles that share 128-byte lines to the same XCD
+        constexpr int G = 128 / (int)(sizeof(cx<T>) << LOGC), GW = 8 * G;
+        const int nt = ctx.grid_x(), base = tile & ~(GW - 1), r = tile & (GW - 1);
+        if (base + GW <= nt) tile = base + G * (r & 7) + (r >> 3);
+    }
+    const int c0 = tile << LOGC;
+    const int k1 = ctx.bid_y();
+    int ncols = a.width - c0;
+    if (ncols > C) ncols = C;
+    cx<T> gv[EPT];
+    cx<T>* twl = s + (1 << (logL + LOGC));                   // forward stage twiddles (W_My)
+    cx<T>* twq = twl + tw_lds_size(logL);                    // inverse stage twiddles (W_Q)
+    cx<T>* ti = twq + tw_lds_size(logQ);                     // W_(4 Mq')^(k1 y_lo), y_lo < Mq'   (k1 y_lo < 4 Mq')
+    FB_STAMP(0);
+    tw_lds_fill<T>(ctx, twl, a.tw, logL, logL, NT);
+    tw_lds_fill<T>(ctx, twq, a.tw, logL, logQ, NT);
+    for (int i = tid; i < Mq; i += NT) ti[i] = a.tw3[(unsigned)k1 * (unsigned)i];
+    ctx.sync();
+    FB_STAMP(1);
+    const long zmap = ctx.bid_z();
+    const int c = tid & (C - 1), m = tid >> LOGC;
+    const bool ok = c < ncols;
+    // filter values of the three kept bins and the butterfly's factors W_Mq'^(m q) = W_(4 Mq')^(4 m q), requested ahead of the forward transform
+    T fgv[3], fhv[3], lyv[3];
+    bool lv[3];
+    const cx<T>* fq = a.fgh ? a.fgh + (((long)k1 * ctx.grid_x() + tile) * 3) * NT + tid : nullptr;
+    const T lx = ldg(a.lxd + (ok ? c0 + c : 0));
+    const cx<T> wq1 = ldg(a.tw3 + 4 * m), wq2 = ldg(a.tw3 + 8 * m);
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        const int yf = k1 + R * fband3_bin<Q>(m, e);         // row of the full-resolution grid
+        bool live = ok;
+        if (a.rband) live = ok && !(yf >= a.rband && yf <= a.ny_full - a.rband);
+        if (fq) {
+            const cx<T> f = ldg(fq + e * NT);
+            fgv[e] = f.x; fhv[e] = f.y;
+        } else {
+            const long fi = live ? (long)yf * a.fpitch + (c0 + c) : 0;
+            fgv[e] = ldg(a.FG + fi);
+            fhv[e] = ldg(a.FH + fi);
+        }
+        lyv[e] = ldg(a.lyd + (live ? yf : 0));
+        lv[e] = live;
+    }
+    FB_STAMP(2);
+    const ColLoad<T> ld{a.in + zmap * a.in_moff + (long)k1 * a.kplane + c0, (unsigned)a.pitch, ncols, false};
+    col_pipeline_to_regs<T, SEQF>(ctx, s, gv, tid, NT, LOGC, twl, logL, ld);
+    ctx.sync();
+    FB_STAMP(3);                                              // every LDS read of the forward precedes the leg regions' writes
+    cx<T> zh[3], zx[3], zy[3];
+    const cx<T> xm = (2 * m >= Q) ? gv[RL - 1] : gv[RL];     // the bin at k2' = m + Q
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        const cx<T> x = e == 0 ? gv[0] : (e == 2 ? gv[2 * RL - 1] : xm);
+        const T fg = lv[e] ? fgv[e] : (T)0, fh = lv[e] ? fhv[e] : (T)0, ly = lv[e] ? lyv[e] : (T)0;
+        const cx<T> g = mul_pi(x * fg);
+        zh[e] = swp(x * fh);                                  // inverse transform = forward transform of the swapped data
+        zx[e] = swp(g * (ok ? lx : (T)0));
+        zy[e] = swp(g * ly);
+    }
+    MrDft<T, 3>::run(zh); MrDft<T, 3>::run(zx); MrDft<T, 3>::run(zy);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const int at = ((q * Q + m) << LOGC) + c;
+        cx<T> h = zh[q], x = zx[q], y = zy[q];
+        if (q == 1) { h = h * wq1; x = x * wq1; y = y * wq1; }
+        if (q == 2) { h = h * wq2; x = x * wq2; y = y * wq2; }
+        s[at] = h;
+        s[(Mq << LOGC) + at] = x;
+        s[2 * (Mq << LOGC) + at] = y;
+    }
+    ctx.sync();
+    FB_STAMP(4);
+    const int sid = tid / NTS, tq = tid - sid * NTS;         // region sid = 3 leg + q; legs 0..2: H, Gx, Gy
+    const int leg = sid / 3, q = sid - 3 * leg;
+    cx<T>* outp = leg == 0 ? a.h : (leg == 1 ? a.gx : a.gy);
+    using SI = typename SeqOf<logQ>::type;
+    const FBand3Store<T> st{outp + zmap * a.out_moff + (long)k1 * a.opitch + c0, (unsigned)(R * a.opitch), leg < 3 ? ncols : 0, ti, q};
+    fft_pipeline<T, false, false, true, SI>(ctx, s + sid * (Q << LOGC), tq, NTS, logQ, LOGC, 0, twq, logQ, NoLoad{}, st);
+    FB_STAMP(5);
+}
+
+// the packed filter table of col_fband3_body: [k1][tile][e][tid], same grid and workgroup size
+template <typename T, class SEQF, int LOGC, class Ctx>
+OA_HD void col_fband3_pack_body(Ctx& ctx, const ColFBandArgs<T>& a, cx<T>* out) {
+    constexpr int logL = seq_total_log<SEQF>(), R = 4, Q = 1 << (logL - 4), C = 1 << LOGC;
+    constexpr int NT = (1 << (logL + LOGC)) / EPT;
+    const int tid = ctx.tid(), tile = ctx.bid_x(), k1 = ctx.bid_y(), c0 = tile << LOGC;
+    const int c = tid & (C - 1), m = tid >> LOGC;
+    cx<T>* o = out + (((long)k1 * ctx.grid_x() + tile) * 3) * NT + tid;
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        const int yf = k1 + R * fband3_bin<Q>(m, e);
+        bool live = c0 + c < a.width;
+        if (a.rband) live = live && !(yf >= a.rband && yf <= a.ny_full - a.rband);
+        cx<T> f = mk<T>((T)0, (T)0);
+        if (live) { const long fi = (long)yf * a.fpitch + (c0 + c); f = mk<T>(a.FG[fi], a.FH[fi]); }
+        o[e * NT] = f;
     }
 }
 

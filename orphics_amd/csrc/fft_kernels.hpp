@@ -129,6 +129,13 @@ OA_HD void tw_lds_fill(Ctx& ctx, cx<T>* tab, const cx<T>* gtw, int logG, int log
     for (int i = ctx.tid(); i < nlo + nhi; i += NT) tab[i] = gtw[(i < nlo ? i : ((i - nlo) << h)) << sh];
 }
 
+// the same table of W_L = W_G^mul from a table of any length G = mul L (3 x 2^k column grids)
+template <typename T, class Ctx>
+OA_HD void tw_lds_fill_mul(Ctx& ctx, cx<T>* tab, const cx<T>* gtw, int mul, int logL, int NT) {
+    const int h = tw_lds_h(logL), nlo = 1 << h, nhi = 1 << (logL - h);
+    for (int i = ctx.tid(); i < nlo + nhi; i += NT) tab[i] = gtw[(i < nlo ? i : ((i - nlo) << h)) * mul];
+}
+
 // multiply v[1..R-1] by w^t, w = W_L^(k << sh); base powers w^1,w^2,w^4,w^8 from the LDS table, rest by products
 template <typename T, int R>
 OA_HD void apply_twiddles(cx<T>* v, const cx<T>* tab, int k, int sh, int h) {
@@ -1896,6 +1903,152 @@ OA_HD void col_div_body(Ctx& ctx, const ColDivArgs<T>& a, Tail tail = Tail{}) {
             outb[i] = d;
         }
     }
+    }
+}
+
+// ===========================================================================
+// (B3) the single-pass form of (B) on a column grid of N = 6 Q rows, Q = 2^LOGQ (1536 = 6 x 256, 768 = 6 x 128): y = r + 6 m,
+//     X[k + Q q] = sum_(r < 6) W_N^(r k) W_6^(r q) F_r[k],   F_r[k] = sum_(m < Q) x[r + 6 m] W_Q^(m k)
+// Six thread groups of Q C / 16 threads run the Q-point transforms F_r (two radix stages, region r of the [N][C] tile: the first
+// gathers rows r + 6 m straight from the product plane), then every thread takes (k, c) positions -- (Q C) / NT = 8 / 3 per thread,
+// the third trip two thirds full -- through the twiddles and one radix-6 butterfly (two radix-3 and three radix-2).  Two LDS round
+// trips per plane, as the power-of-two body's three-stage sequences, on three quarters of the points.  The divergence, Fnorm and the
+// tail see the bins in registers exactly as in col_div_body (a.tw = W_N, a.ny = N).
+// ===========================================================================
+template <typename T> OA_HD void dft6(cx<T>* v) {
+    const T hs = (T)0.86602540378443864676L;
+    cx<T> e[3] = {v[0], v[2], v[4]}, o[3] = {v[1], v[3], v[5]};
+    auto d3 = [&](cx<T>* z) {
+        const cx<T> s = z[1] + z[2], d = (z[1] - z[2]) * hs, m = z[0] - s * (T)0.5;
+        z[0] = z[0] + s; z[1] = add_mi(m, d); z[2] = add_pi(m, d);
+    };
+    d3(e); d3(o);
+    o[1] = o[1] * mk<T>((T)0.5, -hs);                        // W_6
+    o[2] = o[2] * mk<T>((T)-0.5, -hs);                       // W_6^2
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { v[q] = e[q] + o[q]; v[q + 3] = e[q] - o[q]; }
+}
+
+template <typename T, int LOGQ, int LOGC, class Ctx, class Tail = NoDivTail>
+OA_HD void col_div3_body(Ctx& ctx, const ColDivArgs<T>& a, Tail tail = Tail{}) {
+    cx<T>* s = reinterpret_cast<cx<T>*>(ctx.smem());
+    using SEQ = typename SeqOf<LOGQ>::type;
+    static_assert(SEQ::n == 2, "col_div3: two-stage sub-transforms");
+    constexpr int R0 = SEQ::get(0), R1 = SEQ::get(1), l0 = Log2x<R0>::v;
+    constexpr int Q = 1 << LOGQ, N = 6 * Q, C = 1 << LOGC, logC = LOGC;
+    constexpr int NTS = (Q << LOGC) / EPT, NT = 6 * NTS;
+    constexpr int NIT = ((Q << LOGC) + NT - 1) / NT;         // (k, c) positions per thread in the radix-6 stage
+    const int tid = ctx.tid();
+    int tile = ctx.bid_x();
+    if ((sizeof(cx<T>) << LOGC) < 128) {                     // as col_div_body: tiles 2 m, 2 m + 1 to the same XCD
+        const int nt = ctx.grid_x(), base = tile & ~15, r = tile & 15;
+        if (base + 16 <= nt) tile = base + 2 * (r & 7) + (r >> 3);
+    }
+    const int c0 = tile << logC;
+    int ncols = a.width - c0;
+    if (ncols > C) ncols = C;
+    cx<T>* twl = s + (N << logC);
+    tw_lds_fill_mul<T>(ctx, twl, a.tw, 6, LOGQ, NT);
+    const long zmap = ctx.bid_z();
+    const long imo = zmap * a.in_moff, omo = zmap * a.out_moff;
+    const int grp = tid / NTS, tq = tid - grp * NTS;
+    cx<T>* sr = s + grp * (Q << logC);
+    const ColLoad<T> la{a.A + imo + (long)grp * a.pitch + c0, (unsigned)(6 * a.pitch), ncols, false};
+    const ColLoad<T> lb{a.B + imo + (long)grp * a.pitch + c0, (unsigned)(6 * a.pitch), ncols, false};
+    // radix-6 stage: this thread's positions and their factors W_N^k, W_N^(2 k), W_N^(4 k) (k < Q: 4 k < N)
+    int pk[NIT], pc[NIT];
+    bool pv[NIT];
+    cx<T> w1[NIT], w2[NIT], w4[NIT];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int i = tid + it * NT;
+        pv[it] = i < (Q << logC);
+        const int ii = pv[it] ? i : tid;
+        pc[it] = ii & (C - 1); pk[it] = ii >> logC;
+        w1[it] = ldg(a.tw + pk[it]); w2[it] = ldg(a.tw + 2 * pk[it]); w4[it] = ldg(a.tw + 4 * pk[it]);
+    }
+    cx<T> va[EPT], vb[EPT];
+    cx<T> xa[NIT][6], xb[NIT][6];
+    // both planes' global loads are issued back to back before either goes through LDS
+    stage_in<T, R0, false, true>(s, va, tq, NTS, LOGQ, logC, 0, 0, twl, LOGQ, la);
+    stage_in<T, R0, false, true>(s, vb, tq, NTS, LOGQ, logC, 0, 0, twl, LOGQ, lb);
+    ctx.sync();                                              // the stage-twiddle table is complete
+    auto finish = [&](cx<T>* v, cx<T> (*x)[6]) {
+        stage_out<T, R0, false, false>(sr, v, tq, NTS, LOGQ, logC, 0, 0, NoStore{});
+        ctx.sync();
+        stage<T, R1, false, false, false>(ctx, sr, tq, NTS, LOGQ, logC, 0, l0, twl, LOGQ, NoLoad{}, NoStore{});
+        ctx.sync();
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+#pragma unroll
+            for (int r = 0; r < 6; ++r) x[it][r] = s[((r * Q + pk[it]) << logC) + pc[it]];
+            const cx<T> w3 = w1[it] * w2[it], w5 = w4[it] * w1[it];
+            x[it][1] = x[it][1] * w1[it]; x[it][2] = x[it][2] * w2[it]; x[it][3] = x[it][3] * w3;
+            x[it][4] = x[it][4] * w4[it]; x[it][5] = x[it][5] * w5;
+            dft6<T>(x[it]);
+        }
+    };
+    finish(va, xa);
+    ctx.sync();                                              // every radix-6 read of plane A precedes plane B's writes
+    finish(vb, xb);
+    const T* Fnb = a.Fn + zmap * a.fn_moff + c0;
+    cx<T>* outb = a.out + omo + c0;
+    // bin y = k + Q q of position (k, c): row y + (y >= N / 2 ? yshift : 0) of Fn, ly, out
+    if constexpr (Tail::active) {
+        ctx.sync();                                          // the tile is free: the tail's histogram rows
+        tail.begin(ctx, s);
+        ctx.sync();
+        T pw[NIT * 6];
+        int idv[NIT * 6];
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int c = pc[it], k = pk[it];
+            const bool cok = pv[it] && c < ncols;
+            const T lx = cok ? a.lxd[c0 + c] : (T)0;
+#pragma unroll
+            for (int q = 0; q < 6; ++q) {
+                const unsigned y = (unsigned)(k + Q * q);
+                const bool ok = cok && !(a.rband && (int)y >= a.rband && (int)y <= a.ny - a.rband);
+                const unsigned up = (a.yshift && y >= (unsigned)(N >> 1)) ? (unsigned)a.yshift : 0u;
+                const unsigned i = (y + up) * (unsigned)a.opitch + (unsigned)c;
+                pw[it * 6 + q] = (T)0;
+                idv[it * 6 + q] = -1;
+                if (ok) {
+                    const long ti_ = ((long)tile * N + y) * C + c;       // tile-major tables: entry [tile][coarse row][c]
+                    const T fn = a.Fn_t ? a.Fn_t[ti_] : Fnb[i];
+                    cx<T> d = mul_pi(xa[it][q] * lx + xb[it][q] * a.lyd[y + up]) * fn;
+                    if (a.out) {
+                        if (a.accumulate) d = d + outb[i];
+                        outb[i] = d;
+                    }
+                    pw[it * 6 + q] = d.x * d.x + d.y * d.y;
+                    idv[it * 6 + q] = tail.packed_ids() ? tail.id_at_t(ti_) : tail.id_at(y + up, c0 + c);
+                }
+            }
+        }
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+#pragma unroll
+            for (int q = 0; q < 6; ++q) tail.add(ctx, idv[it * 6 + q], pw[it * 6 + q], c0 + pc[it]);
+        }
+        tail.finish(ctx);
+    } else {
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int c = pc[it], k = pk[it];
+            if (!pv[it] || c >= ncols) continue;
+            const T lx = a.lxd[c0 + c];
+#pragma unroll
+            for (int q = 0; q < 6; ++q) {
+                const unsigned y = (unsigned)(k + Q * q);
+                if (a.rband && (int)y >= a.rband && (int)y <= a.ny - a.rband) continue;
+                const unsigned up = (a.yshift && y >= (unsigned)(N >> 1)) ? (unsigned)a.yshift : 0u;
+                const unsigned i = (y + up) * (unsigned)a.opitch + (unsigned)c;
+                cx<T> d = mul_pi(xa[it][q] * lx + xb[it][q] * a.lyd[y + up]) * Fnb[i];
+                if (a.accumulate) d = d + outb[i];
+                outb[i] = d;
+            }
+        }
     }
 }
 

@@ -25,6 +25,9 @@ inline std::vector<cx<T>> make_twiddles(int M) {
 inline long kpitch_for(int nx) { return nx / 2 + 16; }
 
 inline bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+// 3 x 2^k column grids (the from-map R-split path only): m3_pow2 = the power-of-two grid 4/3 of it, whose forward side they keep
+inline bool is_m3(int v) { return v >= 3 && v % 3 == 0 && is_pow2(v / 3); }
+inline int m3_pow2(int v) { return v / 3 * 4; }
 
 // Geometry + device tables of one (ny, nx) transform.
 template <typename T>
@@ -141,10 +144,35 @@ struct Fft2dPlan {
         if (pack_out) q.col_fband_pack((a.width + Cs - 1) / Cs, 1 << (logNy - cv.logNy), cv.logNy, a, pack_out);
         else q.col_fband((a.width + Cs - 1) / Cs, 1 << (logNy - cv.logNy), nmaps, smem, cv.logNy, a);
     }
+    // ---- the same on a 3 x 2^k coarse grid (col_fband3_body): cv.ny = 3 My / 4 rows, cv.tw_y = W_(cv.ny); the forward side stays on
+    //      My = ny / 4 rows (twf = W_My).  Built for My = 2048 (1536 rows: 8192^2 maps) and My = 1024 (768 rows: 4096^2 maps).
+    static bool has_rsplit3(int logNy, int logNx, int my3, int wl) {
+        if (!is_m3(my3)) return false;
+        const int myf = m3_pow2(my3);
+        return (myf == 1024 || myf == 2048) && logNy - ilog2(myf) == 2 && has_rsplit(logNy, logNx, myf, wl) && fband_lt() == (sizeof(T) == 4 ? 14 : 13) &&
+               div_lt() == fband_lt();
+    }
+    template <class Launcher>
+    void legs_fband3(Launcher& q, const Fft2dPlan<T>& cv, const cx<T>* twf, const cx<T>* Y, long kplane, long pin, const T* FG, const T* FH,
+                     const T* lxd, const T* lyd, cx<T>* gx, cx<T>* gy, cx<T>* h, int wmax, int rband, long pout, int nmaps = 1, long in_moff = 0,
+                     long out_moff = 0, const cx<T>* fgh = nullptr, cx<T>* pack_out = nullptr) const {
+        ColFBandArgs<T> a{};
+        a.in = Y; a.kplane = kplane; a.pitch = pin; a.FG = FG; a.FH = FH; a.fpitch = kp; a.lxd = lxd; a.lyd = lyd; a.fgh = fgh;
+        a.gx = gx; a.gy = gy; a.h = h; a.opitch = pout; a.width = clampw(wmax); a.tw = twf; a.tw3 = cv.tw_y; a.ny_full = ny; a.rband = clampr(rband);
+        a.in_moff = in_moff; a.out_moff = out_moff;
+        const int logMy = logNy - 2, lt = fband_lt(), lc = lt - logMy, Cs = 1 << lc, logQ = logMy - 4;
+        const size_t smem = ((size_t)(1 << lt) + tw_lds_size(logMy) + tw_lds_size(logQ) + 3 * (1 << logQ)) * sizeof(cx<T>);
+        if (pack_out) q.col_fband3_pack((a.width + Cs - 1) / Cs, logMy, a, pack_out);
+        else q.col_fband3((a.width + Cs - 1) / Cs, nmaps, smem, logMy, a);
+    }
     // entries (cx<T>) of the packed filter table for `wmax` leg columns on the column grid `cv`
     long fband_table_entries(const Fft2dPlan<T>& cv, int wmax) const {
         const int lc = fband_lt() - cv.logNy, Cs = 1 << lc;
         return (long)((clampw(wmax) + Cs - 1) / Cs) * Cs * cv.ny;          // tiles x C x My
+    }
+    long fband3_table_entries(const Fft2dPlan<T>& cv, int wmax) const {
+        const int lc = fband_lt() - (logNy - 2), Cs = 1 << lc;
+        return (long)((clampw(wmax) + Cs - 1) / Cs) * Cs * cv.ny;          // tiles x C x (3 My / 4)
     }
 
     // ---- fused QE row stage: 3 hc planes (column-transformed legs) -> 2 hc planes -------------
@@ -493,6 +521,21 @@ struct Fft2dPlan {
         a.rband = clampr(rband); a.ny = ny; a.yshift = yshift();
         a.in_moff = tmp_moff; a.out_moff = out_moff; a.fn_moff = fn_moff;
         q.col_div(tiles, (int)N1, a.NT, ((size_t)N2 * C + tw_lds_size(logN2) + N2) * sizeof(cx<T>), logN2, a, nmaps);
+    }
+
+    // (B3) the single-pass divergence of a 3 x 2^k column grid (THIS view: ny = 1536 or 768 rows, tw_y = W_ny): col_div3_body,
+    //      96 KB tiles of 4 / 8 float64 or 8 / 16 float columns
+    static int div3_logc(int rows) { return (sizeof(T) == 4 ? 3 : 2) + (rows == 768 ? 1 : 0); }
+    template <class Launcher>
+    void cols_div3(Launcher& q, const cx<T>* pa, const cx<T>* pb, const T* Fn, const T* lxd, const T* lyd, cx<T>* out, int accumulate,
+                   int wmax = 0x7fffffff, int rband = 0, long pin = 0, int nmaps = 1, long in_moff = 0, long out_moff = 0, long fn_moff = 0) const {
+        const int lc = div3_logc(ny), Cs = 1 << lc, logQ = ilog2(ny / 6);
+        ColDivArgs<T> a{};
+        a.A = pa; a.B = pb; a.Fn = Fn; a.lxd = lxd; a.lyd = lyd; a.out = out; a.pitch = pin > 0 ? pin : kp; a.opitch = kp; a.width = clampw(wmax);
+        a.logC = lc; a.NT = 6 * (((ny / 6) << lc) / EPT); a.tw = tw_y; a.logTw = 0; a.in_gs = 1; a.in_ns = 1; a.out_gs = 1; a.out_ks = 1;
+        a.accumulate = accumulate; a.rband = clampr(rband); a.ny = ny; a.yshift = yshift();
+        a.in_moff = in_moff; a.out_moff = out_moff; a.fn_moff = fn_moff;
+        q.col_div3((a.width + Cs - 1) / Cs, ((size_t)(ny << lc) + tw_lds_size(logQ)) * sizeof(cx<T>), ny, a, nmaps);
     }
 
     // real (ny,nx) -> half-complex (ny, kp); tmp: one hc plane

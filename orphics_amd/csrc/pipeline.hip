@@ -20,6 +20,8 @@ struct Pipeline {
     int wl = 0, wk = 0, rl = 0, rk = 0, mrow = -1;
     int mcol = -1;   // requested column grid (-1 auto, 0 = the map's own ny rows, > 0 explicit)
     int my = 0;      // resolved: rows the legs / row stage / divergence run on (0 = ny)
+    int my3 = 0;     // FROM-MAP GRID: 3 my / 4 when the from-map R-split path runs its coarse side there (include/orphics_amd.h), else 0 = my
+    int map_grid() const { return my3 ? my3 : my; }
     // plan-owned work planes (hc): legs x3, products x2, input transform, kappa
     void* work = nullptr;
     void* c[3] = {nullptr, nullptr, nullptr};
@@ -45,12 +47,18 @@ struct Pipeline {
     size_t lens_bytes = 0;
     // tile-major copies of Fnorm and of the bin ids on the coarse grid of the fused divergence + binning launch (what they were
     // made from: rebuilt when the filters / bins / column grid change)
-    void* fn_t = nullptr; int32_t* ids_t = nullptr;
-    size_t fn_t_bytes = 0, ids_t_bytes = 0;
+    // (one set per grid a plan can carry: [0] the column grid `my`, [1] the from-map grid `my3`)
+    struct DivTabs {
+        void* fn_t = nullptr; int32_t* ids_t = nullptr;
+        size_t fn_t_bytes = 0, ids_t_bytes = 0;
+        unsigned long tab_gen = 0;
+        int tab_rows = 0, tab_logc = 0, tab_wk = 0;
+    } dt[2];
+    DivTabs& tabs_of(int rows) { return (my3 && rows == my3) ? dt[1] : dt[0]; }
+    const DivTabs& tabs_of(int rows) const { return (my3 && rows == my3) ? dt[1] : dt[0]; }
     // keyed on a GENERATION bumped by every oa_plan_set_filters / oa_plan_set_bins call, not on the planes' addresses: a caching
     // allocator hands a new estimator the addresses of a freed one, and a caller may refill Fnorm or the ids in place
-    unsigned long bind_gen = 1, tab_gen = 0;
-    int tab_rows = 0, tab_logc = 0, tab_wk = 0;
+    unsigned long bind_gen = 1;
     // the packed (FG, FH) table of the R-split column stage (ColFBandArgs::fgh), same generation key
     void* fb_t = nullptr;
     size_t fb_t_bytes = 0;
@@ -96,9 +104,8 @@ void pipeline_release(oa_plan* p) {
     if (q->mc_src) (void)hipFree(q->mc_src);
     if (q->mv_rtab) (void)hipFree(q->mv_rtab);
     if (q->lens_pool) (void)hipFree(q->lens_pool);
-    if (q->fn_t) (void)hipFree(q->fn_t);
+    for (auto& t : q->dt) { if (t.fn_t) (void)hipFree(t.fn_t); if (t.ids_t) (void)hipFree(t.ids_t); }
     if (q->fb_t) (void)hipFree(q->fb_t);
-    if (q->ids_t) (void)hipFree(q->ids_t);
     if (q->band) (void)oa_plan_destroy(q->band);
     if (q->bplanes) (void)hipFree(q->bplanes);
     if (q->bids) (void)hipFree(q->bids);
@@ -165,6 +172,7 @@ static int zero_complement(oa_plan* p, void* out, int wk, int rk, hipStream_t st
 static int resolve_my(oa_plan* p, int mcol, int rl, int rk, int* my_out) {
     *my_out = 0;
     if (mcol == 0 || rl <= 0 || rk <= 0) return 0;
+    if (mcol > 0 && is_m3(mcol)) mcol = m3_pow2(mcol);          // a 3 x 2^k request concerns the from-map path only (resolve_col_grid)
     const long need = std::max(2L * rl + rk, 2L * rk);
     int my = mcol;
     if (my < 0) { my = 64; while (my < need && my < p->ny) my <<= 1; }
@@ -174,13 +182,35 @@ static int resolve_my(oa_plan* p, int mcol, int rl, int rk, int* my_out) {
     *my_out = my;
     return 0;
 }
-static int resolve_col_grid(oa_plan* p, Pipeline* q) { return resolve_my(p, q->mcol, q->rl, q->rk, &q->my); }
+// ... and the FROM-MAP GRID: three quarters of `my` when that many rows satisfy the same bound and this geometry's from-map path is the
+// R = 4 R-split one with the 3 x 2^k kernels built (8192 rows -> 1536, 4096 rows -> 768); chosen automatically, or asked for by
+// an explicit 3 x 2^k column grid, which is refused where it would alias or where no such path exists.  Every other entry (Fourier-space
+// legs, pol, MV, Monte Carlo) keeps `my`.
+static int resolve_col_grid(oa_plan* p, Pipeline* q) {
+    q->my3 = 0;
+    const bool want3 = q->mcol > 0 && is_m3(q->mcol);
+    const long need = std::max(2L * q->rl + q->rk, 2L * q->rk);
+    if (want3 && q->rl > 0 && q->rk > 0 && q->mcol < need)
+        return fail("column grid < max(2*leg_rows + kappa_rows, 2*kappa_rows) would alias the leg products into the kept rows");
+    if (int rc = resolve_my(p, q->mcol, q->rl, q->rk, &q->my)) return rc;
+    const int my3 = want3 ? q->mcol : (q->mcol < 0 && q->my > 0 && q->my % 4 == 0 ? q->my / 4 * 3 : 0);
+    bool ok = my3 > 0 && q->my == m3_pow2(my3) && my3 >= need && qe_rsplit_lr(p, q->my, q->wl, q->wk, q->mrow) == 2;
+    if (ok) {
+        if (int rc = plan_ensure_col_grid(p, my3)) return rc;
+        ok = qe_rsplit_lr(p, my3, q->wl, q->wk, q->mrow) == 2;
+    }
+    if (ok) q->my3 = my3;
+    else if (want3) return fail("oa_plan_set_col_grid: this geometry has no from-map path on a 3 x 2^k column grid (built for 8192-row maps on 1536 "
+                                "rows and 4096-row maps on 768 rows, R-split from-map path)");
+    return 0;
+}
 
 }  // namespace oa
 
 using namespace oa;
 
 static int ensure_div_tables(oa_plan* p, oa::Pipeline* q, hipStream_t st);
+static int ensure_div_tables(oa_plan* p, oa::Pipeline* q, hipStream_t st, int rows);
 // BAND GRID (map sides 2^a 3^b 5^c), defined below the Monte-Carlo helpers
 namespace oa {
 static int band_grid_rule(const oa_plan* p, int mrow, int mcol, int wl, int wk, int rl, int rk, int* my, int* mx);
@@ -200,7 +230,8 @@ extern "C" {
 int oa_plan_set_col_grid(oa_plan* p, int mcol) {
     OA_REQUIRE(p, "oa_plan_set_col_grid: NULL plan");
     OA_REQUIRE(p->pow2 || p->mixed, "oa_plan_set_col_grid: map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path");
-    OA_REQUIRE(mcol <= 0 || is_pow2(mcol), "oa_plan_set_col_grid: mcol must be -1 (auto), 0 (off) or a power of two");
+    OA_REQUIRE(mcol <= 0 || is_pow2(mcol) || (is_m3(mcol) && p->pow2),
+               "oa_plan_set_col_grid: mcol must be -1 (auto), 0 (off), a power of two, or 3 x 2^k (from-map path of power-of-two plans)");
     Pipeline* q = pipe_of(p);
     q->mcol = mcol;
     if (p->mixed) {                                // the band grid's rows: re-resolved, the inner plan remade only if they change
@@ -215,7 +246,7 @@ int oa_plan_set_col_grid(oa_plan* p, int mcol) {
     return q->FG ? resolve_col_grid(p, q) : 0;     // oa_qe_pol resolves it per call from its own row bands
 }
 
-int oa_plan_col_grid(const oa_plan* p) { return (p && p->pipe) ? ((Pipeline*)p->pipe)->my : 0; }
+int oa_plan_col_grid(const oa_plan* p) { return (p && p->pipe) ? ((Pipeline*)p->pipe)->map_grid() : 0; }
 
 int oa_plan_band_grid(const oa_plan* p, int* my, int* mx) {
     OA_REQUIRE(p && my && mx, "oa_plan_band_grid: NULL argument");
@@ -255,7 +286,7 @@ extern "C" {
 int oa_plan_rsplit(const oa_plan* p) {
     if (!p || !p->pipe) return 0;
     const Pipeline* q = (const Pipeline*)p->pipe;
-    return q->FG ? (1 << qe_rsplit_lr(p, q->my, q->wl, q->wk, q->mrow)) & ~1 : 0;
+    return q->FG ? (1 << qe_rsplit_lr(p, q->map_grid(), q->wl, q->wk, q->mrow)) & ~1 : 0;
 }
 
 int oa_plan_div_fused(const oa_plan* p) {
@@ -263,9 +294,9 @@ int oa_plan_div_fused(const oa_plan* p) {
     const Pipeline* q = (const Pipeline*)p->pipe;
     if (p->mixed) { band_options((Pipeline*)q); return (q->FG && q->ids && q->band) ? oa_plan_div_fused(q->band) : 0; }
     if (!q->FG || !q->ids || !q->opt_divbin) return 0;
-    const int rows = q->my ? q->my : p->ny;            // rows of the grid the divergence runs on
+    const int rows = q->map_grid() ? q->map_grid() : p->ny;     // rows of the grid the from-map divergence runs on
     const bool sp = p->dtype == OA_F32 ? Fft2dPlan<float>::single_pass_div() : Fft2dPlan<double>::single_pass_div();
-    if (!(sp && (rows == 1024 || rows == 2048 || rows == 4096))) return 0;
+    if (!(sp && (rows == 1024 || rows == 2048 || rows == 4096 || (q->my3 && rows == q->my3)))) return 0;
     const int logc = div_tile_logc(p, rows);           // columns per 128 KB tile of this grid and precision
     const long tiles = ((long)(q->wk > 0 ? q->wk : p->nx / 2 + 1) + (1 << logc) - 1) >> logc;
     return (tiles * MC_BATCH_MAX * q->nids <= (long)(oa_bin_scratch_bytes(q->nids) / 8) * MC_BATCH_MAX) ? 1 : 0;
@@ -332,48 +363,57 @@ static bool divbin_enabled(const Pipeline* q) { return q->opt_divbin; }
 // (re)build the tile-major copies of Fnorm / ids for the single-pass divergence launch on this plan's column grid.  Called where the
 // filters, the bins and the grid are known (oa_plan_set_bins, and again by make_fuse_tabs if any of them changed since): the first
 // build of a size allocates (one device synchronisation), later rebuilds are two small stream-ordered launches.
-static int ensure_div_tables(oa_plan* p, Pipeline* q, hipStream_t st) {
-    const int rows = q->my;
-    if (!(q->Fn && q->ids && (rows == 1024 || rows == 2048 || rows == 4096) && q->wk > 0)) { q->tab_rows = 0; return 0; }
+static int ensure_div_tables(oa_plan* p, Pipeline* q, hipStream_t st, int rows) {
+    Pipeline::DivTabs* const t = &q->tabs_of(rows);
+    if (!(q->Fn && q->ids && (rows == 1024 || rows == 2048 || rows == 4096 || (q->my3 && rows == q->my3)) && q->wk > 0)) { t->tab_rows = 0; return 0; }
     const int logc = div_tile_logc(p, rows);
-    if (q->tab_gen == q->bind_gen && q->tab_rows == rows && q->tab_logc == logc && q->tab_wk == q->wk) return 0;
+    if (t->tab_gen == q->bind_gen && t->tab_rows == rows && t->tab_logc == logc && t->tab_wk == q->wk) return 0;
     const size_t rs = p->dtype == OA_F32 ? 4 : 8;
     const long tiles = ((long)q->wk + (1 << logc) - 1) >> logc, total = (tiles * rows) << logc;
-    if (q->fn_t_bytes < (size_t)total * rs) {
-        if (q->fn_t) { OA_HIP(hipDeviceSynchronize()); (void)hipFree(q->fn_t); q->fn_t = nullptr; }
-        OA_HIP(hipMalloc(&q->fn_t, (size_t)total * rs));
-        q->fn_t_bytes = (size_t)total * rs;
+    if (t->fn_t_bytes < (size_t)total * rs) {
+        if (t->fn_t) { OA_HIP(hipDeviceSynchronize()); (void)hipFree(t->fn_t); t->fn_t = nullptr; }
+        OA_HIP(hipMalloc(&t->fn_t, (size_t)total * rs));
+        t->fn_t_bytes = (size_t)total * rs;
     }
-    if (q->ids_t_bytes < (size_t)total * 4) {
-        if (q->ids_t) { OA_HIP(hipDeviceSynchronize()); (void)hipFree(q->ids_t); q->ids_t = nullptr; }
-        OA_HIP(hipMalloc((void**)&q->ids_t, (size_t)total * 4));
-        q->ids_t_bytes = (size_t)total * 4;
+    if (t->ids_t_bytes < (size_t)total * 4) {
+        if (t->ids_t) { OA_HIP(hipDeviceSynchronize()); (void)hipFree(t->ids_t); t->ids_t = nullptr; }
+        OA_HIP(hipMalloc((void**)&t->ids_t, (size_t)total * 4));
+        t->ids_t_bytes = (size_t)total * 4;
     }
-    if (int rc = pack_tiles(p, q->Fn, q->fn_t, rows, logc, q->wk, (int)rs, st)) return rc;
-    if (int rc = pack_tiles(p, q->ids, q->ids_t, rows, logc, q->wk, 4, st)) return rc;
-    q->tab_gen = q->bind_gen; q->tab_rows = rows; q->tab_logc = logc; q->tab_wk = q->wk;
+    if (int rc = pack_tiles(p, q->Fn, t->fn_t, rows, logc, q->wk, (int)rs, st)) return rc;
+    if (int rc = pack_tiles(p, q->ids, t->ids_t, rows, logc, q->wk, 4, st)) return rc;
+    t->tab_gen = q->bind_gen; t->tab_rows = rows; t->tab_logc = logc; t->tab_wk = q->wk;
     return 0;
+}
+// both grids of the plan (the from-map grid's tables only where it differs)
+static int ensure_div_tables(oa_plan* p, Pipeline* q, hipStream_t st) {
+    if (int rc = ensure_div_tables(p, q, st, q->my)) return rc;
+    return q->my3 ? ensure_div_tables(p, q, st, q->my3) : 0;
 }
 // the packed filter table of the R-split column stage for the bound filters on this plan's column grid, (re)made when the filters, the
 // band or the grid changed: nullptr when this geometry does not take the R-split path (or on failure: the kernel then reads the planes)
 static const void* fband_table(oa_plan* p, Pipeline* q, hipStream_t st) {
     static const bool off = exp_env("OA_NO_FBAND_TABLE") != nullptr;        // A/B switch
-    if (off || !q->FG || q->my <= 0 || !qe_rsplit_lr(p, q->my, q->wl, q->wk, q->mrow)) return nullptr;
-    if (q->fb_t && q->fb_gen == q->bind_gen && q->fb_my == q->my && q->fb_wl == q->wl && q->fb_rl == q->rl) return q->fb_t;
-    const size_t need = (size_t)qe_fband_table_entries(p, q->wl, q->my) * 2 * (p->dtype == OA_F32 ? 4 : 8);
+    const int my = q->map_grid();                  // (the R-split column stage exists on the from-map path only)
+    if (off || !q->FG || my <= 0 || !qe_rsplit_lr(p, my, q->wl, q->wk, q->mrow)) return nullptr;
+    if (q->fb_t && q->fb_gen == q->bind_gen && q->fb_my == my && q->fb_wl == q->wl && q->fb_rl == q->rl) return q->fb_t;
+    const size_t need = (size_t)qe_fband_table_entries(p, q->wl, my) * 2 * (p->dtype == OA_F32 ? 4 : 8);
     if (q->fb_t_bytes < need) {
         if (q->fb_t) { if (hipDeviceSynchronize() != hipSuccess) return nullptr; (void)hipFree(q->fb_t); q->fb_t = nullptr; q->fb_t_bytes = 0; }
         if (hipMalloc(&q->fb_t, need) != hipSuccess) { q->fb_t = nullptr; (void)hipGetLastError(); return nullptr; }
         q->fb_t_bytes = need;
     }
-    if (qe_fband_pack_w(p, q->FG, q->FH, q->fb_t, q->wl, q->rl, q->my, st)) return nullptr;
-    q->fb_gen = q->bind_gen; q->fb_my = q->my; q->fb_wl = q->wl; q->fb_rl = q->rl;
+    if (qe_fband_pack_w(p, q->FG, q->FH, q->fb_t, q->wl, q->rl, my, st)) return nullptr;
+    q->fb_gen = q->bind_gen; q->fb_my = my; q->fb_wl = q->wl; q->fb_rl = q->rl;
     return q->fb_t;
 }
-static DivBinFuse make_fuse(const oa_plan* p, const Pipeline* q, int64_t* n, double* S, double* C, int store) {
+// rows: the grid of the divergence launch the request goes to (-1: the column grid `my`)
+static DivBinFuse make_fuse(const oa_plan* p, const Pipeline* q, int64_t* n, double* S, double* C, int store, int rows = -1) {
     DivBinFuse f{};
-    if (q->tab_rows && q->tab_gen == q->bind_gen && q->tab_rows == q->my && q->tab_wk == q->wk) {
-        f.ids_t = q->ids_t; f.fn_t = q->fn_t; f.tab_logc = q->tab_logc; f.tab_rows = q->tab_rows;
+    if (rows < 0) rows = q->my;
+    const Pipeline::DivTabs& t = q->tabs_of(rows);
+    if (t.tab_rows && t.tab_gen == q->bind_gen && t.tab_rows == rows && t.tab_wk == q->wk) {
+        f.ids_t = t.ids_t; f.fn_t = t.fn_t; f.tab_logc = t.tab_logc; f.tab_rows = t.tab_rows;
     }
     f.ids = q->ids; f.ipitch = p->kp; f.pnorm = q->norm; f.nids = q->nids; f.nxh = p->nx / 2;
     f.part = (double*)q->bin_scratch; f.part_cap = (long)(oa_bin_scratch_bytes(q->nids) / (long)sizeof(double)) * MC_BATCH_MAX;
@@ -405,8 +445,9 @@ static int qe_tt_impl(oa_plan* p, const void* real_map, const void* kX, const vo
     const long pl = work_pitch(p, q->wl), pk = work_pitch(p, q->wk);
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    const int my = q->my;
-    const int lr = (real_map && !rows_done) ? qe_rsplit_lr(p, my, q->wl, q->wk, q->mrow) : 0;     // from a map: R-split row pass + one column kernel
+    // from a map: R-split row pass + one column kernel, on the from-map grid where the plan carries one
+    const int my = (real_map && !rows_done) ? q->map_grid() : q->my;
+    const int lr = (real_map && !rows_done) ? qe_rsplit_lr(p, my, q->wl, q->wk, q->mrow) : 0;
     if (real_map) rc = qe_map_legs_cols_w(p, real_map, q->FG, q->FH, q->c[0], q->c[1], q->c[2], q->wl, q->rl, pl, st, rows_done ? 6 : 7, my, lr,
                                           lr ? fband_table(p, q, st) : nullptr);
     else rc = qe_legs_cols_w(p, kX, kY ? kY : kX, q->FG, q->FH, q->c[0], q->c[1], q->c[2], q->wl, q->rl, pl, st, my);
@@ -537,7 +578,7 @@ int oa_qe_tt_moments(oa_plan* p, const void* real_map, int64_t* n, double* S, do
     Pipeline* q = (Pipeline*)p->pipe;
     if (p->mixed) return mixed_moments(p, q, real_map, n, S, C, (hipStream_t)stream);
     if (int rc = ensure_div_tables(p, q, (hipStream_t)stream)) return rc;
-    DivBinFuse f = make_fuse(p, q, n, S, C, 0);
+    DivBinFuse f = make_fuse(p, q, n, S, C, 0, q->map_grid());
     if (int rc = qe_tt_impl(p, real_map, nullptr, nullptr, nullptr, 0, stream, divbin_enabled(q) ? &f : nullptr)) return rc;
     if (f.done) return 0;                      // binned and accumulated in the divergence launch
     return bandpower_moments(p, q, n, S, C, stream);
@@ -794,9 +835,9 @@ int oa_qe_tt_moments2(oa_plan* p, const void* real_map0, const void* real_map1, 
     // second kappa plane: the plan-owned input-transform plane (unused on the from-map path); only kappa's active region of
     // it is ever read back (binning)
     if (int rc = ensure_div_tables(p, q, (hipStream_t)stream)) return rc;
-    DivBinFuse f = make_fuse(p, q, n, S, C, 0);
+    DivBinFuse f = make_fuse(p, q, n, S, C, 0, q->map_grid());
     int rc = qe_tt_pair_w(p, real_map0, real_map1, q->FG, q->FH, q->Fn, q->c[0], q->c[1], q->c[2], q->g[0], q->g[1], q->kk, q->kT, q->wl,
-                          q->wk, q->rl, q->rk, q->mrow, q->my, pl, pk, (hipStream_t)stream, divbin_enabled(q) ? &f : nullptr,
+                          q->wk, q->rl, q->rk, q->mrow, q->map_grid(), pl, pk, (hipStream_t)stream, divbin_enabled(q) ? &f : nullptr,
                           fband_table(p, q, (hipStream_t)stream));
     if (rc > 0) return rc;
     if (rc == 0 && f.done) return 0;           // both maps binned and accumulated (map order) in the divergence launch
@@ -822,7 +863,7 @@ int oa_qe_tt_stage(oa_plan* p, int stage, const void* real_map, void* stream) {
     Pipeline* q = (Pipeline*)p->pipe;
     const long pl = work_pitch(p, q->wl), pk = work_pitch(p, q->wk);
     hipStream_t st = (hipStream_t)stream;
-    const int my = q->my;
+    const int my = q->map_grid();
     const double s = 1.0 / ((double)p->ny * p->nx), sy = my ? (double)p->ny / my : 1.0;
     const int lr = qe_rsplit_lr(p, my, q->wl, q->wk, q->mrow);
     switch (stage) {
@@ -833,7 +874,7 @@ int oa_qe_tt_stage(oa_plan* p, int stage, const void* real_map, void* stream) {
         case 3: return qe_rows_w(p, q->c[0], q->c[1], q->c[2], q->g[0], q->g[1], s * s * sy, 0, q->wl, q->wk, q->mrow, pl, pk, st, my, lr);
         case 4: {
             if (q->ids && divbin_enabled(q)) {      // as the one-call entries: binning + moments (into dummies) in the divergence launch
-                DivBinFuse f = make_fuse(p, q, (int64_t*)q->kT, (double*)q->kT + 8, (double*)q->kT + 8 + q->nids, 0);
+                DivBinFuse f = make_fuse(p, q, (int64_t*)q->kT, (double*)q->kT + 8, (double*)q->kT + 8 + q->nids, 0, my);
                 return qe_cols_div_w(p, q->g[0], q->g[1], q->Fn, q->kk, 0, q->wk, q->rk, pk, st, my, &f);
             }
             return qe_cols_div_w(p, q->g[0], q->g[1], q->Fn, q->kk, 0, q->wk, q->rk, pk, st, my);

@@ -95,6 +95,7 @@ int oa_plan_destroy(oa_plan* p) {
     if (p->tw_y) (void)hipFree(p->tw_y);
     for (void* t : p->rq8c) if (t) (void)hipFree(t);
     for (void* t : p->tw_y_small) if (t) (void)hipFree(t);
+    for (void* t : p->tw_y_m3) if (t) (void)hipFree(t);
     if (p->scratch) (void)hipFree(p->scratch);
     if (p->ly) (void)hipFree(p->ly);
     if (p->lx) (void)hipFree(p->lx);

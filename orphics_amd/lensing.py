@@ -759,6 +759,8 @@ class Estimator(object):
         Fn = G["Fnorm"] if norm is None else norm
         e._ordered()
         check(e.lib.oa_plan_set_col_grid(e.plan, int(self.mcol)))       # plans are shared per geometry: policy per call
+        if getattr(e, "_pipe_owner", None) is not self._token:
+            e._pipe_owner = None          # the call above re-resolved the grid of another handle's TT binding: it binds again on its next call
         # one estimator through oa_qe_mv (nest = 1): the same pieces as oa_qe_pol, with all distinct leg planes of the estimator
         # in ONE inverse pass-1 launch and one pass-2 launch (a piece pair shares its cos / sin filtered fields)
         one = ctypes.c_void_p * 1
@@ -865,6 +867,8 @@ class Estimator(object):
         kys = (ctypes.c_void_p * a["ne"])(*[f[XY[1]].data_ptr() for XY in estimators])
         e._ordered()
         check(e.lib.oa_plan_set_col_grid(e.plan, int(self.mcol)))
+        if getattr(e, "_pipe_owner", None) is not self._token:
+            e._pipe_owner = None          # the call above re-resolved the grid of another handle's TT binding: it binds again on its next call
         check(e.lib.oa_qe_mv(e.plan, a["ne"], a["npieces"], a["signs"], a["fgs"], a["fhs"], a["swaps"], kxs, kys, a["fns"], _ptr(out), 0,
                              int(a["wl"]), int(wk), int(a["rl"]), int(rk), int(self.mrow), zero, _stream()))
         mark_dirty(out)

@@ -22,7 +22,7 @@ import shutil
 import statistics
 import sys
 
-MARK = ("bin_final_kernel", "col_div_sp_bin_kernel")     # last launch of a reconstruction (fused tail: the divergence kernel itself)
+MARK = ("bin_final_kernel", "col_div_sp_bin_kernel", "col_div3_sp_bin_kernel")     # last launch of a reconstruction (fused tail: the divergence kernel itself)
 
 
 def find(d, suffix):
