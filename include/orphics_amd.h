@@ -43,7 +43,7 @@ typedef struct oa_plan oa_plan;
 const char* oa_last_error(void);
 /* ABI version = 100 x the build round that last changed a signature in this header; bindings must refuse a library
  * that reports less than the version they were written against (OA_ABI_VERSION) */
-#define OA_ABI_VERSION 403
+#define OA_ABI_VERSION 404
 int oa_version(void);
 /* number of HIP devices visible; <0 on error (no compute) */
 int oa_device_count(void);
@@ -56,8 +56,8 @@ int oa_device_count(void);
  * evaluation on an inner power-of-two plan -- both exact: oa_fft_r2c / oa_fft_c2r / oa_fft_c2c, oa_lens_maps(_hc) and all
  * per-mode / binning / RNG kernels work, `width` / `rband` hints are ignored, and the fused oa_qe_rows /
  * oa_qe_*_cols / oa_fft_cols / oa_fft_pass calls return an error (use the modular oa_qe_legs .. oa_qe_div chain,
- * as orphics_amd/lensing.py:_reconstruct_hc_modular does).  The one-call TT entries (oa_qe_tt, oa_qe_tt_moments(2), oa_mc_run)
- * also take 2^a 3^b 5^c sides, on a BAND GRID (see oa_plan_band_grid); chirp-z sides have no one-call path. */
+ * as orphics_amd/lensing.py:_reconstruct_hc_modular does).  The one-call entries oa_qe_tt, oa_qe_tt_moments(2), oa_mc_run, oa_qe_pol
+ * and oa_qe_mv also take 2^a 3^b 5^c sides, on a BAND GRID (see oa_plan_band_grid, oa_qe_band_bind); chirp-z sides have no one-call path. */
 int oa_plan_create(int ny, int nx, int dtype, oa_plan** out);
 int oa_plan_destroy(oa_plan* p);
 long oa_plan_kpitch(const oa_plan* p);
@@ -203,9 +203,30 @@ int oa_plan_col_grid(const oa_plan* p);
  * which synchronise the device; oa_plan_set_bins keeps the WHOLE N-plane mode counts), and every call runs the fused power-of-two
  * pipeline there: only the input transform (one mixed-radix row R2C that stores the leg columns, then an ny-point DFT evaluated at the
  * leg rows), the Monte-Carlo draw (the leg band of oa_grf_hc's N-grid draw, same Philox counters) and the scatter of kappa's band
- * into the N-grid output / mean-field stack see the map's grid.  oa_qe_pol, oa_qe_mv, oa_qe_tt_splits, oa_mc_run_windowed and
- * oa_qe_tt_stage stay power-of-two only.  oa_plan_band_grid reports (My, Mx), or (0, 0) when no band grid is bound. */
+ * into the N-grid output / mean-field stack see the map's grid.  oa_qe_tt_splits, oa_mc_run_windowed and oa_qe_tt_stage stay
+ * power-of-two only.  oa_plan_band_grid reports (My, Mx), or (0, 0) when no band grid is bound.
+ * oa_qe_pol / oa_qe_mv ON A BAND GRID.  The band-limit argument does not depend on the estimator (every separable piece is a product of
+ * fields confined to the leg band; the cos / sin 2 phi_ell factors live on the same ell lattice, so a copy of their band is exact), but
+ * these two entries take their planes per call, and a stream-ordered call may neither allocate nor synchronise.  oa_qe_band_bind is
+ * their set-up entry on such a plan: host_filters = the nfilters DISTINCT leg-filter planes the calls will pass, host_Fnorm = the
+ * nnorms normalisation planes in the order the calls will pass them, the band, the row grid `mrow` and the column-grid policy `mcol`
+ * (both: -1 auto, a power of two explicit), max_leg_planes = the most leg planes (2 per distinct (source, FG), 1 per distinct
+ * (source, FH)) one oa_qe_mv call will need (0: 3 nfilters).  It resolves (My, Mx) by the rule above (same bounds, same refusals), makes
+ * or reuses a private inner plan -- the TT binding of oa_plan_set_filters is not touched, the bands may differ --, copies every plane
+ * into the inner layout (ONE inner plane per distinct N-grid plane, so oa_qe_mv's sharing of leg transforms by (source, filter) address
+ * survives: 17 fields for TT+TE+EE+EB+TB; the normalisation planes stacked in one evenly spaced allocation, scaled by
+ * (My Mx) / (ny nx), so the divergence of all estimators stays one launch) and takes the inner plan's pools.  It synchronises the device
+ * and may allocate; it copies CONTENTS, so a caller that refills a bound plane in place calls it again.  On a power-of-two plan it
+ * returns 0 and does nothing.  oa_qe_pol / oa_qe_mv on a 2^a 3^b 5^c plan then embed the leg band of their distinct source transforms
+ * (at most 6: T, E, B and the Y-leg sources of a split call) into inner planes in one launch, run on the inner plan and scatter kappa's
+ * band back: `accumulate` adds into the band of `out` only, `zero_outside` zero-fills the complement element by element in the scatter
+ * launch.  They refuse -- naming oa_qe_band_bind -- a filter or normalisation pointer that is not bound, band numbers or an mrow that
+ * differ from the bound ones, and an oa_qe_mv call that needs more leg planes than max_leg_planes.  oa_qe_band_grid reports the (My, Mx)
+ * of this binding, (0, 0) when there is none. */
 int oa_plan_band_grid(const oa_plan* p, int* my, int* mx);
+int oa_qe_band_bind(oa_plan* p, int nfilters, const void* const* host_filters, int nnorms, const void* const* host_Fnorm, int leg_cols,
+                    int kappa_cols, int leg_rows, int kappa_rows, int mrow, int mcol, int max_leg_planes);
+int oa_qe_band_grid(const oa_plan* p, int* my, int* mx);
 /* R of the R-SPLIT from-map path this plan's one-call TT entries run (0 = not this geometry; 4: 8192^2 / 4096^2 maps at the reference's
  * band limits, 8: 16384^2 float64, 2: 8192^2 with up to 1280 leg columns -- the T filter to ell = 6000): the row R2C carries the first
  * radix-R butterfly of the column transform (R = ny / column grid) and ONE single-pass column kernel goes from its output to

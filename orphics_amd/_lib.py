@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("ORPHICS_AMD_LIB", os.path.join(_HERE, "liborphics_amd
 
 OA_F32 = 0
 OA_F64 = 1
-ABI_VERSION = 403     # include/orphics_amd.h OA_ABI_VERSION: the signatures below are those of this version
+ABI_VERSION = 404     # include/orphics_amd.h OA_ABI_VERSION: the signatures below are those of this version
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
@@ -44,6 +44,8 @@ SIGNATURES = {
     "oa_plan_set_col_grid": (c_int, [c_void_p, c_int]),
     "oa_plan_col_grid": (c_int, [c_void_p]),
     "oa_plan_band_grid": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "oa_qe_band_bind": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p] + [c_int] * 7),
+    "oa_qe_band_grid": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "oa_plan_rsplit": (c_int, [c_void_p]),
     "oa_plan_div_fused": (c_int, [c_void_p]),
     "oa_plan_set_option": (c_int, [c_void_p, c_int, c_int]),

@@ -1,4 +1,4 @@
-// BAND GRID of the one-call TT entries on map sides 2^a 3^b 5^c (pipeline.hip, include/orphics_amd.h): the estimator is
+// BAND GRID of the one-call entries (TT, and oa_qe_pol / oa_qe_mv behind oa_qe_band_bind) on map sides 2^a 3^b 5^c (pipeline.hip, include/orphics_amd.h): the estimator is
 // band-limited, so after the input transform everything runs on a small power-of-two (My, Mx) grid through the fused pow2
 // pipeline of an inner plan.  The kernels here move data between the map's N-grid and that inner grid:
 //   * band_map_r2c   : real map -> the leg band of its transform (columns < wl, rows |ky| < rl), written in the inner hc layout.
@@ -7,7 +7,11 @@
 //                      rows (pruned-output DFT, double accumulation, split over row segments + an ordered sum) into the inner plane;
 //   * band_copy      : band region (rows |ky| < r, columns < w) of one grid's hc-layout plane -> the other grid's (filters, bin ids,
 //                      Fourier-space legs N -> inner; kappa_hat inner -> N), optionally scaled;
-//   * band_stack_add : the mean-field stack update of oa_mc_run (f64 interleaved N-grid accumulator += inner kappa_hat planes).
+//   * band_stack_add : the mean-field stack update of oa_mc_run (f64 interleaved N-grid accumulator += inner kappa_hat planes);
+//   * band_embed     : the leg band of n Fourier-space source planes (T, E, B [, the Y-leg sources of a split call]) of oa_qe_pol /
+//                      oa_qe_mv -> n inner planes, ONE launch through a device table of sources (planes on grid z);
+//   * band_scatter   : kappa_hat's band, inner -> N grid, overwriting, adding (accumulate) or with the zero-fill of the complement
+//                      in the same launch.
 // A mode of signed index ky sits at row ky mod ny on one grid and ky mod My on the other; the columns are the same.
 #include <algorithm>
 #include "fft_launch.hpp"
@@ -186,6 +190,69 @@ int band_zero_outside(int dtype, void* out, int ny, long kp, int w, int r, hipSt
     dim3 grid((unsigned)std::min<long>(4, (kp + 255) / 256), ny);
     if (dtype == OA_F32) hipLaunchKernelGGL(band_zero_kernel<float>, grid, dim3(256), 0, st, (cx<float>*)out, ny, kp, w, r);
     else hipLaunchKernelGGL(band_zero_kernel<double>, grid, dim3(256), 0, st, (cx<double>*)out, ny, kp, w, r);
+    OA_LAUNCH_CHECK();
+    return 0;
+}
+
+// n source planes (device table `srcs`, N-grid hc layout) -> n inner planes dstride elements apart, band rows |ky| < r, columns < w.
+// A workgroup is 4 band rows x 64 columns: each wave reads and writes one contiguous row segment.
+template <typename T>
+__global__ __launch_bounds__(256) void band_embed_kernel(const cx<T>* const* __restrict__ srcs, long spitch, int sny, cx<T>* __restrict__ dst,
+                                                         long dstride, long dpitch, int dny, int w, int r) {
+    const int x = blockIdx.x * 64 + threadIdx.x, i = blockIdx.y * 4 + threadIdx.y;
+    if (x >= w || i >= 2 * r - 1) return;
+    const cx<T>* __restrict__ src = srcs[blockIdx.z];
+    dst[blockIdx.z * dstride + (long)band_row(i, r, dny) * dpitch + x] = src[(long)band_row(i, r, sny) * spitch + x];
+}
+int band_embed(int dtype, const void* const* dev_srcs, int n, long spitch, int sny, void* dst, long dstride, long dpitch, int dny, int w, int r,
+               hipStream_t st) {
+    OA_REQUIRE(n >= 1 && w >= 1 && r >= 1 && 2 * r - 1 <= std::min(sny, dny), "band embed: bad band");
+    OA_REQUIRE(w <= spitch && w <= dpitch && (long)dny * dpitch <= dstride, "band embed: band wider than a plane's row pitch");
+    dim3 grid((w + 63) / 64, (2 * r - 1 + 3) / 4, n), block(64, 4);
+    if (dtype == OA_F32)
+        hipLaunchKernelGGL(band_embed_kernel<float>, grid, block, 0, st, (const cx<float>* const*)dev_srcs, spitch, sny, (cx<float>*)dst, dstride, dpitch, dny, w, r);
+    else
+        hipLaunchKernelGGL(band_embed_kernel<double>, grid, block, 0, st, (const cx<double>* const*)dev_srcs, spitch, sny, (cx<double>*)dst, dstride, dpitch, dny, w, r);
+    OA_LAUNCH_CHECK();
+    return 0;
+}
+
+// kappa_hat's band of the inner plane -> the N-grid plane `out`: mode 0 overwrites the band, mode 1 (accumulate) reads, adds and
+// writes the band only.  Mode 2 (zero_outside) SHARES ITS LAUNCH with the zero-fill: the workgroups walk every row of `out` and store
+// either the band value or zero, element by element over all okp columns (what band_zero_outside + a band copy wrote in two launches).
+template <typename T>
+__global__ __launch_bounds__(256) void band_scatter_kernel(const cx<T>* __restrict__ src, long spitch, int sny, cx<T>* __restrict__ out, long okp,
+                                                           int ony, int w, int r, int accumulate) {
+    const int x = blockIdx.x * 64 + threadIdx.x, i = blockIdx.y * 4 + threadIdx.y;
+    if (x >= w || i >= 2 * r - 1) return;
+    const cx<T> v = src[(long)band_row(i, r, sny) * spitch + x];
+    cx<T>* o = out + (long)band_row(i, r, ony) * okp + x;
+    *o = accumulate ? *o + v : v;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void band_scatter_zero_kernel(const cx<T>* __restrict__ src, long spitch, int sny, cx<T>* __restrict__ out,
+                                                                long okp, int ony, int w, int r) {
+    const int y = blockIdx.y * 4 + threadIdx.y;
+    if (y >= ony) return;
+    const bool band = y < r || y > ony - r;
+    const cx<T>* __restrict__ srow = src + (long)(y < r ? y : y - ony + sny) * spitch;      // (read on band rows only)
+    cx<T>* __restrict__ orow = out + (long)y * okp;
+    for (long x = blockIdx.x * 64 + threadIdx.x; x < okp; x += (long)gridDim.x * 64)
+        orow[x] = (band && x < w) ? srow[x] : mk<T>((T)0, (T)0);
+}
+int band_scatter(int dtype, const void* src, long spitch, int sny, void* out, long okp, int ony, int w, int r, int mode, hipStream_t st) {
+    OA_REQUIRE(w >= 1 && r >= 1 && 2 * r - 1 <= std::min(sny, ony), "band scatter: bad band");
+    OA_REQUIRE(w <= spitch && w <= okp, "band scatter: band wider than a plane's row pitch");
+    const dim3 block(64, 4);
+    if (mode == 2) {
+        dim3 grid((unsigned)std::min<long>(4, (okp + 63) / 64), (ony + 3) / 4);
+        if (dtype == OA_F32) hipLaunchKernelGGL(band_scatter_zero_kernel<float>, grid, block, 0, st, (const cx<float>*)src, spitch, sny, (cx<float>*)out, okp, ony, w, r);
+        else hipLaunchKernelGGL(band_scatter_zero_kernel<double>, grid, block, 0, st, (const cx<double>*)src, spitch, sny, (cx<double>*)out, okp, ony, w, r);
+    } else {
+        dim3 grid((w + 63) / 64, (2 * r - 1 + 3) / 4);
+        if (dtype == OA_F32) hipLaunchKernelGGL(band_scatter_kernel<float>, grid, block, 0, st, (const cx<float>*)src, spitch, sny, (cx<float>*)out, okp, ony, w, r, mode);
+        else hipLaunchKernelGGL(band_scatter_kernel<double>, grid, block, 0, st, (const cx<double>*)src, spitch, sny, (cx<double>*)out, okp, ony, w, r, mode);
+    }
     OA_LAUNCH_CHECK();
     return 0;
 }

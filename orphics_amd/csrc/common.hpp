@@ -183,6 +183,11 @@ int band_copy(int kind, const void* src, long spitch, int sny, void* dst, long d
 int band_zero_outside(int dtype, void* out, int ny, long kp, int w, int r, hipStream_t st);
 int band_stack_add(int dtype, const void* src, long spitch, int sny, int nbatch, long sstride, double* acc, long apitch, int any, int w, int r,
                    hipStream_t st);
+// oa_qe_pol / oa_qe_mv on the band grid: n source planes through a device table -> inner planes (one launch); kappa's band back
+// (mode 0 overwrite, 1 accumulate, 2 overwrite + zero-fill of the complement in the same launch)
+int band_embed(int dtype, const void* const* dev_srcs, int n, long spitch, int sny, void* dst, long dstride, long dpitch, int dny, int w, int r,
+               hipStream_t st);
+int band_scatter(int dtype, const void* src, long spitch, int sny, void* out, long okp, int ony, int w, int r, int mode, hipStream_t st);
 // the leg band of oa_grf_hc's N-grid draw (same Philox counters) into the hc layout of an (my, okp) grid, nreal planes zstride elements apart
 int grf_band_inner(oa_plan* p, uint64_t seed, uint64_t stream_id, int nreal, const void* covsqrt_hc, void* out, int my, long okp, long zstride,
                    int width, int rband, hipStream_t stream);

@@ -6,6 +6,8 @@
 #include <dlfcn.h>
 #include <cstdlib>
 #include <algorithm>
+#include <string>
+#include <utility>
 #include <vector>
 #include "common.hpp"
 #include "fft_plan.hpp"
@@ -81,7 +83,21 @@ struct Pipeline {
     int32_t* bids = nullptr;          // inner-layout bin ids (-1 outside kappa's band)
     void* brows = nullptr;            // band input transform: row pass (ny x leg_cols complex) + column-pass partial sums
     size_t brows_bytes = 0;
+    // ... and oa_qe_pol / oa_qe_mv there: a PRIVATE inner plan (their bands differ from the TT binding's: kmask_P, the widest band of
+    // an estimator set) with inner-layout copies of the planes handed to oa_qe_band_bind, looked up by their N-grid address
+    struct PolBind {
+        bool bound = false;
+        oa_plan* plan = nullptr;
+        int my = 0, mx = 0;
+        int wl = 0, wk = 0, rl = 0, rk = 0, mrow = -1;
+        std::vector<const void*> fkey, nkey;   // the bound N-grid filter / normalisation planes; inner plane i belongs to key i
+        void* planes = nullptr;                // inner layout: nf filter planes | nn normalisation planes, stacked in the bound order |
+        size_t planes_bytes = 0;               //               POL_SRC_MAX source planes (hc)
+        void** stab = nullptr;                 // device table of the N-grid source planes of the batched embed
+        std::vector<const void*> skey;         // what it holds
+    } pb;
 };
+constexpr int POL_SRC_MAX = 6;                 // T, E, B and the Y-leg sources of a split call
 
 static size_t plane_bytes(const oa_plan* p) { return (size_t)p->ny * p->kp * 2 * (p->dtype == OA_F32 ? 4 : 8); }
 
@@ -110,6 +126,9 @@ void pipeline_release(oa_plan* p) {
     if (q->bplanes) (void)hipFree(q->bplanes);
     if (q->bids) (void)hipFree(q->bids);
     if (q->brows) (void)hipFree(q->brows);
+    if (q->pb.plan) (void)oa_plan_destroy(q->pb.plan);
+    if (q->pb.planes) (void)hipFree(q->pb.planes);
+    if (q->pb.stab) (void)hipFree(q->pb.stab);
     delete q;
     p->pipe = nullptr;
 }
@@ -221,6 +240,12 @@ static int mixed_moments(oa_plan* p, Pipeline* q, const void* map, int64_t* n, d
 static int mixed_mc_run(oa_plan* p, Pipeline* q, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, int64_t* n, double* S,
                         double* C, double* meanfield_acc, hipStream_t st);
 static void band_options(Pipeline* q);
+struct MvCall {            // the arguments of oa_qe_mv (oa_qe_pol: nest = 1 and pol set)
+    int nest; const int* npieces; const double* signs; const void* const* FG; const void* const* FH; const int* swap;
+    const void* const* kX; const void* const* kY; const void* const* Fn; bool pol;
+};
+static int mixed_qe_mv(oa_plan* p, Pipeline* q, const MvCall& c, void* out, int accumulate, int wl, int wk, int rl, int rk, int mrow, int zero_outside,
+                       hipStream_t st);
 }  // namespace oa
 #define OA_NOT_MIXED(p, what) \
     OA_REQUIRE(!(p)->mixed, what ": not available on map sides that are not powers of two (one-call TT entries there: oa_qe_tt, oa_qe_tt_moments(2), oa_mc_run)")
@@ -276,10 +301,12 @@ int oa_plan_set_option(oa_plan* p, int option, int value) {
 namespace oa {
 // the band plan runs the one-call launches of a mixed plan: it follows the options set on the outer plan
 static void band_options(Pipeline* q) {
-    if (!q->band || !q->band->pipe) return;
-    Pipeline* b = (Pipeline*)q->band->pipe;
-    b->opt_mc_batch = q->opt_mc_batch; b->opt_mv_batch = q->opt_mv_batch; b->opt_mv_rowbatch = q->opt_mv_rowbatch;
-    b->opt_mv_chain = q->opt_mv_chain; b->opt_divbin = q->opt_divbin; b->opt_win_fused = q->opt_win_fused;
+    for (oa_plan* inner : {q->band, q->pb.plan}) {
+        if (!inner || !inner->pipe) continue;
+        Pipeline* b = (Pipeline*)inner->pipe;
+        b->opt_mc_batch = q->opt_mc_batch; b->opt_mv_batch = q->opt_mv_batch; b->opt_mv_rowbatch = q->opt_mv_rowbatch;
+        b->opt_mv_chain = q->opt_mv_chain; b->opt_divbin = q->opt_divbin; b->opt_win_fused = q->opt_win_fused;
+    }
 }
 }  // namespace oa
 extern "C" {
@@ -461,8 +488,13 @@ int oa_qe_pol(oa_plan* p, int npieces, const double* host_signs, const void* con
               const int* host_swap, const void* kX, const void* kY, const void* Fnorm, void* out, int accumulate,
               int leg_cols, int kappa_cols, int leg_rows, int kappa_rows, int mrow, int zero_outside, void* stream) {
     OA_REQUIRE(p && npieces >= 1 && host_signs && host_FG && host_FH && kX && kY && Fnorm && out, "oa_qe_pol: bad argument");
-    OA_NEED_POW2(p, "oa_qe_pol");
+    OA_REQUIRE(p->pow2 || p->mixed, "oa_qe_pol: map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path "
+               "(use the modular oa_qe_legs / oa_mul_real / oa_qe_div calls)");
     Pipeline* q = pipe_of(p);
+    if (p->mixed) {                                 // BAND GRID: the planes bound by oa_qe_band_bind, on the inner plan
+        const MvCall c{1, &npieces, host_signs, host_FG, host_FH, host_swap, &kX, &kY, &Fnorm, true};
+        return mixed_qe_mv(p, q, c, out, accumulate, leg_cols, kappa_cols, leg_rows, kappa_rows, mrow, zero_outside, (hipStream_t)stream);
+    }
     if (int rc = ensure_work(p, q)) return rc;
     if (!accumulate && zero_outside && out != q->kk)
         if (int rc = zero_complement(p, out, kappa_cols, kappa_rows, (hipStream_t)stream)) return rc;
@@ -593,8 +625,13 @@ int oa_qe_mv(oa_plan* p, int nest, const int* host_npieces, const double* host_s
              int mrow, int zero_outside, void* stream) {
     OA_REQUIRE(p && nest >= 1 && host_npieces && host_signs && host_FG && host_FH && host_kX && host_kY && host_Fnorm && out,
                "oa_qe_mv: bad argument");
-    OA_NEED_POW2(p, "oa_qe_mv");
+    OA_REQUIRE(p->pow2 || p->mixed, "oa_qe_mv: map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path "
+               "(use the modular oa_qe_legs / oa_mul_real / oa_qe_div calls)");
     Pipeline* q = pipe_of(p);
+    if (p->mixed) {                                 // BAND GRID: the planes bound by oa_qe_band_bind, on the inner plan
+        const MvCall c{nest, host_npieces, host_signs, host_FG, host_FH, host_swap, host_kX, host_kY, host_Fnorm, false};
+        return mixed_qe_mv(p, q, c, out, accumulate, leg_cols, kappa_cols, leg_rows, kappa_rows, mrow, zero_outside, (hipStream_t)stream);
+    }
     if (int rc = ensure_work(p, q)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (!accumulate && zero_outside && out != q->kk)
@@ -989,6 +1026,21 @@ static int band_grid_rule(const oa_plan* p, int mrow, int mcol, int wl, int wk, 
     if (int rc = band_side(mrow, std::max(2L * wl + wk, 2L * wk), p->nx, "x", mx)) return rc;
     return band_side(mcol, std::max(2L * rl + rk, 2L * rk), p->ny, "y", my);
 }
+// an inner power-of-two plan of (my, mx) points on the ell lattice of p
+static int band_inner_plan(const oa_plan* p, int my, int mx, oa_plan** out) {
+    *out = nullptr;
+    oa_plan* b = nullptr;
+    if (int rc = oa_plan_create(my, mx, p->dtype, &b)) return rc;
+    std::vector<double> ly(p->ny), lx(p->nx), bly(my), blx(mx);
+    hipError_t e = hipMemcpy(ly.data(), p->ly64, p->ny * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(lx.data(), p->lx64, p->nx * sizeof(double), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { (void)oa_plan_destroy(b); return fail(std::string("band grid: reading the ell axes: ") + hipGetErrorString(e)); }
+    for (int i = 0; i < my; ++i) bly[i] = ly[i < my / 2 ? i : i - my + p->ny];    // the N grid's ell at the same signed index
+    for (int i = 0; i < mx; ++i) blx[i] = lx[i < mx / 2 ? i : i - mx + p->nx];
+    if (int rc = oa_plan_set_laxes(b, bly.data(), blx.data())) { (void)oa_plan_destroy(b); return rc; }
+    *out = b;
+    return 0;
+}
 static size_t band_real_bytes(const oa_plan* b) { return (size_t)b->ny * b->kp * (b->dtype == OA_F32 ? 4 : 8); }
 // (re)make the band plan for the bound filters, copy the filters (and the bins) into its layout and bind them there.  Set-up call:
 // synchronises the device (the caller's planes may have been written on any stream)
@@ -1001,13 +1053,7 @@ static int mixed_bind(oa_plan* p, Pipeline* q) {
         if (q->bplanes) { (void)hipFree(q->bplanes); q->bplanes = nullptr; }
         if (q->bids) { (void)hipFree(q->bids); q->bids = nullptr; }
         q->bmy = q->bmx = 0;
-        if (int rc = oa_plan_create(my, mx, p->dtype, &q->band)) return rc;
-        std::vector<double> ly(p->ny), lx(p->nx), bly(my), blx(mx);
-        OA_HIP(hipMemcpy(ly.data(), p->ly64, p->ny * sizeof(double), hipMemcpyDeviceToHost));
-        OA_HIP(hipMemcpy(lx.data(), p->lx64, p->nx * sizeof(double), hipMemcpyDeviceToHost));
-        for (int i = 0; i < my; ++i) bly[i] = ly[i < my / 2 ? i : i - my + p->ny];    // the N grid's ell at the same signed index
-        for (int i = 0; i < mx; ++i) blx[i] = lx[i < mx / 2 ? i : i - mx + p->nx];
-        if (int rc = oa_plan_set_laxes(q->band, bly.data(), blx.data())) return rc;
+        if (int rc = band_inner_plan(p, my, mx, &q->band)) return rc;
         OA_HIP(hipMalloc(&q->bplanes, 3 * band_real_bytes(q->band) + 2 * plane_bytes(q->band)));
         OA_HIP(hipMalloc((void**)&q->bids, (size_t)my * q->band->kp * sizeof(int32_t)));
         q->bmy = my; q->bmx = mx;
@@ -1118,9 +1164,159 @@ static int mixed_mc_run(oa_plan* p, Pipeline* q, uint64_t base_seed, long sim_lo
     }
     return 0;
 }
+/* ---- oa_qe_pol / oa_qe_mv on the band grid -------------------------------------------------------------------------------------------
+ * These entries take their filter planes per call, so the inner-layout copies are made by a set-up entry (oa_qe_band_bind, which may
+ * allocate and synchronise) and a call only looks its pointers up: ONE inner plane per distinct N-grid plane, so that the inner
+ * oa_qe_mv's sharing of leg transforms by (source, filter) address is the caller's; the normalisation planes stacked in the bound
+ * order, so that a call that passes them in that order keeps the one-launch divergence.  A call embeds its distinct source transforms
+ * in one launch, runs the inner oa_qe_pol / oa_qe_mv into the inner plan's kappa plane and scatters kappa's band back: no allocation,
+ * no synchronisation (pool, tables and column-grid twiddles of the inner plan are taken at set-up). */
+static int pol_bind(oa_plan* p, Pipeline* q, int nf, const void* const* filters, int nn, const void* const* norms, int wl, int wk, int rl, int rk,
+                    int mrow, int mcol, int max_leg_planes) {
+    Pipeline::PolBind& B = q->pb;
+    B.bound = false;
+    int my = 0, mx = 0;
+    if (int rc = band_grid_rule(p, mrow, mcol, wl, wk, rl, rk, &my, &mx)) return rc;
+    OA_HIP(hipDeviceSynchronize());                 // the caller's planes may have been written on any stream; the old copies may be in use
+    if (!B.plan || B.my != my || B.mx != mx) {
+        if (B.plan) { (void)oa_plan_destroy(B.plan); B.plan = nullptr; }
+        B.my = B.mx = 0;
+        if (int rc = band_inner_plan(p, my, mx, &B.plan)) return rc;
+        B.my = my; B.mx = mx;
+    }
+    oa_plan* b = B.plan;
+    Pipeline* qb = pipe_of(b);
+    band_options(q);
+    const size_t rb = band_real_bytes(b), cb = plane_bytes(b), need = (size_t)(nf + nn) * rb + (size_t)POL_SRC_MAX * cb;
+    if (B.planes_bytes < need) {
+        if (B.planes) { (void)hipFree(B.planes); B.planes = nullptr; B.planes_bytes = 0; }
+        OA_HIP(hipMalloc(&B.planes, need));
+        B.planes_bytes = need;
+    }
+    OA_HIP(hipMemset(B.planes, 0, need));           // zero outside the bands (source planes: only their band is ever written)
+    if (!B.stab) OA_HIP(hipMalloc((void**)&B.stab, POL_SRC_MAX * sizeof(void*)));
+    B.skey.clear();
+    const int kind = p->dtype == OA_F32 ? 0 : 1;
+    const double fscale = (double)b->ny * b->nx / ((double)p->ny * p->nx);
+    char* f = (char*)B.planes;
+    for (int i = 0; i < nf; ++i)
+        if (int rc = band_copy(kind, filters[i], p->kp, p->ny, f + (size_t)i * rb, b->kp, my, wl, rl, 1.0, nullptr)) return rc;
+    for (int i = 0; i < nn; ++i)
+        if (int rc = band_copy(kind, norms[i], p->kp, p->ny, f + (size_t)(nf + i) * rb, b->kp, my, wk, rk, fscale, nullptr)) return rc;
+    // everything the inner entries would otherwise take on first use
+    if (int rc = ensure_work(b, qb)) return rc;
+    const size_t es = 2 * (b->dtype == OA_F32 ? 4 : 8);
+    const size_t lb = (size_t)work_pitch(b, wl) * b->ny * es, lbk = (size_t)work_pitch(b, wk) * b->ny * es;
+    if (int rc = ensure_pool(qb, (size_t)(max_leg_planes > 0 ? max_leg_planes : 3 * nf) * lb + 4 * (size_t)nn * lbk)) return rc;
+    if (!qb->mv_ftab) OA_HIP(hipMalloc((void**)&qb->mv_ftab, 32 * sizeof(void*)));
+    if (!qb->mv_rtab) OA_HIP(hipMalloc(&qb->mv_rtab, 64 * 64 + 1024));
+    int imy = 0;
+    if (int rc = resolve_my(b, qb->mcol, rl, rk, &imy)) return rc;      // (an explicit grid above the automatic one: the inner column grid's table)
+    OA_HIP(hipDeviceSynchronize());
+    B.fkey.assign(filters, filters + nf);
+    B.nkey.assign(norms, norms + nn);
+    B.wl = wl; B.wk = wk; B.rl = rl; B.rk = rk; B.mrow = mrow;
+    B.bound = true;
+    return 0;
+}
+static void* pol_inner(const std::vector<const void*>& key, const void* ptr, char* base, size_t stride) {
+    for (size_t i = 0; i < key.size(); ++i) if (key[i] == ptr) return base + i * stride;
+    return nullptr;
+}
+static int mixed_qe_mv(oa_plan* p, Pipeline* q, const MvCall& c, void* out, int accumulate, int wl, int wk, int rl, int rk, int mrow, int zero_outside,
+                       hipStream_t st) {
+    const char* who = c.pol ? "oa_qe_pol" : "oa_qe_mv";
+    Pipeline::PolBind& B = q->pb;
+    if (!B.bound)
+        return fail(std::string(who) + ": on map sides that are not powers of two the filter and normalisation planes are bound first (oa_qe_band_bind)");
+    if (wl != B.wl || wk != B.wk || rl != B.rl || rk != B.rk || mrow != B.mrow)
+        return fail(std::string(who) + ": leg / kappa columns and rows or the row grid differ from the bound ones (call oa_qe_band_bind for this band)");
+    oa_plan* b = B.plan;
+    Pipeline* qb = (Pipeline*)b->pipe;
+    band_options(q);
+    const size_t rb = band_real_bytes(b), cb = plane_bytes(b), es = 2 * (b->dtype == OA_F32 ? 4 : 8);
+    char* const fbase = (char*)B.planes;
+    char* const nbase = fbase + B.fkey.size() * rb;
+    char* const sbase = nbase + B.nkey.size() * rb;
+    int total = 0;
+    for (int e = 0; e < c.nest; ++e) {
+        OA_REQUIRE(c.npieces[e] >= 1 && c.kX[e] && c.kY[e] && c.Fn[e], "oa_qe_mv: bad estimator entry");
+        total += c.npieces[e];
+    }
+    std::vector<const void*> iFG(total), iFH(total), iFn(c.nest), ikX(c.nest), ikY(c.nest), srcs;
+    for (int i = 0; i < total; ++i) {
+        iFG[i] = pol_inner(B.fkey, c.FG[i], fbase, rb);
+        iFH[i] = pol_inner(B.fkey, c.FH[i], fbase, rb);
+        if (!iFG[i] || !iFH[i]) return fail(std::string(who) + ": a filter plane of this call is not bound (oa_qe_band_bind binds every distinct plane)");
+    }
+    auto source = [&](const void* s) {
+        size_t k = 0;
+        while (k < srcs.size() && srcs[k] != s) ++k;
+        if (k == srcs.size()) srcs.push_back(s);
+        return (const void*)(sbase + k * cb);
+    };
+    for (int e = 0; e < c.nest; ++e) {
+        iFn[e] = pol_inner(B.nkey, c.Fn[e], nbase, rb);
+        if (!iFn[e]) return fail(std::string(who) + ": a normalisation plane of this call is not bound (oa_qe_band_bind)");
+        ikX[e] = source(c.kX[e]);
+        ikY[e] = source(c.kY[e]);
+    }
+    if ((int)srcs.size() > POL_SRC_MAX) return fail(std::string(who) + ": more than 6 distinct source transforms in one call on a band grid");
+    if (!c.pol) {                                     // the inner entry's pool: sized by oa_qe_band_bind, never grown here
+        std::vector<std::pair<const void*, const void*>> grad, hpl;
+        auto add = [](std::vector<std::pair<const void*, const void*>>& v, const void* s, const void* f) {
+            for (auto& k : v) if (k.first == s && k.second == f) return;
+            v.emplace_back(s, f);
+        };
+        int at = 0;
+        for (int e = 0; e < c.nest; ++e)
+            for (int i = 0; i < c.npieces[e]; ++i, ++at) {
+                const bool sw = c.swap && c.swap[at];
+                add(grad, sw ? ikY[e] : ikX[e], iFG[at]);
+                add(hpl, sw ? ikX[e] : ikY[e], iFH[at]);
+            }
+        const size_t lb = (size_t)work_pitch(b, wl) * b->ny * es, lbk = (size_t)work_pitch(b, wk) * b->ny * es;
+        if ((2 * grad.size() + hpl.size()) * lb + 4 * (size_t)c.nest * lbk > qb->split_bytes)
+            return fail("oa_qe_mv: this call needs " + std::to_string(2 * grad.size() + hpl.size()) + " leg planes and " + std::to_string(c.nest) +
+                        " estimators, more than oa_qe_band_bind was told (max_leg_planes, normalisation planes)");
+    }
+    if (srcs != B.skey) {                             // (pageable source: staged before the call returns; ordered on this stream)
+        OA_HIP(hipMemcpyAsync(B.stab, srcs.data(), srcs.size() * sizeof(void*), hipMemcpyHostToDevice, st));
+        B.skey = srcs;
+    }
+    int rc = band_embed(p->dtype, (const void* const*)B.stab, (int)srcs.size(), p->kp, p->ny, sbase, (long)(cb / es), b->kp, b->ny, wl, rl, st);
+    if (rc) return rc;
+    if (c.pol) rc = oa_qe_pol(b, c.npieces[0], c.signs, iFG.data(), iFH.data(), c.swap, ikX[0], ikY[0], iFn[0], qb->kk, 0, wl, wk, rl, rk, -1, 0, st);
+    else rc = oa_qe_mv(b, c.nest, c.npieces, c.signs, iFG.data(), iFH.data(), c.swap, ikX.data(), ikY.data(), iFn.data(), qb->kk, 0, wl, wk, rl, rk,
+                       -1, 0, st);
+    if (rc) return rc;
+    return band_scatter(p->dtype, qb->kk, b->kp, b->ny, out, p->kp, p->ny, wk, rk, accumulate ? 1 : (zero_outside ? 2 : 0), st);
+}
 }  // namespace oa
 
 extern "C" {
+
+int oa_qe_band_bind(oa_plan* p, int nfilters, const void* const* host_filters, int nnorms, const void* const* host_Fnorm, int leg_cols,
+                    int kappa_cols, int leg_rows, int kappa_rows, int mrow, int mcol, int max_leg_planes) {
+    OA_REQUIRE(p && host_filters && host_Fnorm && nfilters >= 1 && nfilters <= 256 && nnorms >= 1 && nnorms <= 64 && max_leg_planes >= 0,
+               "oa_qe_band_bind: bad argument");
+    for (int i = 0; i < nfilters; ++i) OA_REQUIRE(host_filters[i], "oa_qe_band_bind: NULL filter plane");
+    for (int i = 0; i < nnorms; ++i) OA_REQUIRE(host_Fnorm[i], "oa_qe_band_bind: NULL normalisation plane");
+    if (p->pow2) return 0;                          // power-of-two plans take their planes per call
+    OA_REQUIRE(p->mixed, "oa_qe_band_bind: map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path "
+               "(use the modular oa_qe_legs / oa_mul_real / oa_qe_div calls)");
+    OA_REQUIRE(p->have_laxes, "oa_qe_band_bind: call oa_plan_set_laxes first");
+    return pol_bind(p, pipe_of(p), nfilters, host_filters, nnorms, host_Fnorm, leg_cols, kappa_cols, leg_rows, kappa_rows, mrow, mcol, max_leg_planes);
+}
+
+int oa_qe_band_grid(const oa_plan* p, int* my, int* mx) {
+    OA_REQUIRE(p && my && mx, "oa_qe_band_grid: NULL argument");
+    const Pipeline* q = (const Pipeline*)p->pipe;
+    const bool bound = q && q->pb.bound;
+    *my = bound ? q->pb.my : 0;
+    *mx = bound ? q->pb.mx : 0;
+    return 0;
+}
 
 int oa_mc_run(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, int64_t* n, double* S, double* C,
               double* meanfield_acc, void* stream) {

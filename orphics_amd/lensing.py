@@ -30,6 +30,25 @@ def _half(a, nxh):
     return np.ascontiguousarray(a[:, :nxh + 1])
 
 
+def widest(vals):
+    """Active columns / rows common to several band-limited planes: the widest one is exact for all of them (each vanishes outside
+    its own), and 0 (= everything, no pruning) poisons the set."""
+    vals = [int(v) for v in vals]
+    return 0 if any(v == 0 for v in vals) else max(vals)
+
+
+def pol_bands(gens, wK=None):
+    """(leg_cols, kappa_cols, leg_rows, kappa_rows) of ONE call over the estimators whose set-ups (``Estimator._setup_general``: dicts
+    with wl, wk, rl, rk) are ``gens``: the widest leg band; kappa's band is the widest normalisation band or, when the call brings its
+    own normalisation planes (MV weights, ``norm=``), the support ``wK = (cols, rows)`` of the kappa mask that bounds them.  These
+    are the numbers handed to the band-grid rule (``Engine.band_grid``) and to ``oa_qe_band_bind``."""
+    gens = list(gens)
+    wl, rl = widest(g["wl"] for g in gens), widest(g["rl"] for g in gens)
+    if wK is not None:
+        return wl, int(wK[0]), rl, int(wK[1])
+    return wl, widest(g["wk"] for g in gens), rl, widest(g["rk"] for g in gens)
+
+
 def _safe_div(num, den):
     with np.errstate(divide="ignore", invalid="ignore"):
         out = num / den
@@ -727,11 +746,79 @@ class Estimator(object):
                              rl=self._support_rows(*hostf), rk=self._support_rows(Fnorm))
         return self._gen[XY]
 
+    # ---- one-call path of the general estimators on sides 2^a 3^b 5^c (BAND GRID, include/orphics_amd.h oa_qe_band_bind) ----
+    def _pol_args(self, XY_or_estimators, ext_norm):
+        single = isinstance(XY_or_estimators, str)
+        ests = (XY_or_estimators,) if single else tuple(XY_or_estimators)
+        return ests, (not single) if ext_norm is None else bool(ext_norm)
+
+    def _pol_bands(self, estimators, ext_norm):
+        G = [self._setup_general(XY) for XY in estimators]
+        if ext_norm and getattr(self, "_wK", None) is None:
+            self._wK = (self._support_cols(self.mask_K), self._support_rows(self.mask_K))
+        return pol_bands(G, self._wK if ext_norm else None)
+
+    def pol_band_grid(self, XY_or_estimators=("TT", "TE", "EE", "EB", "TB"), ext_norm=None):
+        """(My, Mx) of the band grid ONE ``oa_qe_mv`` call over these estimators runs on (a string: one estimator through
+        :meth:`reconstruct_hc`; a sequence: the MV combination of :meth:`reconstruct_mv_hc`), or None where there is none: power-of-two
+        and chirp-z plans, unbounded filters, the map's own row / column grid, a grid not smaller than the map.  ``ext_norm``: the
+        call brings its own normalisation planes (default: the MV combination does, one estimator does not)."""
+        e = self.eng
+        if not e.mixed:
+            return None
+        ests, ext = self._pol_args(XY_or_estimators, ext_norm)
+        wl, wk, rl, rk = self._pol_bands(ests, ext)
+        return e.band_grid(wl, wk, rl, rk, self.mrow, self.mcol)
+
+    def one_call_pol(self, XY_or_estimators=("TT", "TE", "EE", "EB", "TB"), ext_norm=None):
+        """True when ``oa_qe_pol`` / ``oa_qe_mv`` serve these estimators in one call: power-of-two sides, or sides 2^a 3^b 5^c whose
+        band grid resolves for the call's bands (:meth:`pol_band_grid`).  Otherwise :meth:`reconstruct_hc` and
+        :meth:`reconstruct_mv_hc` take the modular chain."""
+        return True if self.eng.pow2 else self.pol_band_grid(XY_or_estimators, ext_norm) is not None
+
+    def _pol_bind(self, estimators, norms, bands, split):
+        """Bind the distinct filter planes of ``estimators`` and the normalisation planes ``norms`` (in call order) to this estimator's
+        2^a 3^b 5^c plan (``oa_qe_band_bind``: a set-up call, synchronises).  Plans are shared per geometry: bound again whenever
+        another handle, another estimator set, other planes or another grid policy used the plan in between.  The inner copies hold
+        the planes' CONTENTS: a caller that refills one in place drops ``eng._pol_owner``."""
+        import ctypes
+        from ._lib import check
+        e = self.eng
+        planes, seen, gl, hl = [], set(), set(), set()
+        for XY in estimators:
+            sx, sy = (("X", XY[0]), ("Y", XY[1])) if split else (XY[0], XY[1])
+            for (_, fg, fh, sw) in self._gen[XY]["pieces"]:
+                for t in (fg, fh):
+                    if t.data_ptr() not in seen:
+                        seen.add(t.data_ptr())
+                        planes.append(t)
+                gl.add((sy if sw else sx, fg.data_ptr()))
+                hl.add((sx if sw else sy, fh.data_ptr()))
+        nleg = 2 * len(gl) + len(hl)                   # leg planes of one call: a gradient pair / one H plane per distinct filtered field
+        key = (self._token, tuple(t.data_ptr() for t in planes), tuple(t.data_ptr() for t in norms), tuple(bands), self.mrow, self.mcol, nleg)
+        if getattr(e, "_pol_owner", None) != key:
+            e._pol_owner = None
+            wl, wk, rl, rk = bands
+            check(e.lib.oa_qe_band_bind(e.plan, len(planes), (ctypes.c_void_p * len(planes))(*[t.data_ptr() for t in planes]), len(norms),
+                                        (ctypes.c_void_p * len(norms))(*[t.data_ptr() for t in norms]), int(wl), int(wk), int(rl), int(rk),
+                                        int(self.mrow), int(self.mcol), nleg))
+            e._pol_owner = key
+        return e
+
+    @property
+    def pol_bound_grid(self):
+        """(My, Mx) of the plan's current ``oa_qe_band_bind`` binding (``oa_qe_band_grid``); (0, 0) = none."""
+        import ctypes
+        from ._lib import check
+        my, mx = ctypes.c_int(0), ctypes.c_int(0)
+        check(self.eng.lib.oa_qe_band_grid(self.eng.plan, ctypes.byref(my), ctypes.byref(mx)))
+        return my.value, mx.value
+
     def reconstruct_hc(self, XY, kX, kY, out=None, norm=None, accumulate=False):
         """General estimator on hc tensors: kX = DFT of field XY[0], kY = DFT of field XY[1].
         ``norm`` overrides the divergence/normalisation plane (MV weights), ``accumulate`` adds into ``out``."""
         e = self.eng
-        if not e.pow2:
+        if not e.pow2 and not self.one_call_pol(XY, norm is not None):
             return self._reconstruct_hc_modular(XY, kX, kY, out, norm, accumulate)
         import ctypes
         from ._lib import check
@@ -758,9 +845,12 @@ class Estimator(object):
             zero = 1 if ((wk or rk) and not accumulate and owned_clean_region(out) != (wk, rk)) else 0
         Fn = G["Fnorm"] if norm is None else norm
         e._ordered()
-        check(e.lib.oa_plan_set_col_grid(e.plan, int(self.mcol)))       # plans are shared per geometry: policy per call
-        if getattr(e, "_pipe_owner", None) is not self._token:
-            e._pipe_owner = None          # the call above re-resolved the grid of another handle's TT binding: it binds again on its next call
+        if e.mixed:                           # BAND GRID: the planes live on the plan's inner grid (the TT binding is not touched)
+            self._pol_bind((XY,), [Fn], (wl, wk, rl, rk), split=True)
+        else:
+            check(e.lib.oa_plan_set_col_grid(e.plan, int(self.mcol)))       # plans are shared per geometry: policy per call
+            if getattr(e, "_pipe_owner", None) is not self._token:
+                e._pipe_owner = None      # the call above re-resolved the grid of another handle's TT binding: it binds again on its next call
         # one estimator through oa_qe_mv (nest = 1): the same pieces as oa_qe_pol, with all distinct leg planes of the estimator
         # in ONE inverse pass-1 launch and one pass-2 launch (a piece pair shares its cos / sin filtered fields)
         one = ctypes.c_void_p * 1
@@ -829,7 +919,13 @@ class Estimator(object):
                 planes[XY] = stack[i]
             self._mv = (key, planes)
         f = {"T": kT, "E": kE, "B": kB}
-        if not e.pow2 or not fused:
+        if not e.pow2 and not (fused and self.one_call_pol(key)):
+            # sides that are not powers of two without a band grid for this set (or fused=False): the modular chain per estimator
+            out = e.hc() if out is None else out
+            for i, XY in enumerate(estimators):
+                self._reconstruct_hc_modular(XY, f[XY[0]], f[XY[1]], out=out, norm=self._mv[1][XY], accumulate=(i > 0))
+            return out
+        if not fused:
             out = e.hc() if out is None else out
             for i, XY in enumerate(estimators):
                 self.reconstruct_hc(XY, f[XY[0]], f[XY[1]], out=out, norm=self._mv[1][XY], accumulate=(i > 0))
@@ -845,7 +941,6 @@ class Estimator(object):
             if getattr(self, "_wK", None) is None:
                 self._wK = (self._support_cols(self.mask_K), self._support_rows(self.mask_K))
             # common active region: filters vanish outside their own, so the widest one is exact for all (0 = everything)
-            widest = lambda vals: 0 if any(v == 0 for v in vals) else max(vals)      # noqa: E731
             args = dict(ne=len(G), npieces=(ctypes.c_int * len(G))(*[len(g_["pieces"]) for g_ in G]),
                         signs=(ctypes.c_double * n)(*[float(pc[0]) for pc in pcs]),
                         fgs=(ctypes.c_void_p * n)(*[pc[1].data_ptr() for pc in pcs]),
@@ -866,9 +961,12 @@ class Estimator(object):
         kxs = (ctypes.c_void_p * a["ne"])(*[f[XY[0]].data_ptr() for XY in estimators])
         kys = (ctypes.c_void_p * a["ne"])(*[f[XY[1]].data_ptr() for XY in estimators])
         e._ordered()
-        check(e.lib.oa_plan_set_col_grid(e.plan, int(self.mcol)))
-        if getattr(e, "_pipe_owner", None) is not self._token:
-            e._pipe_owner = None          # the call above re-resolved the grid of another handle's TT binding: it binds again on its next call
+        if e.mixed:                           # BAND GRID: every distinct filter plane and the stacked MV planes, bound once per set
+            self._pol_bind(key, [self._mv[1][XY] for XY in estimators], (a["wl"], wk, a["rl"], rk), split=False)
+        else:
+            check(e.lib.oa_plan_set_col_grid(e.plan, int(self.mcol)))
+            if getattr(e, "_pipe_owner", None) is not self._token:
+                e._pipe_owner = None      # the call above re-resolved the grid of another handle's TT binding: it binds again on its next call
         check(e.lib.oa_qe_mv(e.plan, a["ne"], a["npieces"], a["signs"], a["fgs"], a["fhs"], a["swaps"], kxs, kys, a["fns"], _ptr(out), 0,
                              int(a["wl"]), int(wk), int(a["rl"]), int(rk), int(self.mrow), zero, _stream()))
         mark_dirty(out)

@@ -5,7 +5,11 @@ modular chain on the same plan, on the reference notebooks' patches (tutorials/t
     mc_sims_per_s           : GaussianN0MonteCarlo.run_local (oa_mc_run, bandpower moments, no mean field)
     map_bytes               : bytes of the real map the band input transform reads
 --only-onecall N: run N one-call reconstructions per geometry and nothing else (the workload for
-    rocprofv3 --kernel-trace --stats -- python tools/mixed_onecall_bench.py --only-onecall 200)."""
+    rocprofv3 --kernel-trace --stats -- python tools/mixed_onecall_bench.py --only-onecall 200).
+--pol: the polarisation half instead (oa_qe_pol / oa_qe_mv behind oa_qe_band_bind): qe_EB (reconstruct_hc) and the MV of TT, TE, EE,
+    EB, TB (reconstruct_mv_hc) from Fourier-space legs into an estimator-owned plane, one call on the band grid against the modular
+    chain (fused=False) of the same object on the same inputs, in one process.  Per cell the median of --reps timed blocks of --iters
+    calls (HIP events) and the spread of the blocks (10th .. 90th percentile)."""
 import argparse
 import json
 import os
@@ -34,6 +38,75 @@ def setup(n, res, prec):
     return q, tmap, (cl * beam ** 2 + noise)[:, :n // 2 + 1]
 
 
+def setup_pol(n, res):
+    from orphics_amd import cosmology, lensing, maps
+    from orphics_amd.geometry import FlatGeometry
+    shape = (n, n)
+    g = FlatGeometry.from_res(shape, res)
+    th = cosmology.default_theory()
+    ml = g.modlmap()
+    beam = maps.gauss_beam(ml, 1.5)
+    nT = np.full(shape, cosmology.white_noise_power(1.0))
+    tmask = maps.mask_kspace(shape, g, lmin=300, lmax=2000)
+    kmask = maps.mask_kspace(shape, g, lmin=20, lmax=3500)
+    q = lensing.qest(shape, g, th, noise2d=nT, beam2d=beam, kmask=tmask, noise2d_P=2 * nT, kmask_P=tmask, kmask_K=kmask, pol=True,
+                     unlensed_equals_lensed=True, dtype="f64")
+    rng = np.random.default_rng(1)
+    k = {X: np.fft.fft2(rng.standard_normal(shape)) * np.sqrt((th.lCl(X + X, ml) * beam ** 2 + nT) / g.pixarea) for X in "TEB"}
+    return q, k
+
+
+def timed_spread(fn, iters, reps):
+    """median and (p10, p90) over `reps` blocks of `iters` calls, ms per call"""
+    import torch
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(iters):
+            fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b) / iters)
+    return float(np.median(out)), float(np.percentile(out, 10)), float(np.percentile(out, 90))
+
+
+def main_pol(args):
+    import torch
+    ests = ("TT", "TE", "EE", "EB", "TB")
+    for n in [int(s) for s in args.sides.split(",")]:
+        q64, k = setup_pol(n, 0.5)
+        q64.mv_weights(ests)
+        for prec in ("f32", "f64"):
+            q = q64 if prec == "f64" else q64.astype("f32")
+            e = q.eng
+            hk = {X: e.full_to_hc(e.to_complex(k[X])) for X in "TEB"}
+            out, mod_out = q.new_output(), e.hc()
+            cells = {
+                "EB": (lambda: q.reconstruct_hc("EB", hk["E"], hk["B"], out=out),
+                       lambda: q._reconstruct_hc_modular("EB", hk["E"], hk["B"], out=mod_out)),
+                "MV": (lambda: q.reconstruct_mv_hc(hk["T"], hk["E"], hk["B"], out=out),
+                       lambda: q.reconstruct_mv_hc(hk["T"], hk["E"], hk["B"], out=mod_out, fused=False)),
+            }
+            for name, (one, mod) in cells.items():
+                grid = q.pol_band_grid("EB" if name == "EB" else ests)
+                if args.only_onecall:
+                    for _ in range(args.only_onecall):
+                        one()
+                    torch.cuda.synchronize()
+                    continue
+                t1 = timed_spread(one, args.iters, args.reps)
+                t0 = timed_spread(mod, args.iters, args.reps)
+                diff = float((out - mod_out)[:, :e.nxh + 1].abs().max() / mod_out.abs().max())
+                print(json.dumps(dict(side=n, prec=prec, call=name, band_grid=list(grid) if grid else None, onecall_ms=round(t1[0], 4),
+                                      onecall_p10_p90=[round(t1[1], 4), round(t1[2], 4)], modular_ms=round(t0[0], 4),
+                                      modular_p10_p90=[round(t0[1], 4), round(t0[2], 4)], speedup=round(t0[0] / t1[0], 2),
+                                      max_rel_diff=diff)), flush=True)
+
+
 def timed(fn, iters, reps):
     import torch
     fn()
@@ -57,10 +130,13 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sims", type=int, default=600)
     ap.add_argument("--only-onecall", type=int, default=0)
+    ap.add_argument("--pol", action="store_true")
     args = ap.parse_args()
     import torch
     from orphics_amd import mc
     torch.cuda.set_device(0)
+    if args.pol:
+        return main_pol(args)
     for n in [int(s) for s in args.sides.split(",")]:
         for prec in ("f32", "f64"):
             q, tmap, tot_h = setup(n, 0.5, prec)
