@@ -43,7 +43,7 @@ typedef struct oa_plan oa_plan;
 const char* oa_last_error(void);
 /* ABI version = 100 x the build round that last changed a signature in this header; bindings must refuse a library
  * that reports less than the version they were written against (OA_ABI_VERSION) */
-#define OA_ABI_VERSION 404
+#define OA_ABI_VERSION 405
 int oa_version(void);
 /* number of HIP devices visible; <0 on error (no compute) */
 int oa_device_count(void);
@@ -203,7 +203,8 @@ int oa_plan_col_grid(const oa_plan* p);
  * which synchronise the device; oa_plan_set_bins keeps the WHOLE N-plane mode counts), and every call runs the fused power-of-two
  * pipeline there: only the input transform (one mixed-radix row R2C that stores the leg columns, then an ny-point DFT evaluated at the
  * leg rows), the Monte-Carlo draw (the leg band of oa_grf_hc's N-grid draw, same Philox counters) and the scatter of kappa's band
- * into the N-grid output / mean-field stack see the map's grid.  oa_qe_tt_splits, oa_mc_run_windowed and oa_qe_tt_stage stay
+ * into the N-grid output / mean-field stack see the map's grid.  oa_qe_tt_splits runs there too, and oa_qe_tt_split_power is the
+ * split-based estimator evaluated on the inner grid (both below, at their declarations); oa_mc_run_windowed and oa_qe_tt_stage stay
  * power-of-two only.  oa_plan_band_grid reports (My, Mx), or (0, 0) when no band grid is bound.
  * oa_qe_pol / oa_qe_mv ON A BAND GRID.  The band-limit argument does not depend on the estimator (every separable piece is a product of
  * fields confined to the leg band; the cos / sin 2 phi_ell factors live on the same ell lattice, so a copy of their band is exact), but
@@ -288,8 +289,21 @@ int oa_qe_tt_moments2(oa_plan* p, const void* real_map0, const void* real_map1, 
  * oa_split_cross_power: the estimator's combination of those planes per mode, in f64 (the QE is bilinear, so the
  * reference's reconstructions involving the split mean are means of the pairwise ones):
  *   out = (n^4 P(kc) - 4 n^2 sum_i P(kic) + 4 sum_{i<j} P(kij)) / (n (n-1)(n-2)(n-3)),  P(x) = |x|^2 norm,
- * written over columns < active_cols and the band rows of the real half-plane `out_hcreal` only (4 <= nsplits <= 8). */
+ * written over columns < active_cols and the band rows of the real half-plane `out_hcreal` only (4 <= nsplits <= 8).
+ * ON A BAND GRID (sides 2^a 3^b 5^c, TT filters bound) oa_qe_tt_splits embeds the leg band of the nsplits transforms into inner planes in
+ * one launch (device table of sources, re-uploaded only when the pointers change), runs itself on the inner plan into a plan-owned,
+ * evenly spaced (n, n, My, kp_inner) block -- its divergence stays one batched launch -- and scatters kappa's band of all nsplits^2 planes
+ * to host_out in ONE launch (plane on grid z; zero_outside: the complement of every plane is zero-filled in that launch, else nothing is
+ * written outside the band).  The inner source planes and the block belong to the plan: the first call, and a call with more splits
+ * than any before, allocates and synchronises the device once; later calls do neither; oa_plan_release_pools frees them.
+ * oa_qe_tt_split_power is the whole estimate in one call on such a plan: the same embed and inner call, then ONE launch that combines
+ * the nsplits^2 INNER planes per mode (the arithmetic of oa_split_cross_power, f64) and stores the real result to the N-grid half-plane
+ * out_hcreal (kappa's band; zero_outside: zero elsewhere, same launch) -- the K_ij never exist on the map's grid.  norm = area / Npix^2
+ * of the map (FourierCalc.normfact); 4 <= nsplits <= 8 (checked before anything is launched).  A power-of-two plan has no inner grid and
+ * refuses, naming oa_qe_tt_splits + oa_split_cross_power, which are the same two steps there. */
 int oa_qe_tt_splits(oa_plan* p, int nsplits, const void* const* host_kmaps, void* const* host_out, int zero_outside, void* stream);
+int oa_qe_tt_split_power(oa_plan* p, int nsplits, const void* const* host_kmaps, void* out_hcreal, double norm, int zero_outside,
+                         void* stream);
 int oa_split_cross_power(int dtype, int nsplits, const void* const* host_kappa, void* out_hcreal, double norm, int ny, long kpitch,
                          int active_cols, int active_rows, void* stream);
 /* oa_mc_run: realisations sim_lo .. sim_hi-1 (Philox stream = realisation index): GRF draw -> TT estimator -> bandpowers ->

@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("ORPHICS_AMD_LIB", os.path.join(_HERE, "liborphics_amd
 
 OA_F32 = 0
 OA_F64 = 1
-ABI_VERSION = 404     # include/orphics_amd.h OA_ABI_VERSION: the signatures below are those of this version
+ABI_VERSION = 405     # include/orphics_amd.h OA_ABI_VERSION: the signatures below are those of this version
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
@@ -60,6 +60,7 @@ SIGNATURES = {
     "oa_qe_tt_moments": (c_int, [c_void_p] * 6),
     "oa_qe_tt_moments2": (c_int, [c_void_p] * 7),
     "oa_qe_tt_splits": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "oa_qe_tt_split_power": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_double, c_int, c_void_p]),
     "oa_split_cross_power": (c_int, [c_int, c_int, c_void_p, c_void_p, c_double, c_int, c_long, c_int, c_int, c_void_p]),
     "oa_qe_tt_stage": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "oa_mc_run": (c_int, [c_void_p, c_u64, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

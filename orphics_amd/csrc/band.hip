@@ -11,11 +11,16 @@
 //   * band_embed     : the leg band of n Fourier-space source planes (T, E, B [, the Y-leg sources of a split call]) of oa_qe_pol /
 //                      oa_qe_mv -> n inner planes, ONE launch through a device table of sources (planes on grid z);
 //   * band_scatter   : kappa_hat's band, inner -> N grid, overwriting, adding (accumulate) or with the zero-fill of the complement
-//                      in the same launch.
+//                      in the same launch;
+//   * band_scatter_batch : the same for the n^2 evenly spaced inner kappa planes of oa_qe_tt_splits -> n^2 N-grid planes through a
+//                      device table of destinations, ONE launch (planes on grid z);
+//   * band_split_power : the split-based 4-point combination (split_power.hpp) of those n^2 inner planes per mode, stored to the
+//                      N-grid real half-plane -- the K_ij never exist on the N grid.
 // A mode of signed index ky sits at row ky mod ny on one grid and ky mod My on the other; the columns are the same.
 #include <algorithm>
 #include "fft_launch.hpp"
 #include "fft_mixed.hpp"
+#include "split_power.hpp"
 
 namespace oa {
 
@@ -255,6 +260,104 @@ int band_scatter(int dtype, const void* src, long spitch, int sny, void* out, lo
     }
     OA_LAUNCH_CHECK();
     return 0;
+}
+
+// band_scatter for nplanes inner planes sstride elements apart -> the N-grid planes of the device table `outs` (oa_qe_tt_splits on a band
+// grid: all n^2 kappa planes in one launch, plane on grid z).  Same workgroup shape as band_scatter: 4 rows x 64 columns, each wave one
+// contiguous row segment.  Without `zero` only the band of each destination is written; with it the workgroups walk every row of the
+// destination and store the band value or zero over all okp columns.
+template <typename T>
+__global__ __launch_bounds__(256) void band_scatter_batch_kernel(const cx<T>* __restrict__ src, long sstride, long spitch, int sny,
+                                                                 cx<T>* const* __restrict__ outs, long okp, int ony, int w, int r) {
+    const int x = blockIdx.x * 64 + threadIdx.x, i = blockIdx.y * 4 + threadIdx.y;
+    if (x >= w || i >= 2 * r - 1) return;
+    cx<T>* __restrict__ out = outs[blockIdx.z];
+    out[(long)band_row(i, r, ony) * okp + x] = src[blockIdx.z * sstride + (long)band_row(i, r, sny) * spitch + x];
+}
+template <typename T>
+__global__ __launch_bounds__(256) void band_scatter_batch_zero_kernel(const cx<T>* __restrict__ src, long sstride, long spitch, int sny,
+                                                                      cx<T>* const* __restrict__ outs, long okp, int ony, int w, int r) {
+    const int y = blockIdx.y * 4 + threadIdx.y;
+    if (y >= ony) return;
+    const bool band = y < r || y > ony - r;
+    const cx<T>* __restrict__ srow = src + blockIdx.z * sstride + (long)(y < r ? y : y - ony + sny) * spitch;      // (read on band rows only)
+    cx<T>* __restrict__ orow = outs[blockIdx.z] + (long)y * okp;
+    for (long x = blockIdx.x * 64 + threadIdx.x; x < okp; x += (long)gridDim.x * 64)
+        orow[x] = (band && x < w) ? srow[x] : mk<T>((T)0, (T)0);
+}
+int band_scatter_batch(int dtype, const void* src, long sstride, int nplanes, long spitch, int sny, void* const* dev_outs, long okp, int ony, int w,
+                       int r, int zero, hipStream_t st) {
+    OA_REQUIRE(nplanes >= 1 && nplanes <= 65535 && w >= 1 && r >= 1 && 2 * r - 1 <= std::min(sny, ony), "band scatter: bad band");
+    OA_REQUIRE(w <= spitch && w <= okp && (long)sny * spitch <= sstride, "band scatter: band wider than a plane's row pitch");
+    const dim3 block(64, 4);
+    if (zero) {
+        dim3 grid((unsigned)std::min<long>(4, (okp + 63) / 64), (ony + 3) / 4, nplanes);
+        if (dtype == OA_F32) hipLaunchKernelGGL(band_scatter_batch_zero_kernel<float>, grid, block, 0, st, (const cx<float>*)src, sstride, spitch, sny, (cx<float>* const*)dev_outs, okp, ony, w, r);
+        else hipLaunchKernelGGL(band_scatter_batch_zero_kernel<double>, grid, block, 0, st, (const cx<double>*)src, sstride, spitch, sny, (cx<double>* const*)dev_outs, okp, ony, w, r);
+    } else {
+        dim3 grid((w + 63) / 64, (2 * r - 1 + 3) / 4, nplanes);
+        if (dtype == OA_F32) hipLaunchKernelGGL(band_scatter_batch_kernel<float>, grid, block, 0, st, (const cx<float>*)src, sstride, spitch, sny, (cx<float>* const*)dev_outs, okp, ony, w, r);
+        else hipLaunchKernelGGL(band_scatter_batch_kernel<double>, grid, block, 0, st, (const cx<double>*)src, sstride, spitch, sny, (cx<double>* const*)dev_outs, okp, ony, w, r);
+    }
+    OA_LAUNCH_CHECK();
+    return 0;
+}
+
+// The split-based 4-point combination (split_cross_mode: the arithmetic of split_cross_power_kernel, f64 per mode) of the N^2 inner kappa
+// planes K[i*N+j] (sstride elements apart) -> the REAL N-grid half-plane `out` (okp reals per row).  Lanes run along columns: every one of
+// the N^2 loads of a wave is one contiguous row segment of its plane.  ZERO = false writes kappa's band only (grid: band rows x band
+// columns); ZERO = true walks every row of `out` over all okp columns and stores the combination or zero.
+template <typename T>
+struct SplitBlockLoad {                            // plane k of an evenly spaced block at this mode
+    const cx<T>* at; long sstride;
+    OA_D cx<T> operator()(int k) const { return at[k * sstride]; }
+};
+template <typename T, int N, bool ZERO>
+__global__ __launch_bounds__(256) void band_split_power_kernel(const cx<T>* __restrict__ src, long sstride, long spitch, int sny, T* __restrict__ out,
+                                                               long okp, int ony, int w, int r, double norm) {
+    if (ZERO) {
+        const int y = blockIdx.y * 4 + threadIdx.y;
+        if (y >= ony) return;
+        const bool band = y < r || y > ony - r;
+        const cx<T>* __restrict__ srow = src + (long)(y < r ? y : y - ony + sny) * spitch;      // (read on band rows only)
+        T* __restrict__ orow = out + (long)y * okp;
+        for (long x = blockIdx.x * 64 + threadIdx.x; x < okp; x += (long)gridDim.x * 64) {
+            double v = 0.0;
+            if (band && x < w) v = split_cross_mode<N>(SplitBlockLoad<T>{srow + x, sstride}, norm);
+            orow[x] = (T)v;
+        }
+    } else {
+        const int x = blockIdx.x * 64 + threadIdx.x, i = blockIdx.y * 4 + threadIdx.y;
+        if (x >= w || i >= 2 * r - 1) return;
+        const double v = split_cross_mode<N>(SplitBlockLoad<T>{src + (long)band_row(i, r, sny) * spitch + x, sstride}, norm);
+        out[(long)band_row(i, r, ony) * okp + x] = (T)v;
+    }
+}
+template <typename T, bool ZERO>
+static int split_power_t(int n, const void* src, long sstride, long spitch, int sny, void* out, long okp, int ony, int w, int r, double norm,
+                         hipStream_t st) {
+    const dim3 block(64, 4);
+    const dim3 grid = ZERO ? dim3((unsigned)std::min<long>(8, (okp + 63) / 64), (ony + 3) / 4) : dim3((w + 63) / 64, (2 * r - 1 + 3) / 4);
+#define OA_BSPLIT_CASE(NN) \
+    case NN: hipLaunchKernelGGL((band_split_power_kernel<T, NN, ZERO>), grid, block, 0, st, (const cx<T>*)src, sstride, spitch, sny, (T*)out, okp, ony, w, r, norm); break
+    switch (n) {
+        OA_BSPLIT_CASE(4); OA_BSPLIT_CASE(5); OA_BSPLIT_CASE(6); OA_BSPLIT_CASE(7); OA_BSPLIT_CASE(8);
+        default: return fail("band split power: 4 <= nsplits <= 8");
+    }
+#undef OA_BSPLIT_CASE
+    OA_LAUNCH_CHECK();
+    return 0;
+}
+int band_split_power(int dtype, int nsplits, const void* src, long sstride, long spitch, int sny, void* out_real, long okp, int ony, int w, int r,
+                     double norm, int zero, hipStream_t st) {
+    OA_REQUIRE(nsplits >= 4 && nsplits <= 8, "band split power: 4 <= nsplits <= 8");
+    OA_REQUIRE(w >= 1 && r >= 1 && 2 * r - 1 <= std::min(sny, ony), "band split power: bad band");
+    OA_REQUIRE(w <= spitch && w <= okp && (long)sny * spitch <= sstride, "band split power: band wider than a plane's row pitch");
+    if (dtype == OA_F32)
+        return zero ? split_power_t<float, true>(nsplits, src, sstride, spitch, sny, out_real, okp, ony, w, r, norm, st)
+                    : split_power_t<float, false>(nsplits, src, sstride, spitch, sny, out_real, okp, ony, w, r, norm, st);
+    return zero ? split_power_t<double, true>(nsplits, src, sstride, spitch, sny, out_real, okp, ony, w, r, norm, st)
+                : split_power_t<double, false>(nsplits, src, sstride, spitch, sny, out_real, okp, ony, w, r, norm, st);
 }
 
 // acc (N grid, interleaved re / im doubles, apitch complex elements per row) += the nbatch inner planes (sstride complex elements apart), in

@@ -188,6 +188,13 @@ int band_stack_add(int dtype, const void* src, long spitch, int sny, int nbatch,
 int band_embed(int dtype, const void* const* dev_srcs, int n, long spitch, int sny, void* dst, long dstride, long dpitch, int dny, int w, int r,
                hipStream_t st);
 int band_scatter(int dtype, const void* src, long spitch, int sny, void* out, long okp, int ony, int w, int r, int mode, hipStream_t st);
+// oa_qe_tt_splits / oa_qe_tt_split_power on the band grid: nplanes inner kappa planes sstride elements apart -> the N-grid planes of a
+// device table, one launch (zero: + the zero-fill of each destination's complement); the 4-point combination of n^2 such planes per mode
+// -> the real N-grid half-plane (okp reals per row)
+int band_scatter_batch(int dtype, const void* src, long sstride, int nplanes, long spitch, int sny, void* const* dev_outs, long okp, int ony, int w,
+                       int r, int zero, hipStream_t st);
+int band_split_power(int dtype, int nsplits, const void* src, long sstride, long spitch, int sny, void* out_real, long okp, int ony, int w, int r,
+                     double norm, int zero, hipStream_t st);
 // the leg band of oa_grf_hc's N-grid draw (same Philox counters) into the hc layout of an (my, okp) grid, nreal planes zstride elements apart
 int grf_band_inner(oa_plan* p, uint64_t seed, uint64_t stream_id, int nreal, const void* covsqrt_hc, void* out, int my, long okp, long zstride,
                    int width, int rband, hipStream_t stream);

@@ -2,6 +2,7 @@
 // K4 real-space product, K5 divergence, K6 QU<->EB rotation) + layout helpers.
 // All are streaming kernels: 16-byte vector accesses, grid-stride, no LDS.
 #include "common.hpp"
+#include "split_power.hpp"
 
 namespace oa {
 
@@ -120,10 +121,14 @@ __global__ __launch_bounds__(256) void sum_region_kernel(const cx<T>* __restrict
 
 // ---------------------------------------------------------------- split-based 4-point combination
 // SplitLensing.cross_estimator (lensing.py:980-1003) per Fourier mode from the N^2 pairwise reconstructions
-// K[i*N+j] = QE(X leg from split i, Y leg from split j).  The QE is bilinear, so with s = mean of the splits
-//   QE(s,s) = mean_ij K_ij,   (QE(m_i,s) + QE(s,m_i))/2 = sum_j (K_ij + K_ji) / (2N),
-// and every term of the estimator is a linear combination of the K's: one pass, arithmetic in f64.
+// K[i*N+j] = QE(X leg from split i, Y leg from split j); the per-mode arithmetic is split_cross_mode (split_power.hpp, shared with
+// the band-grid form in band.hip).
 struct SplitPlanes { const void* k[64]; };
+template <typename T>
+struct SplitTableLoad {                            // plane k of the kernel-argument table at this mode
+    const SplitPlanes& P; long at;
+    OA_D cx<T> operator()(int k) const { return ((const cx<T>*)P.k[k])[at]; }
+};
 
 template <typename T, int N>
 __global__ __launch_bounds__(256) void split_cross_power_kernel(SplitPlanes P, T* __restrict__ out, double norm, int ny, long kp,
@@ -133,35 +138,8 @@ __global__ __launch_bounds__(256) void split_cross_power_kernel(SplitPlanes P, T
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= w) return;
     const long at = (long)y * kp + x;
-    double rcr[N], rci[N], dr[N], di[N];           // rc_i = sum_j (K_ij + K_ji), d_i = K_ii
-#pragma unroll
-    for (int i = 0; i < N; ++i) rcr[i] = rci[i] = 0.0;
-    double tr = 0.0, ti = 0.0, pij = 0.0;         // sum of all K, sum_{i<j} |K_ij + K_ji|^2
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const cx<T> d = ((const cx<T>*)P.k[i * N + i])[at];
-        dr[i] = (double)d.x; di[i] = (double)d.y;
-        rcr[i] += 2.0 * dr[i]; rci[i] += 2.0 * di[i];
-        tr += dr[i]; ti += di[i];
-#pragma unroll
-        for (int j = i + 1; j < N; ++j) {
-            const cx<T> a = ((const cx<T>*)P.k[i * N + j])[at], b = ((const cx<T>*)P.k[j * N + i])[at];
-            const double sr = (double)a.x + (double)b.x, si = (double)a.y + (double)b.y;
-            rcr[i] += sr; rci[i] += si; rcr[j] += sr; rci[j] += si;
-            tr += sr; ti += si;
-            pij += sr * sr + si * si;
-        }
-    }
-    const double n = (double)N, n2 = n * n;
-    double sdr = 0.0, sdi = 0.0, pic = 0.0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        sdr += dr[i]; sdi += di[i];
-        const double cr = rcr[i] / (2.0 * n) - dr[i] / n, ci = rci[i] / (2.0 * n) - di[i] / n;    // k_i - k_ii / N
-        pic += cr * cr + ci * ci;
-    }
-    const double kcr = (tr - sdr) / n2, kci = (ti - sdi) / n2;                                   // QE(s,s) - sum_i k_ii / N^2
-    const double v = (n2 * n2 * (kcr * kcr + kci * kci) - 4.0 * n2 * pic + pij) * norm / (n * (n - 1.0) * (n - 2.0) * (n - 3.0));
+    const SplitTableLoad<T> ld{P, at};
+    const double v = split_cross_mode<N>(ld, norm);
     out[at] = (T)v;
 }
 

@@ -83,6 +83,14 @@ struct Pipeline {
     int32_t* bids = nullptr;          // inner-layout bin ids (-1 outside kappa's band)
     void* brows = nullptr;            // band input transform: row pass (ny x leg_cols complex) + column-pass partial sums
     size_t brows_bytes = 0;
+    // ... oa_qe_tt_splits / oa_qe_tt_split_power there: bs_cap inner source planes (hc, zero outside the leg band) | the evenly spaced
+    // (n, n, My, kp_inner) block of the inner kappa planes; allocated on first use, grown when a call brings more splits
+    void* bsplit = nullptr;
+    size_t bsplit_bytes = 0;
+    int bs_cap = 0;
+    void** bs_tab = nullptr;          // device table: the n N-grid source planes, then the n^2 N-grid output planes of the batched scatter
+    int bs_tab_cap = 0;
+    std::vector<const void*> bs_key;  // what it holds
     // ... and oa_qe_pol / oa_qe_mv there: a PRIVATE inner plan (their bands differ from the TT binding's: kmask_P, the widest band of
     // an estimator set) with inner-layout copies of the planes handed to oa_qe_band_bind, looked up by their N-grid address
     struct PolBind {
@@ -126,6 +134,8 @@ void pipeline_release(oa_plan* p) {
     if (q->bplanes) (void)hipFree(q->bplanes);
     if (q->bids) (void)hipFree(q->bids);
     if (q->brows) (void)hipFree(q->brows);
+    if (q->bsplit) (void)hipFree(q->bsplit);
+    if (q->bs_tab) (void)hipFree(q->bs_tab);
     if (q->pb.plan) (void)oa_plan_destroy(q->pb.plan);
     if (q->pb.planes) (void)hipFree(q->pb.planes);
     if (q->pb.stab) (void)hipFree(q->pb.stab);
@@ -246,6 +256,8 @@ struct MvCall {            // the arguments of oa_qe_mv (oa_qe_pol: nest = 1 and
 };
 static int mixed_qe_mv(oa_plan* p, Pipeline* q, const MvCall& c, void* out, int accumulate, int wl, int wk, int rl, int rk, int mrow, int zero_outside,
                        hipStream_t st);
+static int mixed_qe_tt_splits(oa_plan* p, Pipeline* q, const char* who, int nsplits, const void* const* host_kmaps, void* const* host_out,
+                              void* out_power, double norm, int zero_outside, hipStream_t st);
 }  // namespace oa
 #define OA_NOT_MIXED(p, what) \
     OA_REQUIRE(!(p)->mixed, what ": not available on map sides that are not powers of two (one-call TT entries there: oa_qe_tt, oa_qe_tt_moments(2), oa_mc_run)")
@@ -584,6 +596,12 @@ int oa_plan_release_pools(oa_plan* p) {
     if (q->lens_pool) { (void)hipFree(q->lens_pool); q->lens_pool = nullptr; q->lens_bytes = 0; }
     if (q->split_legs) { (void)hipFree(q->split_legs); q->split_legs = nullptr; q->split_bytes = 0; }
     if (q->mc_src) { (void)hipFree(q->mc_src); q->mc_src = nullptr; q->mc_cap = 0; }
+    // band grid: the split entries' inner source planes and kappa block, and the pool their inner call grew (regrown on demand)
+    if (q->bsplit) { (void)hipFree(q->bsplit); q->bsplit = nullptr; q->bsplit_bytes = 0; q->bs_cap = 0; }
+    if (q->band && q->band->pipe) {
+        Pipeline* qb = (Pipeline*)q->band->pipe;
+        if (qb->split_legs) { (void)hipFree(qb->split_legs); qb->split_legs = nullptr; qb->split_bytes = 0; }
+    }
     return 0;
 }
 
@@ -814,9 +832,9 @@ int oa_qe_mv(oa_plan* p, int nest, const int* host_npieces, const double* host_s
 int oa_qe_tt_splits(oa_plan* p, int nsplits, const void* const* host_kmaps, void* const* host_out, int zero_outside, void* stream) {
     OA_REQUIRE(p && p->pipe && ((Pipeline*)p->pipe)->FG, "oa_qe_tt_splits: call oa_plan_set_filters first");
     OA_REQUIRE(nsplits >= 1 && nsplits <= 64 && host_kmaps && host_out, "oa_qe_tt_splits: bad argument");
-    OA_NOT_MIXED(p, "oa_qe_tt_splits");
     Pipeline* q = (Pipeline*)p->pipe;
     hipStream_t st = (hipStream_t)stream;
+    if (p->mixed) return mixed_qe_tt_splits(p, q, "oa_qe_tt_splits", nsplits, host_kmaps, host_out, nullptr, 0.0, zero_outside, st);
     const long pl = work_pitch(p, q->wl), pk = work_pitch(p, q->wk);
     const size_t lb = (size_t)pl * p->ny * 2 * (p->dtype == OA_F32 ? 4 : 8);      // one compact leg plane
     const size_t es = 2 * (p->dtype == OA_F32 ? 4 : 8), lbk = (size_t)pk * p->ny * es;
@@ -856,6 +874,17 @@ int oa_qe_tt_splits(oa_plan* p, int nsplits, const void* const* host_kmaps, void
         return qe_cols_div_batch_w(p, prod, prod + lbk, q->Fn, host_out[0], prod + 2 * (size_t)npairs * lbk, npairs, (long)(2 * lbk / es), 0,
                                    out_moff, q->wk, q->rk, pk, st, my);
     return 0;
+}
+
+/* The split-based 4-point estimate of the kappa power straight from the splits' transforms, on a band-grid plan: the n^2 pairwise
+ * reconstructions run on the inner grid and are combined there per mode; only the real result is written on the map's grid. */
+int oa_qe_tt_split_power(oa_plan* p, int nsplits, const void* const* host_kmaps, void* out_hcreal, double norm, int zero_outside, void* stream) {
+    OA_REQUIRE(p && host_kmaps && out_hcreal, "oa_qe_tt_split_power: bad argument");
+    OA_REQUIRE(nsplits >= 4 && nsplits <= 8, "oa_qe_tt_split_power: 4 <= nsplits <= 8");
+    OA_REQUIRE(!p->pow2, "oa_qe_tt_split_power: a power-of-two plan has no band grid; there the estimate is oa_qe_tt_splits + oa_split_cross_power");
+    OA_REQUIRE(p->pipe && ((Pipeline*)p->pipe)->FG, "oa_qe_tt_split_power: call oa_plan_set_filters first");
+    return mixed_qe_tt_splits(p, (Pipeline*)p->pipe, "oa_qe_tt_split_power", nsplits, host_kmaps, nullptr, out_hcreal, norm, zero_outside,
+                              (hipStream_t)stream);
 }
 
 /* Two Monte-Carlo steps in one call: both maps share every launch behind their row transforms (fft.hip qe_tt_pair_impl);
@@ -1052,6 +1081,7 @@ static int mixed_bind(oa_plan* p, Pipeline* q) {
         if (q->band) { (void)oa_plan_destroy(q->band); q->band = nullptr; }
         if (q->bplanes) { (void)hipFree(q->bplanes); q->bplanes = nullptr; }
         if (q->bids) { (void)hipFree(q->bids); q->bids = nullptr; }
+        if (q->bsplit) { (void)hipFree(q->bsplit); q->bsplit = nullptr; q->bsplit_bytes = 0; q->bs_cap = 0; }     // (sized by the inner plane)
         q->bmy = q->bmx = 0;
         if (int rc = band_inner_plan(p, my, mx, &q->band)) return rc;
         OA_HIP(hipMalloc(&q->bplanes, 3 * band_real_bytes(q->band) + 2 * plane_bytes(q->band)));
@@ -1291,6 +1321,59 @@ static int mixed_qe_mv(oa_plan* p, Pipeline* q, const MvCall& c, void* out, int 
                        -1, 0, st);
     if (rc) return rc;
     return band_scatter(p->dtype, qb->kk, b->kp, b->ny, out, p->kp, p->ny, wk, rk, accumulate ? 1 : (zero_outside ? 2 : 0), st);
+}
+/* ---- oa_qe_tt_splits / oa_qe_tt_split_power on the band grid ---------------------------------------------------------------------------
+ * The leg band of the n splits' transforms is embedded into n inner source planes in one launch (device table of sources, re-uploaded
+ * only when the caller's pointers change), the inner plan's own oa_qe_tt_splits writes the n^2 kappa planes into an evenly spaced
+ * plan-owned block (so its divergence stays one batched launch), and ONE launch either scatters kappa's band of all n^2 planes to the
+ * caller's N-grid planes (host_out) or combines them per mode into the real N-grid half-plane (out_power: the K_ij never exist on the
+ * N grid).  The source planes and the block are taken on first use and grown when a call brings more splits than any before: that call
+ * synchronises the device once (the inner plan's pool likewise), later calls with as many splits or fewer neither allocate nor
+ * synchronise. */
+static int mixed_qe_tt_splits(oa_plan* p, Pipeline* q, const char* who, int nsplits, const void* const* host_kmaps, void* const* host_out,
+                              void* out_power, double norm, int zero_outside, hipStream_t st) {
+    if (!(p->mixed && q->FG && q->band)) return fail(std::string(who) + ": call oa_plan_set_filters first");
+    oa_plan* b = q->band;
+    band_options(q);
+    const int n = nsplits, npairs = n * n, nout = host_out ? npairs : 0;
+    for (int i = 0; i < n; ++i)
+        if (!host_kmaps[i]) return fail(std::string(who) + ": NULL split plane");
+    for (int k = 0; k < nout; ++k)
+        if (!host_out[k]) return fail(std::string(who) + ": NULL output plane");
+    const size_t cb = plane_bytes(b), es = 2 * (b->dtype == OA_F32 ? 4 : 8);
+    if (n > q->bs_cap) {
+        if (q->bsplit) { OA_HIP(hipDeviceSynchronize()); (void)hipFree(q->bsplit); q->bsplit = nullptr; q->bsplit_bytes = 0; q->bs_cap = 0; }
+        const size_t need = ((size_t)n + (size_t)npairs) * cb;
+        OA_HIP(hipMalloc(&q->bsplit, need));
+        q->bsplit_bytes = need; q->bs_cap = n;
+        OA_HIP(hipMemsetAsync(q->bsplit, 0, (size_t)n * cb, st));    // source planes: zero outside the leg band (only the band is ever written)
+    }
+    if (n + nout > q->bs_tab_cap) {
+        if (q->bs_tab) { OA_HIP(hipDeviceSynchronize()); (void)hipFree(q->bs_tab); q->bs_tab = nullptr; q->bs_tab_cap = 0; }
+        const int cap = std::max(n + nout, 8 + 64);
+        OA_HIP(hipMalloc((void**)&q->bs_tab, (size_t)cap * sizeof(void*)));
+        q->bs_tab_cap = cap;
+        q->bs_key.clear();
+    }
+    std::vector<const void*> key(host_kmaps, host_kmaps + n);
+    if (nout) key.insert(key.end(), host_out, host_out + nout);
+    if (key != q->bs_key) {                           // (pageable source: staged before the call returns; ordered on this stream)
+        q->bs_key = key;
+        OA_HIP(hipMemcpyAsync(q->bs_tab, q->bs_key.data(), key.size() * sizeof(void*), hipMemcpyHostToDevice, st));
+    }
+    char* const sbase = (char*)q->bsplit;
+    char* const kbase = sbase + (size_t)q->bs_cap * cb;
+    const long pe = (long)(cb / es);                  // complex elements per inner plane
+    int rc = band_embed(p->dtype, (const void* const*)q->bs_tab, n, p->kp, p->ny, sbase, pe, b->kp, b->ny, q->wl, q->rl, st);
+    if (rc) return rc;
+    std::vector<const void*> ins(n);
+    std::vector<void*> outs(npairs);
+    for (int i = 0; i < n; ++i) ins[i] = sbase + (size_t)i * cb;
+    for (int k = 0; k < npairs; ++k) outs[k] = kbase + (size_t)k * cb;
+    if ((rc = oa_qe_tt_splits(b, n, ins.data(), outs.data(), 0, st))) return rc;
+    if (out_power)
+        return band_split_power(p->dtype, n, kbase, pe, b->kp, b->ny, out_power, p->kp, p->ny, q->wk, q->rk, norm, zero_outside, st);
+    return band_scatter_batch(p->dtype, kbase, pe, npairs, b->kp, b->ny, (void* const*)(q->bs_tab + n), p->kp, p->ny, q->wk, q->rk, zero_outside, st);
 }
 }  // namespace oa
 

@@ -485,11 +485,16 @@ class Estimator(object):
     def tt_pairs(self, ksplits, out=None, owned=False):
         """TT reconstructions of every ordered pair of maps in ONE C-ABI call (``oa_qe_tt_splits``): ``ksplits`` = n hc
         transforms; returns an (n, n, Ny, kp) complex tensor K with K[i, j] = QE(X leg from map i, Y leg from map j).
-        The three filtered leg planes of each map are transformed once (n leg stages, not n^2)."""
+        The three filtered leg planes of each map are transformed once (n leg stages, not n^2).  On sides 2^a 3^b 5^c the call
+        runs on the band grid (:attr:`band_grid`) and one launch scatters kappa's band of all n^2 planes back; geometries without a
+        one-call path (:meth:`one_call`) are refused."""
         import ctypes
         torch = _torch()
         from ._lib import check
         from .engine import _stream, mark_dirty
+        if not self.one_call():
+            raise RuntimeError("tt_pairs: this geometry has no one-call TT path (power-of-two sides, or sides 2^a 3^b 5^c whose band "
+                               "grid resolves: Estimator.one_call()); reconstruct the pairs one by one (reconstruct_tt_hc)")
         e = self._bind()
         n = len(ksplits)
         for k in ksplits:
@@ -1020,8 +1025,10 @@ class SplitLensing(object):
 
         n^2 reconstructions instead of the reference's 1 + 3n + n(n-1).  With this package's TT :class:`Estimator`
         (power-of-two sides, 4 <= n <= 8) the whole matrix is ONE ``oa_qe_tt_splits`` call that transforms each split's
-        leg planes once, and the combination is one ``oa_split_cross_power`` launch (f64 arithmetic per mode).  Any
-        other ``qest`` object (duck-typed ``kappa_from_map``) goes through ``qfrag`` pair by pair."""
+        leg planes once, and the combination is one ``oa_split_cross_power`` launch (f64 arithmetic per mode).  On sides
+        2^a 3^b 5^c with a one-call path (band grid) the whole estimate is ONE ``oa_qe_tt_split_power`` call: the K_ij are made
+        and combined on the inner grid and only the real result is written on the map's grid.  Any other ``qest`` object
+        (duck-typed ``kappa_from_map``), any other geometry or n goes through ``qfrag`` pair by pair."""
         half = isinstance(ksplits, HalfPlane)
         if half:
             splits = [ksplits[i] for i in range(ksplits.t.shape[0])]
@@ -1030,8 +1037,11 @@ class SplitLensing(object):
             splits = [arr[i] for i in range(arr.shape[0])]
         n = len(splits)
         q = self.qest
-        if self.est == "TT" and isinstance(q, Estimator) and q.eng.pow2 and 4 <= n <= 8:
-            return self._cross_estimator_device(splits, ksplits)
+        if self.est == "TT" and isinstance(q, Estimator) and 4 <= n <= 8:
+            if q.eng.pow2:
+                return self._cross_estimator_device(splits, ksplits)
+            if q.eng.mixed and q.one_call():
+                return self._cross_estimator_band(splits)
         # generic: pairwise reconstructions through the public qfrag, combined on whatever array type it returns
         val = lambda x: x.t if isinstance(x, HalfPlane) else x      # noqa: E731
         raw = [[self.qfrag(splits[i], splits[j]) for j in range(n)] for i in range(n)]
@@ -1076,6 +1086,27 @@ class SplitLensing(object):
         out = e.hcreal()                              # zero outside kappa's active region, like every K_ij
         planes = (ctypes.c_void_p * (n * n))(*[K[i, j].data_ptr() for i in range(n) for j in range(n)])
         check(e.lib.oa_split_cross_power(e.code, n, planes, _ptr(out), float(self.fc.normfact), e.ny, e.kp, int(wk), int(rk), _stream()))
+        if kind == "half":
+            return HalfPlane(out, e)
+        full = e.hcreal_to_full(out)
+        return full.cpu().numpy() if kind == "np" else full
+
+    def _cross_estimator_band(self, splits):
+        """sides 2^a 3^b 5^c: one ``oa_qe_tt_split_power`` call (the n^2 reconstructions and their combination on the band grid)"""
+        import ctypes
+        from ._lib import check
+        from .engine import _ptr, _stream
+        q = self.qest
+        n = len(splits)
+        hcs = []
+        kind = "half"
+        for m in splits:
+            k, kind = q._as_hc(m, True)
+            hcs.append(k)
+        e = q._bind()
+        out = e.hcreal()                              # zero outside kappa's band: the call writes the band only
+        ins = (ctypes.c_void_p * n)(*[k.data_ptr() for k in hcs])
+        check(e.lib.oa_qe_tt_split_power(e.plan, n, ins, _ptr(out), float(self.fc.normfact), 0, _stream()))
         if kind == "half":
             return HalfPlane(out, e)
         full = e.hcreal_to_full(out)

@@ -9,7 +9,12 @@ modular chain on the same plan, on the reference notebooks' patches (tutorials/t
 --pol: the polarisation half instead (oa_qe_pol / oa_qe_mv behind oa_qe_band_bind): qe_EB (reconstruct_hc) and the MV of TT, TE, EE,
     EB, TB (reconstruct_mv_hc) from Fourier-space legs into an estimator-owned plane, one call on the band grid against the modular
     chain (fused=False) of the same object on the same inputs, in one process.  Per cell the median of --reps timed blocks of --iters
-    calls (HIP events) and the spread of the blocks (10th .. 90th percentile)."""
+    calls (HIP events) and the spread of the blocks (10th .. 90th percentile).
+--splits: the split-based 4-point estimator (SplitLensing.cross_estimator, TT) on n = 4 and 8 splits held as one HalfPlane: the device
+    path (one oa_qe_tt_split_power call on the band grid) against the generic pairwise loop on the same plan (n^2 kappa_from_map calls +
+    host-side power evaluations: what a duck-typed qest gets, and what every qest got on these sides before), in one process on the
+    same inputs.  Per cell the median of --reps timed blocks (HIP events) of --iters device-path / --loop-iters generic-loop estimates and
+    the spread of the blocks."""
 import argparse
 import json
 import os
@@ -107,6 +112,44 @@ def main_pol(args):
                                       max_rel_diff=diff)), flush=True)
 
 
+class _Duck(object):
+    """a qest that is not this package's Estimator: SplitLensing takes the generic pairwise loop"""
+
+    def __init__(self, q):
+        self.q = q
+
+    def kappa_from_map(self, XY, T2DData=None, T2DDataY=None, alreadyFTed=False, returnFt=False, **unused):
+        return self.q.kappa_from_map(XY, T2DData=T2DData, T2DDataY=T2DDataY, alreadyFTed=alreadyFTed, returnFt=returnFt)
+
+
+def main_splits(args):
+    import torch
+    from orphics_amd import lensing
+    from orphics_amd.stats import HalfPlane
+    for n in [int(s) for s in args.sides.split(",")]:
+        q64, tmap, _ = setup(n, 0.5, "f64")
+        rng = np.random.default_rng(2)
+        smaps = [tmap + 0.3 * rng.standard_normal(tmap.shape) for _ in range(8)]
+        for prec in ("f32", "f64"):
+            q = q64 if prec == "f64" else q64.astype("f32")
+            e = q.eng
+            hcs = torch.stack([e.rfft(e.to_real(m)) for m in smaps])
+            dev_sl = lensing.SplitLensing(tmap.shape, q.geom, q, "TT")
+            gen_sl = lensing.SplitLensing(tmap.shape, q.geom, _Duck(q), "TT")
+            for ns in (4, 8):
+                half = HalfPlane(hcs[:ns], e)
+                res = {}
+                t1 = timed_spread(lambda: res.__setitem__("dev", dev_sl.cross_estimator(half)), args.iters, args.reps)
+                t0 = timed_spread(lambda: res.__setitem__("gen", gen_sl.cross_estimator(half)), args.loop_iters, args.reps)
+                a, b = res["dev"].t.double()[:, :e.nxh + 1], res["gen"].t.double()[:, :e.nxh + 1]
+                diff = float((a - b).abs().max() / b.abs().max())
+                print(json.dumps(dict(side=n, prec=prec, call="splits", nsplits=ns, band_grid=list(q.band_grid), device_ms=round(t1[0], 4),
+                                      device_p10_p90=[round(t1[1], 4), round(t1[2], 4)], loop_ms=round(t0[0], 4),
+                                      loop_p10_p90=[round(t0[1], 4), round(t0[2], 4)], speedup=round(t0[0] / t1[0], 2),
+                                      max_rel_diff=diff)), flush=True)
+            e.release_pools()
+
+
 def timed(fn, iters, reps):
     import torch
     fn()
@@ -131,12 +174,16 @@ def main():
     ap.add_argument("--sims", type=int, default=600)
     ap.add_argument("--only-onecall", type=int, default=0)
     ap.add_argument("--pol", action="store_true")
+    ap.add_argument("--splits", action="store_true")
+    ap.add_argument("--loop-iters", type=int, default=3)
     args = ap.parse_args()
     import torch
     from orphics_amd import mc
     torch.cuda.set_device(0)
     if args.pol:
         return main_pol(args)
+    if args.splits:
+        return main_splits(args)
     for n in [int(s) for s in args.sides.split(",")]:
         for prec in ("f32", "f64"):
             q, tmap, tot_h = setup(n, 0.5, prec)
