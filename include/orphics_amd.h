@@ -43,7 +43,7 @@ typedef struct oa_plan oa_plan;
 const char* oa_last_error(void);
 /* ABI version = 100 x the build round that last changed a signature in this header; bindings must refuse a library
  * that reports less than the version they were written against (OA_ABI_VERSION) */
-#define OA_ABI_VERSION 405
+#define OA_ABI_VERSION 406
 int oa_version(void);
 /* number of HIP devices visible; <0 on error (no compute) */
 int oa_device_count(void);
@@ -276,6 +276,28 @@ int oa_qe_mv(oa_plan* p, int nest, const int* host_npieces, const double* host_s
              const void* const* host_FH, const int* host_swap, const void* const* host_kX, const void* const* host_kY,
              const void* const* host_Fnorm, void* out, int accumulate, int leg_cols, int kappa_cols, int leg_rows, int kappa_rows,
              int mrow, int zero_outside, void* stream);
+/* oa_qe_mv FROM REAL MAPS on a 2^a 3^b 5^c plan (band grid, oa_qe_band_bind): host_maps = nmaps device real planes (1 <= nmaps <= 6, each
+ * ny x nx of the plan's dtype); source i is the unnormalised transform of map i (what oa_fft_r2c returns with scale = 1) and
+ * host_xsrc[e] / host_ysrc[e] name the sources of estimator e's X and Y leg by index.  rot_c / rot_s: both NULL, or both (ny, kpitch) real
+ * planes in the half layout holding cos / sin 2 phi_ell; then nmaps is 3 or 6 and the sources (1, 2) and (4, 5) are replaced per mode by
+ * oa_rot2's combination E = Q c - U s, B = Q s + U c.  Only the leg band of the rotation planes is read, straight from the caller's planes
+ * (rows |ky| < leg_rows, columns < leg_cols): nothing is copied or bound for them.  Every other argument is oa_qe_mv's; nest = 1 is one
+ * estimator.  The filter and normalisation planes are looked up in the oa_qe_band_bind binding exactly as oa_qe_mv does (same checks, same
+ * messages naming the set-up entry, same leg-plane budget).  Only the source stage differs: a batched band input transform -- one
+ * mixed-radix row R2C per map row that stores the leg columns, a pruned-output column DFT of all maps at the leg rows (double accumulation
+ * in both precisions, fixed summation order: deterministic), the rotation in double before the single rounding -- writes the leg band of
+ * all sources straight into the binding's inner source planes in three launches.  No N-grid transform plane exists, nothing is embedded,
+ * and no pointer table is uploaded: the map pointers travel in the kernel arguments.  The map-side scratch (per map: ny x leg_cols complex
+ * + the column pass's partial sums) belongs to the binding, like the inner planes of oa_qe_tt_splits on a band grid: it is taken on the
+ * first from-maps call and regrown when a call brings more maps or a wider band than any before -- that call synchronises the device once;
+ * later calls neither allocate nor synchronise --, oa_plan_release_pools frees it, and oa_qe_band_bind drops it when it remakes the inner
+ * plan.  Refused before anything is launched: a power-of-two plan (oa_fft_r2c, oa_rot2 and oa_qe_mv are the same steps there), a chirp-z
+ * plan, no binding or other band numbers / mrow than the bound ones, an unbound filter or normalisation plane, too many leg planes, nmaps
+ * outside 1..6, a NULL map, only one of rot_c / rot_s, rotation planes with nmaps not 3 or 6, a source index outside [0, nmaps). */
+int oa_qe_mv_maps(oa_plan* p, int nmaps, const void* const* host_maps, const void* rot_c, const void* rot_s, int nest,
+                  const int* host_npieces, const double* host_signs, const void* const* host_FG, const void* const* host_FH,
+                  const int* host_swap, const int* host_xsrc, const int* host_ysrc, const void* const* host_Fnorm, void* out,
+                  int accumulate, int leg_cols, int kappa_cols, int leg_rows, int kappa_rows, int mrow, int zero_outside, void* stream);
 int oa_filter_map(oa_plan* p, const void* real_in, const void* filt_hcreal, void* real_out, void* stream);
 int oa_qe_tt_moments(oa_plan* p, const void* real_map, int64_t* n, double* S, double* C, void* stream);
 /* Two Monte-Carlo steps per call (two independent maps): identical results to two oa_qe_tt_moments calls; on the

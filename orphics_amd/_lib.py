@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("ORPHICS_AMD_LIB", os.path.join(_HERE, "liborphics_amd
 
 OA_F32 = 0
 OA_F64 = 1
-ABI_VERSION = 405     # include/orphics_amd.h OA_ABI_VERSION: the signatures below are those of this version
+ABI_VERSION = 406     # include/orphics_amd.h OA_ABI_VERSION: the signatures below are those of this version
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
@@ -56,6 +56,7 @@ SIGNATURES = {
     "oa_qe_pol": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                           c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "oa_qe_mv": (c_int, [c_void_p, c_int] + [c_void_p] * 9 + [c_int] * 7 + [c_void_p]),
+    "oa_qe_mv_maps": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 8 + [c_void_p] + [c_int] * 7 + [c_void_p]),
     "oa_filter_map": (c_int, [c_void_p] * 5),
     "oa_qe_tt_moments": (c_int, [c_void_p] * 6),
     "oa_qe_tt_moments2": (c_int, [c_void_p] * 7),

@@ -1,10 +1,14 @@
-// BAND GRID of the one-call entries (TT, and oa_qe_pol / oa_qe_mv behind oa_qe_band_bind) on map sides 2^a 3^b 5^c (pipeline.hip, include/orphics_amd.h): the estimator is
+// BAND GRID of the one-call entries (TT, and oa_qe_pol / oa_qe_mv / oa_qe_mv_maps behind oa_qe_band_bind) on map sides 2^a 3^b 5^c (pipeline.hip, include/orphics_amd.h): the estimator is
 // band-limited, so after the input transform everything runs on a small power-of-two (My, Mx) grid through the fused pow2
 // pipeline of an inner plan.  The kernels here move data between the map's N-grid and that inner grid:
 //   * band_map_r2c   : real map -> the leg band of its transform (columns < wl, rows |ky| < rl), written in the inner hc layout.
 //                      Row pass: the mixed-radix packed N/2 R2C of mixed.hip (fft_mixed.hpp) with only the columns < wl stored
 //                      (ny x wl complex instead of ny x (nx/2+1)); column pass: an ny-point DFT evaluated only at the 2 rl - 1 kept
 //                      rows (pruned-output DFT, double accumulation, split over row segments + an ordered sum) into the inner plane;
+//   * band_maps_r2c  : the same for the <= 6 real maps of one oa_qe_mv_maps call (T, Q, U [, the Y-leg T, Q, U]) in THREE launches
+//                      (bodies in fft_band.hpp: band_rows on grid (row, map); band_cols with the twiddle tile staged once and applied to
+//                      every map's operand tile; band_cols_fold = the ordered sum + the Q,U -> E,B rotation in double before the one
+//                      rounding), straight into the inner source planes of the oa_qe_band_bind binding; map pointers by value;
 //   * band_copy      : band region (rows |ky| < r, columns < w) of one grid's hc-layout plane -> the other grid's (filters, bin ids,
 //                      Fourier-space legs N -> inner; kappa_hat inner -> N), optionally scaled;
 //   * band_stack_add : the mean-field stack update of oa_mc_run (f64 interleaved N-grid accumulator += inner kappa_hat planes);
@@ -20,12 +24,10 @@
 #include <algorithm>
 #include "fft_launch.hpp"
 #include "fft_mixed.hpp"
+#include "fft_band.hpp"
 #include "split_power.hpp"
 
 namespace oa {
-
-// band row i of 0 .. 2 r - 2 -> signed ky (0 .. r - 1, then -(r - 1) .. -1) -> row of a grid of m rows
-OA_HD int band_row(int i, int r, int m) { return i < r ? i : i - (2 * r - 1) + m; }
 
 // one map row per workgroup: packed N/2-point mixed-radix transform + untangle (mr_row_body, MR_R2C), store of columns < w only
 template <typename T>
@@ -66,16 +68,8 @@ __global__ __launch_bounds__(256) void band_row_kernel(BandRowArgs<T> a) {
 // pruned-output column DFT: out[ky, x] = sum_y rows[y, x] W_ny^(ky y) for |ky| < rl, x < w; a workgroup owns 16 columns x 16 output
 // rows x one SEGMENT of yseg rows and walks it in chunks of 32 (operands and twiddles staged in LDS as doubles; accumulation in double
 // for both precisions); its partial sums go to part[seg][k][x], which band_cols_sum adds in segment order (deterministic).  With one
-// segment per tile the 1200^2 leg band is 28 workgroups of 1200 rows each (~100 us); segments give the chip a few hundred.
-constexpr int BC_TX = 16, BC_TK = 16, BC_YC = 32, BC_TARGET_WG = 512;
-static int band_cols_segments(int ny, int w, int rl, int* yseg) {
-    const long tiles = (long)((w + BC_TX - 1) / BC_TX) * ((2 * rl - 1 + BC_TK - 1) / BC_TK);
-    long nseg = std::max(1L, std::min((long)((ny + BC_YC - 1) / BC_YC), BC_TARGET_WG / tiles));
-    int ys = (int)((ny + nseg - 1) / nseg);
-    ys = (ys + BC_YC - 1) / BC_YC * BC_YC;
-    *yseg = ys;
-    return (ny + ys - 1) / ys;
-}
+// segment per tile the 1200^2 leg band is 28 workgroups of 1200 rows each (~100 us); segments give the chip a few hundred
+// (band_cols_segments, fft_band.hpp).
 size_t band_map_scratch_bytes(const oa_plan* p, int wl, int rl) {
     int ys = 0;
     const int nseg = band_cols_segments(p->ny, wl, rl, &ys);
@@ -151,6 +145,78 @@ int band_map_r2c(oa_plan* p, const void* map, void* rowbuf, int wl, int rl, void
     OA_REQUIRE(p->mixed && wl >= 1 && wl <= p->nx / 2 && rl >= 1 && 2 * rl - 1 <= std::min(p->ny, dny), "band input transform: bad band");
     return p->dtype == OA_F32 ? map_r2c_t<float>(p, map, rowbuf, wl, rl, dst, dny, dkp, st)
                               : map_r2c_t<double>(p, map, rowbuf, wl, rl, dst, dny, dkp, st);
+}
+
+// BATCHED band input transform of oa_qe_mv_maps (bodies: fft_band.hpp): nmaps real maps -> the leg band of their transforms in nmaps
+// inner planes dstride elements apart, with the Q,U -> E,B rotation of the pairs (1, 2) / (4, 5) when rot_c / rot_s are given.  Three
+// launches whatever nmaps is; the map pointers travel by value.  scratch: band_maps_scratch_bytes(p, nmaps, wl, rl) bytes -- the row
+// planes of all maps, then (256-byte aligned) the partial sums of all maps, each sized as in band_map_scratch_bytes.
+template <typename T>
+__global__ __launch_bounds__(256) void band_rows_kernel(BandRowsArgs<T> a) {
+    GpuCtx c{oa_dyn_smem};
+    band_rows_body<T>(c, a);
+}
+template <typename T, int NM>
+__global__ __launch_bounds__(256) void band_colsn_kernel(BandColsArgs<T> a) {
+    __shared__ __attribute__((aligned(16))) char lds[band_cols_lds<NM>()];
+    GpuCtx c{lds};
+    band_cols_body<T, NM>(c, a);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void band_cols_fold_kernel(BandFoldArgs<T> a) {
+    GpuCtx c{nullptr};
+    band_cols_fold_body<T>(c, a);
+}
+static size_t band_maps_rows_bytes(const oa_plan* p, int nmaps, int wl) {
+    const size_t b = (size_t)nmaps * p->ny * wl * 2 * (p->dtype == OA_F32 ? 4 : 8);
+    return (b + 255) / 256 * 256;
+}
+size_t band_maps_scratch_bytes(const oa_plan* p, int nmaps, int wl, int rl) {
+    int ys = 0;
+    const int nseg = band_cols_segments(p->ny, wl, rl, &ys);
+    return band_maps_rows_bytes(p, nmaps, wl) + (size_t)nmaps * nseg * (2 * rl - 1) * wl * sizeof(cx<double>);
+}
+template <typename T>
+static int maps_r2c_t(oa_plan* p, int nmaps, const void* const* maps, const void* rot_c, const void* rot_s, void* scratch, int wl, int rl, void* dst,
+                      long dstride, int dny, long dkp, hipStream_t st) {
+    const int N = p->nx / 2;
+    int rc = 0;
+    BandRowsArgs<T> ra{};
+    for (int m = 0; m < BAND_MAPS_MAX; ++m) ra.maps.m[m] = (const T*)maps[m < nmaps ? m : 0];
+    ra.out = (cx<T>*)scratch; ra.in_pitch = p->nx; ra.out_mstride = (long)p->ny * wl; ra.w = wl; ra.N = N; ra.f = mixed_factor(N);
+    ra.tw = (const cx<T>*)p->mr_twxh; ra.tw2 = (const cx<T>*)p->mr_twx;
+    launch_go(rc, st, band_rows_kernel<T>, dim3(p->ny, nmaps), 256, band_rows_lds<T>(N), ra);
+    if (rc) return rc;
+    BandColsArgs<T> ca{};
+    ca.rows = (const cx<T>*)scratch; ca.rows_mstride = ra.out_mstride; ca.ny = p->ny; ca.w = wl; ca.rl = rl;
+    ca.nseg = band_cols_segments(p->ny, wl, rl, &ca.yseg);
+    ca.tw = (const cx<T>*)p->mr_twy;
+    ca.part = reinterpret_cast<cx<double>*>((char*)scratch + band_maps_rows_bytes(p, nmaps, wl));
+    const dim3 grid((wl + BC_TX - 1) / BC_TX, (2 * rl - 1 + BC_TK - 1) / BC_TK, ca.nseg);
+    switch (nmaps) {
+        case 1: hipLaunchKernelGGL((band_colsn_kernel<T, 1>), grid, dim3(256), 0, st, ca); break;
+        case 2: hipLaunchKernelGGL((band_colsn_kernel<T, 2>), grid, dim3(256), 0, st, ca); break;
+        case 3: hipLaunchKernelGGL((band_colsn_kernel<T, 3>), grid, dim3(256), 0, st, ca); break;
+        case 4: hipLaunchKernelGGL((band_colsn_kernel<T, 4>), grid, dim3(256), 0, st, ca); break;
+        case 5: hipLaunchKernelGGL((band_colsn_kernel<T, 5>), grid, dim3(256), 0, st, ca); break;
+        default: hipLaunchKernelGGL((band_colsn_kernel<T, 6>), grid, dim3(256), 0, st, ca); break;
+    }
+    OA_LAUNCH_CHECK();
+    BandFoldArgs<T> fa{};
+    fa.part = ca.part; fa.nmaps = nmaps; fa.nseg = ca.nseg; fa.w = wl; fa.rl = rl;
+    fa.rot_c = (const T*)rot_c; fa.rot_s = (const T*)rot_s; fa.rot_pitch = p->kp; fa.ny = p->ny;
+    fa.out = (cx<T>*)dst; fa.out_mstride = dstride; fa.okp = dkp; fa.my = dny;
+    hipLaunchKernelGGL(band_cols_fold_kernel<T>, dim3((wl + 255) / 256, 2 * rl - 1), dim3(256), 0, st, fa);
+    OA_LAUNCH_CHECK();
+    return 0;
+}
+int band_maps_r2c(oa_plan* p, int nmaps, const void* const* maps, const void* rot_c, const void* rot_s, void* scratch, int wl, int rl, void* dst,
+                  long dstride, int dny, long dkp, hipStream_t st) {
+    OA_REQUIRE(p->mixed && wl >= 1 && wl <= p->nx / 2 && rl >= 1 && 2 * rl - 1 <= std::min(p->ny, dny), "band input transform: bad band");
+    OA_REQUIRE(nmaps >= 1 && nmaps <= BAND_MAPS_MAX && wl <= dkp && wl <= p->kp && (long)dny * dkp <= dstride, "band input transform: bad planes");
+    OA_REQUIRE((!rot_c && !rot_s) || (rot_c && rot_s && (nmaps == 3 || nmaps == 6)), "band input transform: bad rotation planes");
+    return p->dtype == OA_F32 ? maps_r2c_t<float>(p, nmaps, maps, rot_c, rot_s, scratch, wl, rl, dst, dstride, dny, dkp, st)
+                              : maps_r2c_t<double>(p, nmaps, maps, rot_c, rot_s, scratch, wl, rl, dst, dstride, dny, dkp, st);
 }
 
 template <typename E> OA_D E band_scaled(E v, double) { return v; }

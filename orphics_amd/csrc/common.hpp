@@ -179,6 +179,11 @@ int qe_tt_pair_w(oa_plan* p, const void* map0, const void* map1, const void* FG,
 // rowbuf: band_map_scratch_bytes(p, wl, rl) bytes (row pass + the column pass's per-segment partial sums)
 int band_map_r2c(oa_plan* p, const void* map, void* rowbuf, int wl, int rl, void* dst, int dny, long dkp, hipStream_t st);
 size_t band_map_scratch_bytes(const oa_plan* p, int wl, int rl);
+// the same for the nmaps <= 6 real maps of oa_qe_mv_maps in three launches (map pointers by value), into inner planes dstride elements apart,
+// with the Q,U -> E,B rotation of the pairs (1, 2) / (4, 5) by the band of the N-grid planes rot_c / rot_s (both or neither)
+int band_maps_r2c(oa_plan* p, int nmaps, const void* const* maps, const void* rot_c, const void* rot_s, void* scratch, int wl, int rl, void* dst,
+                  long dstride, int dny, long dkp, hipStream_t st);
+size_t band_maps_scratch_bytes(const oa_plan* p, int nmaps, int wl, int rl);
 int band_copy(int kind, const void* src, long spitch, int sny, void* dst, long dpitch, int dny, int w, int r, double scale, hipStream_t st);
 int band_zero_outside(int dtype, void* out, int ny, long kp, int w, int r, hipStream_t st);
 int band_stack_add(int dtype, const void* src, long spitch, int sny, int nbatch, long sstride, double* acc, long apitch, int any, int w, int r,

@@ -103,6 +103,8 @@ struct Pipeline {
         size_t planes_bytes = 0;               //               POL_SRC_MAX source planes (hc)
         void** stab = nullptr;                 // device table of the N-grid source planes of the batched embed
         std::vector<const void*> skey;         // what it holds
+        void* mrows = nullptr;                 // oa_qe_mv_maps: row planes + column partial sums of the batched band input transform
+        size_t mrows_bytes = 0;                // (band_maps_scratch_bytes; taken on the first from-maps call, grown on demand)
     } pb;
 };
 constexpr int POL_SRC_MAX = 6;                 // T, E, B and the Y-leg sources of a split call
@@ -139,6 +141,7 @@ void pipeline_release(oa_plan* p) {
     if (q->pb.plan) (void)oa_plan_destroy(q->pb.plan);
     if (q->pb.planes) (void)hipFree(q->pb.planes);
     if (q->pb.stab) (void)hipFree(q->pb.stab);
+    if (q->pb.mrows) (void)hipFree(q->pb.mrows);
     delete q;
     p->pipe = nullptr;
 }
@@ -253,6 +256,8 @@ static void band_options(Pipeline* q);
 struct MvCall {            // the arguments of oa_qe_mv (oa_qe_pol: nest = 1 and pol set)
     int nest; const int* npieces; const double* signs; const void* const* FG; const void* const* FH; const int* swap;
     const void* const* kX; const void* const* kY; const void* const* Fn; bool pol;
+    // oa_qe_mv_maps (nmaps > 0): the sources are real maps, the estimators name them by index; kX / kY are unused
+    int nmaps; const void* const* maps; const void* rot_c; const void* rot_s; const int* xsrc; const int* ysrc;
 };
 static int mixed_qe_mv(oa_plan* p, Pipeline* q, const MvCall& c, void* out, int accumulate, int wl, int wk, int rl, int rk, int mrow, int zero_outside,
                        hipStream_t st);
@@ -602,6 +607,8 @@ int oa_plan_release_pools(oa_plan* p) {
         Pipeline* qb = (Pipeline*)q->band->pipe;
         if (qb->split_legs) { (void)hipFree(qb->split_legs); qb->split_legs = nullptr; qb->split_bytes = 0; }
     }
+    // ... and the map-side scratch of oa_qe_mv_maps (retaken by the next from-maps call)
+    if (q->pb.mrows) { (void)hipFree(q->pb.mrows); q->pb.mrows = nullptr; q->pb.mrows_bytes = 0; }
     return 0;
 }
 
@@ -632,6 +639,30 @@ int oa_qe_tt_moments(oa_plan* p, const void* real_map, int64_t* n, double* S, do
     if (int rc = qe_tt_impl(p, real_map, nullptr, nullptr, nullptr, 0, stream, divbin_enabled(q) ? &f : nullptr)) return rc;
     if (f.done) return 0;                      // binned and accumulated in the divergence launch
     return bandpower_moments(p, q, n, S, C, stream);
+}
+
+/* oa_qe_mv from REAL MAPS on a 2^a 3^b 5^c plan (include/orphics_amd.h): the arguments are checked here, everything behind the source
+ * stage is mixed_qe_mv's. */
+int oa_qe_mv_maps(oa_plan* p, int nmaps, const void* const* host_maps, const void* rot_c, const void* rot_s, int nest, const int* host_npieces,
+                  const double* host_signs, const void* const* host_FG, const void* const* host_FH, const int* host_swap, const int* host_xsrc,
+                  const int* host_ysrc, const void* const* host_Fnorm, void* out, int accumulate, int leg_cols, int kappa_cols, int leg_rows,
+                  int kappa_rows, int mrow, int zero_outside, void* stream) {
+    OA_REQUIRE(p && host_maps && nest >= 1 && host_npieces && host_signs && host_FG && host_FH && host_xsrc && host_ysrc && host_Fnorm && out,
+               "oa_qe_mv_maps: bad argument");
+    OA_REQUIRE(!p->pow2, "oa_qe_mv_maps: a power-of-two plan has no band grid: oa_fft_r2c per map, oa_rot2 for Q, U and oa_qe_mv are the same "
+               "steps there");
+    OA_REQUIRE(p->mixed, "oa_qe_mv_maps: map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path "
+               "(use the modular oa_qe_legs / oa_mul_real / oa_qe_div calls)");
+    OA_REQUIRE(nmaps >= 1 && nmaps <= POL_SRC_MAX, "oa_qe_mv_maps: 1 <= nmaps <= 6 real maps per call");
+    for (int i = 0; i < nmaps; ++i) OA_REQUIRE(host_maps[i], "oa_qe_mv_maps: NULL map");
+    OA_REQUIRE((rot_c != nullptr) == (rot_s != nullptr), "oa_qe_mv_maps: rot_c and rot_s are given together or not at all");
+    OA_REQUIRE(!rot_c || nmaps == 3 || nmaps == 6, "oa_qe_mv_maps: the rotation planes need nmaps = 3 (T, Q, U) or 6 (and the Y-leg T, Q, U)");
+    for (int e = 0; e < nest; ++e)
+        OA_REQUIRE(host_xsrc[e] >= 0 && host_xsrc[e] < nmaps && host_ysrc[e] >= 0 && host_ysrc[e] < nmaps,
+                   "oa_qe_mv_maps: source index outside [0, nmaps)");
+    const MvCall c{nest, host_npieces, host_signs, host_FG, host_FH, host_swap, nullptr, nullptr, host_Fnorm, false,
+                   nmaps, host_maps, rot_c, rot_s, host_xsrc, host_ysrc};
+    return mixed_qe_mv(p, pipe_of(p), c, out, accumulate, leg_cols, kappa_cols, leg_rows, kappa_rows, mrow, zero_outside, (hipStream_t)stream);
 }
 
 /* Several estimators accumulated into one kappa plane (minimum-variance combination) with every distinct filtered field
@@ -1210,6 +1241,7 @@ static int pol_bind(oa_plan* p, Pipeline* q, int nf, const void* const* filters,
     OA_HIP(hipDeviceSynchronize());                 // the caller's planes may have been written on any stream; the old copies may be in use
     if (!B.plan || B.my != my || B.mx != mx) {
         if (B.plan) { (void)oa_plan_destroy(B.plan); B.plan = nullptr; }
+        if (B.mrows) { (void)hipFree(B.mrows); B.mrows = nullptr; B.mrows_bytes = 0; }      // (the from-maps calls' scratch: retaken on demand)
         B.my = B.mx = 0;
         if (int rc = band_inner_plan(p, my, mx, &B.plan)) return rc;
         B.my = my; B.mx = mx;
@@ -1253,9 +1285,37 @@ static void* pol_inner(const std::vector<const void*>& key, const void* ptr, cha
     for (size_t i = 0; i < key.size(); ++i) if (key[i] == ptr) return base + i * stride;
     return nullptr;
 }
+// SOURCE STAGE of oa_qe_pol / oa_qe_mv: the leg band of the distinct N-grid source transforms -> the inner source planes, one launch
+// through the device table (re-uploaded only when the caller's pointers change)
+static int mv_sources_embed(oa_plan* p, Pipeline::PolBind& B, const std::vector<const void*>& srcs, char* sbase, size_t cb, int wl, int rl,
+                            hipStream_t st) {
+    const oa_plan* b = B.plan;
+    const size_t es = 2 * (b->dtype == OA_F32 ? 4 : 8);
+    if (srcs != B.skey) {                             // (pageable source: staged before the call returns; ordered on this stream)
+        OA_HIP(hipMemcpyAsync(B.stab, srcs.data(), srcs.size() * sizeof(void*), hipMemcpyHostToDevice, st));
+        B.skey = srcs;
+    }
+    return band_embed(p->dtype, (const void* const*)B.stab, (int)srcs.size(), p->kp, p->ny, sbase, (long)(cb / es), b->kp, b->ny, wl, rl, st);
+}
+// SOURCE STAGE of oa_qe_mv_maps: the batched band input transform of the call's real maps (with the Q,U -> E,B rotation) straight into
+// the inner source planes -- no N-grid hc plane, no embed, no device table.  The map-side scratch belongs to the binding: taken on the
+// first from-maps call and regrown when a call brings more maps or a wider band than any before (that call synchronises the device
+// once); later calls neither allocate nor synchronise
+static int mv_sources_maps(oa_plan* p, Pipeline::PolBind& B, const MvCall& c, char* sbase, size_t cb, int wl, int rl, hipStream_t st) {
+    const oa_plan* b = B.plan;
+    const size_t es = 2 * (b->dtype == OA_F32 ? 4 : 8), need = band_maps_scratch_bytes(p, c.nmaps, wl, rl);
+    if (B.mrows_bytes < need) {
+        OA_HIP(hipDeviceSynchronize());
+        if (B.mrows) { (void)hipFree(B.mrows); B.mrows = nullptr; B.mrows_bytes = 0; }
+        OA_HIP(hipMalloc(&B.mrows, need));
+        B.mrows_bytes = need;
+    }
+    return band_maps_r2c(p, c.nmaps, c.maps, c.rot_c, c.rot_s, B.mrows, wl, rl, sbase, (long)(cb / es), b->ny, b->kp, st);
+}
 static int mixed_qe_mv(oa_plan* p, Pipeline* q, const MvCall& c, void* out, int accumulate, int wl, int wk, int rl, int rk, int mrow, int zero_outside,
                        hipStream_t st) {
-    const char* who = c.pol ? "oa_qe_pol" : "oa_qe_mv";
+    const bool from_maps = c.nmaps > 0;
+    const char* who = from_maps ? "oa_qe_mv_maps" : (c.pol ? "oa_qe_pol" : "oa_qe_mv");
     Pipeline::PolBind& B = q->pb;
     if (!B.bound)
         return fail(std::string(who) + ": on map sides that are not powers of two the filter and normalisation planes are bound first (oa_qe_band_bind)");
@@ -1270,7 +1330,7 @@ static int mixed_qe_mv(oa_plan* p, Pipeline* q, const MvCall& c, void* out, int 
     char* const sbase = nbase + B.nkey.size() * rb;
     int total = 0;
     for (int e = 0; e < c.nest; ++e) {
-        OA_REQUIRE(c.npieces[e] >= 1 && c.kX[e] && c.kY[e] && c.Fn[e], "oa_qe_mv: bad estimator entry");
+        OA_REQUIRE(c.npieces[e] >= 1 && (from_maps || (c.kX[e] && c.kY[e])) && c.Fn[e], "oa_qe_mv: bad estimator entry");
         total += c.npieces[e];
     }
     std::vector<const void*> iFG(total), iFH(total), iFn(c.nest), ikX(c.nest), ikY(c.nest), srcs;
@@ -1288,8 +1348,13 @@ static int mixed_qe_mv(oa_plan* p, Pipeline* q, const MvCall& c, void* out, int 
     for (int e = 0; e < c.nest; ++e) {
         iFn[e] = pol_inner(B.nkey, c.Fn[e], nbase, rb);
         if (!iFn[e]) return fail(std::string(who) + ": a normalisation plane of this call is not bound (oa_qe_band_bind)");
-        ikX[e] = source(c.kX[e]);
-        ikY[e] = source(c.kY[e]);
+        if (from_maps) {                              // source i IS map i (checked by the entry: 0 <= index < nmaps <= 6)
+            ikX[e] = sbase + (size_t)c.xsrc[e] * cb;
+            ikY[e] = sbase + (size_t)c.ysrc[e] * cb;
+        } else {
+            ikX[e] = source(c.kX[e]);
+            ikY[e] = source(c.kY[e]);
+        }
     }
     if ((int)srcs.size() > POL_SRC_MAX) return fail(std::string(who) + ": more than 6 distinct source transforms in one call on a band grid");
     if (!c.pol) {                                     // the inner entry's pool: sized by oa_qe_band_bind, never grown here
@@ -1307,14 +1372,10 @@ static int mixed_qe_mv(oa_plan* p, Pipeline* q, const MvCall& c, void* out, int 
             }
         const size_t lb = (size_t)work_pitch(b, wl) * b->ny * es, lbk = (size_t)work_pitch(b, wk) * b->ny * es;
         if ((2 * grad.size() + hpl.size()) * lb + 4 * (size_t)c.nest * lbk > qb->split_bytes)
-            return fail("oa_qe_mv: this call needs " + std::to_string(2 * grad.size() + hpl.size()) + " leg planes and " + std::to_string(c.nest) +
+            return fail(std::string(who) + ": this call needs " + std::to_string(2 * grad.size() + hpl.size()) + " leg planes and " + std::to_string(c.nest) +
                         " estimators, more than oa_qe_band_bind was told (max_leg_planes, normalisation planes)");
     }
-    if (srcs != B.skey) {                             // (pageable source: staged before the call returns; ordered on this stream)
-        OA_HIP(hipMemcpyAsync(B.stab, srcs.data(), srcs.size() * sizeof(void*), hipMemcpyHostToDevice, st));
-        B.skey = srcs;
-    }
-    int rc = band_embed(p->dtype, (const void* const*)B.stab, (int)srcs.size(), p->kp, p->ny, sbase, (long)(cb / es), b->kp, b->ny, wl, rl, st);
+    int rc = from_maps ? mv_sources_maps(p, B, c, sbase, cb, wl, rl, st) : mv_sources_embed(p, B, srcs, sbase, cb, wl, rl, st);
     if (rc) return rc;
     if (c.pol) rc = oa_qe_pol(b, c.npieces[0], c.signs, iFG.data(), iFH.data(), c.swap, ikX[0], ikY[0], iFn[0], qb->kk, 0, wl, wk, rl, rk, -1, 0, st);
     else rc = oa_qe_mv(b, c.nest, c.npieces, c.signs, iFG.data(), iFH.data(), c.swap, ikX.data(), ikY.data(), iFn.data(), qb->kk, 0, wl, wk, rl, rk,

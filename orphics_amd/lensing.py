@@ -527,6 +527,12 @@ class Estimator(object):
             kind = "np" if isinstance(xsrc, np.ndarray) else "torch"
             kft = self.reconstruct_tt_from_map(self.eng.to_real(xsrc))
             kX = kY = None
+        elif (XY != "TT" and not alreadyFTed and not isinstance(xsrc, HalfPlane) and not isinstance(ysrc, HalfPlane)
+              and self.eng.mixed and self.one_call_pol(XY)):
+            # sides 2^a 3^b 5^c with a band grid: only the leg band of each real map's transform is computed (oa_qe_mv_maps)
+            kind = "np" if isinstance(xsrc, np.ndarray) else "torch"
+            kft = self.reconstruct_from_maps(XY, self.eng.to_real(xsrc), None if ysrc is xsrc else self.eng.to_real(ysrc))
+            kX = kY = None
         else:
             kX, kind = self._as_hc(xsrc, alreadyFTed)
             kY = kX if (ysrc is xsrc) else self._as_hc(ysrc, alreadyFTed)[0]
@@ -819,17 +825,87 @@ class Estimator(object):
         check(self.eng.lib.oa_qe_band_grid(self.eng.plan, ctypes.byref(my), ctypes.byref(mx)))
         return my.value, mx.value
 
+    # ---- from real maps (sides 2^a 3^b 5^c with a band grid: oa_qe_mv_maps) ---------------------------------------------
+    def _qu_rot(self, iau):
+        """half-layout cos / sin 2 phi_ell planes of the run precision (``FourierCalc((3,) + shape, wcs, iau=iau)``), cached per
+        (precision, iau)"""
+        if getattr(self, "_rot_fc", None) is None:
+            self._rot_fc = {}
+        cache = self._rot_fc
+        if bool(iau) not in cache:
+            cache[bool(iau)] = maps.FourierCalc((3,) + tuple(self.shape[-2:]), self.wcs, iau=bool(iau), layout="half")
+        return cache[bool(iau)]._rot_planes(self.eng, True)
+
+    def _maps_to_hc(self, triples, qu, iau):
+        """what the from-maps entries replace: ``rfft`` per map, ``rot2`` of every (Q, U) pair"""
+        e = self.eng
+        out = []
+        for tr in triples:
+            ks = [e.rfft(e._chk(m, "real")) for m in tr]
+            if qu:
+                c, s = self._qu_rot(iau)
+                ks[1], ks[2] = e.rot2(c, s, ks[1], ks[2])
+            out.append(ks)
+        return out
+
+    def reconstruct_from_maps(self, XY, xmap, ymap=None, out=None, norm=None, accumulate=False, qu=False, iau=False):
+        """:meth:`reconstruct_hc` fed with REAL maps: ``xmap`` is the map of field XY[0], ``ymap`` that of field XY[1] (None: the
+        same map).  ``qu=True``: ``xmap`` (and ``ymap``, for the Y leg of a split call) is a (T, Q, U) triple of real maps; each leg
+        takes its field from its triple after the per-mode Q, U -> E, B rotation (``iau``: the angle convention).  On sides
+        2^a 3^b 5^c with a band grid one ``oa_qe_mv_maps`` call computes only the leg band of each map's transform; elsewhere:
+        ``rfft`` per map, ``rot2``, :meth:`reconstruct_hc`."""
+        e = self.eng
+        f = {"T": 0, "E": 1, "B": 2}
+        if qu:
+            triples = [tuple(xmap)] + ([tuple(ymap)] if ymap is not None else [])
+            if any(len(t) != 3 for t in triples):
+                raise ValueError("qu=True takes (T, Q, U) triples of real maps")
+            xi, yi = f[XY[0]], f[XY[1]] + 3 * (len(triples) - 1)
+            planes = [m for t in triples for m in t]
+        else:
+            planes = [xmap] + ([ymap] if ymap is not None else [])
+            xi, yi = 0, len(planes) - 1
+        if not (e.mixed and self.one_call_pol(XY, norm is not None)):
+            if qu:
+                ks = [k for t in self._maps_to_hc(triples, True, iau) for k in t]
+            else:
+                ks = [e.rfft(e._chk(m, "real")) for m in planes]
+            return self.reconstruct_hc(XY, ks[xi], ks[yi], out=out, norm=norm, accumulate=accumulate)
+        return self._reconstruct_one(XY, None, None, out, norm, accumulate, src_maps=(planes, self._qu_rot(iau) if qu else None, xi, yi))
+
+    def reconstruct_mv_from_maps(self, tmap, m1, m2, estimators=("TT", "TE", "EE", "EB", "TB"), qu=False, iau=False, out=None):
+        """:meth:`reconstruct_mv_hc` fed with REAL maps of T and of (E, B) -- or, with ``qu=True``, of (Q, U), rotated per mode
+        (``iau``: the angle convention).  On sides 2^a 3^b 5^c with a band grid ONE ``oa_qe_mv_maps`` call: the leg band of the
+        three transforms goes straight into the inner grid.  Elsewhere: ``rfft`` per map, ``rot2``, :meth:`reconstruct_mv_hc`."""
+        e = self.eng
+        key = tuple(estimators)
+        if not (e.mixed and self.one_call_pol(key)):
+            kT, kE, kB = self._maps_to_hc([(tmap, m1, m2)], qu, iau)[0]
+            return self.reconstruct_mv_hc(kT, kE, kB, estimators=key, out=out)
+        return self.reconstruct_mv_hc(None, None, None, estimators=key, out=out,
+                                      _maps=([tmap, m1, m2], self._qu_rot(iau) if qu else None))
+
     def reconstruct_hc(self, XY, kX, kY, out=None, norm=None, accumulate=False):
         """General estimator on hc tensors: kX = DFT of field XY[0], kY = DFT of field XY[1].
         ``norm`` overrides the divergence/normalisation plane (MV weights), ``accumulate`` adds into ``out``."""
         e = self.eng
         if not e.pow2 and not self.one_call_pol(XY, norm is not None):
             return self._reconstruct_hc_modular(XY, kX, kY, out, norm, accumulate)
+        return self._reconstruct_one(XY, kX, kY, out, norm, accumulate)
+
+    def _reconstruct_one(self, XY, kX, kY, out, norm, accumulate, src_maps=None):
+        """one estimator in one call: ``oa_qe_mv`` on the transforms kX, kY, or -- ``src_maps`` = (real planes, rotation planes or None,
+        index of the X source, index of the Y source) -- ``oa_qe_mv_maps``"""
         import ctypes
         from ._lib import check
         from .engine import _ptr, _stream, mark_dirty, owned_clean_region, set_clean_region
+        e = self.eng
         G = self._setup_general(XY)
-        e._chk(kX, "hc"); e._chk(kY, "hc")
+        if src_maps is None:
+            e._chk(kX, "hc"); e._chk(kY, "hc")
+        else:
+            for m in src_maps[0]:
+                e._chk(m, "real")
         # active columns: legs from this estimator's filters; kappa from its normalisation (an external
         # ``norm`` plane -- MV weights -- is bounded by the kappa mask)
         wl, rl = G["wl"], G["rl"]
@@ -859,9 +935,16 @@ class Estimator(object):
         # one estimator through oa_qe_mv (nest = 1): the same pieces as oa_qe_pol, with all distinct leg planes of the estimator
         # in ONE inverse pass-1 launch and one pass-2 launch (a piece pair shares its cos / sin filtered fields)
         one = ctypes.c_void_p * 1
-        check(e.lib.oa_qe_mv(e.plan, 1, (ctypes.c_int * 1)(n), signs, fgs, fhs, swaps, one(kX.data_ptr()), one(kY.data_ptr()),
-                             one(Fn.data_ptr()), _ptr(out), 1 if accumulate else 0, int(wl), int(wk), int(rl), int(rk), int(self.mrow), zero,
-                             _stream()))
+        if src_maps is None:
+            check(e.lib.oa_qe_mv(e.plan, 1, (ctypes.c_int * 1)(n), signs, fgs, fhs, swaps, one(kX.data_ptr()), one(kY.data_ptr()),
+                                 one(Fn.data_ptr()), _ptr(out), 1 if accumulate else 0, int(wl), int(wk), int(rl), int(rk), int(self.mrow), zero,
+                                 _stream()))
+        else:
+            planes, rot, xi, yi = src_maps
+            check(e.lib.oa_qe_mv_maps(e.plan, len(planes), (ctypes.c_void_p * len(planes))(*[m.data_ptr() for m in planes]),
+                                      _ptr(rot[0]) if rot else None, _ptr(rot[1]) if rot else None, 1, (ctypes.c_int * 1)(n), signs, fgs, fhs,
+                                      swaps, (ctypes.c_int * 1)(xi), (ctypes.c_int * 1)(yi), one(Fn.data_ptr()), _ptr(out),
+                                      1 if accumulate else 0, int(wl), int(wk), int(rl), int(rk), int(self.mrow), zero, _stream()))
         mark_dirty(out)
         if wk or rk:
             set_clean_region(out, (wk, rk))
@@ -907,10 +990,11 @@ class Estimator(object):
         self.Nlkk["MV"] = _safe_div(np.ones_like(tot), tot)
         return w
 
-    def reconstruct_mv_hc(self, kT, kE, kB, estimators=("TT", "TE", "EE", "EB", "TB"), out=None, fused=True):
+    def reconstruct_mv_hc(self, kT, kE, kB, estimators=("TT", "TE", "EE", "EB", "TB"), out=None, fused=True, _maps=None):
         """kappa_hat^MV = sum_a w_a kappa_hat^a, accumulated in the divergence kernel.  fused (default): one ``oa_qe_mv``
         call in which every distinct filtered field is transformed once (TT+TE+EE+EB+TB: 17 leg planes, not 30);
-        fused=False: one ``oa_qe_pol`` call per estimator."""
+        fused=False: one ``oa_qe_pol`` call per estimator.  (``_maps``: :meth:`reconstruct_mv_from_maps`' real planes of T and the
+        two polarisation fields + rotation planes or None, on a band grid: the same call through ``oa_qe_mv_maps``.)"""
         e = self.eng
         key = tuple(estimators)
         if getattr(self, "_mv", None) is None or self._mv[0] != key:
@@ -955,16 +1039,21 @@ class Estimator(object):
                         wl=widest([g_["wl"] for g_ in G]), rl=widest([g_["rl"] for g_ in G]))
             self._mv = (self._mv[0], self._mv[1], args)
         a = self._mv[2]
-        for XY in estimators:
-            e._chk(f[XY[0]], "hc"); e._chk(f[XY[1]], "hc")
+        if _maps is None:
+            for XY in estimators:
+                e._chk(f[XY[0]], "hc"); e._chk(f[XY[1]], "hc")
+        else:
+            for m in _maps[0]:
+                e._chk(m, "real")
         wk, rk = self._wK
         if out is None:
             out, zero = e.hc(), 0
         else:
             e._chk(out, "hc")
             zero = 1 if ((wk or rk) and owned_clean_region(out) != (wk, rk)) else 0
-        kxs = (ctypes.c_void_p * a["ne"])(*[f[XY[0]].data_ptr() for XY in estimators])
-        kys = (ctypes.c_void_p * a["ne"])(*[f[XY[1]].data_ptr() for XY in estimators])
+        if _maps is None:
+            kxs = (ctypes.c_void_p * a["ne"])(*[f[XY[0]].data_ptr() for XY in estimators])
+            kys = (ctypes.c_void_p * a["ne"])(*[f[XY[1]].data_ptr() for XY in estimators])
         e._ordered()
         if e.mixed:                           # BAND GRID: every distinct filter plane and the stacked MV planes, bound once per set
             self._pol_bind(key, [self._mv[1][XY] for XY in estimators], (a["wl"], wk, a["rl"], rk), split=False)
@@ -972,8 +1061,17 @@ class Estimator(object):
             check(e.lib.oa_plan_set_col_grid(e.plan, int(self.mcol)))
             if getattr(e, "_pipe_owner", None) is not self._token:
                 e._pipe_owner = None      # the call above re-resolved the grid of another handle's TT binding: it binds again on its next call
-        check(e.lib.oa_qe_mv(e.plan, a["ne"], a["npieces"], a["signs"], a["fgs"], a["fhs"], a["swaps"], kxs, kys, a["fns"], _ptr(out), 0,
-                             int(a["wl"]), int(wk), int(a["rl"]), int(rk), int(self.mrow), zero, _stream()))
+        if _maps is None:
+            check(e.lib.oa_qe_mv(e.plan, a["ne"], a["npieces"], a["signs"], a["fgs"], a["fhs"], a["swaps"], kxs, kys, a["fns"], _ptr(out), 0,
+                                 int(a["wl"]), int(wk), int(a["rl"]), int(rk), int(self.mrow), zero, _stream()))
+        else:
+            planes, rot = _maps
+            idx = {"T": 0, "E": 1, "B": 2}
+            check(e.lib.oa_qe_mv_maps(e.plan, 3, (ctypes.c_void_p * 3)(*[m.data_ptr() for m in planes]), _ptr(rot[0]) if rot else None,
+                                      _ptr(rot[1]) if rot else None, a["ne"], a["npieces"], a["signs"], a["fgs"], a["fhs"], a["swaps"],
+                                      (ctypes.c_int * a["ne"])(*[idx[XY[0]] for XY in estimators]),
+                                      (ctypes.c_int * a["ne"])(*[idx[XY[1]] for XY in estimators]), a["fns"], _ptr(out), 0,
+                                      int(a["wl"]), int(wk), int(a["rl"]), int(rk), int(self.mrow), zero, _stream()))
         mark_dirty(out)
         if wk or rk:
             set_clean_region(out, (wk, rk))

@@ -14,7 +14,13 @@ modular chain on the same plan, on the reference notebooks' patches (tutorials/t
     path (one oa_qe_tt_split_power call on the band grid) against the generic pairwise loop on the same plan (n^2 kappa_from_map calls +
     host-side power evaluations: what a duck-typed qest gets, and what every qest got on these sides before), in one process on the
     same inputs.  Per cell the median of --reps timed blocks (HIP events) of --iters device-path / --loop-iters generic-loop estimates and
-    the spread of the blocks."""
+    the spread of the blocks.
+--from-maps: the polarisation entries from REAL T, Q, U maps resident on the device (oa_qe_mv_maps): (a) ONE reconstruct_mv_from_maps(T, Q, U,
+    qu=True) call for the MV of five / ONE reconstruct_from_maps("EB", (T, Q, U), qu=True) call, against (b) what the same inputs cost
+    without the entry: Engine.rfft of T, Q, U (EB: of Q, U only) into resident planes, rot2, reconstruct_mv_hc / reconstruct_hc -- in one
+    process on the same plan and maps, the two paths ALTERNATED block by block after a warm-up of every shape.  Per cell the median and
+    the 10th .. 90th percentile of --reps blocks of --iters calls (HIP events; the issue's setting: --reps 50 --iters 10) and the maximum
+    relative difference of the two outputs.  --precs picks the precisions; with --only-onecall N: N calls of path (a) and nothing else."""
 import argparse
 import json
 import os
@@ -112,6 +118,76 @@ def main_pol(args):
                                       max_rel_diff=diff)), flush=True)
 
 
+def timed_alternating(fa, fb, iters, reps):
+    """blocks of `iters` calls of fa and of fb in turn: (median, p10, p90) ms per call of each"""
+    import torch
+    for _ in range(3):
+        fa(); fb()
+    torch.cuda.synchronize()
+    out = ([], [])
+    for _ in range(reps):
+        for fn, acc in ((fa, out[0]), (fb, out[1])):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(iters):
+                fn()
+            b.record()
+            b.synchronize()
+            acc.append(a.elapsed_time(b) / iters)
+    return tuple((float(np.median(o)), float(np.percentile(o, 10)), float(np.percentile(o, 90))) for o in out)
+
+
+def main_frommaps(args):
+    import torch
+    from orphics_amd import maps
+    ests = ("TT", "TE", "EE", "EB", "TB")
+    sides = [int(s) for s in args.sides.split(",")]
+    precs = args.precs.split(",")
+    cells = []
+    for n in sides:
+        q64, k = setup_pol(n, 0.5)
+        q64.mv_weights(ests)
+        rot = maps.queb_rotmat(q64.geom.lmap())
+        c, s = rot[0, 0], rot[1, 0]
+        real = [np.fft.ifft2(a).real for a in (k["T"], c * k["E"] + s * k["B"], -s * k["E"] + c * k["B"])]        # T, Q, U
+        for prec in precs:
+            q = q64 if prec == "f64" else q64.astype("f32")
+            e = q.eng
+            T, Q, U = (e.to_real(a) for a in real)
+            kb = [e.hc(), e.hc(), e.hc()]
+            out, ref_out = q.new_output(), e.hc()
+            rc, rs = q._qu_rot(False)
+
+            def mv_ref(q=q, e=e, T=T, Q=Q, U=U, kb=kb, ref_out=ref_out, rc=rc, rs=rs):
+                e.rfft(T, out=kb[0]); e.rfft(Q, out=kb[1]); e.rfft(U, out=kb[2])
+                kE, kB = e.rot2(rc, rs, kb[1], kb[2])
+                return q.reconstruct_mv_hc(kb[0], kE, kB, out=ref_out)
+
+            def eb_ref(q=q, e=e, Q=Q, U=U, kb=kb, ref_out=ref_out, rc=rc, rs=rs):
+                e.rfft(Q, out=kb[1]); e.rfft(U, out=kb[2])
+                kE, kB = e.rot2(rc, rs, kb[1], kb[2])
+                return q.reconstruct_hc("EB", kE, kB, out=ref_out)
+            cells.append((n, prec, "MV", q, e, out, ref_out, lambda q=q, T=T, Q=Q, U=U, out=out: q.reconstruct_mv_from_maps(T, Q, U, qu=True, out=out), mv_ref))
+            cells.append((n, prec, "EB", q, e, out, ref_out, lambda q=q, T=T, Q=Q, U=U, out=out: q.reconstruct_from_maps("EB", (T, Q, U), qu=True, out=out), eb_ref))
+    for cell in cells:                                 # warm-up of every shape before anything is timed
+        cell[7](); cell[8]()
+    torch.cuda.synchronize()
+    for n, prec, name, q, e, out, ref_out, one, ref in cells:
+        if args.only_onecall:
+            for _ in range(args.only_onecall):
+                one()
+            torch.cuda.synchronize()
+            continue
+        ta, tb = timed_alternating(one, ref, args.iters, args.reps)
+        one(); ref()
+        diff = float((out - ref_out)[:, :e.nxh + 1].abs().max() / ref_out.abs().max())
+        grid = q.pol_band_grid("EB" if name == "EB" else ests)
+        print(json.dumps(dict(side=n, prec=prec, call=name, band_grid=list(grid) if grid else None, frommaps_ms=round(ta[0], 4),
+                              frommaps_p10_p90=[round(ta[1], 4), round(ta[2], 4)], transforms_ms=round(tb[0], 4),
+                              transforms_p10_p90=[round(tb[1], 4), round(tb[2], 4)], speedup=round(tb[0] / ta[0], 2), max_rel_diff=diff)),
+              flush=True)
+
+
 class _Duck(object):
     """a qest that is not this package's Estimator: SplitLensing takes the generic pairwise loop"""
 
@@ -176,6 +252,8 @@ def main():
     ap.add_argument("--pol", action="store_true")
     ap.add_argument("--splits", action="store_true")
     ap.add_argument("--loop-iters", type=int, default=3)
+    ap.add_argument("--from-maps", action="store_true")
+    ap.add_argument("--precs", default="f32,f64")
     args = ap.parse_args()
     import torch
     from orphics_amd import mc
@@ -184,6 +262,8 @@ def main():
         return main_pol(args)
     if args.splits:
         return main_splits(args)
+    if args.from_maps:
+        return main_frommaps(args)
     for n in [int(s) for s in args.sides.split(",")]:
         for prec in ("f32", "f64"):
             q, tmap, tot_h = setup(n, 0.5, prec)
