@@ -169,33 +169,57 @@ struct GrfMixArgs {
 };
 // NC and the input mode are compile-time: every loop unrolls, the pointer tables and the per-component values stay in registers
 // (with run-time indices they went through scratch: 400-660 us per call at 4096^2 float64 instead of 100-250).  A thread owns the
-// column pair (2p, 2p + 1) of one row and moves it with ONE load / store per plane (32 B float64, 16 B float32: kp is a multiple
-// of 16, so pairs are aligned and in bounds, row padding included); all loads are issued before the Philox / Box-Muller arithmetic.
+// column pair (2p, 2p + 1) of one row and, where kp = nx/2 + 16 is even (VEC), moves it with ONE load / store per plane (32 B
+// float64, 16 B float32: pairs are aligned and in bounds, row padding included).  nx/2 odd makes kp odd: the pairs of every other
+// row are then misaligned and the last pair of a row has no second column (it would be column 0 of the next row, or one element
+// behind the plane), so those plans move the two columns one by one and skip the missing one.  All loads are issued before the
+// Philox / Box-Muller arithmetic.
 template <typename T> struct alignas(2 * sizeof(T)) Pair { T a, b; };
-template <typename T, int NC, bool HAS_IN>
+template <bool VEC, typename E>
+OA_D Pair<E> load_pair(const E* p, long i0, bool second) {
+    if constexpr (VEC) {
+        return *reinterpret_cast<const Pair<E>*>(p + i0);
+    } else {
+        Pair<E> r;
+        r.a = p[i0];
+        r.b = second ? p[i0 + 1] : p[i0];
+        return r;
+    }
+}
+template <bool VEC, typename E>
+OA_D void store_pair(E* p, long i0, bool second, const Pair<E>& v) {
+    if constexpr (VEC) {
+        *reinterpret_cast<Pair<E>*>(p + i0) = v;
+    } else {
+        p[i0] = v.a;
+        if (second) p[i0 + 1] = v.b;
+    }
+}
+template <typename T, int NC, bool HAS_IN, bool VEC>
 __global__ __launch_bounds__(256) void grf_mix_kernel(GrfMixArgs<T> a) {
     const int nxh = a.nx / 2, npair = nxh / 2 + 1, ny = a.ny;
     const int pr = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (2L * pr >= a.kp) return;
     const long i0 = (long)y * a.kp + 2 * pr;
+    const bool second = 2L * pr + 1 < a.kp;       // always true with VEC
     typedef Pair<T> R2;
     typedef Pair<cx<T>> C2;
     // ---- loads ----
     R2 sv[NC * NC];
 #pragma unroll
-    for (int k = 0; k < NC * NC; ++k) { sv[k].a = (T)0; sv[k].b = (T)0; if (a.cs[k]) sv[k] = *reinterpret_cast<const R2*>(a.cs[k] + i0); }
+    for (int k = 0; k < NC * NC; ++k) { sv[k].a = (T)0; sv[k].b = (T)0; if (a.cs[k]) sv[k] = load_pair<VEC>(a.cs[k], i0, second); }
     R2 rc{(T)1, (T)1}, rs{(T)0, (T)0}, fl{(T)1, (T)1};
-    if (NC == 3 && a.rc) { rc = *reinterpret_cast<const R2*>(a.rc + i0); rs = *reinterpret_cast<const R2*>(a.rs + i0); }
+    if (NC == 3 && a.rc) { rc = load_pair<VEC>(a.rc, i0, second); rs = load_pair<VEC>(a.rs, i0, second); }
     C2 u[NC];
     if constexpr (HAS_IN) {
-        if (a.filt) fl = *reinterpret_cast<const R2*>(a.filt + i0);
+        if (a.filt) fl = load_pair<VEC>(a.filt, i0, second);
 #pragma unroll
-        for (int c = 0; c < NC; ++c) u[c] = *reinterpret_cast<const C2*>(a.in[c] + i0);
+        for (int c = 0; c < NC; ++c) u[c] = load_pair<VEC>(a.in[c], i0, second);
     }
     // ---- draws: columns 2p, 2p + 1 share a counter unless one of them is a self-conjugate column read at the mirrored row ----
     const T rs2 = (T)0.70710678118654752440;
     cx<T> w[2][NC];
-    float n[NC][4];
+    float n[NC][4] = {};                        // a pair that lies in the row padding draws nothing and stores zeros
     int cur_ys = -1;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -263,7 +287,7 @@ __global__ __launch_bounds__(256) void grf_mix_kernel(GrfMixArgs<T> a) {
         }
     }
 #pragma unroll
-    for (int c = 0; c < NC; ++c) *reinterpret_cast<C2*>(a.out[c] + i0) = o[c];
+    for (int c = 0; c < NC; ++c) store_pair<VEC>(a.out[c], i0, second, o[c]);
 }
 
 template <typename T>
@@ -320,10 +344,17 @@ static int grf_mix_launch(oa_plan* p, uint64_t seed, uint64_t sid0, int ncomp, c
     a.ncomp = ncomp; a.ny = p->ny; a.nx = p->nx; a.kp = p->kp;
     const int npair = (int)((p->kp + 1) / 2), bs = npair >= 256 ? 256 : 64;          // pairs of columns, the row padding included
     const dim3 grid((npair + bs - 1) / bs, p->ny);
+    // the pair moves (grf_mix_kernel, VEC) need an even pitch and planes that start on a pair boundary; anything else goes column by column
+    auto on_pair = [](const void* q, size_t unit) { return q == nullptr || (uintptr_t)q % unit == 0; };
+    bool vec = p->kp % 2 == 0 && on_pair(rc, 2 * sizeof(T)) && on_pair(rs, 2 * sizeof(T)) && on_pair(filt, 2 * sizeof(T));
+    for (int i = 0; i < ncomp * ncomp; ++i) vec = vec && on_pair(cs[i], 2 * sizeof(T));
+    for (int i = 0; i < ncomp; ++i) vec = vec && on_pair(out[i], 4 * sizeof(T)) && (!in || on_pair(in[i], 4 * sizeof(T)));
 #define OA_MIX(NC) \
     do { \
-        if (in) hipLaunchKernelGGL((grf_mix_kernel<T, NC, true>), grid, dim3(bs), 0, st, a); \
-        else hipLaunchKernelGGL((grf_mix_kernel<T, NC, false>), grid, dim3(bs), 0, st, a); \
+        if (in && vec) hipLaunchKernelGGL((grf_mix_kernel<T, NC, true, true>), grid, dim3(bs), 0, st, a); \
+        else if (in) hipLaunchKernelGGL((grf_mix_kernel<T, NC, true, false>), grid, dim3(bs), 0, st, a); \
+        else if (vec) hipLaunchKernelGGL((grf_mix_kernel<T, NC, false, true>), grid, dim3(bs), 0, st, a); \
+        else hipLaunchKernelGGL((grf_mix_kernel<T, NC, false, false>), grid, dim3(bs), 0, st, a); \
     } while (0)
     if (ncomp == 1) OA_MIX(1);
     else if (ncomp == 2) OA_MIX(2);
