@@ -43,7 +43,7 @@ typedef struct oa_plan oa_plan;
 const char* oa_last_error(void);
 /* ABI version = 100 x the build round that last changed a signature in this header; bindings must refuse a library
  * that reports less than the version they were written against (OA_ABI_VERSION) */
-#define OA_ABI_VERSION 406
+#define OA_ABI_VERSION 407
 int oa_version(void);
 /* number of HIP devices visible; <0 on error (no compute) */
 int oa_device_count(void);
@@ -342,6 +342,31 @@ int oa_mc_run(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const vo
  * window == 1 the moments equal oa_mc_run's up to rounding; with a taper the stack holds the window's mean field. */
 int oa_mc_run_windowed(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, const void* window_real,
                        int64_t* n, double* S, double* C, double* meanfield_acc, void* stream);
+/* oa_mc_run_mv: the Gaussian N0 Monte-Carlo shard [sim_lo, sim_hi) of an estimator SET (TT, TE, EE, EB, TB ... and their MV combination),
+ * power-of-two plans.  The estimator arguments are oa_qe_mv's (nest <= 6, pieces flattened in estimator order) except that the sources
+ * are named by index -- host_xsrc[e] / host_ysrc[e]: 0 T, 1 E, 2 B, oa_qe_mv_maps' convention -- and that host_Fnorm holds the PURE
+ * normalisations (no MV weight).  host_covsqrt: oa_grf_mix's nine hc-real blocks for the fields T, E, B (NULL = zero block), amplitude
+ * scaling included.  Per realisation i, stream-ordered, nothing leaving the device and no host work on the data:
+ *   1. oa_grf_mix_band(seed = base_seed, stream_id0 = 3 i, ncomp = 3, width = leg_cols, rband = leg_rows) into three hc planes owned by
+ *      the entry (the plan's work planes are where step 2 puts the per-estimator kappa_hat);
+ *   2. oa_qe_mv's launch sequence without its final sum: estimator e's normalised kappa_hat ends in plane e of an evenly spaced block --
+ *      the plan-owned planes of the one-launch divergence when that is engaged (2 <= nest, evenly spaced host_Fnorm, OA_OPT_MV_BATCH = 1),
+ *      else the estimators run one at a time into a block the entry owns;
+ *   3. oa_bin_power_multi over the block: fields 0 .. nest-1 are the estimators, field nest (only with mv_weights: nest hc-real planes
+ *      mv_wstride elements apart) is the MV combination sum_e w_e kappa_hat_e, formed in registers; spectrum s = (host_a[s], host_b[s]),
+ *      kappa's band (kappa_cols, kappa_rows) as the active region, ids_hc / nids / norm as for oa_bin_power;
+ *   4. one launch: x[s * d + j] = sums[s][j + 1] / counts[j + 1], d = nids - 2 (counts: device int64[nids], the data-independent mode
+ *      counts of a full-plane oa_bin_power call), then n += 1, S += x, C += x x^T with D = nspec * d  (S: D doubles, C: D x D).
+ * Realisation i's contribution does not depend on how a range is cut into calls.  The first call (and a call that needs more than any
+ * before) allocates the entry's planes and synchronises the device once; oa_plan_release_pools frees them.  Refused before anything is
+ * launched: a 2^a 3^b 5^c or chirp-z plan (the band-grid binding carries no bin ids; the message names the host loop of the existing
+ * entries that mc.GaussianN0MonteCarloPol runs there), nest outside 1..6, a source index outside [0, 3), and every refusal of
+ * oa_bin_power_multi (with nfields = nest). */
+int oa_mc_run_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest, const int* host_npieces,
+                 const double* host_signs, const void* const* host_FG, const void* const* host_FH, const int* host_swap, const int* host_xsrc,
+                 const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights, long mv_wstride, int nspec, const int* host_a,
+                 const int* host_b, const int32_t* ids_hc, int nids, const int64_t* counts, double norm, int leg_cols, int kappa_cols,
+                 int leg_rows, int kappa_rows, int mrow, int64_t* n, double* S, double* C, void* stream);
 /* One stage of oa_qe_tt_moments on the plan's own work planes, for per-kernel timing (bench.py roofline; the
  * one-call path keeps its intermediates on COMPACT planes -- pitch = active columns rounded up to a 32-column tile
  * -- so its kernels are not the same launches as the fine-grained calls on caller planes of pitch kpitch):
@@ -481,6 +506,22 @@ int oa_bin(int dtype, const void* data, const int32_t* ids, const void* weights,
 int oa_bin_power(int dtype, const void* k1, const void* k2, double norm, const int32_t* ids, const void* weights, long n,
                  int nids, long herm_pitch, int herm_nxh, double* sums, int64_t* counts, double* wsums, void* scratch, int active_cols, int active_rows,
                  void* stream);
+/* oa_bin_power_multi: nspec binned (cross-)spectra of a few hc planes in ONE pass and one launch pair.  Field f (0 <= f < nfields <= 6) is
+ * the hc plane at k0 + f * fstride (complex elements, row pitch kpitch, ny rows); with w0 != NULL, w0 + f * wstride are hc-real weight
+ * planes and field index nfields names the per-mode weighted sum sum_f w_f k_f, formed in registers and never stored.  Spectrum s is
+ * Re(conj(F_a[s]) F_b[s]) * norm times oa_bin_power's Hermitian multiplicity (1 for column 0 and column nxh, 2 between); the stored
+ * values are converted to double first, products and sums are formed in double in both precisions.  sums[s * nids + id] is overwritten
+ * (device, nspec * nids doubles); scratch: oa_bin_power_multi_scratch_bytes(nspec, nids) device bytes (-1 for a refused pair).  A mode's
+ * nfields values are loaded once and feed all nspec products.  active_cols / active_rows: oa_bin_power's contract (planes that vanish
+ * outside the region give the sums of a full visit; rows only together with columns).  Deterministic: per-workgroup partial sums folded
+ * in a fixed order, no floating-point atomics -- two runs give bit-identical sums.  Refused before any launch: nspec outside 1..28 (seven
+ * fields have 28 distinct pairs), nids outside 1..1024, nspec * nids > 4096 (the workgroup keeps one table of partial sums per wave in
+ * LDS: 4 waves x 4096 x 8 B = 128 KiB of the 160 KiB a gfx950 workgroup can take), nfields outside 1..6, a field index outside
+ * [0, nfields], index nfields without w0, NULL pointers, a bad dtype. */
+long oa_bin_power_multi_scratch_bytes(int nspec, int nids);
+int oa_bin_power_multi(int dtype, int nfields, const void* k0, long fstride, const void* w0, long wstride, int nspec, const int* host_a,
+                       const int* host_b, double norm, const int32_t* ids_hc, int nids, int ny, long kpitch, int nxh, int active_cols,
+                       int active_rows, double* sums, void* scratch, void* stream);
 
 /* ---- Gaussian random fields (MapGen.get_map, maps.py:1576-1587) --------------
  * Fills an hc plane with Hermitian-consistent complex white noise of unit
@@ -505,6 +546,12 @@ int oa_grf_hc_band(oa_plan* p, uint64_t seed, uint64_t stream_id, const void* co
  * filt_hcreal may be NULL (= 1); hc_out[i] may alias hc_in[i]. */
 int oa_grf_mix(oa_plan* p, uint64_t seed, uint64_t stream_id0, int ncomp, const void* const* covsqrt_hc, const void* rot_c, const void* rot_s,
                const void* const* hc_in, const void* filt_hcreal, double scale, void* const* hc_out, void* stream);
+/* The leg band of oa_grf_mix(p, seed, stream_id0, ncomp, covsqrt_hc, NULL, NULL, NULL, NULL, scale, hc_out, stream): columns < width and
+ * rows y < rband or y > ny - rband (0 = all), a bit-identical subset of the full draw -- every mode keeps its Philox counter and the
+ * self-conjugate edge rules --; the rest of each output plane is not written.  Any plan kind (element-wise on the N-grid hc layout),
+ * ncomp 1..3, NULL blocks are zero.  What oa_grf_hc_band is to oa_grf_hc. */
+int oa_grf_mix_band(oa_plan* p, uint64_t seed, uint64_t stream_id0, int ncomp, const void* const* covsqrt_hc, double scale,
+                    void* const* hc_out, int width, int rband, void* stream);
 /* real white noise N(0,1) plane of n elements (enmap.rand_gauss) */
 int oa_randn(int dtype, uint64_t seed, uint64_t stream_id, void* out, long n, void* stream);
 

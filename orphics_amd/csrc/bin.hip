@@ -424,6 +424,172 @@ int bin_power_moments(int dtype, const void* k, double norm, const int32_t* ids,
                             active_cols, active_rows, &t, nbatch, 2 * kstride);
 }
 
+
+// ---- oa_bin_power_multi: nspec binned (cross-)spectra of nfields <= 6 hc planes in ONE pass ---------------------------------------
+// A lane owns one mode: its nfields values are loaded once, converted to double, the weighted sum (field index nfields) is formed in
+// registers, and every spectrum of the list takes its two operands from those registers.  The rows of the visited region are padded to a
+// whole number of waves in the virtual index, so a wave never straddles two rows and its radial ids are sorted along the lanes: ONE
+// sortedness test and one set of segment predicates per wave serve all spectra; each spectrum is then a 6-step segmented scan whose run
+// tails add to the wave's private LDS row [spectrum][id] (distinct addresses, fixed order).  Unsorted keys (never on a radial binning of
+// the half plane) take the match loop.  Partials per workgroup, folded in a fixed order by bin_multi_final_kernel: deterministic.
+constexpr int MULTI_MAX_FIELDS = 6;
+constexpr int MULTI_MAX_SPEC = 28;                 // 7 fields (six stored + the weighted sum): 7 autos + 21 crosses
+constexpr int MULTI_MAX_TABLE = 4096;              // nspec * nids: x 4 waves x 8 B = 128 KiB of the workgroup's 160 KiB LDS
+constexpr int MULTI_GMAX = 256;                    // workgroups (one per CU)
+struct MultiSpec { int nspec; unsigned char a[MULTI_MAX_SPEC], b[MULTI_MAX_SPEC]; };
+
+template <typename T>
+__global__ __launch_bounds__(BIN_BLOCK) void bin_multi_kernel(const T* __restrict__ k0, long fstride, const T* __restrict__ w0, long wstride,
+                                                              int nf, MultiSpec spec, double norm, const int32_t* __restrict__ ids, int nids,
+                                                              int ny, long kp, int nxh, int cols, int rb, double* __restrict__ part) {
+    extern __shared__ __attribute__((aligned(16))) char sm_raw[];
+    double* s_sum = reinterpret_cast<double*>(sm_raw);                        // [WAVES][nspec][nids]
+    __shared__ int s_a[MULTI_MAX_SPEC], s_b[MULTI_MAX_SPEC];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int nspec = spec.nspec, ntab = nspec * nids;
+    if (tid < MULTI_MAX_SPEC) { s_a[tid] = spec.a[tid]; s_b[tid] = spec.b[tid]; }
+    for (int i = tid; i < BIN_WAVES * ntab; i += BIN_BLOCK) s_sum[i] = 0.0;
+    __syncthreads();
+    double* row = s_sum + wv * ntab;
+    const long nrows = rb ? 2L * rb - 1 : (long)ny;
+    const long rowp = ((long)cols + 63) & ~63L;                               // lanes per visited row: a wave stays inside one row
+    const long total = nrows * rowp;
+    for (long base = (long)blockIdx.x * BIN_BLOCK; base < total; base += (long)gridDim.x * BIN_BLOCK) {
+        const long cv = base + tid;
+        const long r = cv / rowp;
+        const int x = (int)(cv - r * rowp);
+        const bool in = cv < total && x < cols;
+        const long y = (!rb || r < rb) ? r : (long)ny - nrows + r;
+        const long i = y * kp + x;
+        int id = 0x7fffffff;
+        double fr[MULTI_MAX_FIELDS + 1], fi[MULTI_MAX_FIELDS + 1];
+#pragma unroll
+        for (int f = 0; f <= MULTI_MAX_FIELDS; ++f) { fr[f] = 0.0; fi[f] = 0.0; }
+        if (in) {
+            id = ids[i];
+            double mr = 0.0, mi = 0.0;
+#pragma unroll
+            for (int f = 0; f < MULTI_MAX_FIELDS; ++f) {
+                if (f < nf) {
+                    const T* k = k0 + 2 * ((long)f * fstride + i);
+                    const double re = (double)k[0], im = (double)k[1];
+                    if (w0) { const double w = (double)w0[(long)f * wstride + i]; mr += w * re; mi += w * im; }
+                    fr[f] = re; fi[f] = im;
+                }
+            }
+#pragma unroll
+            for (int g = 1; g <= MULTI_MAX_FIELDS; ++g)                       // slot nf: the weighted sum (compile-time register indices)
+                if (g == nf) { fr[g] = mr; fi[g] = mi; }
+        }
+        const int m = (x == 0 || x == nxh) ? 1 : (x < nxh ? 2 : 0);          // Hermitian multiplicity of oa_bin_power
+        const bool valid = in && id >= 0 && id < nids && m > 0;
+        const int key = in ? id : 0x7fffffff;                                 // lanes beyond the row's end keep the sequence sorted
+        const double scale = valid ? norm * (double)m : 0.0;
+        const int prev = __shfl_up(key, 1, 64);
+        const bool sorted = !__ballot(lane > 0 && prev > key);
+        unsigned same = 0;                                                    // bit t: lane - 2^t holds the same key
+#pragma unroll
+        for (int t = 0; t < 6; ++t) {
+            const int pk = __shfl_up(key, 1 << t, 64);
+            if (lane >= (1 << t) && pk == key) same |= 1u << t;
+        }
+        const int next = __shfl_down(key, 1, 64);
+        const bool tail = (lane == 63 || next != key) && valid;
+        for (int s = 0; s < nspec; ++s) {
+            const int a = s_a[s], b = s_b[s];
+            double ar = 0.0, ai = 0.0, br = 0.0, bi = 0.0;
+#pragma unroll
+            for (int g = 0; g <= MULTI_MAX_FIELDS; ++g) {
+                if (a == g) { ar = fr[g]; ai = fi[g]; }
+                if (b == g) { br = fr[g]; bi = fi[g]; }
+            }
+            double v = (ar * br + ai * bi) * scale;
+            if (sorted) {
+                // (equal keys are contiguous: a lane's invalid neighbours with the same key contribute zeros)
+#pragma unroll
+                for (int t = 0; t < 6; ++t) {
+                    const double pv = __shfl_up(v, 1 << t, 64);
+                    if (same & (1u << t)) v += pv;
+                }
+                if (tail) row[s * nids + key] += v;
+            } else {
+                unsigned long long act = __ballot(valid);
+                while (act) {
+                    const int leader = __ffsll((long long)act) - 1;
+                    const int lid = __shfl(id, leader, 64);
+                    const bool mine = valid && id == lid;
+                    const double sv = wave_sum(mine ? v : 0.0);
+                    if (lane == leader) row[s * nids + lid] += sv;
+                    act &= ~__ballot(mine);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < ntab; i += BIN_BLOCK) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < BIN_WAVES; ++k) s += s_sum[k * ntab + i];
+        part[(long)blockIdx.x * ntab + i] = s;
+    }
+}
+
+// one workgroup per (spectrum, id): fixed-order strided sum of the workgroups' partials + fixed-order LDS tree
+__global__ __launch_bounds__(256) void bin_multi_final_kernel(const double* __restrict__ part, int nblocks, int ntab, double* __restrict__ sums) {
+    __shared__ double sh[256];
+    const int i = blockIdx.x, t = threadIdx.x;
+    double s = 0.0;
+    for (int b = t; b < nblocks; b += 256) s += part[(long)b * ntab + i];
+    sh[t] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) sh[t] += sh[t + o];
+        __syncthreads();
+    }
+    if (t == 0) sums[i] = sh[0];
+}
+
+int bin_power_multi_check(const char* who, int dtype, int nfields, bool have_w, int nspec, const int* host_a, const int* host_b, int nids) {
+    const std::string w(who);
+    OA_REQUIRE(dtype == OA_F32 || dtype == OA_F64, w + ": bad dtype");
+    OA_REQUIRE(nfields >= 1 && nfields <= MULTI_MAX_FIELDS, w + ": nfields must be in [1,6]");
+    OA_REQUIRE(nspec >= 1 && nspec <= MULTI_MAX_SPEC, w + ": nspec must be in [1,28]");
+    OA_REQUIRE(nids >= 1 && nids <= BIN_MAX_IDS, w + ": nids (= nedges+1) must be in [1,1024]");
+    OA_REQUIRE((long)nspec * nids <= MULTI_MAX_TABLE, w + ": nspec * nids must not exceed 4096 (the workgroup's table of partial sums)");
+    OA_REQUIRE(host_a && host_b, w + ": NULL spectrum list");
+    for (int s = 0; s < nspec; ++s) {
+        OA_REQUIRE(host_a[s] >= 0 && host_a[s] <= nfields && host_b[s] >= 0 && host_b[s] <= nfields, w + ": field index outside [0, nfields]");
+        OA_REQUIRE(have_w || (host_a[s] < nfields && host_b[s] < nfields), w + ": field index nfields (the weighted sum) needs weight planes");
+    }
+    return 0;
+}
+
+template <typename T>
+static int bin_multi_impl(int nf, const void* k0, long fstride, const void* w0, long wstride, int nspec, const int* ha, const int* hb, double norm,
+                          const int32_t* ids, int nids, int ny, long kp, int nxh, int active_cols, int active_rows, double* sums, void* scratch,
+                          hipStream_t st) {
+    MultiSpec spec{};
+    spec.nspec = nspec;
+    for (int s = 0; s < nspec; ++s) { spec.a[s] = (unsigned char)ha[s]; spec.b[s] = (unsigned char)hb[s]; }
+    const int cols = (active_cols > 0 && active_cols < nxh + 1) ? active_cols : nxh + 1;          // the row padding holds no mode
+    const int rb = (active_cols > 0 && active_rows > 0 && 2L * active_rows - 1 < ny) ? active_rows : 0;
+    const long total = (rb ? 2L * rb - 1 : (long)ny) * (((long)cols + 63) & ~63L);
+    int G = (int)((total + BIN_BLOCK - 1) / BIN_BLOCK);
+    if (G < 1) G = 1;
+    if (G > MULTI_GMAX) G = MULTI_GMAX;
+    const int ntab = nspec * nids;
+    const size_t smem = (size_t)BIN_WAVES * ntab * sizeof(double);
+    auto k = bin_multi_kernel<T>;
+    if (smem > 48 * 1024)
+        OA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    hipLaunchKernelGGL(k, dim3(G), dim3(BIN_BLOCK), smem, st, (const T*)k0, fstride, (const T*)w0, wstride, nf, spec, norm, ids, nids, ny, kp,
+                       nxh, cols, rb, (double*)scratch);
+    OA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bin_multi_final_kernel, dim3(ntab), dim3(256), 0, st, (const double*)scratch, G, ntab, sums);
+    OA_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace oa
 
 using namespace oa;
@@ -488,6 +654,25 @@ int oa_bin_power(int dtype, const void* k1, const void* k2, double norm, const i
         return bin_impl<double>(k1, k2, norm, true, ids, weights, nullptr, n, nids, 0, 0, herm_pitch, herm_nxh, sums, counts,
                                 wsums, scratch, (hipStream_t)stream, active_cols, active_rows);
     return fail("oa_bin_power: bad dtype");
+}
+
+long oa_bin_power_multi_scratch_bytes(int nspec, int nids) {
+    if (nspec < 1 || nspec > MULTI_MAX_SPEC || nids < 1 || nids > BIN_MAX_IDS || (long)nspec * nids > MULTI_MAX_TABLE) return -1;
+    return (long)MULTI_GMAX * nspec * nids * (long)sizeof(double);
+}
+
+int oa_bin_power_multi(int dtype, int nfields, const void* k0, long fstride, const void* w0, long wstride, int nspec, const int* host_a,
+                       const int* host_b, double norm, const int32_t* ids_hc, int nids, int ny, long kpitch, int nxh, int active_cols,
+                       int active_rows, double* sums, void* scratch, void* stream) {
+    OA_REQUIRE(k0 && ids_hc && sums && scratch, "oa_bin_power_multi: NULL argument");
+    if (int rc = bin_power_multi_check("oa_bin_power_multi", dtype, nfields, w0 != nullptr, nspec, host_a, host_b, nids)) return rc;
+    OA_REQUIRE(ny >= 1 && nxh >= 1 && kpitch >= nxh + 1, "oa_bin_power_multi: bad geometry (kpitch >= nxh + 1)");
+    OA_REQUIRE(nfields == 1 || fstride >= (long)ny * kpitch || fstride <= -(long)ny * kpitch, "oa_bin_power_multi: field stride smaller than a plane");
+    if (dtype == OA_F32)
+        return bin_multi_impl<float>(nfields, k0, fstride, w0, wstride, nspec, host_a, host_b, norm, ids_hc, nids, ny, kpitch, nxh, active_cols,
+                                     active_rows, sums, scratch, (hipStream_t)stream);
+    return bin_multi_impl<double>(nfields, k0, fstride, w0, wstride, nspec, host_a, host_b, norm, ids_hc, nids, ny, kpitch, nxh, active_cols,
+                                  active_rows, sums, scratch, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -166,6 +166,10 @@ int qe_rows_chain_w(oa_plan* p, int nest, int total, const void* const* gx, cons
                     long pl, long pk, hipStream_t st, int my);
 int grf_hc_band_batch(oa_plan* p, uint64_t seed, uint64_t stream_id, int nreal, const void* covsqrt_hc, void* hc_out, long zstride,
                       int width, int rband, hipStream_t stream);
+// oa_mc_run_mv: the interior bins of nspec binned spectra (oa_bin_power_multi's layout) over the mode counts -> n += 1, S += x, C += x x^T (rng.hip);
+// the argument checks of oa_bin_power_multi without its launches (bin.hip): 0, or the failure already reported
+int moments_add_binned_multi(const double* sums, const int64_t* counts, int nspec, int nids, int64_t* n, double* S, double* C, hipStream_t st);
+int bin_power_multi_check(const char* who, int dtype, int nfields, bool have_w, int nspec, const int* host_a, const int* host_b, int nids);
 int qe_legs_pass2_w(oa_plan* p, void* pool, int nplanes, long stride, int width, long pl, hipStream_t st, int my = 0);
 int qe_rows_w(oa_plan* p, const void* gx, const void* gy, const void* h, void* px, void* py, double scale, int accumulate,
               int win, int wout, int mrow, long pl, long pk, hipStream_t st, int my = 0, int lr = 0);

@@ -47,6 +47,8 @@ struct Pipeline {
     int mc_cap = 0;
     void* lens_pool = nullptr;        // oa_lens_maps: transforms + derivative planes (hc and real) of the maps of one call
     size_t lens_bytes = 0;
+    void* mvmc = nullptr;             // oa_mc_run_mv: the three drawn hc planes | per-estimator kappa planes (only when the one-launch divergence
+    size_t mvmc_bytes = 0;            // is not engaged) | oa_bin_power_multi's partials | its sums
     // tile-major copies of Fnorm and of the bin ids on the coarse grid of the fused divergence + binning launch (what they were
     // made from: rebuilt when the filters / bins / column grid change)
     // (one set per grid a plan can carry: [0] the column grid `my`, [1] the from-map grid `my3`)
@@ -130,6 +132,7 @@ void pipeline_release(oa_plan* p) {
     if (q->mc_src) (void)hipFree(q->mc_src);
     if (q->mv_rtab) (void)hipFree(q->mv_rtab);
     if (q->lens_pool) (void)hipFree(q->lens_pool);
+    if (q->mvmc) (void)hipFree(q->mvmc);
     for (auto& t : q->dt) { if (t.fn_t) (void)hipFree(t.fn_t); if (t.ids_t) (void)hipFree(t.ids_t); }
     if (q->fb_t) (void)hipFree(q->fb_t);
     if (q->band) (void)oa_plan_destroy(q->band);
@@ -467,6 +470,8 @@ static DivBinFuse make_fuse(const oa_plan* p, const Pipeline* q, int64_t* n, dou
 
 static int qe_tt_impl(oa_plan* p, const void* real_map, const void* kX, const void* kY, void* out_kappa_hc, int zero_outside,
                       void* stream, DivBinFuse* fuse, int rows_done = 0);
+static int qe_mv_pow2(oa_plan* p, Pipeline* q, const MvCall& c, void* out, int accumulate, int leg_cols, int kappa_cols, int leg_rows,
+                      int kappa_rows, int mrow, int zero_outside, hipStream_t st, bool keep_planes);
 int oa_qe_tt(oa_plan* p, const void* real_map, const void* kX, const void* kY, void* out_kappa_hc, int zero_outside,
              void* stream) {
     if (p && p->mixed) {
@@ -591,7 +596,7 @@ int oa_lens_maps_hc(oa_plan* p, int nmaps, const void* hc_in, long hc_stride, do
     return lens_maps_impl(p, nmaps, nullptr, 0, hc_in, hc_stride, scale, order, shift_x, shift_y, dx, dy, real_out, out_stride, stream);
 }
 
-/* frees the plan-owned pools that the multi-map entries grow on demand (oa_lens_maps, oa_qe_mv / oa_qe_tt_splits, oa_mc_run): they
+/* frees the plan-owned pools that the multi-map entries grow on demand (oa_lens_maps, oa_qe_mv / oa_qe_tt_splits, oa_mc_run, oa_mc_run_mv): they
  * are reallocated by the next call that needs them.  Synchronises the device. */
 int oa_plan_release_pools(oa_plan* p) {
     OA_REQUIRE(p, "oa_plan_release_pools: NULL plan");
@@ -601,6 +606,7 @@ int oa_plan_release_pools(oa_plan* p) {
     if (q->lens_pool) { (void)hipFree(q->lens_pool); q->lens_pool = nullptr; q->lens_bytes = 0; }
     if (q->split_legs) { (void)hipFree(q->split_legs); q->split_legs = nullptr; q->split_bytes = 0; }
     if (q->mc_src) { (void)hipFree(q->mc_src); q->mc_src = nullptr; q->mc_cap = 0; }
+    if (q->mvmc) { (void)hipFree(q->mvmc); q->mvmc = nullptr; q->mvmc_bytes = 0; }
     // band grid: the split entries' inner source planes and kappa block, and the pool their inner call grew (regrown on demand)
     if (q->bsplit) { (void)hipFree(q->bsplit); q->bsplit = nullptr; q->bsplit_bytes = 0; q->bs_cap = 0; }
     if (q->band && q->band->pipe) {
@@ -681,9 +687,38 @@ int oa_qe_mv(oa_plan* p, int nest, const int* host_npieces, const double* host_s
         const MvCall c{nest, host_npieces, host_signs, host_FG, host_FH, host_swap, host_kX, host_kY, host_Fnorm, false};
         return mixed_qe_mv(p, q, c, out, accumulate, leg_cols, kappa_cols, leg_rows, kappa_rows, mrow, zero_outside, (hipStream_t)stream);
     }
+    const MvCall c{nest, host_npieces, host_signs, host_FG, host_FH, host_swap, host_kX, host_kY, host_Fnorm, false};
+    return qe_mv_pow2(p, q, c, out, accumulate, leg_cols, kappa_cols, leg_rows, kappa_rows, mrow, zero_outside, (hipStream_t)stream, false);
+}
+
+// the one-launch divergence of oa_qe_mv: 2 .. 6 estimators whose normalisation planes are evenly spaced (one stacked allocation)
+static bool mv_div_batched(const Pipeline* q, int nest, const void* const* host_Fnorm, size_t rs, long* fn_moff) {
+    bool dbatch = nest >= 2 && nest <= 6 && q->opt_mv_batch;
+    if (dbatch) {
+        const long d = (long)((const char*)host_Fnorm[1] - (const char*)host_Fnorm[0]);
+        dbatch = d > 0 && d % (long)rs == 0;
+        for (int e = 2; e < nest && dbatch; ++e) dbatch = ((const char*)host_Fnorm[e] - (const char*)host_Fnorm[0]) == e * d;
+        *fn_moff = d / (long)rs;
+    }
+    return dbatch;
+}
+
+/* The body of oa_qe_mv on a power-of-two plan, shared with oa_mc_run_mv.  keep_planes (the caller has checked mv_div_batched): the
+ * estimators' kappa_hat stay in the plan-owned planes c[0] + e planes, where the one-launch divergence writes them; they are not summed
+ * and `out` is not touched. */
+static int qe_mv_pow2(oa_plan* p, Pipeline* q, const MvCall& c, void* out, int accumulate, int leg_cols, int kappa_cols, int leg_rows,
+                      int kappa_rows, int mrow, int zero_outside, hipStream_t st, bool keep_planes) {
+    const int nest = c.nest;
+    const int* const host_npieces = c.npieces;
+    const double* const host_signs = c.signs;
+    const void* const* const host_FG = c.FG;
+    const void* const* const host_FH = c.FH;
+    const int* const host_swap = c.swap;
+    const void* const* const host_kX = c.kX;
+    const void* const* const host_kY = c.kY;
+    const void* const* const host_Fnorm = c.Fn;
     if (int rc = ensure_work(p, q)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (!accumulate && zero_outside && out != q->kk)
+    if (!keep_planes && !accumulate && zero_outside && out != q->kk)
         if (int rc = zero_complement(p, out, kappa_cols, kappa_rows, st)) return rc;
     const long pl = work_pitch(p, leg_cols), pk = work_pitch(p, kappa_cols);
     int my = 0;
@@ -761,13 +796,7 @@ int oa_qe_mv(oa_plan* p, int nest, const int* host_npieces, const double* host_s
     // then one pass sums them in estimator order
     const size_t rs = es / 2, pb = plane_bytes(p);
     long fn_moff = 0;
-    bool dbatch = nest >= 2 && nest <= 6 && q->opt_mv_batch;
-    if (dbatch) {
-        const long d = (long)((const char*)host_Fnorm[1] - (const char*)host_Fnorm[0]);
-        dbatch = d > 0 && d % (long)rs == 0;
-        for (int e = 2; e < nest && dbatch; ++e) dbatch = ((const char*)host_Fnorm[e] - (const char*)host_Fnorm[0]) == e * d;
-        fn_moff = d / (long)rs;
-    }
+    bool dbatch = mv_div_batched(q, nest, host_Fnorm, rs, &fn_moff);
     // ROW STAGE: the k-th separable piece of every estimator in ONE launch (they write different product planes; a launch
     // of one piece is 1024 workgroups of two waves and leaves most of the chip's wave slots empty), per-piece planes and
     // scales through a device table; pieces k > 0 accumulate.  Same arithmetic per piece, same order per estimator.
@@ -853,6 +882,7 @@ int oa_qe_mv(oa_plan* p, int nest, const int* host_npieces, const double* host_s
     if (dbatch) {
         if (int rc = qe_cols_div_batch_w(p, prod, prod + lbk, host_Fnorm[0], q->c[0], tmp, nest, (long)(2 * lbk / es), fn_moff, (long)(pb / es),
                                          kappa_cols, kappa_rows, pk, st, my)) return rc;
+        if (keep_planes) return 0;
         // (the divergence writes columns <= nx/2 only: the planes' row padding beyond holds whatever the work planes held)
         const int wsum = (kappa_cols > 0 && kappa_cols <= p->nx / 2 + 1) ? kappa_cols : p->nx / 2 + 1;
         return sum_region(p->dtype, q->c[0], (long)(pb / es), nest, out, accumulate ? 1 : 0, p->ny, p->kp, wsum, kappa_rows, st);
@@ -1499,6 +1529,75 @@ int oa_mc_run(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const vo
         if ((rc = bandpower_moments(p, q, n, S, C, stream))) return rc;
         // kappa_hat vanishes outside its active region (the plan-owned plane was zero-filled once): stack only that
         if (meanfield_acc && (rc = stack_add_region(p->dtype, q->kk, meanfield_acc, p->ny, p->kp, q->wk, q->rk, (hipStream_t)stream))) return rc;
+    }
+    return 0;
+}
+
+/* oa_mc_run_mv (include/orphics_amd.h): the Gaussian N0 Monte-Carlo shard of an estimator SET.  Per realisation: the leg band of
+ * oa_grf_mix's T, E, B draw (streams 3 i, 3 i + 1, 3 i + 2) into three entry-owned planes -- not the plan's work planes: c[0..2], g[0..1]
+ * and kT are where the one-launch divergence puts the per-estimator kappa_hat --, the launch sequence of oa_qe_mv with the sum left out
+ * (qe_mv_pow2), one oa_bin_power_multi pass over the estimators' planes, one moment launch. */
+int oa_mc_run_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest, const int* host_npieces,
+                 const double* host_signs, const void* const* host_FG, const void* const* host_FH, const int* host_swap, const int* host_xsrc,
+                 const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights, long mv_wstride, int nspec, const int* host_a,
+                 const int* host_b, const int32_t* ids_hc, int nids, const int64_t* counts, double norm, int leg_cols, int kappa_cols,
+                 int leg_rows, int kappa_rows, int mrow, int64_t* n, double* S, double* C, void* stream) {
+    OA_REQUIRE(p && host_covsqrt && host_npieces && host_signs && host_FG && host_FH && host_xsrc && host_ysrc && host_Fnorm && ids_hc && counts &&
+               n && S && C && sim_hi >= sim_lo, "oa_mc_run_mv: bad argument");
+    OA_REQUIRE(p->pow2, "oa_mc_run_mv: power-of-two map sides only; on other sides run the host loop of the existing entries "
+               "(mc.GaussianN0MonteCarloPol with one_call=False: Engine.grf_mix, reconstruct_hc per estimator, Engine.bin_power, Statistics.add)");
+    OA_REQUIRE(nest >= 1 && nest <= 6, "oa_mc_run_mv: 1 <= nest <= 6 estimators");
+    OA_REQUIRE(nids >= 3, "oa_mc_run_mv: nids must be at least 3 (two outer bins around the bandpowers)");
+    if (int rc = bin_power_multi_check("oa_mc_run_mv", p->dtype, nest, mv_weights != nullptr, nspec, host_a, host_b, nids)) return rc;
+    const int hw = p->nx / 2 + 1;
+    OA_REQUIRE(leg_cols >= 0 && kappa_cols >= 0 && leg_rows >= 0 && kappa_rows >= 0 && leg_cols <= hw && kappa_cols <= hw &&
+               2L * leg_rows - 1 <= p->ny && 2L * kappa_rows - 1 <= p->ny, "oa_mc_run_mv: leg / kappa band beyond the hc plane");
+    int total = 0;
+    for (int e = 0; e < nest; ++e) {
+        OA_REQUIRE(host_npieces[e] >= 1 && host_Fnorm[e], "oa_mc_run_mv: bad estimator entry");
+        OA_REQUIRE(host_xsrc[e] >= 0 && host_xsrc[e] < 3 && host_ysrc[e] >= 0 && host_ysrc[e] < 3, "oa_mc_run_mv: source index outside [0, 3) (0 T, 1 E, 2 B)");
+        total += host_npieces[e];
+    }
+    for (int i = 0; i < total; ++i) OA_REQUIRE(host_FG[i] && host_FH[i], "oa_mc_run_mv: NULL filter plane");
+    Pipeline* q = pipe_of(p);
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = ensure_work(p, q)) return rc;
+    const size_t es = 2 * (p->dtype == OA_F32 ? 4 : 8), rs = es / 2, pb = plane_bytes(p);
+    long fn_moff = 0;
+    const bool engaged = mv_div_batched(q, nest, host_Fnorm, rs, &fn_moff);
+    // entry-owned pool, taken on the first call (and regrown when a call needs more): that call synchronises the device once
+    const size_t sb = (size_t)oa_bin_power_multi_scratch_bytes(nspec, nids), ub = (size_t)nspec * nids * sizeof(double);
+    const size_t need = (3 + (engaged ? 0 : (size_t)nest)) * pb + sb + ub;
+    if (q->mvmc_bytes < need) {
+        if (q->mvmc) { OA_HIP(hipDeviceSynchronize()); (void)hipFree(q->mvmc); q->mvmc = nullptr; q->mvmc_bytes = 0; }
+        OA_HIP(hipMalloc(&q->mvmc, need));
+        OA_HIP(hipMemset(q->mvmc, 0, need));
+        q->mvmc_bytes = need;
+    }
+    char* const base = (char*)q->mvmc;
+    void* const draw[3] = {base, base + pb, base + 2 * pb};
+    char* const own = base + 3 * pb;                                      // per-estimator kappa planes when the plan's are not used
+    void* const scratch = base + q->mvmc_bytes - sb - ub;
+    double* const sums = (double*)(base + q->mvmc_bytes - ub);
+    const void* const block = engaged ? q->c[0] : (const void*)own;
+    std::vector<const void*> kX(nest), kY(nest);
+    for (int e = 0; e < nest; ++e) { kX[e] = draw[host_xsrc[e]]; kY[e] = draw[host_ysrc[e]]; }
+    for (long i = sim_lo; i < sim_hi; ++i) {
+        int rc = oa_grf_mix_band(p, base_seed, 3 * (uint64_t)i, 3, host_covsqrt, 1.0, draw, leg_cols, leg_rows, stream);
+        if (rc) return rc;
+        if (engaged) {
+            const MvCall c{nest, host_npieces, host_signs, host_FG, host_FH, host_swap, kX.data(), kY.data(), host_Fnorm, false};
+            if ((rc = qe_mv_pow2(p, q, c, nullptr, 0, leg_cols, kappa_cols, leg_rows, kappa_rows, mrow, 0, st, true))) return rc;
+        } else {
+            for (int e = 0, at = 0; e < nest; at += host_npieces[e], ++e) {      // one at a time, each into its plane of the entry's block
+                const MvCall c{1, host_npieces + e, host_signs + at, host_FG + at, host_FH + at, host_swap ? host_swap + at : nullptr,
+                               kX.data() + e, kY.data() + e, host_Fnorm + e, false};
+                if ((rc = qe_mv_pow2(p, q, c, own + (size_t)e * pb, 0, leg_cols, kappa_cols, leg_rows, kappa_rows, mrow, 0, st, false))) return rc;
+            }
+        }
+        if ((rc = oa_bin_power_multi(p->dtype, nest, block, (long)(pb / es), mv_weights, mv_wstride, nspec, host_a, host_b, norm, ids_hc, nids,
+                                     p->ny, p->kp, p->nx / 2, kappa_cols, kappa_rows, sums, scratch, stream))) return rc;
+        if ((rc = moments_add_binned_multi(sums, counts, nspec, nids, n, S, C, st))) return rc;
     }
     return 0;
 }

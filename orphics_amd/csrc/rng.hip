@@ -166,6 +166,7 @@ struct GrfMixArgs {
     T scale;
     int ncomp, ny, nx;
     long kp;
+    int wpairs, width, rband;      // BAND launches (oa_grf_mix_band): column pairs / columns drawn, row band (0 = every row)
 };
 // NC and the input mode are compile-time: every loop unrolls, the pointer tables and the per-component values stay in registers
 // (with run-time indices they went through scratch: 400-660 us per call at 4096^2 float64 instead of 100-250).  A thread owns the
@@ -195,13 +196,22 @@ OA_D void store_pair(E* p, long i0, bool second, const Pair<E>& v) {
         if (second) p[i0 + 1] = v.b;
     }
 }
-template <typename T, int NC, bool HAS_IN, bool VEC>
+// BAND (oa_grf_mix_band; HAS_IN and VEC off): the same thread body on the leg band only -- grid y enumerates the band rows as
+// grf_hc_kernel does, the columns stop at a.width (<= nx/2 + 1), and nothing else of the output planes is written.  Every mode keeps
+// its Philox counter and goes through the same expressions as the full draw: a bit-identical subset of it.
+template <typename T, int NC, bool HAS_IN, bool VEC, bool BAND = false>
 __global__ __launch_bounds__(256) void grf_mix_kernel(GrfMixArgs<T> a) {
     const int nxh = a.nx / 2, npair = nxh / 2 + 1, ny = a.ny;
-    const int pr = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (2L * pr >= a.kp) return;
+    const int pr = blockIdx.x * blockDim.x + threadIdx.x;
+    int y = blockIdx.y;
+    if constexpr (BAND) {
+        if (a.rband > 0 && y >= a.rband) y += ny - (2 * a.rband - 1);
+        if (pr >= a.wpairs) return;
+    } else {
+        if (2L * pr >= a.kp) return;
+    }
     const long i0 = (long)y * a.kp + 2 * pr;
-    const bool second = 2L * pr + 1 < a.kp;       // always true with VEC
+    const bool second = BAND ? 2 * pr + 1 < a.width : 2L * pr + 1 < a.kp;       // always true with VEC
     typedef Pair<T> R2;
     typedef Pair<cx<T>> C2;
     // ---- loads ----
@@ -342,6 +352,7 @@ static int grf_mix_launch(oa_plan* p, uint64_t seed, uint64_t sid0, int ncomp, c
     a.filt = (const T*)filt;
     a.scale = (T)scale;
     a.ncomp = ncomp; a.ny = p->ny; a.nx = p->nx; a.kp = p->kp;
+    a.wpairs = 0; a.width = 0; a.rband = 0;
     const int npair = (int)((p->kp + 1) / 2), bs = npair >= 256 ? 256 : 64;          // pairs of columns, the row padding included
     const dim3 grid((npair + bs - 1) / bs, p->ny);
     // the pair moves (grf_mix_kernel, VEC) need an even pitch and planes that start on a pair boundary; anything else goes column by column
@@ -364,11 +375,70 @@ static int grf_mix_launch(oa_plan* p, uint64_t seed, uint64_t sid0, int ncomp, c
     return 0;
 }
 
+// the leg band of grf_mix_launch's draw (no inputs, no rotation): columns < width, rows y < rband or y > ny - rband
+template <typename T>
+static int grf_mix_band_launch(oa_plan* p, uint64_t seed, uint64_t sid0, int ncomp, const void* const* cs, double scale, void* const* out,
+                               int width, int rband, hipStream_t st) {
+    GrfMixArgs<T> a;
+    a.seed = seed; a.sid0 = sid0;
+    for (int i = 0; i < 9; ++i) a.cs[i] = i < ncomp * ncomp ? (const T*)cs[i] : nullptr;
+    a.rc = nullptr; a.rs = nullptr; a.filt = nullptr;
+    for (int i = 0; i < 3; ++i) { a.in[i] = nullptr; a.out[i] = i < ncomp ? (cx<T>*)out[i] : nullptr; }
+    a.scale = (T)scale;
+    a.ncomp = ncomp; a.ny = p->ny; a.nx = p->nx; a.kp = p->kp;
+    const int hw = p->nx / 2 + 1;
+    a.width = (width > 0 && width < hw) ? width : hw;
+    a.wpairs = (a.width + 1) / 2;
+    a.rband = (rband > 0 && 2L * rband - 1 < p->ny) ? rband : 0;
+    const int bs = a.wpairs >= 256 ? 256 : 64;
+    const dim3 grid((a.wpairs + bs - 1) / bs, a.rband ? 2 * a.rband - 1 : p->ny);
+    if (ncomp == 1) hipLaunchKernelGGL((grf_mix_kernel<T, 1, false, false, true>), grid, dim3(bs), 0, st, a);
+    else if (ncomp == 2) hipLaunchKernelGGL((grf_mix_kernel<T, 2, false, false, true>), grid, dim3(bs), 0, st, a);
+    else hipLaunchKernelGGL((grf_mix_kernel<T, 3, false, false, true>), grid, dim3(bs), 0, st, a);
+    OA_LAUNCH_CHECK();
+    return 0;
+}
+
+// x[s * d + j] = sums[s * nids + j + 1] / counts[j + 1], d = nids - 2 (the interior bins of nspec binned spectra, oa_bin_power_multi's
+// layout, over the data-independent mode counts): n += 1, S += x, C += x x^T with D = nspec * d (oa_mc_run_mv)
+__global__ __launch_bounds__(256) void moments_add_binned_multi_kernel(const double* __restrict__ sums, const int64_t* __restrict__ counts,
+                                                                       int nspec, int nids, int64_t* __restrict__ n, double* __restrict__ S,
+                                                                       double* __restrict__ C) {
+    const int d = nids - 2;
+    const long D = (long)nspec * d, tot = D * D;
+    const long stride = (long)gridDim.x * blockDim.x;
+    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    auto x = [&](long i) { const int s = (int)(i / d), j = (int)(i - (long)s * d); return sums[(long)s * nids + j + 1] / (double)counts[j + 1]; };
+    for (long i = gid; i < tot; i += stride) {
+        const long a = i / D, b = i - a * D;
+        C[i] += x(a) * x(b);
+    }
+    for (long i = gid; i < D; i += stride) S[i] += x(i);
+    if (gid == 0) n[0] += 1;
+}
+int moments_add_binned_multi(const double* sums, const int64_t* counts, int nspec, int nids, int64_t* n, double* S, double* C, hipStream_t st) {
+    OA_REQUIRE(sums && counts && n && S && C && nspec >= 1 && nids >= 3, "moments_add_binned_multi: bad argument");
+    const long D = (long)nspec * (nids - 2);
+    const int g = flat_grid(D * D, 256, 64);
+    hipLaunchKernelGGL(moments_add_binned_multi_kernel, dim3(g), dim3(256), 0, st, sums, counts, nspec, nids, n, S, C);
+    OA_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace oa
 
 using namespace oa;
 
 extern "C" {
+
+int oa_grf_mix_band(oa_plan* p, uint64_t seed, uint64_t stream_id0, int ncomp, const void* const* covsqrt_hc, double scale, void* const* hc_out,
+                    int width, int rband, void* stream) {
+    OA_REQUIRE(p && covsqrt_hc && hc_out && ncomp >= 1 && ncomp <= 3, "oa_grf_mix_band: bad argument (1 <= ncomp <= 3)");
+    OA_REQUIRE(width >= 0 && rband >= 0, "oa_grf_mix_band: negative band");
+    for (int i = 0; i < ncomp; ++i) OA_REQUIRE(hc_out[i], "oa_grf_mix_band: NULL output plane");
+    return p->dtype == OA_F32 ? grf_mix_band_launch<float>(p, seed, stream_id0, ncomp, covsqrt_hc, scale, hc_out, width, rband, (hipStream_t)stream)
+                              : grf_mix_band_launch<double>(p, seed, stream_id0, ncomp, covsqrt_hc, scale, hc_out, width, rband, (hipStream_t)stream);
+}
 
 int oa_grf_hc_band(oa_plan* p, uint64_t seed, uint64_t stream_id, const void* covsqrt_hc, void* hc_out, int width, int rband,
                    void* stream) {

@@ -496,7 +496,7 @@ class Engine(object):
         return my.value, mx.value
 
     def release_pools(self):
-        """free the plan-owned pools of the multi-map entries (oa_lens_maps, oa_qe_mv, oa_qe_tt_splits, oa_mc_run)"""
+        """free the plan-owned pools of the multi-map entries (oa_lens_maps, oa_qe_mv, oa_qe_tt_splits, oa_mc_run, oa_mc_run_mv)"""
         check(self.lib.oa_plan_release_pools(self.plan))
 
     def set_laxes(self, ly, lx):
@@ -619,6 +619,45 @@ class Engine(object):
         check(self.lib.oa_grf_mix(self.plan, int(seed), int(stream_id0), n, cs, _ptr(rot[0]) if rot is not None else None,
                                   _ptr(rot[1]) if rot is not None else None, ins, _ptr(filt), float(scale), outs, _stream()))
         return list(out)
+
+    def grf_mix_band(self, seed, covsqrt_hc, out, width=0, rband=0, scale=1.0, stream_id0=0):
+        """``oa_grf_mix_band``: the leg band (columns < width, rows |ky index| < rband; 0 = all) of :meth:`grf_mix`'s plain draw
+        (no rotation, no inputs) -- the same values as the full draw there, the rest of the ``out`` planes untouched."""
+        n = len(covsqrt_hc)
+        if not (1 <= n <= 3) or any(len(r) != n for r in covsqrt_hc) or len(out) != n:
+            raise ValueError("grf_mix_band: covsqrt_hc must be an n x n table and out n planes, 1 <= n <= 3")
+        for r in covsqrt_hc:
+            for c in r:
+                if c is not None:
+                    self._chk(c, "hcreal")
+        for k in out:
+            _dirty(self._chk(k, "hc"))
+        cs = (ctypes.c_void_p * (n * n))(*[_ptr(covsqrt_hc[i][j]) for i in range(n) for j in range(n)])
+        outs = (ctypes.c_void_p * n)(*[_ptr(k) for k in out])
+        check(self.lib.oa_grf_mix_band(self.plan, int(seed), int(stream_id0), n, cs, float(scale), outs, int(width), int(rband), _stream()))
+        return list(out)
+
+    def bin_power_multi(self, fields, pairs, norm, ids, nids, weights=None, active_cols=0, active_rows=0):
+        """``oa_bin_power_multi``: the binned spectra Re(conj F_a F_b) * norm of the (nf, ny, kp) hc stack ``fields`` for every
+        (a, b) of ``pairs`` in one pass; ``weights`` (nf, ny, kp) hc-real: index nf names sum_f w_f k_f.  Returns sums, a float64
+        (len(pairs), nids) tensor (counts: one full :meth:`bin_power` call -- they do not depend on the data)."""
+        nf = fields.shape[0]
+        if fields.dim() != 3 or tuple(fields.shape[1:]) != (self.ny, self.kp) or fields.dtype != self.cdt or not fields.is_contiguous():
+            raise ValueError("bin_power_multi: fields must be a contiguous (nf, ny, kp) stack of hc planes")
+        if weights is not None and (tuple(weights.shape) != tuple(fields.shape) or weights.dtype != self.rdt or not weights.is_contiguous()):
+            raise ValueError("bin_power_multi: weights must be a contiguous (nf, ny, kp) stack of hc-real planes")
+        ns = len(pairs)
+        need = int(self.lib.oa_bin_power_multi_scratch_bytes(ns, int(nids)))
+        if need < 0:
+            raise ValueError("bin_power_multi: 1 <= len(pairs) <= 28, 1 <= nids <= 1024 and len(pairs) * nids <= 4096")
+        scr = torch.empty(need, dtype=torch.uint8, device=self.device)
+        sums = torch.empty((ns, int(nids)), dtype=torch.float64, device=self.device)
+        a = (ctypes.c_int * ns)(*[int(p[0]) for p in pairs])
+        b = (ctypes.c_int * ns)(*[int(p[1]) for p in pairs])
+        plane = self.ny * self.kp
+        check(self.lib.oa_bin_power_multi(self.code, int(nf), _ptr(fields), plane, _ptr(weights), plane, ns, a, b, float(norm), _ptr(ids), int(nids),
+                                          self.ny, self.kp, self.nxh, int(active_cols), int(active_rows), _ptr(sums), _ptr(scr), _stream()))
+        return sums
 
     def randn(self, seed, stream_id, shape=None):
         out = torch.empty(shape if shape is not None else (self.ny, self.nx), dtype=self.rdt, device=self.device)

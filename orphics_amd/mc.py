@@ -196,6 +196,213 @@ class GaussianN0MonteCarlo(object):
         return (self.edges[1:] + self.edges[:-1]) / 2.
 
 
+def pol_spectrum_list(estimators, cross=True, mv=True):
+    """The sample vector of :class:`GaussianN0MonteCarloPol`: (labels, pairs).  Autos in estimator order, then -- ``cross`` -- the
+    upper-triangle crosses row by row, then -- ``mv`` -- the auto of the MV combination.  A label is the pair of names, e.g.
+    ("TT", "TT"), ("TT", "EB"), ("MV", "MV"); a pair holds the field indices ``oa_bin_power_multi`` takes (estimator e = field e, the
+    MV combination = field ``len(estimators)``)."""
+    ests = tuple(estimators)
+    n = len(ests)
+    if not 1 <= n <= 6 or len(set(ests)) != n:
+        raise ValueError("1 to 6 distinct estimators, got %r" % (ests,))
+    labels = [(x, x) for x in ests]
+    pairs = [(i, i) for i in range(n)]
+    if cross:
+        for i in range(n):
+            for j in range(i + 1, n):
+                labels.append((ests[i], ests[j]))
+                pairs.append((i, j))
+    if mv:
+        labels.append(("MV", "MV"))
+        pairs.append((n, n))
+    return labels, pairs
+
+
+def teb_covsqrt(total_power):
+    """Lower-triangular square root of the observed T, E, B covariance per mode: total_power = dict(TT, EE, BB, TE) of equally shaped
+    arrays; returns (a, b, c, d) with T = a w0, E = b w0 + c w1, B = d w2 for unit white fields w: a = sqrt(TT), b = TE / a (0 where
+    TT = 0), c = sqrt(EE - b^2), d = sqrt(BB), so that a^2 = TT, a b = TE, b^2 + c^2 = EE, d^2 = BB."""
+    TT, EE, BB, TE = (np.asarray(total_power[k], dtype=np.float64) for k in ("TT", "EE", "BB", "TE"))
+    a = np.sqrt(TT)
+    b = np.zeros_like(a)
+    np.divide(TE, a, out=b, where=a > 0)
+    c = np.sqrt(np.maximum(EE - b ** 2, 0.0))
+    d = np.sqrt(BB)
+    return a, b, c, d
+
+
+class GaussianN0MonteCarloPol(object):
+    """N0 Monte Carlo of an estimator set (TT, TE, EE, EB, TB) and its MV combination on Gaussian T, E, B fields with the observed
+    total powers: per realisation the bandpowers of every estimator's auto spectrum, of the N0 cross spectra N0^{ab} and of the MV
+    kappa_hat's auto spectrum are ONE sample vector (``spectra`` = its blocks, ``len(bin_edges) - 1`` bins each), accumulated as
+    (n, sum, cross) under the label "n0".  The MV auto is the variance of the kappa_hat that ``reconstruct_mv_hc`` returns -- which
+    ``Estimator.Nlkk["MV"]`` (diagonal approximation) is not.
+
+    Realisation i draws T, E, B with the Philox streams (base_seed, 3 i .. 3 i + 2), mixed by the lower-triangular square root of the
+    covariance (:func:`teb_covsqrt`).  On power-of-two sides the shard runs as ``oa_mc_run_mv`` calls (leg-band draw, the ``oa_qe_mv``
+    launch sequence, one ``oa_bin_power_multi`` pass, one moment launch; nothing leaves the device).  Elsewhere, or with
+    ``one_call=False``, it runs a host loop of the existing entries with the same seeds and streams: ``Engine.grf_mix``,
+    ``reconstruct_hc`` per estimator, the weighted sum, ``Engine.bin_power`` per spectrum, ``Statistics.add``."""
+
+    def __init__(self, qest, total_power_half, bin_edges, estimators=("TT", "TE", "EE", "EB", "TB"), cross=True, mv=True, comm=None,
+                 base_seed=1234, one_call=None):
+        torch = _torch()
+        from .lensing import pol_bands
+        self.q = qest
+        e = self.eng = qest.eng
+        self.comm = comm if comm is not None else _mpi.get_world()
+        self.base_seed = int(base_seed)
+        self.estimators = tuple(estimators)
+        self.spectra, self.pairs = pol_spectrum_list(self.estimators, cross, mv)
+        self.mv = bool(mv)
+        self.one_call = e.pow2 if one_call is None else bool(one_call)
+        geom = qest.geom
+        nE = len(self.estimators)
+        # unnormalised DFT of a unit-pixel-variance white map has |k|^2 = Npix; power p -> k = sqrt(p Npix^2/area) w
+        scale = np.sqrt(float(e.npix) ** 2 / geom.area)
+        a, b, c, d = (qest._hcreal(e, x * scale) for x in teb_covsqrt(total_power_half))
+        self.cs = [[a, None, None], [b, c, None], [None, None, d]]
+        G = [qest._setup_general(XY) for XY in self.estimators]
+        self._G = G
+        # pure normalisations in ONE allocation: evenly spaced planes let the divergence of all estimators run as one launch
+        self.fn = e.hcreal(nE)
+        for i, g_ in enumerate(G):
+            self.fn[i].copy_(g_["Fnorm"])
+        self.w = None
+        if self.mv:
+            w = qest.mv_weights(self.estimators)
+            self.w = e.hcreal(nE)
+            for i, XY in enumerate(self.estimators):
+                self.w[i].copy_(qest._hcreal(e, w[XY]))
+        self.wl, self.wk, self.rl, self.rk = pol_bands(G)
+        self.edges = np.asarray(bin_edges, dtype=np.float64)
+        self.ids = e.modl_digitize(torch.as_tensor(self.edges, device=e.device), half=True)
+        self.nids = self.edges.size + 1
+        self.d = self.nids - 2
+        self.D = len(self.spectra) * self.d
+        self.norm = geom.area / float(e.npix) ** 2
+        # data-independent mode counts per bin over the whole half plane
+        zero = e.hc()
+        self.counts = e.bin_power(zero, zero, self.norm, self.ids, self.nids, herm=True)[1]
+        self.acc = Statistics(comm=self.comm if hasattr(self.comm, "dist") else None, device=e.device)
+        self._host = None
+        self._c_args = None
+
+    # ---- the one-call path ------------------------------------------------------------------------------------------------------
+    def _entry_args(self):
+        import ctypes
+        if self._c_args is None:
+            pcs = [pc for g_ in self._G for pc in g_["pieces"]]
+            n, nE, nS = len(pcs), len(self.estimators), len(self.spectra)
+            idx = {"T": 0, "E": 1, "B": 2}
+            ptr = lambda t: t.data_ptr() if t is not None else None
+            self._c_args = dict(
+                cs=(ctypes.c_void_p * 9)(*[ptr(self.cs[i][j]) for i in range(3) for j in range(3)]),
+                npieces=(ctypes.c_int * nE)(*[len(g_["pieces"]) for g_ in self._G]),
+                signs=(ctypes.c_double * n)(*[float(pc[0]) for pc in pcs]),
+                fgs=(ctypes.c_void_p * n)(*[pc[1].data_ptr() for pc in pcs]),
+                fhs=(ctypes.c_void_p * n)(*[pc[2].data_ptr() for pc in pcs]),
+                swaps=(ctypes.c_int * n)(*[1 if pc[3] else 0 for pc in pcs]),
+                xsrc=(ctypes.c_int * nE)(*[idx[XY[0]] for XY in self.estimators]),
+                ysrc=(ctypes.c_int * nE)(*[idx[XY[1]] for XY in self.estimators]),
+                fns=(ctypes.c_void_p * nE)(*[self.fn[i].data_ptr() for i in range(nE)]),
+                a=(ctypes.c_int * nS)(*[p_[0] for p_ in self.pairs]), b=(ctypes.c_int * nS)(*[p_[1] for p_ in self.pairs]))
+        return self._c_args
+
+    def _run_block(self, lo, hi, n, S, C):
+        from ._lib import check
+        from .engine import _ptr, _stream
+        e, q, A = self.eng, self.q, self._entry_args()
+        e._ordered()
+        if e.pow2:
+            check(e.lib.oa_plan_set_col_grid(e.plan, int(q.mcol)))       # plans are shared per geometry: policy per call
+            if getattr(e, "_pipe_owner", None) is not q._token:
+                e._pipe_owner = None
+        wstride = self.w[0].numel() if self.w is not None else 0
+        check(e.lib.oa_mc_run_mv(e.plan, self.base_seed, int(lo), int(hi), A["cs"], len(self.estimators), A["npieces"], A["signs"], A["fgs"],
+                                 A["fhs"], A["swaps"], A["xsrc"], A["ysrc"], A["fns"], _ptr(self.w), wstride, len(self.spectra), A["a"], A["b"],
+                                 _ptr(self.ids), self.nids, _ptr(self.counts), float(self.norm), int(self.wl), int(self.wk), int(self.rl),
+                                 int(self.rk), int(q.mrow), _ptr(n), _ptr(S), _ptr(C), _stream()))
+
+    # ---- the host loop of existing entries (every side the estimators run on; the reference of the one-call path) -------------------
+    def sample_host(self, i):
+        """realisation ``i``'s sample vector (device, float64) through the existing entries"""
+        torch = _torch()
+        e, q = self.eng, self.q
+        if self._host is None:
+            t = torch.empty((3, e.ny, e.kp), dtype=e.cdt, device=e.device)
+            self._host = ([t[j] for j in range(3)], [q.new_output() for _ in self.estimators], self.counts[1:-1].double())
+        draw, outs, cnt = self._host
+        e.grf_mix(self.base_seed, self.cs, out=draw, stream_id0=3 * int(i))
+        f = {"T": draw[0], "E": draw[1], "B": draw[2]}
+        fields = [q.reconstruct_hc(XY, f[XY[0]], f[XY[1]], out=outs[j]) for j, XY in enumerate(self.estimators)]
+        if self.mv:
+            kmv = self.w[0] * fields[0]
+            for j in range(1, len(fields)):
+                kmv += self.w[j] * fields[j]
+            fields = fields + [kmv]
+        x = []
+        for (a, b) in self.pairs:
+            s, _ = e.bin_power(fields[a], fields[b], self.norm, self.ids, self.nids, herm=True, active_cols=self.wk, active_rows=self.rk)
+            x.append(s[1:-1] / cnt)
+        return torch.cat(x)
+
+    def run_local(self, sims):
+        """Process the given global sim indices on this rank's GPU: every contiguous block of indices is ONE ``oa_mc_run_mv`` call,
+        or -- host loop -- one :meth:`sample_host` + ``Statistics.add`` per index."""
+        sims = [int(i) for i in sims]
+        if not sims:
+            return self
+        if not self.one_call:
+            for i in sims:
+                self.acc.add("n0", self.sample_host(i))
+            return self
+        n, S, C = self.acc.device_moments("n0", self.D)
+        start = prev = sims[0]
+        for i in sims[1:] + [None]:
+            if i is None or i != prev + 1:
+                self._run_block(start, prev + 1, n, S, C)
+                start = i
+            prev = i
+        self.acc.note_samples("n0", len(sims))
+        return self
+
+    def run(self, nsims):
+        """Shard ``nsims`` with mpi.mpi_distribute, run, reduce once; returns the reduced :class:`Statistics` (label "n0")."""
+        comm = self.comm
+        size, rank = comm.Get_size(), comm.Get_rank()
+        _, tasks = _mpi.mpi_distribute(nsims, size, allow_empty=True)
+        self.run_local(tasks[rank])
+        self.acc.allreduce()
+        return self.acc
+
+    def _slot(self, a, b=None):
+        key = (a, a if b is None else b)
+        if key not in self.spectra and (key[1], key[0]) in self.spectra:
+            key = (key[1], key[0])
+        if key not in self.spectra:
+            raise KeyError("no spectrum %s x %s in this run (spectra: %s)" % (key[0], key[1], self.spectra))
+        k = self.spectra.index(key)
+        return slice(k * self.d, (k + 1) * self.d)
+
+    def mean(self, a, b=None):
+        """N0^{ab} bandpowers of the (reduced) run: ``mean("EB")`` an auto, ``mean("TT", "TE")`` a cross, ``mean("MV")`` the MV auto"""
+        return self.acc.mean("n0")[self._slot(a, b)]
+
+    def sem(self, a, b=None):
+        """standard error of :meth:`mean` from the run's own covariance"""
+        sl = self._slot(a, b)
+        return np.sqrt(np.diag(self.acc.cov("n0"))[sl] / self.acc.count("n0"))
+
+    def cov(self):
+        """D x D covariance of the sample vector (D = len(spectra) * number of bins)"""
+        return self.acc.cov("n0")
+
+    @property
+    def centers(self):
+        return (self.edges[1:] + self.edges[:-1]) / 2.
+
+
 class LensedSimsMonteCarlo(object):
     """The reference's verification loop (tutorials/tt_verification.ipynb cells 4-5) as a sharded,
     device-resident driver: per realisation
