@@ -43,7 +43,7 @@ typedef struct oa_plan oa_plan;
 const char* oa_last_error(void);
 /* ABI version = 100 x the build round that last changed a signature in this header; bindings must refuse a library
  * that reports less than the version they were written against (OA_ABI_VERSION) */
-#define OA_ABI_VERSION 407
+#define OA_ABI_VERSION 408
 int oa_version(void);
 /* number of HIP devices visible; <0 on error (no compute) */
 int oa_device_count(void);
@@ -343,7 +343,7 @@ int oa_mc_run(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const vo
 int oa_mc_run_windowed(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, const void* window_real,
                        int64_t* n, double* S, double* C, double* meanfield_acc, void* stream);
 /* oa_mc_run_mv: the Gaussian N0 Monte-Carlo shard [sim_lo, sim_hi) of an estimator SET (TT, TE, EE, EB, TB ... and their MV combination),
- * power-of-two plans.  The estimator arguments are oa_qe_mv's (nest <= 6, pieces flattened in estimator order) except that the sources
+ * on power-of-two plans and, behind two set-up calls, on the band grid of 2^a 3^b 5^c plans (below).  The estimator arguments are oa_qe_mv's (nest <= 6, pieces flattened in estimator order) except that the sources
  * are named by index -- host_xsrc[e] / host_ysrc[e]: 0 T, 1 E, 2 B, oa_qe_mv_maps' convention -- and that host_Fnorm holds the PURE
  * normalisations (no MV weight).  host_covsqrt: oa_grf_mix's nine hc-real blocks for the fields T, E, B (NULL = zero block), amplitude
  * scaling included.  Per realisation i, stream-ordered, nothing leaving the device and no host work on the data:
@@ -357,11 +357,25 @@ int oa_mc_run_windowed(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi,
  *      kappa's band (kappa_cols, kappa_rows) as the active region, ids_hc / nids / norm as for oa_bin_power;
  *   4. one launch: x[s * d + j] = sums[s][j + 1] / counts[j + 1], d = nids - 2 (counts: device int64[nids], the data-independent mode
  *      counts of a full-plane oa_bin_power call), then n += 1, S += x, C += x x^T with D = nspec * d  (S: D doubles, C: D x D).
- * Realisation i's contribution does not depend on how a range is cut into calls.  The first call (and a call that needs more than any
- * before) allocates the entry's planes and synchronises the device once; oa_plan_release_pools frees them.  Refused before anything is
- * launched: a 2^a 3^b 5^c or chirp-z plan (the band-grid binding carries no bin ids; the message names the host loop of the existing
- * entries that mc.GaussianN0MonteCarloPol runs there), nest outside 1..6, a source index outside [0, 3), and every refusal of
- * oa_bin_power_multi (with nfields = nest). */
+ * Realisation i's contribution does not depend on how a range is cut into calls.  On a power-of-two plan the first call (and a call that
+ * needs more than any before) allocates the entry's planes and synchronises the device once; oa_plan_release_pools frees them.
+ * ON A BAND GRID (2^a 3^b 5^c plans).  The filter and normalisation planes are bound by oa_qe_band_bind (the pure normalisations, in the
+ * order of host_Fnorm); then oa_mc_mv_band_bind(plan, mv_weights, mv_wstride, nest, ids_hc, nids, nspec_max) -- a set-up call like that
+ * one: it may allocate and synchronises the device -- copies kappa's band of the nest weight planes (nothing when mv_weights is NULL)
+ * and of the N-grid bin ids into the inner layout (-1 outside the band), takes everything a shard would otherwise allocate on first use
+ * (the three inner draw planes, zero-filled once; nest inner kappa planes; oa_bin_power_multi's scratch and sums for
+ * nspec_max x nids) and remembers the caller's pointers, the stride, nest and nids.  A later oa_qe_band_bind drops it; on a
+ * power-of-two plan it returns 0 and does nothing.  A shard then neither allocates nor synchronises: step 1 is
+ * oa_grf_mix_band_inner -- the same draw, written into the inner layout --, steps 2 and 3 run on the inner plan with the inner copies
+ * (kappa_hat per mode is the same on both grids; the inner Nyquist column lies outside kappa's band, so column 0 is the only visited
+ * one of multiplicity 1, as on the N grid), step 4 divides by the caller's counts, those of the whole N plane.
+ * Refused before anything is launched, n, S, C untouched: a chirp-z plan; a 2^a 3^b 5^c plan without an oa_qe_band_bind binding or
+ * without an oa_mc_mv_band_bind binding on it, or whose bands, mrow, weights pointer and stride, ids pointer, nids or nest differ from
+ * the bound ones, or with nspec > nspec_max (these messages name both set-up entries and the host loop of the existing entries that
+ * mc.GaussianN0MonteCarloPol runs with one_call=False); a filter or normalisation plane that is not bound; more leg planes than
+ * oa_qe_band_bind's max_leg_planes; nest outside 1..6, a source index outside [0, 3), and every refusal of oa_bin_power_multi (with
+ * nfields = nest). */
+int oa_mc_mv_band_bind(oa_plan* p, const void* mv_weights, long mv_wstride, int nest, const int32_t* ids_hc, int nids, int nspec_max);
 int oa_mc_run_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest, const int* host_npieces,
                  const double* host_signs, const void* const* host_FG, const void* const* host_FH, const int* host_swap, const int* host_xsrc,
                  const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights, long mv_wstride, int nspec, const int* host_a,
@@ -552,6 +566,14 @@ int oa_grf_mix(oa_plan* p, uint64_t seed, uint64_t stream_id0, int ncomp, const 
  * ncomp 1..3, NULL blocks are zero.  What oa_grf_hc_band is to oa_grf_hc. */
 int oa_grf_mix_band(oa_plan* p, uint64_t seed, uint64_t stream_id0, int ncomp, const void* const* covsqrt_hc, double scale,
                     void* const* hc_out, int width, int rband, void* stream);
+/* The band of oa_grf_mix_band written into the hc layout of an INNER grid of `my` rows and row pitch `out_pitch` (complex elements): Philox
+ * counters, self-conjugate edge rules and the covsqrt planes are those of the plan's N grid at row y, the value goes to row y of the
+ * output planes for y < rband and to row y - ny + my above (ky mod my: the band grid's layout), same column.  Bit-identical to
+ * oa_grf_mix_band's values at the same mode; nothing outside the band of the output planes is written.  Refused before any launch:
+ * ncomp outside 1..3, a band that is not positive, 2 rband - 1 > min(ny, my), width > nx/2 + 1, 2 ceil(width / 2) > out_pitch, a NULL
+ * output plane. */
+int oa_grf_mix_band_inner(oa_plan* p, uint64_t seed, uint64_t stream_id0, int ncomp, const void* const* covsqrt_hc, double scale,
+                          void* const* hc_out, int my, long out_pitch, int width, int rband, void* stream);
 /* real white noise N(0,1) plane of n elements (enmap.rand_gauss) */
 int oa_randn(int dtype, uint64_t seed, uint64_t stream_id, void* out, long n, void* stream);
 

@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("ORPHICS_AMD_LIB", os.path.join(_HERE, "liborphics_amd
 
 OA_F32 = 0
 OA_F64 = 1
-ABI_VERSION = 407     # include/orphics_amd.h OA_ABI_VERSION: the signatures below are those of this version
+ABI_VERSION = 408     # include/orphics_amd.h OA_ABI_VERSION: the signatures below are those of this version
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
@@ -68,6 +68,7 @@ SIGNATURES = {
     "oa_mc_run_windowed": (c_int, [c_void_p, c_u64, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "oa_mc_run_mv": (c_int, [c_void_p, c_u64, c_long, c_long, c_void_p, c_int] + [c_void_p] * 9 + [c_long, c_int, c_void_p, c_void_p, c_void_p, c_int,
                              c_void_p, c_double] + [c_int] * 5 + [c_void_p] * 4),
+    "oa_mc_mv_band_bind": (c_int, [c_void_p, c_void_p, c_long, c_int, c_void_p, c_int, c_int]),
     "oa_malloc": (c_int, [ctypes.POINTER(c_void_p), ctypes.c_size_t]),
     "oa_free": (c_int, [c_void_p]),
     "oa_memcpy": (c_int, [c_void_p, c_void_p, ctypes.c_size_t, c_int, c_void_p]),
@@ -110,6 +111,7 @@ SIGNATURES = {
     "oa_grf_hc_band": (c_int, [c_void_p, c_u64, c_u64, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "oa_grf_mix": (c_int, [c_void_p, c_u64, c_u64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
     "oa_grf_mix_band": (c_int, [c_void_p, c_u64, c_u64, c_int, c_void_p, c_double, c_void_p, c_int, c_int, c_void_p]),
+    "oa_grf_mix_band_inner": (c_int, [c_void_p, c_u64, c_u64, c_int, c_void_p, c_double, c_void_p, c_int, c_long, c_int, c_int, c_void_p]),
     "oa_randn": (c_int, [c_int, c_u64, c_u64, c_void_p, c_long, c_void_p]),
     "oa_moments_add": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "oa_moments_add_binned": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -107,6 +107,18 @@ struct Pipeline {
         std::vector<const void*> skey;         // what it holds
         void* mrows = nullptr;                 // oa_qe_mv_maps: row planes + column partial sums of the batched band input transform
         size_t mrows_bytes = 0;                // (band_maps_scratch_bytes; taken on the first from-maps call, grown on demand)
+        // oa_mc_run_mv on this binding (oa_mc_mv_band_bind; dropped by the next oa_qe_band_bind): what the caller's shard calls must
+        // bring again (the key), and one pool in the inner layout: nest weight planes (real; none without weights) | bin ids (-1 outside
+        // kappa's band) | the three drawn hc planes (zero outside the leg band) | nest kappa planes (for when the one-launch divergence
+        // is not engaged) | oa_bin_power_multi's partials | its sums
+        struct McBind {
+            bool bound = false;
+            const void* w = nullptr; long wstride = 0;
+            const int32_t* ids = nullptr;
+            int nids = 0, nest = 0, nspec_max = 0;
+            void* pool = nullptr;
+            size_t pool_bytes = 0, off_ids = 0, off_draw = 0, off_kappa = 0, off_scratch = 0, off_sums = 0;
+        } mc;
     } pb;
 };
 constexpr int POL_SRC_MAX = 6;                 // T, E, B and the Y-leg sources of a split call
@@ -145,6 +157,7 @@ void pipeline_release(oa_plan* p) {
     if (q->pb.planes) (void)hipFree(q->pb.planes);
     if (q->pb.stab) (void)hipFree(q->pb.stab);
     if (q->pb.mrows) (void)hipFree(q->pb.mrows);
+    if (q->pb.mc.pool) (void)hipFree(q->pb.mc.pool);
     delete q;
     p->pipe = nullptr;
 }
@@ -615,6 +628,8 @@ int oa_plan_release_pools(oa_plan* p) {
     }
     // ... and the map-side scratch of oa_qe_mv_maps (retaken by the next from-maps call)
     if (q->pb.mrows) { (void)hipFree(q->pb.mrows); q->pb.mrows = nullptr; q->pb.mrows_bytes = 0; }
+    // ... and the Monte-Carlo binding's pool: oa_mc_mv_band_bind makes it again
+    if (q->pb.mc.pool) { (void)hipFree(q->pb.mc.pool); q->pb.mc = Pipeline::PolBind::McBind(); }
     return 0;
 }
 
@@ -1266,6 +1281,7 @@ static int pol_bind(oa_plan* p, Pipeline* q, int nf, const void* const* filters,
                     int mrow, int mcol, int max_leg_planes) {
     Pipeline::PolBind& B = q->pb;
     B.bound = false;
+    B.mc.bound = false;                             // the Monte-Carlo binding belongs to the binding it was made on
     int my = 0, mx = 0;
     if (int rc = band_grid_rule(p, mrow, mcol, wl, wk, rl, rk, &my, &mx)) return rc;
     OA_HIP(hipDeviceSynchronize());                 // the caller's planes may have been written on any stream; the old copies may be in use
@@ -1466,9 +1482,165 @@ static int mixed_qe_tt_splits(oa_plan* p, Pipeline* q, const char* who, int nspl
         return band_split_power(p->dtype, n, kbase, pe, b->kp, b->ny, out_power, p->kp, p->ny, q->wk, q->rk, norm, zero_outside, st);
     return band_scatter_batch(p->dtype, kbase, pe, npairs, b->kp, b->ny, (void* const*)(q->bs_tab + n), p->kp, p->ny, q->wk, q->rk, zero_outside, st);
 }
+/* ---- oa_mc_run_mv on the band grid ----------------------------------------------------------------------------------------------------
+ * The shard's per-call planes that are not filters -- the MV weights and the bin ids -- get their inner-layout copies from a second set-up
+ * entry, oa_mc_mv_band_bind, which also takes every plane the shard would otherwise allocate on first use.  A shard call then looks its
+ * pointers up (pol_inner, and the key below) and runs the loop of the power-of-two plans on the inner plan: no allocation, no
+ * synchronisation. */
+static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+static int mc_mv_bind(oa_plan* p, Pipeline* q, const void* w, long wstride, int nest, const int32_t* ids, int nids, int nspec_max) {
+    Pipeline::PolBind& B = q->pb;
+    Pipeline::PolBind::McBind& M = B.mc;
+    M.bound = false;
+    if (!B.bound) return fail("oa_mc_mv_band_bind: bind the filter and normalisation planes first (oa_qe_band_bind)");
+    const long sbl = oa_bin_power_multi_scratch_bytes(nspec_max, nids);
+    if (sbl < 0) return fail("oa_mc_mv_band_bind: nspec_max outside 1..28, nids outside 1..1024 or nspec_max * nids > 4096 (oa_bin_power_multi)");
+    oa_plan* b = B.plan;
+    const size_t rb = band_real_bytes(b), cb = plane_bytes(b), rs = b->dtype == OA_F32 ? 4 : 8;
+    const size_t ib = (size_t)b->ny * b->kp * sizeof(int32_t), ub = (size_t)nspec_max * nids * sizeof(double);
+    const size_t off_ids = up256(w ? (size_t)nest * rb : 0), off_draw = up256(off_ids + ib), off_kappa = off_draw + 3 * cb;
+    const size_t off_scratch = up256(off_kappa + (size_t)nest * cb), off_sums = up256(off_scratch + (size_t)sbl), need = off_sums + ub;
+    OA_HIP(hipDeviceSynchronize());                 // the caller's planes may have been written on any stream; the old copies may be in use
+    if (M.pool_bytes < need) {
+        if (M.pool) { (void)hipFree(M.pool); M.pool = nullptr; M.pool_bytes = 0; }
+        OA_HIP(hipMalloc(&M.pool, need));
+        M.pool_bytes = need;
+    }
+    char* const base = (char*)M.pool;
+    OA_HIP(hipMemset(base, 0, need));               // weights, draws and kappa planes: only their band is ever written
+    OA_HIP(hipMemset(base + off_ids, 0xFF, ib));
+    if (w)
+        for (int e = 0; e < nest; ++e)
+            if (int rc = band_copy(p->dtype == OA_F32 ? 0 : 1, (const char*)w + (size_t)e * wstride * rs, p->kp, p->ny, base + (size_t)e * rb, b->kp, b->ny,
+                                   B.wk, B.rk, 1.0, nullptr)) return rc;
+    if (int rc = band_copy(2, ids, p->kp, p->ny, base + off_ids, b->kp, b->ny, B.wk, B.rk, 1.0, nullptr)) return rc;
+    OA_HIP(hipDeviceSynchronize());
+    M.w = w; M.wstride = wstride; M.ids = ids; M.nids = nids; M.nest = nest; M.nspec_max = nspec_max;
+    M.off_ids = off_ids; M.off_draw = off_draw; M.off_kappa = off_kappa; M.off_scratch = off_scratch; M.off_sums = off_sums;
+    M.bound = true;
+    return 0;
+}
+
+/* The per-realisation loop of oa_mc_run_mv, shared by both plan kinds.  `grid` is the map's plan: Philox counters, self-conjugate edge
+ * rules and the covsqrt planes are its.  `run` is the plan the estimators and the binning run on -- `grid` itself (power of two), or
+ * the inner plan of its band grid, into whose layout the draw then goes directly (oa_grf_mix_band_inner); every plane below is in `run`'s
+ * layout.  Nothing here allocates or synchronises once the pools exist. */
+struct McMvLoop {
+    oa_plan* grid; oa_plan* run; Pipeline* rq;
+    bool engaged;                                   // the one-launch divergence: kappa planes = run's work planes c[0] + e
+    void* draw[3]; char* own; void* scratch; double* sums;
+    const void* w; long wstride; const int32_t* ids;
+    int mrow;
+};
+static int mc_mv_loop(const McMvLoop& L, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest,
+                      const int* host_npieces, const double* host_signs, const void* const* FG, const void* const* FH, const int* host_swap,
+                      const int* host_xsrc, const int* host_ysrc, const void* const* Fn, int nspec, const int* host_a, const int* host_b, int nids,
+                      const int64_t* counts, double norm, int leg_cols, int kappa_cols, int leg_rows, int kappa_rows, int64_t* n, double* S,
+                      double* C, hipStream_t st) {
+    oa_plan* r = L.run;
+    const size_t es = 2 * (r->dtype == OA_F32 ? 4 : 8), pb = plane_bytes(r);
+    const void* const block = L.engaged ? L.rq->c[0] : (const void*)L.own;
+    std::vector<const void*> kX(nest), kY(nest);
+    for (int e = 0; e < nest; ++e) { kX[e] = L.draw[host_xsrc[e]]; kY[e] = L.draw[host_ysrc[e]]; }
+    for (long i = sim_lo; i < sim_hi; ++i) {
+        int rc = L.grid == r ? oa_grf_mix_band(r, base_seed, 3 * (uint64_t)i, 3, host_covsqrt, 1.0, L.draw, leg_cols, leg_rows, st)
+                             : oa_grf_mix_band_inner(L.grid, base_seed, 3 * (uint64_t)i, 3, host_covsqrt, 1.0, L.draw, r->ny, r->kp, leg_cols,
+                                                     leg_rows, st);
+        if (rc) return rc;
+        if (L.engaged) {
+            const MvCall c{nest, host_npieces, host_signs, FG, FH, host_swap, kX.data(), kY.data(), Fn, false};
+            if ((rc = qe_mv_pow2(r, L.rq, c, nullptr, 0, leg_cols, kappa_cols, leg_rows, kappa_rows, L.mrow, 0, st, true))) return rc;
+        } else {
+            for (int e = 0, at = 0; e < nest; at += host_npieces[e], ++e) {      // one at a time, each into its plane of the entry's block
+                const MvCall c{1, host_npieces + e, host_signs + at, FG + at, FH + at, host_swap ? host_swap + at : nullptr,
+                               kX.data() + e, kY.data() + e, Fn + e, false};
+                if ((rc = qe_mv_pow2(r, L.rq, c, L.own + (size_t)e * pb, 0, leg_cols, kappa_cols, leg_rows, kappa_rows, L.mrow, 0, st, false))) return rc;
+            }
+        }
+        if ((rc = oa_bin_power_multi(r->dtype, nest, block, (long)(pb / es), L.w, L.wstride, nspec, host_a, host_b, norm, L.ids, nids,
+                                     r->ny, r->kp, r->nx / 2, kappa_cols, kappa_rows, L.sums, L.scratch, st))) return rc;
+        if ((rc = moments_add_binned_multi(L.sums, counts, nspec, nids, n, S, C, st))) return rc;
+    }
+    return 0;
+}
+
+/* oa_mc_run_mv on a 2^a 3^b 5^c plan: every pointer of the call is looked up in the two bindings and everything is refused before the
+ * first launch; then the loop above on the inner plan.  kappa_hat per mode is the same on both grids (the bound normalisations carry
+ * My Mx / (ny nx)), the inner ids are the N grid's at the same mode, and since Mx >= 2 kappa_cols the inner Nyquist column is never
+ * visited: column 0 is the only visited one of Hermitian multiplicity 1, as on the N grid.  The caller's counts are the N plane's. */
+static int mixed_mc_run_mv(oa_plan* p, Pipeline* q, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest,
+                           const int* host_npieces, const double* host_signs, const void* const* host_FG, const void* const* host_FH,
+                           const int* host_swap, const int* host_xsrc, const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights,
+                           long mv_wstride, int nspec, const int* host_a, const int* host_b, const int32_t* ids_hc, int nids, const int64_t* counts,
+                           double norm, int wl, int wk, int rl, int rk, int mrow, int64_t* n, double* S, double* C, hipStream_t st) {
+    static const char* const how = " -- bind the estimator set with oa_qe_band_bind, then oa_mc_mv_band_bind, or run the host loop of the "
+                                   "existing entries (mc.GaussianN0MonteCarloPol with one_call=False)";
+    Pipeline::PolBind& B = q->pb;
+    const Pipeline::PolBind::McBind& M = B.mc;
+    if (!B.bound) return fail(std::string("oa_mc_run_mv: on map sides 2^a 3^b 5^c the filter and normalisation planes are bound first") + how);
+    if (wl != B.wl || wk != B.wk || rl != B.rl || rk != B.rk || mrow != B.mrow)
+        return fail(std::string("oa_mc_run_mv: leg / kappa columns and rows or the row grid differ from the bound ones") + how);
+    if (!M.bound) return fail(std::string("oa_mc_run_mv: no Monte-Carlo binding on the current oa_qe_band_bind binding") + how);
+    if (mv_weights != M.w || (mv_weights && mv_wstride != M.wstride) || ids_hc != M.ids || nids != M.nids || nest != M.nest || nspec > M.nspec_max)
+        return fail(std::string("oa_mc_run_mv: the weights, their stride, the bin ids, nids, nest or nspec differ from the Monte-Carlo binding's") + how);
+    oa_plan* b = B.plan;
+    Pipeline* qb = (Pipeline*)b->pipe;
+    band_options(q);
+    const size_t rb = band_real_bytes(b), es = 2 * (b->dtype == OA_F32 ? 4 : 8);
+    char* const fbase = (char*)B.planes;
+    char* const nbase = fbase + B.fkey.size() * rb;
+    int total = 0;
+    for (int e = 0; e < nest; ++e) total += host_npieces[e];
+    std::vector<const void*> iFG(total), iFH(total), iFn(nest);
+    for (int i = 0; i < total; ++i) {
+        iFG[i] = pol_inner(B.fkey, host_FG[i], fbase, rb);
+        iFH[i] = pol_inner(B.fkey, host_FH[i], fbase, rb);
+        if (!iFG[i] || !iFH[i]) return fail("oa_mc_run_mv: a filter plane of this call is not bound (oa_qe_band_bind binds every distinct plane)");
+    }
+    for (int e = 0; e < nest; ++e) {
+        iFn[e] = pol_inner(B.nkey, host_Fnorm[e], nbase, rb);
+        if (!iFn[e]) return fail("oa_mc_run_mv: a normalisation plane of this call is not bound (oa_qe_band_bind)");
+    }
+    {                                               // the inner plan's leg pool: sized by oa_qe_band_bind, never grown here
+        std::vector<std::pair<int, const void*>> grad, hpl;
+        auto add = [](std::vector<std::pair<int, const void*>>& v, int s, const void* f) {
+            for (auto& k : v) if (k.first == s && k.second == f) return;
+            v.emplace_back(s, f);
+        };
+        for (int e = 0, at = 0; e < nest; ++e)
+            for (int i = 0; i < host_npieces[e]; ++i, ++at) {
+                const bool sw = host_swap && host_swap[at];
+                add(grad, sw ? host_ysrc[e] : host_xsrc[e], iFG[at]);
+                add(hpl, sw ? host_xsrc[e] : host_ysrc[e], iFH[at]);
+            }
+        const size_t lb = (size_t)work_pitch(b, wl) * b->ny * es, lbk = (size_t)work_pitch(b, wk) * b->ny * es;
+        if ((2 * grad.size() + hpl.size()) * lb + 4 * (size_t)nest * lbk > qb->split_bytes)
+            return fail("oa_mc_run_mv: this call needs " + std::to_string(2 * grad.size() + hpl.size()) + " leg planes and " + std::to_string(nest) +
+                        " estimators, more than oa_qe_band_bind was told (max_leg_planes, normalisation planes)");
+    }
+    char* const base = (char*)M.pool;
+    const size_t cb = plane_bytes(b);
+    long fn_moff = 0;
+    McMvLoop L{p, b, qb, mv_div_batched(qb, nest, iFn.data(), es / 2, &fn_moff),
+               {base + M.off_draw, base + M.off_draw + cb, base + M.off_draw + 2 * cb}, base + M.off_kappa, base + M.off_scratch,
+               (double*)(base + M.off_sums), mv_weights ? (const void*)base : nullptr, (long)(rb / (es / 2)), (const int32_t*)(base + M.off_ids), -1};
+    return mc_mv_loop(L, base_seed, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, iFG.data(), iFH.data(), host_swap, host_xsrc,
+                      host_ysrc, iFn.data(), nspec, host_a, host_b, nids, counts, norm, wl, wk, rl, rk, n, S, C, st);
+}
 }  // namespace oa
 
 extern "C" {
+
+int oa_mc_mv_band_bind(oa_plan* p, const void* mv_weights, long mv_wstride, int nest, const int32_t* ids_hc, int nids, int nspec_max) {
+    OA_REQUIRE(p && ids_hc, "oa_mc_mv_band_bind: NULL argument");
+    OA_REQUIRE(nest >= 1 && nest <= 6, "oa_mc_mv_band_bind: 1 <= nest <= 6 estimators");
+    OA_REQUIRE(nids >= 3, "oa_mc_mv_band_bind: nids must be at least 3 (two outer bins around the bandpowers)");
+    OA_REQUIRE(!mv_weights || mv_wstride >= (long)p->ny * p->kp, "oa_mc_mv_band_bind: weight planes closer than one hc-real plane");
+    if (p->pow2) return 0;                          // power-of-two plans take their planes per call
+    OA_REQUIRE(p->mixed, "oa_mc_mv_band_bind: map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path "
+               "(mc.GaussianN0MonteCarloPol with one_call=False runs the host loop of the existing entries)");
+    return mc_mv_bind(p, pipe_of(p), mv_weights, mv_wstride, nest, ids_hc, nids, nspec_max);
+}
 
 int oa_qe_band_bind(oa_plan* p, int nfilters, const void* const* host_filters, int nnorms, const void* const* host_Fnorm, int leg_cols,
                     int kappa_cols, int leg_rows, int kappa_rows, int mrow, int mcol, int max_leg_planes) {
@@ -1533,10 +1705,11 @@ int oa_mc_run(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const vo
     return 0;
 }
 
-/* oa_mc_run_mv (include/orphics_amd.h): the Gaussian N0 Monte-Carlo shard of an estimator SET.  Per realisation: the leg band of
- * oa_grf_mix's T, E, B draw (streams 3 i, 3 i + 1, 3 i + 2) into three entry-owned planes -- not the plan's work planes: c[0..2], g[0..1]
+/* oa_mc_run_mv (include/orphics_amd.h): the Gaussian N0 Monte-Carlo shard of an estimator SET.  Per realisation (mc_mv_loop): the leg band
+ * of oa_grf_mix's T, E, B draw (streams 3 i, 3 i + 1, 3 i + 2) into three entry-owned planes -- not the plan's work planes: c[0..2], g[0..1]
  * and kT are where the one-launch divergence puts the per-estimator kappa_hat --, the launch sequence of oa_qe_mv with the sum left out
- * (qe_mv_pow2), one oa_bin_power_multi pass over the estimators' planes, one moment launch. */
+ * (qe_mv_pow2), one oa_bin_power_multi pass over the estimators' planes, one moment launch.  On a 2^a 3^b 5^c plan the same loop runs on
+ * the inner plan of the band grid (mixed_mc_run_mv). */
 int oa_mc_run_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest, const int* host_npieces,
                  const double* host_signs, const void* const* host_FG, const void* const* host_FH, const int* host_swap, const int* host_xsrc,
                  const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights, long mv_wstride, int nspec, const int* host_a,
@@ -1544,8 +1717,9 @@ int oa_mc_run_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const
                  int leg_rows, int kappa_rows, int mrow, int64_t* n, double* S, double* C, void* stream) {
     OA_REQUIRE(p && host_covsqrt && host_npieces && host_signs && host_FG && host_FH && host_xsrc && host_ysrc && host_Fnorm && ids_hc && counts &&
                n && S && C && sim_hi >= sim_lo, "oa_mc_run_mv: bad argument");
-    OA_REQUIRE(p->pow2, "oa_mc_run_mv: power-of-two map sides only; on other sides run the host loop of the existing entries "
-               "(mc.GaussianN0MonteCarloPol with one_call=False: Engine.grf_mix, reconstruct_hc per estimator, Engine.bin_power, Statistics.add)");
+    OA_REQUIRE(p->pow2 || p->mixed, "oa_mc_run_mv: map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path; "
+               "run the host loop of the existing entries (mc.GaussianN0MonteCarloPol with one_call=False: Engine.grf_mix, reconstruct_hc per "
+               "estimator, Engine.bin_power, Statistics.add)");
     OA_REQUIRE(nest >= 1 && nest <= 6, "oa_mc_run_mv: 1 <= nest <= 6 estimators");
     OA_REQUIRE(nids >= 3, "oa_mc_run_mv: nids must be at least 3 (two outer bins around the bandpowers)");
     if (int rc = bin_power_multi_check("oa_mc_run_mv", p->dtype, nest, mv_weights != nullptr, nspec, host_a, host_b, nids)) return rc;
@@ -1561,6 +1735,10 @@ int oa_mc_run_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const
     for (int i = 0; i < total; ++i) OA_REQUIRE(host_FG[i] && host_FH[i], "oa_mc_run_mv: NULL filter plane");
     Pipeline* q = pipe_of(p);
     hipStream_t st = (hipStream_t)stream;
+    if (p->mixed)                                   // BAND GRID: the planes of the two bindings, on the inner plan
+        return mixed_mc_run_mv(p, q, base_seed, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, host_FG, host_FH, host_swap, host_xsrc,
+                               host_ysrc, host_Fnorm, mv_weights, mv_wstride, nspec, host_a, host_b, ids_hc, nids, counts, norm, leg_cols, kappa_cols,
+                               leg_rows, kappa_rows, mrow, n, S, C, st);
     if (int rc = ensure_work(p, q)) return rc;
     const size_t es = 2 * (p->dtype == OA_F32 ? 4 : 8), rs = es / 2, pb = plane_bytes(p);
     long fn_moff = 0;
@@ -1575,31 +1753,10 @@ int oa_mc_run_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const
         q->mvmc_bytes = need;
     }
     char* const base = (char*)q->mvmc;
-    void* const draw[3] = {base, base + pb, base + 2 * pb};
-    char* const own = base + 3 * pb;                                      // per-estimator kappa planes when the plan's are not used
-    void* const scratch = base + q->mvmc_bytes - sb - ub;
-    double* const sums = (double*)(base + q->mvmc_bytes - ub);
-    const void* const block = engaged ? q->c[0] : (const void*)own;
-    std::vector<const void*> kX(nest), kY(nest);
-    for (int e = 0; e < nest; ++e) { kX[e] = draw[host_xsrc[e]]; kY[e] = draw[host_ysrc[e]]; }
-    for (long i = sim_lo; i < sim_hi; ++i) {
-        int rc = oa_grf_mix_band(p, base_seed, 3 * (uint64_t)i, 3, host_covsqrt, 1.0, draw, leg_cols, leg_rows, stream);
-        if (rc) return rc;
-        if (engaged) {
-            const MvCall c{nest, host_npieces, host_signs, host_FG, host_FH, host_swap, kX.data(), kY.data(), host_Fnorm, false};
-            if ((rc = qe_mv_pow2(p, q, c, nullptr, 0, leg_cols, kappa_cols, leg_rows, kappa_rows, mrow, 0, st, true))) return rc;
-        } else {
-            for (int e = 0, at = 0; e < nest; at += host_npieces[e], ++e) {      // one at a time, each into its plane of the entry's block
-                const MvCall c{1, host_npieces + e, host_signs + at, host_FG + at, host_FH + at, host_swap ? host_swap + at : nullptr,
-                               kX.data() + e, kY.data() + e, host_Fnorm + e, false};
-                if ((rc = qe_mv_pow2(p, q, c, own + (size_t)e * pb, 0, leg_cols, kappa_cols, leg_rows, kappa_rows, mrow, 0, st, false))) return rc;
-            }
-        }
-        if ((rc = oa_bin_power_multi(p->dtype, nest, block, (long)(pb / es), mv_weights, mv_wstride, nspec, host_a, host_b, norm, ids_hc, nids,
-                                     p->ny, p->kp, p->nx / 2, kappa_cols, kappa_rows, sums, scratch, stream))) return rc;
-        if ((rc = moments_add_binned_multi(sums, counts, nspec, nids, n, S, C, st))) return rc;
-    }
-    return 0;
+    McMvLoop L{p, p, q, engaged, {base, base + pb, base + 2 * pb}, base + 3 * pb /* per-estimator kappa planes when the plan's are not used */,
+               base + q->mvmc_bytes - sb - ub, (double*)(base + q->mvmc_bytes - ub), mv_weights, mv_wstride, ids_hc, mrow};
+    return mc_mv_loop(L, base_seed, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, host_FG, host_FH, host_swap, host_xsrc, host_ysrc,
+                      host_Fnorm, nspec, host_a, host_b, nids, counts, norm, leg_cols, kappa_cols, leg_rows, kappa_rows, n, S, C, st);
 }
 
 /* Monte-Carlo shard with a REAL-SPACE WINDOW (the reference's analysis flow multiplies every map by its apodisation taper

@@ -167,6 +167,8 @@ struct GrfMixArgs {
     int ncomp, ny, nx;
     long kp;
     int wpairs, width, rband;      // BAND launches (oa_grf_mix_band): column pairs / columns drawn, row band (0 = every row)
+    int my;                        // INNER launches (oa_grf_mix_band_inner): rows and row pitch of the output planes
+    long okp;
 };
 // NC and the input mode are compile-time: every loop unrolls, the pointer tables and the per-component values stay in registers
 // (with run-time indices they went through scratch: 400-660 us per call at 4096^2 float64 instead of 100-250).  A thread owns the
@@ -199,13 +201,21 @@ OA_D void store_pair(E* p, long i0, bool second, const Pair<E>& v) {
 // BAND (oa_grf_mix_band; HAS_IN and VEC off): the same thread body on the leg band only -- grid y enumerates the band rows as
 // grf_hc_kernel does, the columns stop at a.width (<= nx/2 + 1), and nothing else of the output planes is written.  Every mode keeps
 // its Philox counter and goes through the same expressions as the full draw: a bit-identical subset of it.
-template <typename T, int NC, bool HAS_IN, bool VEC, bool BAND = false>
+// INNER (oa_grf_mix_band_inner; with BAND, a.rband >= 1): counters, edge rules and the cs loads are those of N-grid row y as before, the
+// stores go to row yo = ky mod a.my of (a.my, a.okp) planes -- the band in the hc layout of an inner grid (grf_band_inner_kernel's
+// mapping).  Only the store offset differs: the values are those of the BAND launch.
+template <typename T, int NC, bool HAS_IN, bool VEC, bool BAND = false, bool INNER = false>
 __global__ __launch_bounds__(256) void grf_mix_kernel(GrfMixArgs<T> a) {
+    static_assert(!INNER || (BAND && !VEC && !HAS_IN), "the inner layout is a BAND launch");
     const int nxh = a.nx / 2, npair = nxh / 2 + 1, ny = a.ny;
     const int pr = blockIdx.x * blockDim.x + threadIdx.x;
     int y = blockIdx.y;
+    [[maybe_unused]] int yo = y;
     if constexpr (BAND) {
-        if (a.rband > 0 && y >= a.rband) y += ny - (2 * a.rband - 1);
+        if (a.rband > 0 && y >= a.rband) {
+            y += ny - (2 * a.rband - 1);
+            if constexpr (INNER) yo += a.my - (2 * a.rband - 1);
+        }
         if (pr >= a.wpairs) return;
     } else {
         if (2L * pr >= a.kp) return;
@@ -297,7 +307,10 @@ __global__ __launch_bounds__(256) void grf_mix_kernel(GrfMixArgs<T> a) {
         }
     }
 #pragma unroll
-    for (int c = 0; c < NC; ++c) store_pair<VEC>(a.out[c], i0, second, o[c]);
+    for (int c = 0; c < NC; ++c) {
+        if constexpr (INNER) store_pair<VEC>(a.out[c], (long)yo * a.okp + 2 * pr, second, o[c]);
+        else store_pair<VEC>(a.out[c], i0, second, o[c]);
+    }
 }
 
 template <typename T>
@@ -352,7 +365,7 @@ static int grf_mix_launch(oa_plan* p, uint64_t seed, uint64_t sid0, int ncomp, c
     a.filt = (const T*)filt;
     a.scale = (T)scale;
     a.ncomp = ncomp; a.ny = p->ny; a.nx = p->nx; a.kp = p->kp;
-    a.wpairs = 0; a.width = 0; a.rband = 0;
+    a.wpairs = 0; a.width = 0; a.rband = 0; a.my = 0; a.okp = 0;
     const int npair = (int)((p->kp + 1) / 2), bs = npair >= 256 ? 256 : 64;          // pairs of columns, the row padding included
     const dim3 grid((npair + bs - 1) / bs, p->ny);
     // the pair moves (grf_mix_kernel, VEC) need an even pitch and planes that start on a pair boundary; anything else goes column by column
@@ -390,11 +403,34 @@ static int grf_mix_band_launch(oa_plan* p, uint64_t seed, uint64_t sid0, int nco
     a.width = (width > 0 && width < hw) ? width : hw;
     a.wpairs = (a.width + 1) / 2;
     a.rband = (rband > 0 && 2L * rband - 1 < p->ny) ? rband : 0;
+    a.my = 0; a.okp = 0;
     const int bs = a.wpairs >= 256 ? 256 : 64;
     const dim3 grid((a.wpairs + bs - 1) / bs, a.rband ? 2 * a.rband - 1 : p->ny);
     if (ncomp == 1) hipLaunchKernelGGL((grf_mix_kernel<T, 1, false, false, true>), grid, dim3(bs), 0, st, a);
     else if (ncomp == 2) hipLaunchKernelGGL((grf_mix_kernel<T, 2, false, false, true>), grid, dim3(bs), 0, st, a);
     else hipLaunchKernelGGL((grf_mix_kernel<T, 3, false, false, true>), grid, dim3(bs), 0, st, a);
+    OA_LAUNCH_CHECK();
+    return 0;
+}
+
+// the same band into the hc layout of an inner (my, okp) grid (the caller has checked the band against both grids)
+template <typename T>
+static int grf_mix_band_inner_launch(oa_plan* p, uint64_t seed, uint64_t sid0, int ncomp, const void* const* cs, double scale, void* const* out,
+                                     int my, long okp, int width, int rband, hipStream_t st) {
+    GrfMixArgs<T> a;
+    a.seed = seed; a.sid0 = sid0;
+    for (int i = 0; i < 9; ++i) a.cs[i] = i < ncomp * ncomp ? (const T*)cs[i] : nullptr;
+    a.rc = nullptr; a.rs = nullptr; a.filt = nullptr;
+    for (int i = 0; i < 3; ++i) { a.in[i] = nullptr; a.out[i] = i < ncomp ? (cx<T>*)out[i] : nullptr; }
+    a.scale = (T)scale;
+    a.ncomp = ncomp; a.ny = p->ny; a.nx = p->nx; a.kp = p->kp;
+    a.width = width; a.wpairs = (width + 1) / 2; a.rband = rband;
+    a.my = my; a.okp = okp;
+    const int bs = a.wpairs >= 256 ? 256 : 64;
+    const dim3 grid((a.wpairs + bs - 1) / bs, 2 * rband - 1);
+    if (ncomp == 1) hipLaunchKernelGGL((grf_mix_kernel<T, 1, false, false, true, true>), grid, dim3(bs), 0, st, a);
+    else if (ncomp == 2) hipLaunchKernelGGL((grf_mix_kernel<T, 2, false, false, true, true>), grid, dim3(bs), 0, st, a);
+    else hipLaunchKernelGGL((grf_mix_kernel<T, 3, false, false, true, true>), grid, dim3(bs), 0, st, a);
     OA_LAUNCH_CHECK();
     return 0;
 }
@@ -438,6 +474,19 @@ int oa_grf_mix_band(oa_plan* p, uint64_t seed, uint64_t stream_id0, int ncomp, c
     for (int i = 0; i < ncomp; ++i) OA_REQUIRE(hc_out[i], "oa_grf_mix_band: NULL output plane");
     return p->dtype == OA_F32 ? grf_mix_band_launch<float>(p, seed, stream_id0, ncomp, covsqrt_hc, scale, hc_out, width, rband, (hipStream_t)stream)
                               : grf_mix_band_launch<double>(p, seed, stream_id0, ncomp, covsqrt_hc, scale, hc_out, width, rband, (hipStream_t)stream);
+}
+
+int oa_grf_mix_band_inner(oa_plan* p, uint64_t seed, uint64_t stream_id0, int ncomp, const void* const* covsqrt_hc, double scale,
+                          void* const* hc_out, int my, long out_pitch, int width, int rband, void* stream) {
+    OA_REQUIRE(p && covsqrt_hc && hc_out, "oa_grf_mix_band_inner: NULL argument");
+    OA_REQUIRE(ncomp >= 1 && ncomp <= 3, "oa_grf_mix_band_inner: bad argument (1 <= ncomp <= 3)");
+    OA_REQUIRE(my >= 1 && out_pitch >= 1 && width >= 1 && rband >= 1, "oa_grf_mix_band_inner: the inner grid and the band must be positive");
+    OA_REQUIRE(2L * rband - 1 <= std::min(p->ny, my), "oa_grf_mix_band_inner: row band beyond the rows of the map's or the inner grid (2 rband - 1 <= min(ny, my))");
+    OA_REQUIRE(width <= p->nx / 2 + 1, "oa_grf_mix_band_inner: width beyond the hc columns (width <= nx/2 + 1)");
+    OA_REQUIRE(2L * ((width + 1) / 2) <= out_pitch, "oa_grf_mix_band_inner: the band's column pairs do not fit the output row pitch");
+    for (int i = 0; i < ncomp; ++i) OA_REQUIRE(hc_out[i], "oa_grf_mix_band_inner: NULL output plane");
+    return p->dtype == OA_F32 ? grf_mix_band_inner_launch<float>(p, seed, stream_id0, ncomp, covsqrt_hc, scale, hc_out, my, out_pitch, width, rband, (hipStream_t)stream)
+                              : grf_mix_band_inner_launch<double>(p, seed, stream_id0, ncomp, covsqrt_hc, scale, hc_out, my, out_pitch, width, rband, (hipStream_t)stream);
 }
 
 int oa_grf_hc_band(oa_plan* p, uint64_t seed, uint64_t stream_id, const void* covsqrt_hc, void* hc_out, int width, int rband,

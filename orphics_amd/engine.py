@@ -498,6 +498,7 @@ class Engine(object):
     def release_pools(self):
         """free the plan-owned pools of the multi-map entries (oa_lens_maps, oa_qe_mv, oa_qe_tt_splits, oa_mc_run, oa_mc_run_mv)"""
         check(self.lib.oa_plan_release_pools(self.plan))
+        self._mc_owner = None             # the Monte-Carlo binding of a band grid went with its pool (mc.GaussianN0MonteCarloPol binds again)
 
     def set_laxes(self, ly, lx):
         ly = np.ascontiguousarray(ly, dtype=np.float64)
@@ -560,6 +561,19 @@ class Engine(object):
                        herm_pitch=self.kp if herm else 0, herm_nxh=self.nxh if herm else -1)
 
     def bin_power(self, k1, k2, norm, ids, nids, herm=True, active_cols=0, active_rows=0):
+        if herm and self.kp % 4 and tuple(k1.shape) == tuple(k2.shape) == tuple(ids.shape) == (self.ny, self.kp):
+            # oa_bin_power moves four columns per lane and refuses a row pitch that is no multiple of 4 (nx/2 odd: 750 -> 375 + 16):
+            # such planes are binned from copies padded to the next multiple, the padding ignored (id -1)
+            kp4 = self.kp + (-self.kp) % 4
+
+            def padded(t, fill):
+                o = torch.full((self.ny, kp4), fill, dtype=t.dtype, device=t.device)
+                o[:, :self.kp] = t
+                return o
+            p1 = padded(k1, 0)
+            p2 = p1 if k2 is k1 else padded(k2, 0)
+            return dev_bin_power(p1, p2, norm, padded(ids, -1), nids, herm_pitch=kp4, herm_nxh=self.nxh, active_cols=active_cols,
+                                 active_rows=active_rows)
         return dev_bin_power(k1, k2, norm, ids, nids, herm_pitch=self.kp if herm else 0, herm_nxh=self.nxh if herm else -1,
                              active_cols=active_cols if herm else 0, active_rows=active_rows if herm else 0)
 
@@ -635,6 +649,27 @@ class Engine(object):
         cs = (ctypes.c_void_p * (n * n))(*[_ptr(covsqrt_hc[i][j]) for i in range(n) for j in range(n)])
         outs = (ctypes.c_void_p * n)(*[_ptr(k) for k in out])
         check(self.lib.oa_grf_mix_band(self.plan, int(seed), int(stream_id0), n, cs, float(scale), outs, int(width), int(rband), _stream()))
+        return list(out)
+
+    def grf_mix_band_inner(self, seed, covsqrt_hc, out, my, pitch, width, rband, scale=1.0, stream_id0=0):
+        """``oa_grf_mix_band_inner``: the band of :meth:`grf_mix_band` written into the hc layout of an inner grid -- ``out``: n
+        contiguous (my, pitch) complex planes; the value of N-grid row y goes to row y (y < rband) or y - ny + my.  The same values as
+        the N-grid draw at the same mode, the rest of the ``out`` planes untouched."""
+        n = len(covsqrt_hc)
+        if not (1 <= n <= 3) or any(len(r) != n for r in covsqrt_hc) or len(out) != n:
+            raise ValueError("grf_mix_band_inner: covsqrt_hc must be an n x n table and out n planes, 1 <= n <= 3")
+        for r in covsqrt_hc:
+            for c in r:
+                if c is not None:
+                    self._chk(c, "hcreal")
+        for k in out:
+            if tuple(k.shape) != (int(my), int(pitch)) or k.dtype != self.cdt or not k.is_contiguous() or k.device != self.device:
+                raise ValueError("grf_mix_band_inner: out planes must be contiguous (my, pitch) = (%d, %d) %s planes on %s"
+                                 % (int(my), int(pitch), self.cdt, self.device))
+        cs = (ctypes.c_void_p * (n * n))(*[_ptr(covsqrt_hc[i][j]) for i in range(n) for j in range(n)])
+        outs = (ctypes.c_void_p * n)(*[_ptr(k) for k in out])
+        check(self.lib.oa_grf_mix_band_inner(self.plan, int(seed), int(stream_id0), n, cs, float(scale), outs, int(my), int(pitch), int(width),
+                                             int(rband), _stream()))
         return list(out)
 
     def bin_power_multi(self, fields, pairs, norm, ids, nids, weights=None, active_cols=0, active_rows=0):

@@ -242,7 +242,13 @@ class GaussianN0MonteCarloPol(object):
     covariance (:func:`teb_covsqrt`).  On power-of-two sides the shard runs as ``oa_mc_run_mv`` calls (leg-band draw, the ``oa_qe_mv``
     launch sequence, one ``oa_bin_power_multi`` pass, one moment launch; nothing leaves the device).  Elsewhere, or with
     ``one_call=False``, it runs a host loop of the existing entries with the same seeds and streams: ``Engine.grf_mix``,
-    ``reconstruct_hc`` per estimator, the weighted sum, ``Engine.bin_power`` per spectrum, ``Statistics.add``."""
+    ``reconstruct_hc`` per estimator, the weighted sum, ``Engine.bin_power`` per spectrum, ``Statistics.add``.
+
+    ``one_call``: None (default) = the one call on power-of-two sides, the host loop elsewhere.  ``one_call=True`` opts in to the one
+    call on sides 2^a 3^b 5^c as well: it runs on the band grid of the estimator set (``qest.one_call_pol(estimators,
+    ext_norm=True)``; ``oa_qe_band_bind`` + ``oa_mc_mv_band_bind`` bind the planes, re-bound whenever anything else used the plan in
+    between -- :meth:`sample_host` included, so the two paths may be interleaved), and raises where there is no such path (chirp-z
+    sides, unbounded filters, a band grid not smaller than the map): pass ``one_call=False`` there."""
 
     def __init__(self, qest, total_power_half, bin_edges, estimators=("TT", "TE", "EE", "EB", "TB"), cross=True, mv=True, comm=None,
                  base_seed=1234, one_call=None):
@@ -275,6 +281,14 @@ class GaussianN0MonteCarloPol(object):
             for i, XY in enumerate(self.estimators):
                 self.w[i].copy_(qest._hcreal(e, w[XY]))
         self.wl, self.wk, self.rl, self.rk = pol_bands(G)
+        self._bands = (self.wl, self.wk, self.rl, self.rk)
+        if self.one_call and not e.pow2:
+            if not qest.one_call_pol(self.estimators, ext_norm=True):
+                from ._lib import OrphicsAmdError
+                raise OrphicsAmdError("GaussianN0MonteCarloPol: no one-call path on this %d x %d geometry (chirp-z sides, unbounded filters or a "
+                                      "band grid not smaller than the map): construct the driver with one_call=False" % (e.ny, e.nx))
+            # BAND GRID: kappa's band is the kappa mask's support, which also bounds the MV weights (what one_call_pol resolved)
+            self._bands = qest._pol_bands(self.estimators, True)
         self.edges = np.asarray(bin_edges, dtype=np.float64)
         self.ids = e.modl_digitize(torch.as_tensor(self.edges, device=e.device), half=True)
         self.nids = self.edges.size + 1
@@ -287,6 +301,7 @@ class GaussianN0MonteCarloPol(object):
         self.acc = Statistics(comm=self.comm if hasattr(self.comm, "dist") else None, device=e.device)
         self._host = None
         self._c_args = None
+        self._token = object()        # identity of this driver for the plan-level Monte-Carlo binding (its ids and weights planes)
 
     # ---- the one-call path ------------------------------------------------------------------------------------------------------
     def _entry_args(self):
@@ -319,10 +334,22 @@ class GaussianN0MonteCarloPol(object):
             if getattr(e, "_pipe_owner", None) is not q._token:
                 e._pipe_owner = None
         wstride = self.w[0].numel() if self.w is not None else 0
+        wl, wk, rl, rk = self._bands
+        if e.mixed:
+            # the estimator set with its pure normalisations in order, then the weights and bin ids, on the plan's inner grid; the plan
+            # is shared: both are bound again whenever anything else bound it in between (sample_host's reconstruct_hc does)
+            nE, nS = len(self.estimators), len(self.spectra)
+            q._pol_bind(self.estimators, [self.fn[i] for i in range(nE)], self._bands, split=False)
+            key = (self._token, self.w.data_ptr() if self.w is not None else 0, wstride, self.ids.data_ptr(), self.nids, nE, nS)
+            own = getattr(e, "_mc_owner", None)
+            if own is None or own[0] is not e._pol_owner or own[1] != key:
+                e._mc_owner = None
+                check(e.lib.oa_mc_mv_band_bind(e.plan, _ptr(self.w), wstride, nE, _ptr(self.ids), self.nids, nS))
+                e._mc_owner = (e._pol_owner, key)
         check(e.lib.oa_mc_run_mv(e.plan, self.base_seed, int(lo), int(hi), A["cs"], len(self.estimators), A["npieces"], A["signs"], A["fgs"],
                                  A["fhs"], A["swaps"], A["xsrc"], A["ysrc"], A["fns"], _ptr(self.w), wstride, len(self.spectra), A["a"], A["b"],
-                                 _ptr(self.ids), self.nids, _ptr(self.counts), float(self.norm), int(self.wl), int(self.wk), int(self.rl),
-                                 int(self.rk), int(q.mrow), _ptr(n), _ptr(S), _ptr(C), _stream()))
+                                 _ptr(self.ids), self.nids, _ptr(self.counts), float(self.norm), int(wl), int(wk), int(rl), int(rk), int(q.mrow),
+                                 _ptr(n), _ptr(S), _ptr(C), _stream()))
 
     # ---- the host loop of existing entries (every side the estimators run on; the reference of the one-call path) -------------------
     def sample_host(self, i):

@@ -71,7 +71,7 @@ def main():
         q64, tot = setup(n, args.res)
         for prec in args.precs.split(","):
             q = q64 if prec == "f64" else q64.astype("f32")
-            one = mc.GaussianN0MonteCarloPol(q, tot, edges, estimators=ESTS, base_seed=5)
+            one = mc.GaussianN0MonteCarloPol(q, tot, edges, estimators=ESTS, base_seed=5, one_call=True)
             host = mc.GaussianN0MonteCarloPol(q, tot, edges, estimators=ESTS, base_seed=5, one_call=False)
             if not one.one_call:
                 raise SystemExit("side %d has no one-call path" % n)
