@@ -90,7 +90,8 @@ int oa_plan_set_laxes(oa_plan* p, const double* host_ly, const double* host_lx);
 int oa_fft_r2c(oa_plan* p, const void* real_in, void* hc_out, double scale, int width, int rband, void* stream);
 int oa_fft_c2r(oa_plan* p, const void* hc_in, void* real_out, double scale, int width, void* stream);
 /* oa_fft_c2r with a real-space window multiplied into the result at the last pass's store: real_out = window_real *
- * scale * IDFT(hc_in) (window_real: ny x nx reals of the plan's dtype; power-of-two sides).  The apodisation step of the
+ * scale * IDFT(hc_in) (window_real: ny x nx reals of the plan's dtype; power-of-two sides and sides 2^a 3^b 5^c, where the window
+ * rides on the store of the mixed-radix C2R row pass; chirp-z sides are refused).  The apodisation step of the
  * reference's analysis flow (maps.py:1350-1361 binned_power(imap * mask)) without another pass over the map. */
 int oa_fft_c2r_windowed(oa_plan* p, const void* hc_in, void* real_out, double scale, const void* window_real, void* stream);
 int oa_fft_c2c(oa_plan* p, const void* full_in, void* full_out, int inverse, double scale, void* stream);
@@ -200,12 +201,13 @@ int oa_plan_col_grid(const oa_plan* p);
  * power of two is checked against the bound; 0 (the map's own grid), unbounded filters (0 = all) and a grid not smaller than the map
  * side are refused with a message naming the reason (the modular chain serves those).  The plan then owns an inner power-of-two plan
  * of My x Mx points with inner-layout copies of FG, FH, Fnorm and of the bin ids (made by oa_plan_set_filters / oa_plan_set_bins,
- * which synchronise the device; oa_plan_set_bins keeps the WHOLE N-plane mode counts), and every call runs the fused power-of-two
+ * which synchronise the device; oa_plan_set_bins keeps the WHOLE N-plane mode counts, also where the N-grid row pitch nx / 2 + 16
+ * is odd, as at nx = 750), and every call runs the fused power-of-two
  * pipeline there: only the input transform (one mixed-radix row R2C that stores the leg columns, then an ny-point DFT evaluated at the
  * leg rows), the Monte-Carlo draw (the leg band of oa_grf_hc's N-grid draw, same Philox counters) and the scatter of kappa's band
  * into the N-grid output / mean-field stack see the map's grid.  oa_qe_tt_splits runs there too, and oa_qe_tt_split_power is the
- * split-based estimator evaluated on the inner grid (both below, at their declarations); oa_mc_run_windowed and oa_qe_tt_stage stay
- * power-of-two only.  oa_plan_band_grid reports (My, Mx), or (0, 0) when no band grid is bound.
+ * split-based estimator evaluated on the inner grid (both below, at their declarations); oa_mc_run_windowed runs there behind a
+ * full-plane N-grid front end (at its declaration); oa_qe_tt_stage stays power-of-two only.  oa_plan_band_grid reports (My, Mx), or (0, 0) when no band grid is bound.
  * oa_qe_pol / oa_qe_mv ON A BAND GRID.  The band-limit argument does not depend on the estimator (every separable piece is a product of
  * fields confined to the leg band; the cos / sin 2 phi_ell factors live on the same ell lattice, so a copy of their band is exact), but
  * these two entries take their planes per call, and a stream-ordered call may neither allocate nor synchronise.  oa_qe_band_bind is
@@ -253,7 +255,10 @@ int oa_plan_div_fused(const oa_plan* p);
  *   OA_OPT_DIV_BIN     moment entries: radial binning + moment update in the tail of the single-pass divergence launch
  *                      (default 1, where the geometry has that kernel: oa_plan_div_fused); 0: the separate histogram launches
  *   OA_OPT_WIN_FUSED   oa_mc_run_windowed: inverse columns, then C2R x window -> R2C of every row in ONE kernel (default 1: the
- *                      real map exists in LDS only); 0: C2R with the window at its store, real map in HBM, from-map estimator path */
+ *                      real map exists in LDS only); 0: C2R with the window at its store, real map in HBM, from-map estimator path
+ *                      (sides 2^a 3^b 5^c: the band input transform; until the option is set, or after a value < 0, such a plan takes
+ *                      what measured faster: the unfused flow for rows of up to 1200 points, the fused pass for longer ones up to
+ *                      the 8192 points its kernel holds) */
 enum { OA_OPT_MC_BATCH = 1, OA_OPT_MV_BATCH = 2, OA_OPT_MV_ROWBATCH = 3, OA_OPT_MV_CHAIN = 4, OA_OPT_DIV_BIN = 5, OA_OPT_WIN_FUSED = 6 };
 int oa_plan_set_option(oa_plan* p, int option, int value);
 int oa_plan_set_bins(oa_plan* p, const int32_t* ids_hc, int nids, double norm, void* stream);
@@ -339,7 +344,13 @@ int oa_mc_run(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const vo
 /* The same shard with a real-space window applied to every realisation before its transform (the reference's analysis
  * flow: maps.py:1873-1878 get_taper, maps.py:1350-1361): full-plane draw (same Philox counters as oa_mc_run) -> C2R / Npix
  * -> x window_real (ny x nx reals of the plan's dtype) -> TT estimator -> bandpower moments (+ mean-field stack).  With
- * window == 1 the moments equal oa_mc_run's up to rounding; with a taper the stack holds the window's mean field. */
+ * window == 1 the moments equal oa_mc_run's up to rounding; with a taper the stack holds the window's mean field.
+ * ON A BAND GRID (sides 2^a 3^b 5^c with filters that bound one; chirp-z sides and a binding without a band grid are refused by name):
+ * per realisation the full-plane draw on the N grid and its mixed-radix inverse column transform in place; per batch of up to 6 ONE
+ * fused row launch (C2R -> x window / Npix -> R2C per row, the real map in LDS only, the leg columns stored) and the pruned column
+ * DFT onto the inner plan's source planes, then oa_mc_run's batched launches there and the N-grid stack update.  OA_OPT_WIN_FUSED = 0:
+ * one by one, oa_fft_c2r_windowed -> real map in HBM -> the band input transform.  The first windowed call on such a plan takes the
+ * draw and row planes (one device synchronisation); oa_plan_release_pools frees them. */
 int oa_mc_run_windowed(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, const void* window_real,
                        int64_t* n, double* S, double* C, double* meanfield_acc, void* stream);
 /* oa_mc_run_mv: the Gaussian N0 Monte-Carlo shard [sim_lo, sim_hi) of an estimator SET (TT, TE, EE, EB, TB ... and their MV combination),

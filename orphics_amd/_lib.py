@@ -32,6 +32,7 @@ SIGNATURES = {
     "oa_plan_set_laxes": (c_int, [c_void_p, c_void_p, c_void_p]),
     "oa_fft_r2c": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int, c_int, c_void_p]),
     "oa_fft_c2r": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int, c_void_p]),
+    # C2R with a real-space window at the last pass's store: power-of-two sides and sides 2^a 3^b 5^c (chirp-z sides are refused)
     "oa_fft_c2r_windowed": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
     "oa_fft_c2c": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p]),
     "oa_fft_pass": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
@@ -65,6 +66,8 @@ SIGNATURES = {
     "oa_split_cross_power": (c_int, [c_int, c_int, c_void_p, c_void_p, c_double, c_int, c_long, c_int, c_int, c_void_p]),
     "oa_qe_tt_stage": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "oa_mc_run": (c_int, [c_void_p, c_u64, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # windowed N0 / mean-field shard: power-of-two plans, and plans of sides 2^a 3^b 5^c whose bound filters have a band grid (full-plane
+    # draw + inverse columns + fused windowed row pass on the map's grid, everything behind on the inner grid); same signature on both
     "oa_mc_run_windowed": (c_int, [c_void_p, c_u64, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "oa_mc_run_mv": (c_int, [c_void_p, c_u64, c_long, c_long, c_void_p, c_int] + [c_void_p] * 9 + [c_long, c_int, c_void_p, c_void_p, c_void_p, c_int,
                              c_void_p, c_double] + [c_int] * 5 + [c_void_p] * 4),

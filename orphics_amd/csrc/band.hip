@@ -9,6 +9,8 @@
 //                      (bodies in fft_band.hpp: band_rows on grid (row, map); band_cols with the twiddle tile staged once and applied to
 //                      every map's operand tile; band_cols_fold = the ordered sum + the Q,U -> E,B rotation in double before the one
 //                      rounding), straight into the inner source planes of the oa_qe_band_bind binding; map pointers by value;
+//   * band_win_r2c   : the front end of oa_mc_run_windowed: <= 6 inverse-column-transformed spectra -> fused C2R x window -> R2C rows
+//                      (band_rows_win, fft_band.hpp; the real map in LDS only, the leg columns stored) -> the same pruned column DFT;
 //   * band_copy      : band region (rows |ky| < r, columns < w) of one grid's hc-layout plane -> the other grid's (filters, bin ids,
 //                      Fourier-space legs N -> inner; kappa_hat inner -> N), optionally scaled;
 //   * band_stack_add : the mean-field stack update of oa_mc_run (f64 interleaved N-grid accumulator += inner kappa_hat planes);
@@ -124,13 +126,9 @@ __global__ __launch_bounds__(256) void band_cols_sum(const double2* __restrict__
     out[(long)band_row(ki, rl, my) * okp + x] = mk<T>((T)ar, (T)ai);
 }
 
+// the column stage of ONE row plane (rowbuf: ny x wl complex, then the partial sums: band_map_scratch_bytes) -> the inner plane dst
 template <typename T>
-static int map_r2c_t(oa_plan* p, const void* map, void* rowbuf, int wl, int rl, void* dst, int dny, long dkp, hipStream_t st) {
-    const int N = p->nx / 2;
-    int rc = 0;
-    BandRowArgs<T> a{(const T*)map, (cx<T>*)rowbuf, (long)p->nx, wl, N, mixed_factor(N), (const cx<T>*)p->mr_twxh, (const cx<T>*)p->mr_twx};
-    launch_go(rc, st, band_row_kernel<T>, dim3(p->ny), 256, 2 * ((size_t)N + 1) * sizeof(cx<T>), a);
-    if (rc) return rc;
+static int cols_single_t(oa_plan* p, void* rowbuf, int wl, int rl, void* dst, int dny, long dkp, hipStream_t st) {
     int yseg = 0;
     const int nseg = band_cols_segments(p->ny, wl, rl, &yseg);
     double2* part = reinterpret_cast<double2*>((char*)rowbuf + (size_t)p->ny * wl * sizeof(cx<T>));     // (band_map_scratch_bytes)
@@ -140,6 +138,15 @@ static int map_r2c_t(oa_plan* p, const void* map, void* rowbuf, int wl, int rl, 
     hipLaunchKernelGGL(band_cols_sum<T>, dim3((wl + 255) / 256, 2 * rl - 1), dim3(256), 0, st, (const double2*)part, nseg, wl, rl, (cx<T>*)dst, dny, dkp);
     OA_LAUNCH_CHECK();
     return 0;
+}
+template <typename T>
+static int map_r2c_t(oa_plan* p, const void* map, void* rowbuf, int wl, int rl, void* dst, int dny, long dkp, hipStream_t st) {
+    const int N = p->nx / 2;
+    int rc = 0;
+    BandRowArgs<T> a{(const T*)map, (cx<T>*)rowbuf, (long)p->nx, wl, N, mixed_factor(N), (const cx<T>*)p->mr_twxh, (const cx<T>*)p->mr_twx};
+    launch_go(rc, st, band_row_kernel<T>, dim3(p->ny), 256, 2 * ((size_t)N + 1) * sizeof(cx<T>), a);
+    if (rc) return rc;
+    return cols_single_t<T>(p, rowbuf, wl, rl, dst, dny, dkp, st);
 }
 int band_map_r2c(oa_plan* p, const void* map, void* rowbuf, int wl, int rl, void* dst, int dny, long dkp, hipStream_t st) {
     OA_REQUIRE(p->mixed && wl >= 1 && wl <= p->nx / 2 && rl >= 1 && 2 * rl - 1 <= std::min(p->ny, dny), "band input transform: bad band");
@@ -176,6 +183,35 @@ size_t band_maps_scratch_bytes(const oa_plan* p, int nmaps, int wl, int rl) {
     const int nseg = band_cols_segments(p->ny, wl, rl, &ys);
     return band_maps_rows_bytes(p, nmaps, wl) + (size_t)nmaps * nseg * (2 * rl - 1) * wl * sizeof(cx<double>);
 }
+// the column stage of n row planes (scratch: the planes ny x wl complex each, then -- 256-byte aligned -- their partial sums:
+// band_maps_scratch_bytes) -> n inner planes dstride elements apart, with the rotation of the pairs (1, 2) / (4, 5) when rot_c / rot_s
+// are given: the pruned column DFT of all planes in one launch, then the ordered fold
+template <typename T>
+static int cols_batched_t(oa_plan* p, int n, void* scratch, int wl, int rl, const void* rot_c, const void* rot_s, void* dst, long dstride, int dny,
+                          long dkp, hipStream_t st) {
+    BandColsArgs<T> ca{};
+    ca.rows = (const cx<T>*)scratch; ca.rows_mstride = (long)p->ny * wl; ca.ny = p->ny; ca.w = wl; ca.rl = rl;
+    ca.nseg = band_cols_segments(p->ny, wl, rl, &ca.yseg);
+    ca.tw = (const cx<T>*)p->mr_twy;
+    ca.part = reinterpret_cast<cx<double>*>((char*)scratch + band_maps_rows_bytes(p, n, wl));
+    const dim3 grid((wl + BC_TX - 1) / BC_TX, (2 * rl - 1 + BC_TK - 1) / BC_TK, ca.nseg);
+    switch (n) {
+        case 1: hipLaunchKernelGGL((band_colsn_kernel<T, 1>), grid, dim3(256), 0, st, ca); break;
+        case 2: hipLaunchKernelGGL((band_colsn_kernel<T, 2>), grid, dim3(256), 0, st, ca); break;
+        case 3: hipLaunchKernelGGL((band_colsn_kernel<T, 3>), grid, dim3(256), 0, st, ca); break;
+        case 4: hipLaunchKernelGGL((band_colsn_kernel<T, 4>), grid, dim3(256), 0, st, ca); break;
+        case 5: hipLaunchKernelGGL((band_colsn_kernel<T, 5>), grid, dim3(256), 0, st, ca); break;
+        default: hipLaunchKernelGGL((band_colsn_kernel<T, 6>), grid, dim3(256), 0, st, ca); break;
+    }
+    OA_LAUNCH_CHECK();
+    BandFoldArgs<T> fa{};
+    fa.part = ca.part; fa.nmaps = n; fa.nseg = ca.nseg; fa.w = wl; fa.rl = rl;
+    fa.rot_c = (const T*)rot_c; fa.rot_s = (const T*)rot_s; fa.rot_pitch = p->kp; fa.ny = p->ny;
+    fa.out = (cx<T>*)dst; fa.out_mstride = dstride; fa.okp = dkp; fa.my = dny;
+    hipLaunchKernelGGL(band_cols_fold_kernel<T>, dim3((wl + 255) / 256, 2 * rl - 1), dim3(256), 0, st, fa);
+    OA_LAUNCH_CHECK();
+    return 0;
+}
 template <typename T>
 static int maps_r2c_t(oa_plan* p, int nmaps, const void* const* maps, const void* rot_c, const void* rot_s, void* scratch, int wl, int rl, void* dst,
                       long dstride, int dny, long dkp, hipStream_t st) {
@@ -187,28 +223,39 @@ static int maps_r2c_t(oa_plan* p, int nmaps, const void* const* maps, const void
     ra.tw = (const cx<T>*)p->mr_twxh; ra.tw2 = (const cx<T>*)p->mr_twx;
     launch_go(rc, st, band_rows_kernel<T>, dim3(p->ny, nmaps), 256, band_rows_lds<T>(N), ra);
     if (rc) return rc;
-    BandColsArgs<T> ca{};
-    ca.rows = (const cx<T>*)scratch; ca.rows_mstride = ra.out_mstride; ca.ny = p->ny; ca.w = wl; ca.rl = rl;
-    ca.nseg = band_cols_segments(p->ny, wl, rl, &ca.yseg);
-    ca.tw = (const cx<T>*)p->mr_twy;
-    ca.part = reinterpret_cast<cx<double>*>((char*)scratch + band_maps_rows_bytes(p, nmaps, wl));
-    const dim3 grid((wl + BC_TX - 1) / BC_TX, (2 * rl - 1 + BC_TK - 1) / BC_TK, ca.nseg);
-    switch (nmaps) {
-        case 1: hipLaunchKernelGGL((band_colsn_kernel<T, 1>), grid, dim3(256), 0, st, ca); break;
-        case 2: hipLaunchKernelGGL((band_colsn_kernel<T, 2>), grid, dim3(256), 0, st, ca); break;
-        case 3: hipLaunchKernelGGL((band_colsn_kernel<T, 3>), grid, dim3(256), 0, st, ca); break;
-        case 4: hipLaunchKernelGGL((band_colsn_kernel<T, 4>), grid, dim3(256), 0, st, ca); break;
-        case 5: hipLaunchKernelGGL((band_colsn_kernel<T, 5>), grid, dim3(256), 0, st, ca); break;
-        default: hipLaunchKernelGGL((band_colsn_kernel<T, 6>), grid, dim3(256), 0, st, ca); break;
-    }
-    OA_LAUNCH_CHECK();
-    BandFoldArgs<T> fa{};
-    fa.part = ca.part; fa.nmaps = nmaps; fa.nseg = ca.nseg; fa.w = wl; fa.rl = rl;
-    fa.rot_c = (const T*)rot_c; fa.rot_s = (const T*)rot_s; fa.rot_pitch = p->kp; fa.ny = p->ny;
-    fa.out = (cx<T>*)dst; fa.out_mstride = dstride; fa.okp = dkp; fa.my = dny;
-    hipLaunchKernelGGL(band_cols_fold_kernel<T>, dim3((wl + 255) / 256, 2 * rl - 1), dim3(256), 0, st, fa);
-    OA_LAUNCH_CHECK();
-    return 0;
+    return cols_batched_t<T>(p, nmaps, scratch, wl, rl, rot_c, rot_s, dst, dstride, dny, dkp, st);
+}
+// FRONT END of oa_mc_run_windowed on these sides (body: fft_band.hpp band_rows_win_body): the fused windowed row pass of B realisations in one
+// launch, then the pruned column DFT with the realisations in the place of maps and no rotation (batched: band_colsn_kernel +
+// band_cols_fold_kernel on the layout of band_maps_scratch_bytes; single: band_cols_kernel + band_cols_sum on band_map_scratch_bytes')
+template <typename T>
+__global__ __launch_bounds__(BRW_NT, waves_per_eu<T>()) void band_rows_win_kernel(BandRowsWinArgs<T> a) {
+    GpuCtx c{oa_dyn_smem};
+    band_rows_win_body<T>(c, a);
+}
+template <typename T>
+static int win_r2c_t(oa_plan* p, int B, const void* hc_in, long in_bstride, const void* window, double scale, void* scratch, int single, int wl,
+                     int rl, void* dst, long dstride, int dny, long dkp, hipStream_t st) {
+    const int N = p->nx / 2;
+    int rc = 0;
+    BandRowsWinArgs<T> ra{};
+    ra.in = (const cx<T>*)hc_in; ra.in_pitch = p->kp; ra.in_bstride = in_bstride; ra.win = (const T*)window;
+    ra.out = (cx<T>*)scratch; ra.out_bstride = (long)p->ny * wl; ra.w = wl; ra.N = N; ra.scale = (T)scale; ra.f = mixed_factor(N);
+    ra.tw = (const cx<T>*)p->mr_twxh; ra.tw2 = (const cx<T>*)p->mr_twx;
+    launch_go(rc, st, band_rows_win_kernel<T>, dim3(p->ny, B), BRW_NT, band_rows_lds<T>(N), ra);
+    if (rc) return rc;
+    if (single) return cols_single_t<T>(p, scratch, wl, rl, dst, dny, dkp, st);
+    return cols_batched_t<T>(p, B, scratch, wl, rl, nullptr, nullptr, dst, dstride, dny, dkp, st);
+}
+bool band_rows_win_ok(const oa_plan* p) { return band_rows_win_fits(p->nx / 2); }
+int band_win_r2c(oa_plan* p, int B, const void* hc_in, long in_bstride, const void* window, double scale, void* scratch, int single, int wl, int rl,
+                 void* dst, long dstride, int dny, long dkp, hipStream_t st) {
+    OA_REQUIRE(p->mixed && wl >= 1 && wl <= p->nx / 2 && rl >= 1 && 2 * rl - 1 <= std::min(p->ny, dny), "band windowed front end: bad band");
+    OA_REQUIRE(B >= 1 && B <= BAND_MAPS_MAX && (!single || B == 1) && wl <= dkp && (B == 1 || (long)dny * dkp <= dstride) &&
+               (B == 1 || (long)p->ny * p->kp <= in_bstride), "band windowed front end: bad planes");
+    OA_REQUIRE(band_rows_win_fits(p->nx / 2), "band windowed front end: map rows longer than 8192 points");
+    return p->dtype == OA_F32 ? win_r2c_t<float>(p, B, hc_in, in_bstride, window, scale, scratch, single, wl, rl, dst, dstride, dny, dkp, st)
+                              : win_r2c_t<double>(p, B, hc_in, in_bstride, window, scale, scratch, single, wl, rl, dst, dstride, dny, dkp, st);
 }
 int band_maps_r2c(oa_plan* p, int nmaps, const void* const* maps, const void* rot_c, const void* rot_s, void* scratch, int wl, int rl, void* dst,
                   long dstride, int dny, long dkp, hipStream_t st) {

@@ -107,6 +107,8 @@ void mixed_release(oa_plan* p);
 int mixed_c2c(oa_plan* p, const void* in, void* out, int inverse, double scale, hipStream_t st);
 int mixed_r2c(oa_plan* p, const void* real_in, void* hc_out, double scale, hipStream_t st);
 int mixed_c2r(oa_plan* p, const void* hc_in, void* real_out, double scale, hipStream_t st);
+int mixed_c2r_windowed(oa_plan* p, const void* hc_in, void* real_out, double scale, const void* window, hipStream_t st);
+int mixed_cols_inverse(oa_plan* p, const void* hc_in, void* hc_out, hipStream_t st);      // unscaled, nx / 2 + 1 columns; in place allowed
 int mixed_lens_derivs(oa_plan* p, int nmaps, const void* real_in, long in_stride, void* k0, void* hc_pool, void* real_pool, int nd, hipStream_t st,
                       const void* hc_in, long hc_stride, double hc_scale);
 void pipeline_release(oa_plan* p);
@@ -188,6 +190,13 @@ size_t band_map_scratch_bytes(const oa_plan* p, int wl, int rl);
 int band_maps_r2c(oa_plan* p, int nmaps, const void* const* maps, const void* rot_c, const void* rot_s, void* scratch, int wl, int rl, void* dst,
                   long dstride, int dny, long dkp, hipStream_t st);
 size_t band_maps_scratch_bytes(const oa_plan* p, int nmaps, int wl, int rl);
+// FRONT END of oa_mc_run_windowed on these sides: B <= 6 inverse-column-transformed spectra (N-grid hc planes in_bstride elements apart)
+// -> fused C2R x window x scale -> R2C rows (the real map in LDS only) -> pruned column DFT onto B inner planes dstride elements apart.
+// single = 0: the batched kernels, scratch of band_maps_scratch_bytes(p, B, wl, rl); single != 0 (B = 1): band_map_r2c's column
+// kernels, scratch of band_map_scratch_bytes(p, wl, rl)
+int band_win_r2c(oa_plan* p, int B, const void* hc_in, long in_bstride, const void* window, double scale, void* scratch, int single, int wl, int rl,
+                 void* dst, long dstride, int dny, long dkp, hipStream_t st);
+bool band_rows_win_ok(const oa_plan* p);                 // the fused windowed row kernel holds a row of this plan (nx <= 8192)
 int band_copy(int kind, const void* src, long spitch, int sny, void* dst, long dpitch, int dny, int w, int r, double scale, hipStream_t st);
 int band_zero_outside(int dtype, void* out, int ny, long kp, int w, int r, hipStream_t st);
 int band_stack_add(int dtype, const void* src, long spitch, int sny, int nbatch, long sstride, double* acc, long apitch, int any, int w, int r,

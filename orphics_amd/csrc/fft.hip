@@ -1240,7 +1240,8 @@ int oa_fft_c2r(oa_plan* p, const void* hc_in, void* real_out, double scale, int 
 int oa_fft_c2r_windowed(oa_plan* p, const void* hc_in, void* real_out, double scale, const void* window_real, void* stream) {
     OA_REQUIRE(p && hc_in && real_out && window_real, "oa_fft_c2r_windowed: NULL argument");
     OA_REQUIRE(hc_in != real_out && window_real != real_out, "oa_fft_c2r_windowed: in-place not supported");
-    OA_NEED_POW2(p, "oa_fft_c2r_windowed");
+    if (p->mixed) return mixed_c2r_windowed(p, hc_in, real_out, scale, window_real, (hipStream_t)stream);
+    OA_REQUIRE(p->pow2, "oa_fft_c2r_windowed: needs map sides of the form 2^a 3^b 5^c (chirp-z sides: oa_fft_c2r, then multiply by the window)");
     return p->dtype == OA_F32 ? c2r_impl<float>(p, hc_in, real_out, scale, 0, (hipStream_t)stream, window_real)
                               : c2r_impl<double>(p, hc_in, real_out, scale, 0, (hipStream_t)stream, window_real);
 }

@@ -1,9 +1,12 @@
 // BATCHED BAND INPUT STAGE of oa_qe_mv_maps on map sides 2^a 3^b 5^c (band.hip, pipeline.hip): up to BAND_MAPS_MAX real maps -> the leg
 // band (columns < w, rows |ky| < rl) of their transforms, written in the hc layout of the inner power-of-two grid, optionally with the
-// per-mode Q,U -> E,B rotation.  Three kernel bodies, templated on the context type so that the CPU thread emulator
-// (tests/emul/emul_band.cpp) runs the same code as the GPU:
+// per-mode Q,U -> E,B rotation; and the FUSED WINDOWED ROW PASS of oa_mc_run_windowed on these sides, which feeds the same column bodies
+// with realisations in the place of maps.  Four kernel bodies, templated on the context type so that the CPU thread emulator
+// (tests/emul/emul_band.cpp, emul_band_win.cpp) runs the same code as the GPU:
 //   * band_rows_body      : grid (row, map); one map row per workgroup: packed N/2-point mixed-radix transform (mr_transform) + untangle,
 //                           store of columns < w only into the row plane of its map (the arithmetic of band_row_kernel);
+//   * band_rows_win_body  : grid (row, realisation); C2R of an inverse-column-transformed spectrum row -> x window / Npix -> R2C, the real
+//                           row in LDS only, store of columns < w into the row plane of its realisation;
 //   * band_cols_body      : grid (column tile, output-row tile, segment); the pruned-output column DFT of band_cols_kernel -- same
 //                           segments, same 32-row chunks, double accumulation, same fma order per output -- for all maps of the call: the
 //                           twiddle tile W[16][32] (with its (k y) mod ny index arithmetic) is staged once per chunk and applied to the
@@ -74,6 +77,73 @@ OA_HD void band_rows_body(Ctx& c, const BandRowsArgs<T>& a) {
     cx<T>* dst = a.out + m * a.out_mstride + row * w;
     for (int k = tid; k < w; k += NT) {
         const cx<T> Zk = r[k == N ? 0 : k], Zm = conj(r[k == 0 ? 0 : N - k]);
+        const cx<T> E = (Zk + Zm) * (T)0.5, O = mul_mi(Zk - Zm) * (T)0.5;
+        dst[k] = E + a.tw2[k] * O;
+    }
+}
+
+// FUSED WINDOWED ROW PASS of oa_mc_run_windowed on these sides (the mixed-radix counterpart of the pow2 ROW_WIN pass, fft_kernels.hpp):
+// grid (map row, realisation); per row C2R of the inverse-column-transformed spectrum -> x window x scale -> R2C, the real row in LDS
+// only, store of columns < w into the row plane of its realisation.  A thread owns the packed elements n = tid + q NT, q < BRW_MAXQ
+// (256 threads: N <= 4096), and keeps its window values in registers across the inverse transform: every global load of the row --
+// spectrum and window -- is issued before the first barrier, none between the transforms.
+constexpr int BRW_NT = 256, BRW_MAXQ = 16;
+inline bool band_rows_win_fits(int N) { return N >= 1 && N <= BRW_NT * BRW_MAXQ; }
+
+template <typename T>
+struct BandRowsWinArgs {
+    const cx<T>* in;                 // inverse-column-transformed spectra: realisation b at in + b * in_bstride, in_pitch complex per row
+    long in_pitch, in_bstride;
+    const T* win;                    // (ny, 2 N) real window, rows back to back
+    cx<T>* out;                      // row planes: realisation b at out + b * out_bstride, w complex per row
+    long out_bstride;
+    int w, N;                        // stored columns (<= N); packed transform length nx / 2
+    T scale;                         // 1 / Npix of the inverse transform, applied with the window
+    MrFactors f;
+    const cx<T>* tw;                 // W_N^e
+    const cx<T>* tw2;                // W_2N^e ((un)tangle)
+};
+
+template <typename T, class Ctx>
+OA_HD void band_rows_win_body(Ctx& c, const BandRowsWinArgs<T>& a) {
+    const int N = a.N, w = a.w;
+    cx<T>* b0 = reinterpret_cast<cx<T>*>(c.smem());
+    cx<T>* b1 = b0 + N + 1;
+    const int tid = c.tid(), NT = c.nthreads(), b = c.bid_y();
+    const long row = c.bid_x();
+    const cx<T>* src = a.in + b * a.in_bstride + row * a.in_pitch;
+    const cx<T>* wrow = reinterpret_cast<const cx<T>*>(a.win + row * 2 * (long)N);
+    // all loads of the row, back to back: N window pairs (kept in registers across the inverse transform), N + 1 spectrum columns
+    // (to LDS: nothing reads them before the barrier, so the loop's loads are issued together)
+    cx<T> wv[BRW_MAXQ];
+#pragma unroll
+    for (int q = 0; q < BRW_MAXQ; ++q) { const int n = tid + q * NT; wv[q] = n < N ? wrow[n] : mk<T>((T)0, (T)0); }
+#pragma unroll
+    for (int q = 0; q < BRW_MAXQ; ++q) { const int n = tid + q * NT; if (n < N) b1[n] = src[n]; }
+    if (tid == 0) b1[N] = src[N];
+    c.sync();
+    // C2R pre-twist (mr_row_body, MR_C2R): Z'[k] = (X[k] + conj X[N - k]) + i conj(W_2N^k) (X[k] - conj X[N - k]); the self-conjugate
+    // columns k = 0 and k = N keep their real part only; inverse as the forward transform of the swapped data
+    for (int k = tid; k < N; k += NT) {
+        cx<T> A = b1[k], B = b1[N - k];
+        if (k == 0) { A.y = (T)0; B.y = (T)0; }
+        const cx<T> z = (A + conj(B)) + mul_pi(conj(a.tw2[k]) * (A - conj(B)));
+        b0[k] = swp(z);
+    }
+    c.sync();
+    cx<T>* r = mr_transform<T>(c, b0, b1, N, a.f, 0, a.tw, tid, NT);
+    cx<T>* other = r == b0 ? b1 : b0;
+    // packed real row z[n] = x[2 n] + i x[2 n + 1] (the swapped result): x window x scale, in place -- a thread touches its own n only
+#pragma unroll
+    for (int q = 0; q < BRW_MAXQ; ++q) {
+        const int n = tid + q * NT;
+        if (n < N) { const cx<T> v = swp(r[n]); r[n] = mk<T>(v.x * (wv[q].x * a.scale), v.y * (wv[q].y * a.scale)); }
+    }
+    c.sync();
+    const cx<T>* z = mr_transform<T>(c, r, other, N, a.f, 0, a.tw, tid, NT);
+    cx<T>* dst = a.out + b * a.out_bstride + row * w;
+    for (int k = tid; k < w; k += NT) {
+        const cx<T> Zk = z[k == N ? 0 : k], Zm = conj(z[k == 0 ? 0 : N - k]);
         const cx<T> E = (Zk + Zm) * (T)0.5, O = mul_mi(Zk - Zm) * (T)0.5;
         dst[k] = E + a.tw2[k] * O;
     }

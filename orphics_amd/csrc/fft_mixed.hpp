@@ -211,6 +211,9 @@ struct MrRowArgs {
     const T* dlx;
     int dpow0, dcol_b;
     long out_zoff;
+    // MR_C2R with a REAL-SPACE WINDOW at the store (oa_fft_c2r_windowed on these sides): mul != nullptr -> a real plane of out_pitch reals
+    // per row that multiplies the stored value
+    const T* mul;
 };
 
 // one row per workgroup; IP: the in-place stages (one buffer of N values)
@@ -267,7 +270,12 @@ OA_HD void mr_row_body(Ctx& ctx, const MrRowArgs<T>& a) {
         }
         ctx.sync();
         const cx<T>* r = mr_run<T, IP>(ctx, b0, b1, N, a.f, 0, a.tw, tid, NT);
-        for (int n = tid; n < N; n += NT) dst[n] = swp(r[n]) * a.scale;
+        const cx<T>* mrow = a.mul ? reinterpret_cast<const cx<T>*>(a.mul + row * a.out_pitch) : nullptr;
+        for (int n = tid; n < N; n += NT) {
+            cx<T> v = swp(r[n]) * a.scale;
+            if (mrow) { const cx<T> m = mrow[n]; v = mk<T>(v.x * m.x, v.y * m.y); }
+            dst[n] = v;
+        }
     }
 }
 

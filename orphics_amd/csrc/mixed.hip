@@ -60,11 +60,11 @@ void mixed_release(oa_plan* p) {
 
 template <typename T>
 static int rows(oa_plan* p, int mode, const void* in, long ipitch, void* out, long opitch, int N, const void* tw, double scale, hipStream_t st,
-                const T* dlx = nullptr, int dpow0 = 0, int dcol_b = 0, int nz = 1, long out_zoff = 0) {
+                const T* dlx = nullptr, int dpow0 = 0, int dcol_b = 0, int nz = 1, long out_zoff = 0, const T* mul = nullptr) {
     MrRowArgs<T> a{};
     a.in = in; a.out = out; a.in_pitch = ipitch; a.out_pitch = opitch; a.N = N; a.f = mixed_factor(N);
     a.tw = (const cx<T>*)tw; a.tw2 = (const cx<T>*)p->mr_twx; a.scale = (T)scale; a.mode = mode;
-    a.dlx = dlx; a.dpow0 = dpow0; a.dcol_b = dcol_b; a.out_zoff = out_zoff;
+    a.dlx = dlx; a.dpow0 = dpow0; a.dcol_b = dcol_b; a.out_zoff = out_zoff; a.mul = mul;
     int rc = 0;
     if (mr_row_lds<T>(N) <= LDS_MAX) launch_go(rc, st, mr_row_kernel<T>, dim3(p->ny, nz), 256, mr_row_lds<T>(N), a);
     else if (mr_ip_fits(a.f, N, 0, MR_IP_NT)) launch_go(rc, st, mr_row_ip_kernel<T>, dim3(p->ny, nz), MR_IP_NT, (size_t)N * sizeof(cx<T>), a);
@@ -93,9 +93,9 @@ static int r2c_t(oa_plan* p, const void* real_in, void* hc_out, double scale, hi
     return cols<T>(p, hc_out, p->kp, hc_out, p->kp, p->nx / 2 + 1, false, scale, st);
 }
 template <typename T>
-static int c2r_t(oa_plan* p, const void* hc_in, void* real_out, double scale, hipStream_t st) {
+static int c2r_t(oa_plan* p, const void* hc_in, void* real_out, double scale, hipStream_t st, const void* window = nullptr) {
     if (int rc = cols<T>(p, hc_in, p->kp, p->scratch, p->kp, p->nx / 2 + 1, true, 1.0, st)) return rc;
-    return rows<T>(p, MR_C2R, p->scratch, p->kp, real_out, p->nx, p->nx / 2, p->mr_twxh, scale, st);
+    return rows<T>(p, MR_C2R, p->scratch, p->kp, real_out, p->nx, p->nx / 2, p->mr_twxh, scale, st, nullptr, 0, 0, 1, 0, (const T*)window);
 }
 template <typename T>
 static int c2c_t(oa_plan* p, const void* in, void* out, int inverse, double scale, hipStream_t st) {
@@ -137,6 +137,16 @@ int mixed_r2c(oa_plan* p, const void* real_in, void* hc_out, double scale, hipSt
 }
 int mixed_c2r(oa_plan* p, const void* hc_in, void* real_out, double scale, hipStream_t st) {
     return p->dtype == OA_F32 ? c2r_t<float>(p, hc_in, real_out, scale, st) : c2r_t<double>(p, hc_in, real_out, scale, st);
+}
+// oa_fft_c2r_windowed on these sides: the real-space window (ny x nx reals) multiplies the row pass's store
+int mixed_c2r_windowed(oa_plan* p, const void* hc_in, void* real_out, double scale, const void* window, hipStream_t st) {
+    return p->dtype == OA_F32 ? c2r_t<float>(p, hc_in, real_out, scale, st, window) : c2r_t<double>(p, hc_in, real_out, scale, st, window);
+}
+// the unscaled inverse column transform over the nx / 2 + 1 columns of an hc plane (the first half of mixed_c2r); may run in place: a
+// workgroup holds its whole column tile in LDS before it stores
+int mixed_cols_inverse(oa_plan* p, const void* hc_in, void* hc_out, hipStream_t st) {
+    return p->dtype == OA_F32 ? cols<float>(p, hc_in, p->kp, hc_out, p->kp, p->nx / 2 + 1, true, 1.0, st)
+                              : cols<double>(p, hc_in, p->kp, hc_out, p->kp, p->nx / 2 + 1, true, 1.0, st);
 }
 int mixed_c2c(oa_plan* p, const void* in, void* out, int inverse, double scale, hipStream_t st) {
     return p->dtype == OA_F32 ? c2c_t<float>(p, in, out, inverse, scale, st) : c2c_t<double>(p, in, out, inverse, scale, st);

@@ -77,6 +77,7 @@ struct Pipeline {
     bool opt_mv_chain = true;         // oa_qe_mv: estimator chains (pieces summed in real space inside one row-stage launch)
     bool opt_divbin = true;           // moment entries: radial binning + moments in the tail of the single-pass divergence launch
     bool opt_win_fused = true;        // oa_mc_run_windowed: C2R x window -> R2C as one row pass (the real map stays in LDS)
+    bool opt_win_fused_set = false;   // ... set by the caller (until then a band-grid plan picks by row length: mixed_mc_run_windowed)
     // BAND GRID (map sides 2^a 3^b 5^c, p->mixed; include/orphics_amd.h): the one-call TT entries run on an inner power-of-two plan of
     // (bmy, bmx) points that holds inner-layout copies of the filters and bin ids; made by oa_plan_set_filters / oa_plan_set_col_grid
     oa_plan* band = nullptr;
@@ -85,6 +86,11 @@ struct Pipeline {
     int32_t* bids = nullptr;          // inner-layout bin ids (-1 outside kappa's band)
     void* brows = nullptr;            // band input transform: row pass (ny x leg_cols complex) + column-pass partial sums
     size_t brows_bytes = 0;
+    // ... oa_mc_run_windowed there: MC_BATCH_MAX N-grid hc planes (the full-plane draws, inverse-column-transformed in place; plane 1
+    // holds the real map of the unfused flow) | the row planes and column partial sums of a batch (band_maps_scratch_bytes); taken on
+    // the first windowed call, regrown when the band widens
+    void* bwin = nullptr;
+    size_t bwin_bytes = 0;
     // ... oa_qe_tt_splits / oa_qe_tt_split_power there: bs_cap inner source planes (hc, zero outside the leg band) | the evenly spaced
     // (n, n, My, kp_inner) block of the inner kappa planes; allocated on first use, grown when a call brings more splits
     void* bsplit = nullptr;
@@ -151,6 +157,7 @@ void pipeline_release(oa_plan* p) {
     if (q->bplanes) (void)hipFree(q->bplanes);
     if (q->bids) (void)hipFree(q->bids);
     if (q->brows) (void)hipFree(q->brows);
+    if (q->bwin) (void)hipFree(q->bwin);
     if (q->bsplit) (void)hipFree(q->bsplit);
     if (q->bs_tab) (void)hipFree(q->bs_tab);
     if (q->pb.plan) (void)oa_plan_destroy(q->pb.plan);
@@ -268,6 +275,8 @@ static int mixed_qe_tt(oa_plan* p, Pipeline* q, const void* map, const void* kX,
 static int mixed_moments(oa_plan* p, Pipeline* q, const void* map, int64_t* n, double* S, double* C, hipStream_t st);
 static int mixed_mc_run(oa_plan* p, Pipeline* q, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, int64_t* n, double* S,
                         double* C, double* meanfield_acc, hipStream_t st);
+static int mixed_mc_run_windowed(oa_plan* p, Pipeline* q, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, const void* window,
+                                 int64_t* n, double* S, double* C, double* meanfield_acc, hipStream_t st);
 static void band_options(Pipeline* q);
 struct MvCall {            // the arguments of oa_qe_mv (oa_qe_pol: nest = 1 and pol set)
     int nest; const int* npieces; const double* signs; const void* const* FG; const void* const* FH; const int* swap;
@@ -326,7 +335,8 @@ int oa_plan_set_option(oa_plan* p, int option, int value) {
         case OA_OPT_MV_ROWBATCH: q->opt_mv_rowbatch = value != 0; return 0;
         case OA_OPT_MV_CHAIN: q->opt_mv_chain = value != 0; return 0;
         case OA_OPT_DIV_BIN: q->opt_divbin = value != 0; return 0;
-        case OA_OPT_WIN_FUSED: q->opt_win_fused = value != 0; return 0;
+        case OA_OPT_WIN_FUSED:                     // (< 0: back to the automatic choice of a band-grid plan; pow2 plans: the fused pass)
+            q->opt_win_fused = value != 0; q->opt_win_fused_set = value >= 0; return 0;
         default: return fail("oa_plan_set_option: unknown option");
     }
 }
@@ -408,8 +418,32 @@ int oa_plan_set_bins(oa_plan* p, const int32_t* ids_hc, int nids, double norm, v
     q->ids = ids_hc; q->nids = nids; q->norm = norm;
     ++q->bind_gen;
     // mode counts per bin over the WHOLE plane (the per-call binning visits only kappa's active region)
-    if (int rc = oa_bin_power(p->dtype, q->c[0], q->c[0], norm, ids_hc, nullptr, (long)p->ny * p->kp, nids, p->kp, p->nx / 2, q->sums,
-                              q->counts_full, nullptr, q->bin_scratch, 0, 0, stream)) return rc;
+    if (p->kp % 4 == 0) {
+        if (int rc = oa_bin_power(p->dtype, q->c[0], q->c[0], norm, ids_hc, nullptr, (long)p->ny * p->kp, nids, p->kp, p->nx / 2, q->sums,
+                                  q->counts_full, nullptr, q->bin_scratch, 0, 0, stream)) return rc;
+    } else {
+        // nx / 2 odd (750 -> kp = 391): oa_bin_power moves four columns per lane and refuses such a pitch; the counts are taken from
+        // copies padded to the next multiple of 4, the padding ignored (id -1) -- what Engine.bin_power does.  Set-up call: the
+        // temporaries are released after a stream synchronisation
+        const long kp4 = (p->kp + 3) / 4 * 4;
+        const size_t es = 2 * (p->dtype == OA_F32 ? 4 : 8);
+        int32_t* ids4 = nullptr;
+        void* z4 = nullptr;
+        OA_HIP(hipMalloc((void**)&ids4, (size_t)p->ny * kp4 * sizeof(int32_t)));
+        hipError_t e = hipMalloc(&z4, (size_t)p->ny * kp4 * es);
+        if (e == hipSuccess) e = hipMemsetAsync(ids4, 0xFF, (size_t)p->ny * kp4 * sizeof(int32_t), (hipStream_t)stream);
+        if (e == hipSuccess) e = hipMemsetAsync(z4, 0, (size_t)p->ny * kp4 * es, (hipStream_t)stream);
+        if (e == hipSuccess)
+            e = hipMemcpy2DAsync(ids4, kp4 * sizeof(int32_t), ids_hc, p->kp * sizeof(int32_t), p->kp * sizeof(int32_t), p->ny, hipMemcpyDeviceToDevice,
+                                 (hipStream_t)stream);
+        int rc = e == hipSuccess ? oa_bin_power(p->dtype, z4, z4, norm, ids4, nullptr, (long)p->ny * kp4, nids, kp4, p->nx / 2, q->sums, q->counts_full,
+                                                nullptr, q->bin_scratch, 0, 0, stream)
+                                 : fail(std::string("oa_plan_set_bins: padded bin ids: ") + hipGetErrorString(e));
+        (void)hipStreamSynchronize((hipStream_t)stream);
+        (void)hipFree(ids4);
+        if (z4) (void)hipFree(z4);
+        if (rc) return rc;
+    }
     if (p->mixed) return (q->FG && q->band) ? mixed_bins(p, q, (hipStream_t)stream) : 0;     // (else: when the filters are bound)
     return ensure_div_tables(p, q, (hipStream_t)stream);
 }
@@ -626,6 +660,8 @@ int oa_plan_release_pools(oa_plan* p) {
         Pipeline* qb = (Pipeline*)q->band->pipe;
         if (qb->split_legs) { (void)hipFree(qb->split_legs); qb->split_legs = nullptr; qb->split_bytes = 0; }
     }
+    // ... the draw planes and row planes of oa_mc_run_windowed there (retaken by the next windowed call)
+    if (q->bwin) { (void)hipFree(q->bwin); q->bwin = nullptr; q->bwin_bytes = 0; }
     // ... and the map-side scratch of oa_qe_mv_maps (retaken by the next from-maps call)
     if (q->pb.mrows) { (void)hipFree(q->pb.mrows); q->pb.mrows = nullptr; q->pb.mrows_bytes = 0; }
     // ... and the Monte-Carlo binding's pool: oa_mc_mv_band_bind makes it again
@@ -1158,6 +1194,7 @@ static int mixed_bind(oa_plan* p, Pipeline* q) {
         if (q->bplanes) { (void)hipFree(q->bplanes); q->bplanes = nullptr; }
         if (q->bids) { (void)hipFree(q->bids); q->bids = nullptr; }
         if (q->bsplit) { (void)hipFree(q->bsplit); q->bsplit = nullptr; q->bsplit_bytes = 0; q->bs_cap = 0; }     // (sized by the inner plane)
+        if (q->bwin) { (void)hipFree(q->bwin); q->bwin = nullptr; q->bwin_bytes = 0; }                            // (retaken by the next windowed call)
         q->bmy = q->bmx = 0;
         if (int rc = band_inner_plan(p, my, mx, &q->band)) return rc;
         OA_HIP(hipMalloc(&q->bplanes, 3 * band_real_bytes(q->band) + 2 * plane_bytes(q->band)));
@@ -1263,6 +1300,72 @@ static int mixed_mc_run(oa_plan* p, Pipeline* q, uint64_t base_seed, long sim_lo
     void* bx = band_in(q, 0);
     for (; i < sim_hi; ++i) {
         int rc = grf_band_inner(p, base_seed, (uint64_t)i, 1, covsqrt_hc, bx, b->ny, b->kp, 0, q->wl, q->rl, st);
+        if (rc) return rc;
+        if ((rc = qe_tt_impl(b, nullptr, bx, nullptr, nullptr, 0, st, nullptr))) return rc;
+        if ((rc = bandpower_moments(b, qb, n, S, C, st))) return rc;
+        if (meanfield_acc && (rc = band_stack_add(p->dtype, qb->kk, b->kp, b->ny, 1, 0, meanfield_acc, p->kp, p->ny, q->wk, q->rk, st))) return rc;
+    }
+    return 0;
+}
+// oa_mc_run_windowed: per realisation the full-plane draw on the N grid and its inverse column transform (in place); per batch ONE fused
+// windowed row launch (C2R x window -> R2C, columns < wl stored: band_rows_win_kernel) and the pruned column DFT onto the band plan's
+// source planes, then oa_mc_run's batched launches there.  OA_OPT_WIN_FUSED = 0: one by one, C2R with the window at the row store -> real
+// map in HBM -> band_map_r2c.
+static int mixed_mc_run_windowed(oa_plan* p, Pipeline* q, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, const void* window,
+                                 int64_t* n, double* S, double* C, double* meanfield_acc, hipStream_t st) {
+    oa_plan* b = q->band;
+    Pipeline* qb = (Pipeline*)b->pipe;
+    band_options(q);
+    const int BMAX = std::max(1, std::min(MC_BATCH_MAX, qb->opt_mc_batch));
+    const size_t pb = plane_bytes(p), es = 2 * (p->dtype == OA_F32 ? 4 : 8);
+    const long pbe = (long)(plane_bytes(b) / es), pne = (long)(pb / es);                // complex elements per band plane / per N-grid plane
+    // entry-owned planes, taken on the first windowed call (and regrown when the band widens): that call synchronises the device once
+    const size_t need = (size_t)MC_BATCH_MAX * pb + std::max(band_maps_scratch_bytes(p, MC_BATCH_MAX, q->wl, q->rl), band_map_scratch_bytes(p, q->wl, q->rl));
+    if (q->bwin_bytes < need) {
+        if (q->bwin) { OA_HIP(hipDeviceSynchronize()); (void)hipFree(q->bwin); q->bwin = nullptr; q->bwin_bytes = 0; }
+        OA_HIP(hipMalloc(&q->bwin, need));
+        q->bwin_bytes = need;
+    }
+    char* const draw = (char*)q->bwin;
+    void* const rows = draw + (size_t)MC_BATCH_MAX * pb;
+    const double inv = 1.0 / ((double)p->ny * p->nx);
+    long i = sim_lo;
+    // fused row pass or the unfused flow: the caller's OA_OPT_WIN_FUSED; until it is set, what measured faster (DESIGN 5a,
+    // profiles/band_grid_windowed.jsonl): the unfused flow at 1200^2 (by 1 % f32, 5 % f64), the fused pass at 2400^2 (by up to 1 %)
+    // (rows the fused kernel does not hold -- more than 8192 points -- take the unfused flow, whose row passes have an in-place form)
+    const bool fused = q->opt_win_fused_set ? q->opt_win_fused : (p->nx > 1200 && band_rows_win_ok(p));
+    // (an inner plan whose row stage takes one map per launch -- row grids below 1024 points -- abandons its first batch of every call
+    // after the front end has run: about 1 % of a 300-realisation call)
+    bool batched = fused;
+    while (batched && i < sim_hi) {
+        const int B = (int)std::min<long>(BMAX, sim_hi - i);
+        if (int rc = ensure_mc_src(b, qb)) return rc;                            // (taken by oa_plan_set_bins: no allocation here)
+        if (int rc = ensure_pool(qb, mc_pool_bytes(b, qb, B))) return rc;
+        int rc = 0;
+        for (int k = 0; k < B; ++k) {
+            void* pl = draw + (size_t)k * pb;
+            if ((rc = oa_grf_hc(p, base_seed, (uint64_t)(i + k), covsqrt_hc, pl, st))) return rc;
+            if ((rc = mixed_cols_inverse(p, pl, pl, st))) return rc;
+        }
+        if ((rc = band_win_r2c(p, B, draw, pne, window, inv, rows, 0, q->wl, q->rl, qb->mc_src, pbe, b->ny, b->kp, st))) return rc;
+        int fallback = 0;
+        if ((rc = mc_batch_tail(b, qb, B, n, S, C, nullptr, st, &fallback, meanfield_acc != nullptr))) return rc;
+        if (fallback) { batched = false; break; }
+        if (meanfield_acc && (rc = band_stack_add(p->dtype, qb->c[0], b->kp, b->ny, B, pbe, meanfield_acc, p->kp, p->ny, q->wk, q->rk, st))) return rc;
+        i += B;
+    }
+    void* bx = band_in(q, 0);
+    for (; i < sim_hi; ++i) {
+        int rc = oa_grf_hc(p, base_seed, (uint64_t)i, covsqrt_hc, draw, st);
+        if (rc) return rc;
+        if (fused) {
+            if ((rc = mixed_cols_inverse(p, draw, draw, st))) return rc;
+            rc = band_win_r2c(p, 1, draw, pne, window, inv, rows, 1, q->wl, q->rl, bx, 0, b->ny, b->kp, st);
+        } else {
+            void* tmap = draw + pb;                                              // ny x nx reals fit an hc plane
+            if ((rc = oa_fft_c2r_windowed(p, draw, tmap, inv, window, st))) return rc;
+            rc = band_map_r2c(p, tmap, rows, q->wl, q->rl, bx, b->ny, b->kp, st);
+        }
         if (rc) return rc;
         if ((rc = qe_tt_impl(b, nullptr, bx, nullptr, nullptr, 0, st, nullptr))) return rc;
         if ((rc = bandpower_moments(b, qb, n, S, C, st))) return rc;
@@ -1768,10 +1871,17 @@ int oa_mc_run_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const
  * row pass has consumed the map. */
 int oa_mc_run_windowed(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, const void* window_real,
                        int64_t* n, double* S, double* C, double* meanfield_acc, void* stream) {
-    OA_REQUIRE(p && p->pipe && ((Pipeline*)p->pipe)->FG && ((Pipeline*)p->pipe)->ids, "oa_mc_run_windowed: call oa_plan_set_filters and oa_plan_set_bins first");
+    OA_REQUIRE(p, "oa_mc_run_windowed: NULL plan");
+    OA_REQUIRE(p->pow2 || p->mixed, "oa_mc_run_windowed: map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call "
+               "path; run the host loop of the existing entries (mc.GaussianN0MonteCarlo with one_call=False: Engine.grf_hc, Engine.irfft, "
+               "x window, Estimator.tt_moments)");
+    OA_REQUIRE(p->pipe && ((Pipeline*)p->pipe)->FG && ((Pipeline*)p->pipe)->ids, "oa_mc_run_windowed: call oa_plan_set_filters and oa_plan_set_bins first");
     OA_REQUIRE(covsqrt_hc && window_real && n && S && C && sim_hi >= sim_lo, "oa_mc_run_windowed: bad argument");
-    OA_NEED_POW2(p, "oa_mc_run_windowed");
     Pipeline* q = (Pipeline*)p->pipe;
+    if (p->mixed) {
+        OA_REQUIRE(q->band && q->band->pipe, "oa_mc_run_windowed: the bound filters have no band grid on this plan (oa_plan_set_filters reports why)");
+        return mixed_mc_run_windowed(p, q, base_seed, sim_lo, sim_hi, covsqrt_hc, window_real, n, S, C, meanfield_acc, (hipStream_t)stream);
+    }
     void* tmap = q->c[0];
     const double inv = 1.0 / ((double)p->ny * p->nx);
     const long pl = work_pitch(p, q->wl);

@@ -33,7 +33,8 @@ class GaussianN0MonteCarlo(object):
     C_l^TT B_l^2 + N_l, generated on the device in harmonic space
     (MapGen semantics, maps.py:1576-1587, with the Philox stream (base_seed, sim index))."""
 
-    def __init__(self, qest, total_power_half, bin_edges, comm=None, base_seed=1234, mean_field=False, streams=1, window=None):
+    def __init__(self, qest, total_power_half, bin_edges, comm=None, base_seed=1234, mean_field=False, streams=1, window=None,
+                 one_call=None):
         """qest: lensing.Estimator; total_power_half: (Ny, Nx/2+1) host array of the
         observed-map power (C B^2 + N); bin_edges: kappa bandpower edges.
         window: (Ny, Nx) real-space apodisation (``maps.get_taper(shape, ...)[0]``) applied to every realisation before
@@ -43,7 +44,14 @@ class GaussianN0MonteCarlo(object):
         map) carry a factor mean(w^4) that the caller divides out (``debiased_mean``).
         streams > 1: this rank's simulations are split into that many contiguous blocks, each issued on its own HIP
         stream through a forked estimator handle (private plan and accumulators, summed at the end): the small
-        latency-bound launches of independent realisations overlap."""
+        latency-bound launches of independent realisations overlap.
+        one_call (with a window): None (default) = ``oa_mc_run_windowed`` on power-of-two sides, a refusal elsewhere.
+        ``one_call=True`` opts in to that call on sides 2^a 3^b 5^c as well: it runs on the estimator's band grid
+        (``qest.one_call()``) and raises where there is none (chirp-z sides, unbounded filters, a band grid not smaller than
+        the map).  ``one_call=False`` runs a host loop of the existing entries on any side, with the same seeds and
+        Philox stream ids, on ONE HIP stream (``streams`` is not used there): ``Engine.grf_hc`` -> ``Engine.irfft`` -> x window -> ``Estimator.tt_moments`` (+ ``reconstruct_tt_from_map``
+        into the mean-field stack); where the estimator has no one-call path at all, the modular reconstruction,
+        ``Engine.bin_power`` and ``Statistics.add``."""
         torch = _torch()
         self.streams = max(1, int(streams))
         self.q = qest
@@ -66,10 +74,18 @@ class GaussianN0MonteCarlo(object):
         qest.bind_bins(self.ids, self.nids, self.norm)
         self.window = None
         self.window_moments = (1.0, 1.0)
-        if window is not None and not e.pow2:
+        self.one_call = None if one_call is None else bool(one_call)
+        if window is not None and not e.pow2 and self.one_call is None:
             from ._lib import OrphicsAmdError
             raise OrphicsAmdError("GaussianN0MonteCarlo: a window needs power-of-two map sides (oa_mc_run_windowed); %dx%d runs "
-                                  "oa_mc_run on its band grid without a window only" % (e.ny, e.nx))
+                                  "oa_mc_run on its band grid without a window only by default -- construct the driver with one_call=True "
+                                  "(oa_mc_run_windowed on the band grid of sides 2^a 3^b 5^c) or one_call=False (host loop of the "
+                                  "existing entries, any side)" % (e.ny, e.nx))
+        if window is not None and not e.pow2 and self.one_call and not qest.one_call():
+            from ._lib import OrphicsAmdError
+            raise OrphicsAmdError("GaussianN0MonteCarlo: no one-call path on this %d x %d geometry (chirp-z sides, unbounded filters or a "
+                                  "band grid not smaller than the map): construct the driver with one_call=False" % (e.ny, e.nx))
+        self._host = None
         if window is not None:
             w = np.asarray(window, dtype=np.float64)
             if w.shape != (e.ny, e.nx):
@@ -86,6 +102,8 @@ class GaussianN0MonteCarlo(object):
         if not sims:
             return self
         q = self.q
+        if self.window is not None and self.one_call is False:
+            return self._run_host(sims)
         # (re)bind THIS driver's bins: another driver -- or a direct bind_bins call -- may have given the shared estimator
         # other edges since __init__, and the accumulators below are sized for self.d
         q.bind_bins(self.ids, self.nids, self.norm)
@@ -117,6 +135,46 @@ class GaussianN0MonteCarlo(object):
             for lo, hi in blocks:
                 check(e.lib.oa_mc_run(e.plan, self.base_seed, lo, hi, _ptr(self.cs), _ptr(n), _ptr(S), _ptr(C), _ptr(mf), _stream()))
         self.acc.note_samples("n0", len(sims))
+        if self.mean_field:
+            self.acc.note_stacked("mf", len(sims))
+        return self
+
+    def _run_host(self, sims):
+        """The windowed realisations ``sims`` through the existing entries, one by one (``one_call=False``): the full-plane draw of
+        ``oa_mc_run_windowed`` (same seed and stream), ``Engine.irfft``, x window, then ``tt_moments`` -- or, where the estimator has no
+        one-call path, the modular reconstruction, ``Engine.bin_power`` over kappa's band and ``Statistics.add``."""
+        torch = _torch()
+        q, e = self.q, self.eng
+        sup = (q.kappa_rows, q.kappa_cols) if (q.kappa_cols and q.kappa_rows) else None
+        mf = self.acc.device_stack("mf", (e.ny, e.kp, 2), support=sup) if self.mean_field else None
+        fused = q.one_call()
+        if self._host is None:
+            cnt = None
+            if not fused:     # data-independent mode counts per bin over the whole half plane
+                zero = e.hc()
+                cnt = e.bin_power(zero, zero, self.norm, self.ids, self.nids, herm=True)[1][1:-1].double()
+            self._host = (e.hc(), e.real(), q.new_output(), cnt)
+        draw, tmap, out, cnt = self._host
+        if fused:
+            q.bind_bins(self.ids, self.nids, self.norm)
+            n, S, C = self.acc.device_moments("n0", self.d)
+        for i in sims:
+            e.grf_hc(self.base_seed, i, self.cs, out=draw)
+            e.irfft(draw, out=tmap)
+            tmap.mul_(self.window)
+            kap = None
+            if fused:
+                q.tt_moments(tmap, n, S, C)
+            else:
+                kap = q.reconstruct_tt_from_map(tmap, out=out)
+                s, _ = e.bin_power(kap, kap, self.norm, self.ids, self.nids, herm=True, active_cols=q.kappa_cols, active_rows=q.kappa_rows)
+                self.acc.add("n0", s[1:-1] / cnt)
+            if mf is not None:
+                if kap is None:
+                    kap = q.reconstruct_tt_from_map(tmap, out=out)
+                mf += torch.view_as_real(kap).to(torch.float64)
+        if fused:
+            self.acc.note_samples("n0", len(sims))
         if self.mean_field:
             self.acc.note_stacked("mf", len(sims))
         return self

@@ -20,7 +20,12 @@ modular chain on the same plan, on the reference notebooks' patches (tutorials/t
     without the entry: Engine.rfft of T, Q, U (EB: of Q, U only) into resident planes, rot2, reconstruct_mv_hc / reconstruct_hc -- in one
     process on the same plan and maps, the two paths ALTERNATED block by block after a warm-up of every shape.  Per cell the median and
     the 10th .. 90th percentile of --reps blocks of --iters calls (HIP events; the issue's setting: --reps 50 --iters 10) and the maximum
-    relative difference of the two outputs.  --precs picks the precisions; with --only-onecall N: N calls of path (a) and nothing else."""
+    relative difference of the two outputs.  --precs picks the precisions; with --only-onecall N: N calls of path (a) and nothing else.
+--windowed: the windowed N0 / mean-field Monte Carlo, GaussianN0MonteCarlo(window=taper, mean_field=True): one_call=True (oa_mc_run_windowed
+    on the band grid) with the fused row pass (win_fused = 1) and with the unfused flow (win_fused = 0), against the one_call=False host loop
+    of existing entries on the same plan -- the three paths ALTERNATED block by block in one process after a warm-up of each.  A block is
+    --sims realisations (host loop: --loop-sims); per path the median and the 10th .. 90th percentile of --reps blocks, in sims/s.
+    --out appends the raw lines to a file.  With --only-onecall N: N realisations of the fused one call per cell and nothing else."""
 import argparse
 import json
 import os
@@ -118,15 +123,17 @@ def main_pol(args):
                                       max_rel_diff=diff)), flush=True)
 
 
-def timed_alternating(fa, fb, iters, reps):
-    """blocks of `iters` calls of fa and of fb in turn: (median, p10, p90) ms per call of each"""
+def timed_alternating(fa, fb, iters, reps, *more):
+    """blocks of `iters` calls of fa, of fb (and of every further function) in turn: (median, p10, p90) ms per call of each"""
     import torch
+    fns = (fa, fb) + tuple(more)
     for _ in range(3):
-        fa(); fb()
+        for fn in fns:
+            fn()
     torch.cuda.synchronize()
-    out = ([], [])
+    out = tuple([] for _ in fns)
     for _ in range(reps):
-        for fn, acc in ((fa, out[0]), (fb, out[1])):
+        for fn, acc in zip(fns, out):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
             for _ in range(iters):
@@ -186,6 +193,53 @@ def main_frommaps(args):
                               frommaps_p10_p90=[round(ta[1], 4), round(ta[2], 4)], transforms_ms=round(tb[0], 4),
                               transforms_p10_p90=[round(tb[1], 4), round(tb[2], 4)], speedup=round(tb[0] / ta[0], 2), max_rel_diff=diff)),
               flush=True)
+
+
+def main_windowed(args):
+    import torch
+    from orphics_amd import maps, mc
+    edges = np.linspace(100, 3000, 12)
+    lines = []
+    for n in [int(s) for s in args.sides.split(",")]:
+        for prec in args.precs.split(","):
+            q, _, tot_h = setup(n, 0.5, prec)
+            e = q.eng
+            taper, _ = maps.get_taper((n, n), q.geom, taper_percent=12.0, pad_percent=3.0)
+            kw = dict(base_seed=3, mean_field=True, window=taper)
+            one = mc.GaussianN0MonteCarlo(q, tot_h, edges, one_call=True, **kw)
+            host = mc.GaussianN0MonteCarlo(q, tot_h, edges, one_call=False, **kw)
+            state = {"lo": 1000}
+
+            def block(drv, fused, count):
+                e.set_option("win_fused", fused)
+                drv.run_local(range(state["lo"], state["lo"] + count))
+                state["lo"] += count
+            if args.only_onecall:
+                block(one, 1, args.only_onecall)
+                torch.cuda.synchronize()
+                continue
+            # one "call" of timed_alternating is a block of realisations (the drivers bind their own bin ids when they take turns: a
+            # set-up launch per block, inside the timed window of each path alike)
+            names = ("onecall_fused", "onecall_unfused", "host_loop")
+            counts = (args.sims, args.sims, args.loop_sims)
+            ms = timed_alternating(lambda: block(one, 1, args.sims), lambda: block(one, 0, args.sims), 1, args.reps,
+                                   lambda: block(host, 1, args.loop_sims))
+            rates = {name: [c / (t / 1e3) for t in (m[0], m[2], m[1])] for name, c, m in zip(names, counts, ms)}      # median, p10, p90 of the rate
+            e.set_option("win_fused", -1)
+            rec = dict(side=n, prec=prec, call="windowed_n0_mean_field", band_grid=list(q.band_grid), reps=args.reps, sims_per_block=args.sims,
+                       loop_sims_per_block=args.loop_sims)
+            for name, r in rates.items():
+                rec[name + "_sims_per_s"] = round(r[0], 1)
+                rec[name + "_p10_p90"] = [round(r[1], 1), round(r[2], 1)]
+            rec["speedup_vs_host_loop"] = round(rec["onecall_fused_sims_per_s"] / rec["host_loop_sims_per_s"], 2)
+            rec["fused_vs_unfused"] = round(rec["onecall_fused_sims_per_s"] / rec["onecall_unfused_sims_per_s"], 3)
+            line = json.dumps(rec)
+            print(line, flush=True)
+            lines.append(line)
+            e.release_pools()
+    if args.out and lines:
+        with open(args.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
 
 
 class _Duck(object):
@@ -254,6 +308,9 @@ def main():
     ap.add_argument("--loop-iters", type=int, default=3)
     ap.add_argument("--from-maps", action="store_true")
     ap.add_argument("--precs", default="f32,f64")
+    ap.add_argument("--windowed", action="store_true")
+    ap.add_argument("--loop-sims", type=int, default=60)
+    ap.add_argument("--out", default="")
     args = ap.parse_args()
     import torch
     from orphics_amd import mc
@@ -264,6 +321,8 @@ def main():
         return main_splits(args)
     if args.from_maps:
         return main_frommaps(args)
+    if args.windowed:
+        return main_windowed(args)
     for n in [int(s) for s in args.sides.split(",")]:
         for prec in ("f32", "f64"):
             q, tmap, tot_h = setup(n, 0.5, prec)
