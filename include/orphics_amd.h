@@ -43,7 +43,7 @@ typedef struct oa_plan oa_plan;
 const char* oa_last_error(void);
 /* ABI version = 100 x the build round that last changed a signature in this header; bindings must refuse a library
  * that reports less than the version they were written against (OA_ABI_VERSION) */
-#define OA_ABI_VERSION 408
+#define OA_ABI_VERSION 409
 int oa_version(void);
 /* number of HIP devices visible; <0 on error (no compute) */
 int oa_device_count(void);
@@ -207,7 +207,7 @@ int oa_plan_col_grid(const oa_plan* p);
  * leg rows), the Monte-Carlo draw (the leg band of oa_grf_hc's N-grid draw, same Philox counters) and the scatter of kappa's band
  * into the N-grid output / mean-field stack see the map's grid.  oa_qe_tt_splits runs there too, and oa_qe_tt_split_power is the
  * split-based estimator evaluated on the inner grid (both below, at their declarations); oa_mc_run_windowed runs there behind a
- * full-plane N-grid front end (at its declaration); oa_qe_tt_stage stays power-of-two only.  oa_plan_band_grid reports (My, Mx), or (0, 0) when no band grid is bound.
+ * full-plane N-grid front end (at its declaration); oa_qe_tt_stage and oa_mc_run_mv_windowed stay power-of-two only.  oa_plan_band_grid reports (My, Mx), or (0, 0) when no band grid is bound.
  * oa_qe_pol / oa_qe_mv ON A BAND GRID.  The band-limit argument does not depend on the estimator (every separable piece is a product of
  * fields confined to the leg band; the cos / sin 2 phi_ell factors live on the same ell lattice, so a copy of their band is exact), but
  * these two entries take their planes per call, and a stream-ordered call may neither allocate nor synchronise.  oa_qe_band_bind is
@@ -254,7 +254,7 @@ int oa_plan_div_fused(const oa_plan* p);
  *                      (default 1); 0: the k-th piece of every estimator per launch, accumulated in Fourier space
  *   OA_OPT_DIV_BIN     moment entries: radial binning + moment update in the tail of the single-pass divergence launch
  *                      (default 1, where the geometry has that kernel: oa_plan_div_fused); 0: the separate histogram launches
- *   OA_OPT_WIN_FUSED   oa_mc_run_windowed: inverse columns, then C2R x window -> R2C of every row in ONE kernel (default 1: the
+ *   OA_OPT_WIN_FUSED   oa_mc_run_windowed, oa_mc_run_mv_windowed: inverse columns, then C2R x window -> R2C of every row in ONE kernel (default 1: the
  *                      real map exists in LDS only); 0: C2R with the window at its store, real map in HBM, from-map estimator path
  *                      (sides 2^a 3^b 5^c: the band input transform; until the option is set, or after a value < 0, such a plan takes
  *                      what measured faster: the unfused flow for rows of up to 1200 points, the fused pass for longer ones up to
@@ -392,6 +392,38 @@ int oa_mc_run_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const
                  const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights, long mv_wstride, int nspec, const int* host_a,
                  const int* host_b, const int32_t* ids_hc, int nids, const int64_t* counts, double norm, int leg_cols, int kappa_cols,
                  int leg_rows, int kappa_rows, int mrow, int64_t* n, double* S, double* C, void* stream);
+/* oa_mc_run_mv_windowed: oa_mc_run_mv with a real-space window on the T, Q, U maps of every realisation and with the mean-field stacks of the
+ * estimator set.  The arguments are oa_mc_run_mv's, plus
+ *   window_real     ny x nx reals of the plan's dtype (the apodisation every map is multiplied by before its transform), or NULL;
+ *   rot_c, rot_s    (ny, kpitch) hc-real planes cos / sin 2 phi_l, as oa_qe_mv_maps takes them (needed with a window);
+ *   host_meanfield  NULL, or a host array of nest (+ 1 when mv_weights is given) device float64 planes (ny, kpitch, 2): the sums of the
+ *                   per-estimator kappa_hat in estimator order, then of the MV combination sum_e w_e kappa_hat_e.
+ * POWER-OF-TWO PLANS ONLY: a 2^a 3^b 5^c or chirp-z plan is refused before anything is launched (n, S, C and the stacks untouched), naming
+ * this entry and the host loop mc.GaussianN0MonteCarloPol runs with one_call=False.
+ * The window multiplies Q and U, not E and B: a taper leaks E into B.  Per realisation i, stream-ordered, nothing leaving the device:
+ * without a window, step 1 is oa_mc_run_mv's band draw (the moments are then oa_mc_run_mv's bit for bit); with one it is
+ *   a. the full-plane oa_grf_mix draw of T, E, B (streams 3 i .. 3 i + 2: the counters of the band draw, so window == 1 reproduces the
+ *      unwindowed run to rounding) rotated to T, Q, U in the same pass by the inverse of oa_rot2's combination, Q = E c + B s,
+ *      U = -E s + B c, into three hc planes the entry owns;
+ *   b. one batched inverse column launch over the three planes, then ONE fused row launch over them (C2R / Npix -> x window -> R2C per row,
+ *      the real rows in LDS only, the window shared by the planes): leg_cols columns stored at the compact pitch;
+ *   c. one batched forward column launch onto the leg band of the three source planes of oa_mc_run_mv's loop;
+ *   d. Q, U -> E, B (oa_rot2's combination) on the leg band only -- rows |ky| < leg_rows, columns < leg_cols --, c and s read from the
+ *      caller's planes, arithmetic in double before the one rounding.
+ * The real maps never exist in HBM.  oa_plan_set_option(p, OA_OPT_WIN_FUSED, 0): per plane oa_fft_c2r_windowed -> real map in HBM ->
+ * oa_fft_r2c(width = leg_cols, rband = leg_rows), then d. (the A/B path, as for oa_mc_run_windowed).  Steps 2-4 are oa_mc_run_mv's.  With
+ * host_meanfield one more launch per realisation: a thread owns one mode of kappa's band (kappa_cols, kappa_rows), loads the nest kappa_hat
+ * values once, adds each into its stack and the weighted sum, formed in registers, into the MV stack (no atomics: deterministic).
+ * Realisation i's contribution to n, S, C and the stacks does not depend on how a range is cut into calls.  The entry's planes (three draw
+ * planes, one column temporary per plane, the compact row planes) are taken by the first windowed call, which synchronises the device
+ * once; oa_plan_release_pools frees them.  Refused before anything is launched: a window without rot_c / rot_s, a NULL stack plane, and
+ * every refusal of oa_mc_run_mv. */
+int oa_mc_run_mv_windowed(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest,
+                          const int* host_npieces, const double* host_signs, const void* const* host_FG, const void* const* host_FH,
+                          const int* host_swap, const int* host_xsrc, const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights,
+                          long mv_wstride, int nspec, const int* host_a, const int* host_b, const int32_t* ids_hc, int nids, const int64_t* counts,
+                          double norm, int leg_cols, int kappa_cols, int leg_rows, int kappa_rows, int mrow, const void* window_real,
+                          const void* rot_c, const void* rot_s, int64_t* n, double* S, double* C, double* const* host_meanfield, void* stream);
 /* One stage of oa_qe_tt_moments on the plan's own work planes, for per-kernel timing (bench.py roofline; the
  * one-call path keeps its intermediates on COMPACT planes -- pitch = active columns rounded up to a 32-column tile
  * -- so its kernels are not the same launches as the fine-grained calls on caller planes of pitch kpitch):

@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("ORPHICS_AMD_LIB", os.path.join(_HERE, "liborphics_amd
 
 OA_F32 = 0
 OA_F64 = 1
-ABI_VERSION = 408     # include/orphics_amd.h OA_ABI_VERSION: the signatures below are those of this version
+ABI_VERSION = 409     # include/orphics_amd.h OA_ABI_VERSION: the signatures below are those of this version
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
@@ -71,6 +71,9 @@ SIGNATURES = {
     "oa_mc_run_windowed": (c_int, [c_void_p, c_u64, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "oa_mc_run_mv": (c_int, [c_void_p, c_u64, c_long, c_long, c_void_p, c_int] + [c_void_p] * 9 + [c_long, c_int, c_void_p, c_void_p, c_void_p, c_int,
                              c_void_p, c_double] + [c_int] * 5 + [c_void_p] * 4),
+    # oa_mc_run_mv's arguments + (window_real, rot_c, rot_s) behind mrow and host_meanfield in front of the stream; power-of-two plans only
+    "oa_mc_run_mv_windowed": (c_int, [c_void_p, c_u64, c_long, c_long, c_void_p, c_int] + [c_void_p] * 9 + [c_long, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_int, c_void_p, c_double] + [c_int] * 5 + [c_void_p] * 8),
     "oa_mc_mv_band_bind": (c_int, [c_void_p, c_void_p, c_long, c_int, c_void_p, c_int, c_int]),
     "oa_malloc": (c_int, [ctypes.POINTER(c_void_p), ctypes.c_size_t]),
     "oa_free": (c_int, [c_void_p]),

@@ -118,6 +118,14 @@ int bin_power_moments(int dtype, const void* k, double norm, const int32_t* ids,
                       int64_t* counts, void* scratch, int active_cols, int active_rows, unsigned* ticket,
                       const int64_t* mcounts, int64_t* mn, double* S, double* C, hipStream_t st, int nbatch = 1, long kstride = 0);
 int stack_add_region(int dtype, const void* x, double* acc, int ny, long kp, int w, int rb, hipStream_t st, int nbatch = 1, long xstride = 0);
+// oa_mc_run_mv_windowed (mc_pol.hpp, elementwise.hip; rng.hip): Q, U -> E, B in place on the leg band of two hc planes by the caller's
+// (ny, kp) cos / sin planes; the nest kappa_hat planes of an estimator set (kstride complex elements apart) added into nest float64 stacks
+// and -- acc_mv -- their weighted sum into one more, over kappa's band; the full-plane T, E, B draw rotated to T, Q, U in the same pass
+int band_rot2(int dtype, const void* c, const void* s, void* q, void* u, int ny, long kp, int w, int rb, hipStream_t st);
+int stack_add_region_multi(int dtype, const void* k, long kstride, const void* wt, long wstride, int nest, double* const* acc, double* acc_mv,
+                           int ny, long kp, int w, int rb, hipStream_t st);
+int grf_mix_teb_to_tqu(oa_plan* p, uint64_t seed, uint64_t sid0, const void* const* cs, const void* rot_c, const void* rot_s, void* const* out,
+                       hipStream_t st);
 // my > 0: COLUMN GRID -- legs, row stage and divergence run on my < ny rows (plan_ensure_col_grid(p, my) first)
 int plan_ensure_col_grid(oa_plan* p, int my);
 // lr > 0 (qe_rsplit_lr): R-SPLIT path -- row R2C with the first radix-R column butterfly, then one single-pass column kernel;
@@ -140,8 +148,10 @@ int qe_lens_derivs_w(oa_plan* p, int nmaps, const void* real_in, long in_stride,
                      const void* hc_in = nullptr, long hc_stride = 0, double hc_scale = 1.0);
 // windowed simulation front end: hc spectrum -> inverse columns -> fused C2R x window -> R2C rows onto the plan's scratch plane
 // (then qe_map_legs_cols_w with stages = 6, lr = 0)
+// nz > 0: that many spectra per launch (one batched inverse column launch, one row launch with grid y = plane; the window is shared):
+// plane z of hc_in and of cols_tmp sits z * in_moff, its row-transformed plane z * out_moff complex elements behind the first
 int qe_windowed_rows_w(oa_plan* p, const void* hc_in, void* cols_tmp, const void* window, int width, long pl, double scale, hipStream_t st,
-                       void* out = nullptr);
+                       void* out = nullptr, int nz = 0, long in_moff = 0, long out_moff = 0);
 int qe_fwd_cols_batch_w(oa_plan* p, const void* in, long pin, void* out, int B, long in_moff, long out_moff, int width, int rband, hipStream_t st);
 // one filtered field (subset 1: H plane into a; 2: gradient pair into a, b), inverse pass 1 only; then pass 2 over a pool of planes
 int qe_legs_subset_w(oa_plan* p, const void* src, const void* F, void* a, void* b, int subset, int width, int rband, long pl,

@@ -3,6 +3,7 @@
 // All are streaming kernels: 16-byte vector accesses, grid-stride, no LDS.
 #include "common.hpp"
 #include "split_power.hpp"
+#include "mc_pol.hpp"
 
 namespace oa {
 
@@ -410,6 +411,57 @@ int sum_region(int dtype, const void* parts, long part_stride, int nparts, void*
         hipLaunchKernelGGL(sum_region_kernel<double>, grid, dim3(256), 0, st, (const cx<double>*)parts, part_stride, nparts, (cx<double>*)out, accumulate, ny, kp, w, rb);
     OA_LAUNCH_CHECK();
     return 0;
+}
+// oa_mc_run_mv_windowed (mc_pol.hpp): one thread per mode of a band, grid y = band row
+struct ModeCtx {
+    OA_D int tid() const { return threadIdx.x; }
+    OA_D int nthreads() const { return blockDim.x; }
+    OA_D int bid_x() const { return blockIdx.x; }
+    OA_D int bid_y() const { return blockIdx.y; }
+};
+template <typename T>
+__global__ __launch_bounds__(256) void band_rot2_kernel(BandRotArgs<T> a) {
+    ModeCtx c;
+    band_rot2_body<T>(c, a);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void stack_add_region_multi_kernel(StackMultiArgs<T> a) {
+    ModeCtx c;
+    stack_add_region_multi_body<T>(c, a);
+}
+template <typename T>
+static int band_rot2_t(const void* c, const void* s, void* q, void* u, int ny, long kp, int w, int rb, hipStream_t st) {
+    BandRotArgs<T> a{(const T*)c, (const T*)s, (cx<T>*)q, (cx<T>*)u, kp, ny, w, rb};
+    hipLaunchKernelGGL(band_rot2_kernel<T>, dim3((w + 255) / 256, rb ? 2 * rb - 1 : ny), dim3(256), 0, st, a);
+    OA_LAUNCH_CHECK();
+    return 0;
+}
+int band_rot2(int dtype, const void* c, const void* s, void* q, void* u, int ny, long kp, int w, int rb, hipStream_t st) {
+    OA_REQUIRE(c && s && q && u && ny > 0 && kp > 0, "band_rot2: bad argument");
+    if (w <= 0 || w > kp) w = (int)kp;
+    if (!(rb > 0 && 2L * rb - 1 < ny)) rb = 0;
+    return dtype == OA_F32 ? band_rot2_t<float>(c, s, q, u, ny, kp, w, rb, st) : band_rot2_t<double>(c, s, q, u, ny, kp, w, rb, st);
+}
+template <typename T>
+static int stack_multi_t(const void* k, long kstride, const void* wt, long wstride, int nest, double* const* acc, double* acc_mv, int ny, long kp,
+                         int w, int rb, hipStream_t st) {
+    StackMultiArgs<T> a{};
+    a.k = (const cx<T>*)k; a.kstride = kstride; a.wt = acc_mv ? (const T*)wt : nullptr; a.wstride = wstride;
+    for (int e = 0; e < nest; ++e) a.acc[e] = (cx<double>*)acc[e];
+    a.acc_mv = (cx<double>*)acc_mv;
+    a.pitch = kp; a.nest = nest; a.ny = ny; a.w = w; a.rb = rb;
+    hipLaunchKernelGGL(stack_add_region_multi_kernel<T>, dim3((w + 255) / 256, rb ? 2 * rb - 1 : ny), dim3(256), 0, st, a);
+    OA_LAUNCH_CHECK();
+    return 0;
+}
+// acc: nest host-side pointers to device float64 (ny, kp, 2) planes; acc_mv: the MV stack, or nullptr (then wt is not read)
+int stack_add_region_multi(int dtype, const void* k, long kstride, const void* wt, long wstride, int nest, double* const* acc, double* acc_mv,
+                           int ny, long kp, int w, int rb, hipStream_t st) {
+    OA_REQUIRE(k && acc && nest >= 1 && nest <= STACK_MULTI_MAX && (!acc_mv || wt), "stack_add_region_multi: bad argument");
+    if (w <= 0 || w > kp) w = (int)kp;
+    if (!(rb > 0 && 2L * rb - 1 < ny)) rb = 0;
+    return dtype == OA_F32 ? stack_multi_t<float>(k, kstride, wt, wstride, nest, acc, acc_mv, ny, kp, w, rb, st)
+                           : stack_multi_t<double>(k, kstride, wt, wstride, nest, acc, acc_mv, ny, kp, w, rb, st);
 }
 // mean-field stack of the one-call Monte-Carlo driver (pipeline.hip)
 int stack_add_region(int dtype, const void* x, double* acc, int ny, long kp, int w, int rb, hipStream_t st, int nbatch, long xstride) {

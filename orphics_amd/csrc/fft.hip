@@ -941,19 +941,21 @@ int qe_map_legs_cols_w(oa_plan* p, const void* map, const void* FG, const void* 
 // there, so the caller continues with stages 2 | 4.  The real map never exists in HBM.
 template <typename T>
 static int windowed_rows_impl(oa_plan* p, const void* hc_in, void* cols_tmp, const void* window, int width, long pl, double scale, hipStream_t st,
-                              void* out) {
+                              void* out, int nz, long in_moff, long out_moff) {
     const size_t plane = (size_t)p->ny * p->kp * sizeof(cx<T>);
     if (int rc = plan_ensure_scratch(p, 2 * plane)) return rc;
     HipLauncher q{st};
     auto f = view<T>(p);
-    f.cols(q, (const cx<T>*)hc_in, p->kp, (cx<T>*)cols_tmp, p->kp, p->nx / 2 + 1, true, (T)1);
-    f.rows(q, ROW_WIN, cols_tmp, p->kp, out ? out : p->scratch, pl > 0 ? pl : p->kp, (T)scale, f.clampw(width), window);
+    if (nz > 0) f.cols(q, (const cx<T>*)hc_in, p->kp, (cx<T>*)cols_tmp, p->kp, p->nx / 2 + 1, true, (T)1, 0, 1, nullptr, nullptr, 0, false, -1, nz, in_moff, in_moff);
+    else f.cols(q, (const cx<T>*)hc_in, p->kp, (cx<T>*)cols_tmp, p->kp, p->nx / 2 + 1, true, (T)1);
+    f.rows(q, ROW_WIN, cols_tmp, p->kp, out ? out : p->scratch, pl > 0 ? pl : p->kp, (T)scale, f.clampw(width), window, nz, in_moff, out_moff);
     return q.rc;
 }
 // out = nullptr: the plan's first scratch plane (what qe_map_legs_cols_w stages 2 | 4 read); else a caller plane of pitch pl
-int qe_windowed_rows_w(oa_plan* p, const void* hc_in, void* cols_tmp, const void* window, int width, long pl, double scale, hipStream_t st, void* out) {
-    return p->dtype == OA_F32 ? windowed_rows_impl<float>(p, hc_in, cols_tmp, window, width, pl, scale, st, out)
-                              : windowed_rows_impl<double>(p, hc_in, cols_tmp, window, width, pl, scale, st, out);
+int qe_windowed_rows_w(oa_plan* p, const void* hc_in, void* cols_tmp, const void* window, int width, long pl, double scale, hipStream_t st, void* out,
+                       int nz, long in_moff, long out_moff) {
+    return p->dtype == OA_F32 ? windowed_rows_impl<float>(p, hc_in, cols_tmp, window, width, pl, scale, st, out, nz, in_moff, out_moff)
+                              : windowed_rows_impl<double>(p, hc_in, cols_tmp, window, width, pl, scale, st, out, nz, in_moff, out_moff);
 }
 // forward column transform of B row-transformed compact planes (pitch pin, in_moff apart) onto the leg band (columns < width, rows
 // |ky index| < rband, natural order) of B full-pitch hc planes out_moff apart: two launches for the batch

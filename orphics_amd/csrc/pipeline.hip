@@ -6,6 +6,7 @@
 #include <dlfcn.h>
 #include <cstdlib>
 #include <algorithm>
+#include <functional>
 #include <string>
 #include <utility>
 #include <vector>
@@ -49,6 +50,8 @@ struct Pipeline {
     size_t lens_bytes = 0;
     void* mvmc = nullptr;             // oa_mc_run_mv: the three drawn hc planes | per-estimator kappa planes (only when the one-launch divergence
     size_t mvmc_bytes = 0;            // is not engaged) | oa_bin_power_multi's partials | its sums
+    void* mvwin = nullptr;            // oa_mc_run_mv_windowed: the three full-plane T, Q, U draws | one column temporary per plane (the real maps of
+    size_t mvwin_bytes = 0;           // the unfused flow) | the three compact row-transformed planes
     // tile-major copies of Fnorm and of the bin ids on the coarse grid of the fused divergence + binning launch (what they were
     // made from: rebuilt when the filters / bins / column grid change)
     // (one set per grid a plan can carry: [0] the column grid `my`, [1] the from-map grid `my3`)
@@ -151,6 +154,7 @@ void pipeline_release(oa_plan* p) {
     if (q->mv_rtab) (void)hipFree(q->mv_rtab);
     if (q->lens_pool) (void)hipFree(q->lens_pool);
     if (q->mvmc) (void)hipFree(q->mvmc);
+    if (q->mvwin) (void)hipFree(q->mvwin);
     for (auto& t : q->dt) { if (t.fn_t) (void)hipFree(t.fn_t); if (t.ids_t) (void)hipFree(t.ids_t); }
     if (q->fb_t) (void)hipFree(q->fb_t);
     if (q->band) (void)oa_plan_destroy(q->band);
@@ -643,7 +647,7 @@ int oa_lens_maps_hc(oa_plan* p, int nmaps, const void* hc_in, long hc_stride, do
     return lens_maps_impl(p, nmaps, nullptr, 0, hc_in, hc_stride, scale, order, shift_x, shift_y, dx, dy, real_out, out_stride, stream);
 }
 
-/* frees the plan-owned pools that the multi-map entries grow on demand (oa_lens_maps, oa_qe_mv / oa_qe_tt_splits, oa_mc_run, oa_mc_run_mv): they
+/* frees the plan-owned pools that the multi-map entries grow on demand (oa_lens_maps, oa_qe_mv / oa_qe_tt_splits, oa_mc_run, oa_mc_run_mv, oa_mc_run_mv_windowed): they
  * are reallocated by the next call that needs them.  Synchronises the device. */
 int oa_plan_release_pools(oa_plan* p) {
     OA_REQUIRE(p, "oa_plan_release_pools: NULL plan");
@@ -654,6 +658,7 @@ int oa_plan_release_pools(oa_plan* p) {
     if (q->split_legs) { (void)hipFree(q->split_legs); q->split_legs = nullptr; q->split_bytes = 0; }
     if (q->mc_src) { (void)hipFree(q->mc_src); q->mc_src = nullptr; q->mc_cap = 0; }
     if (q->mvmc) { (void)hipFree(q->mvmc); q->mvmc = nullptr; q->mvmc_bytes = 0; }
+    if (q->mvwin) { (void)hipFree(q->mvwin); q->mvwin = nullptr; q->mvwin_bytes = 0; }
     // band grid: the split entries' inner source planes and kappa block, and the pool their inner call grew (regrown on demand)
     if (q->bsplit) { (void)hipFree(q->bsplit); q->bsplit = nullptr; q->bsplit_bytes = 0; q->bs_cap = 0; }
     if (q->band && q->band->pipe) {
@@ -1627,13 +1632,18 @@ static int mc_mv_bind(oa_plan* p, Pipeline* q, const void* w, long wstride, int 
 /* The per-realisation loop of oa_mc_run_mv, shared by both plan kinds.  `grid` is the map's plan: Philox counters, self-conjugate edge
  * rules and the covsqrt planes are its.  `run` is the plan the estimators and the binning run on -- `grid` itself (power of two), or
  * the inner plan of its band grid, into whose layout the draw then goes directly (oa_grf_mix_band_inner); every plane below is in `run`'s
- * layout.  Nothing here allocates or synchronises once the pools exist. */
+ * layout.  Nothing here allocates or synchronises once the pools exist.
+ * SOURCE STAGE HOOK: `source` (when set) replaces the band draw -- it leaves realisation i's T, E, B on the leg band of `draw`
+ * (oa_mc_run_mv_windowed's windowed front end).  `mf` (when set): nest host-side pointers to float64 stack planes, and `mf_mv` the MV
+ * stack or nullptr -- one stack_add_region_multi launch per realisation over kappa's band. */
 struct McMvLoop {
     oa_plan* grid; oa_plan* run; Pipeline* rq;
     bool engaged;                                   // the one-launch divergence: kappa planes = run's work planes c[0] + e
     void* draw[3]; char* own; void* scratch; double* sums;
     const void* w; long wstride; const int32_t* ids;
     int mrow;
+    std::function<int(long)> source;
+    double* const* mf = nullptr; double* mf_mv = nullptr;
 };
 static int mc_mv_loop(const McMvLoop& L, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest,
                       const int* host_npieces, const double* host_signs, const void* const* FG, const void* const* FH, const int* host_swap,
@@ -1646,7 +1656,8 @@ static int mc_mv_loop(const McMvLoop& L, uint64_t base_seed, long sim_lo, long s
     std::vector<const void*> kX(nest), kY(nest);
     for (int e = 0; e < nest; ++e) { kX[e] = L.draw[host_xsrc[e]]; kY[e] = L.draw[host_ysrc[e]]; }
     for (long i = sim_lo; i < sim_hi; ++i) {
-        int rc = L.grid == r ? oa_grf_mix_band(r, base_seed, 3 * (uint64_t)i, 3, host_covsqrt, 1.0, L.draw, leg_cols, leg_rows, st)
+        int rc = L.source    ? L.source(i)
+               : L.grid == r ? oa_grf_mix_band(r, base_seed, 3 * (uint64_t)i, 3, host_covsqrt, 1.0, L.draw, leg_cols, leg_rows, st)
                              : oa_grf_mix_band_inner(L.grid, base_seed, 3 * (uint64_t)i, 3, host_covsqrt, 1.0, L.draw, r->ny, r->kp, leg_cols,
                                                      leg_rows, st);
         if (rc) return rc;
@@ -1663,6 +1674,8 @@ static int mc_mv_loop(const McMvLoop& L, uint64_t base_seed, long sim_lo, long s
         if ((rc = oa_bin_power_multi(r->dtype, nest, block, (long)(pb / es), L.w, L.wstride, nspec, host_a, host_b, norm, L.ids, nids,
                                      r->ny, r->kp, r->nx / 2, kappa_cols, kappa_rows, L.sums, L.scratch, st))) return rc;
         if ((rc = moments_add_binned_multi(L.sums, counts, nspec, nids, n, S, C, st))) return rc;
+        if (L.mf && (rc = stack_add_region_multi(r->dtype, block, (long)(pb / es), L.w, L.wstride, nest, L.mf, L.mf_mv, r->ny, r->kp, kappa_cols,
+                                                 kappa_rows, st))) return rc;
     }
     return 0;
 }
@@ -1808,6 +1821,56 @@ int oa_mc_run(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const vo
     return 0;
 }
 
+} // extern "C"
+namespace oa {
+// the argument checks oa_mc_run_mv and oa_mc_run_mv_windowed share (everything but the plan kind), under the caller's name
+static int mc_mv_check(const std::string& who, bool plan_ok, const char* plan_msg, oa_plan* p, long sim_lo, long sim_hi,
+                       const void* const* host_covsqrt, int nest, const int* host_npieces, const double* host_signs, const void* const* host_FG, const void* const* host_FH, const int* host_xsrc, const int* host_ysrc,
+                       const void* const* host_Fnorm, const void* mv_weights, int nspec, const int* host_a, const int* host_b, const int32_t* ids_hc,
+                       int nids, const int64_t* counts, int leg_cols, int kappa_cols, int leg_rows, int kappa_rows, const int64_t* n, const double* S,
+                       const double* C) {
+    OA_REQUIRE(p && host_covsqrt && host_npieces && host_signs && host_FG && host_FH && host_xsrc && host_ysrc && host_Fnorm && ids_hc && counts &&
+               n && S && C && sim_hi >= sim_lo, who + ": bad argument");
+    OA_REQUIRE(plan_ok, who + plan_msg);
+    OA_REQUIRE(nest >= 1 && nest <= 6, who + ": 1 <= nest <= 6 estimators");
+    OA_REQUIRE(nids >= 3, who + ": nids must be at least 3 (two outer bins around the bandpowers)");
+    if (int rc = bin_power_multi_check(who.c_str(), p->dtype, nest, mv_weights != nullptr, nspec, host_a, host_b, nids)) return rc;
+    const int hw = p->nx / 2 + 1;
+    OA_REQUIRE(leg_cols >= 0 && kappa_cols >= 0 && leg_rows >= 0 && kappa_rows >= 0 && leg_cols <= hw && kappa_cols <= hw &&
+               2L * leg_rows - 1 <= p->ny && 2L * kappa_rows - 1 <= p->ny, who + ": leg / kappa band beyond the hc plane");
+    int total = 0;
+    for (int e = 0; e < nest; ++e) {
+        OA_REQUIRE(host_npieces[e] >= 1 && host_Fnorm[e], who + ": bad estimator entry");
+        OA_REQUIRE(host_xsrc[e] >= 0 && host_xsrc[e] < 3 && host_ysrc[e] >= 0 && host_ysrc[e] < 3, who + ": source index outside [0, 3) (0 T, 1 E, 2 B)");
+        total += host_npieces[e];
+    }
+    for (int i = 0; i < total; ++i) OA_REQUIRE(host_FG[i] && host_FH[i], who + ": NULL filter plane");
+    return 0;
+}
+// the entry-owned pool of a power-of-two plan, taken on the first call (and regrown when a call needs more): that call synchronises the
+// device once; and the loop's description on it
+static int mc_mv_pow2_loop(oa_plan* p, Pipeline* q, int nest, const void* const* host_Fnorm, const void* mv_weights, long mv_wstride, int nspec,
+                           const int32_t* ids_hc, int nids, int mrow, McMvLoop* L) {
+    if (int rc = ensure_work(p, q)) return rc;
+    const size_t es = 2 * (p->dtype == OA_F32 ? 4 : 8), rs = es / 2, pb = plane_bytes(p);
+    long fn_moff = 0;
+    const bool engaged = mv_div_batched(q, nest, host_Fnorm, rs, &fn_moff);
+    const size_t sb = (size_t)oa_bin_power_multi_scratch_bytes(nspec, nids), ub = (size_t)nspec * nids * sizeof(double);
+    const size_t need = (3 + (engaged ? 0 : (size_t)nest)) * pb + sb + ub;
+    if (q->mvmc_bytes < need) {
+        if (q->mvmc) { OA_HIP(hipDeviceSynchronize()); (void)hipFree(q->mvmc); q->mvmc = nullptr; q->mvmc_bytes = 0; }
+        OA_HIP(hipMalloc(&q->mvmc, need));
+        OA_HIP(hipMemset(q->mvmc, 0, need));
+        q->mvmc_bytes = need;
+    }
+    char* const base = (char*)q->mvmc;
+    *L = McMvLoop{p, p, q, engaged, {base, base + pb, base + 2 * pb}, base + 3 * pb /* per-estimator kappa planes when the plan's are not used */,
+                  base + q->mvmc_bytes - sb - ub, (double*)(base + q->mvmc_bytes - ub), mv_weights, mv_wstride, ids_hc, mrow};
+    return 0;
+}
+}  // namespace oa
+extern "C" {
+
 /* oa_mc_run_mv (include/orphics_amd.h): the Gaussian N0 Monte-Carlo shard of an estimator SET.  Per realisation (mc_mv_loop): the leg band
  * of oa_grf_mix's T, E, B draw (streams 3 i, 3 i + 1, 3 i + 2) into three entry-owned planes -- not the plan's work planes: c[0..2], g[0..1]
  * and kT are where the one-launch divergence puts the per-estimator kappa_hat --, the launch sequence of oa_qe_mv with the sum left out
@@ -1818,46 +1881,88 @@ int oa_mc_run_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const
                  const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights, long mv_wstride, int nspec, const int* host_a,
                  const int* host_b, const int32_t* ids_hc, int nids, const int64_t* counts, double norm, int leg_cols, int kappa_cols,
                  int leg_rows, int kappa_rows, int mrow, int64_t* n, double* S, double* C, void* stream) {
-    OA_REQUIRE(p && host_covsqrt && host_npieces && host_signs && host_FG && host_FH && host_xsrc && host_ysrc && host_Fnorm && ids_hc && counts &&
-               n && S && C && sim_hi >= sim_lo, "oa_mc_run_mv: bad argument");
-    OA_REQUIRE(p->pow2 || p->mixed, "oa_mc_run_mv: map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path; "
-               "run the host loop of the existing entries (mc.GaussianN0MonteCarloPol with one_call=False: Engine.grf_mix, reconstruct_hc per "
-               "estimator, Engine.bin_power, Statistics.add)");
-    OA_REQUIRE(nest >= 1 && nest <= 6, "oa_mc_run_mv: 1 <= nest <= 6 estimators");
-    OA_REQUIRE(nids >= 3, "oa_mc_run_mv: nids must be at least 3 (two outer bins around the bandpowers)");
-    if (int rc = bin_power_multi_check("oa_mc_run_mv", p->dtype, nest, mv_weights != nullptr, nspec, host_a, host_b, nids)) return rc;
-    const int hw = p->nx / 2 + 1;
-    OA_REQUIRE(leg_cols >= 0 && kappa_cols >= 0 && leg_rows >= 0 && kappa_rows >= 0 && leg_cols <= hw && kappa_cols <= hw &&
-               2L * leg_rows - 1 <= p->ny && 2L * kappa_rows - 1 <= p->ny, "oa_mc_run_mv: leg / kappa band beyond the hc plane");
-    int total = 0;
-    for (int e = 0; e < nest; ++e) {
-        OA_REQUIRE(host_npieces[e] >= 1 && host_Fnorm[e], "oa_mc_run_mv: bad estimator entry");
-        OA_REQUIRE(host_xsrc[e] >= 0 && host_xsrc[e] < 3 && host_ysrc[e] >= 0 && host_ysrc[e] < 3, "oa_mc_run_mv: source index outside [0, 3) (0 T, 1 E, 2 B)");
-        total += host_npieces[e];
-    }
-    for (int i = 0; i < total; ++i) OA_REQUIRE(host_FG[i] && host_FH[i], "oa_mc_run_mv: NULL filter plane");
+    OA_REQUIRE(p, "oa_mc_run_mv: bad argument");
+    if (int rc = mc_mv_check("oa_mc_run_mv", p->pow2 || p->mixed,
+                             ": map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path; "
+                             "run the host loop of the existing entries (mc.GaussianN0MonteCarloPol with one_call=False: Engine.grf_mix, reconstruct_hc per "
+                             "estimator, Engine.bin_power, Statistics.add)", p, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, host_FG, host_FH, host_xsrc, host_ysrc,
+                             host_Fnorm, mv_weights, nspec, host_a, host_b, ids_hc, nids, counts, leg_cols, kappa_cols, leg_rows, kappa_rows, n, S, C))
+        return rc;
     Pipeline* q = pipe_of(p);
     hipStream_t st = (hipStream_t)stream;
     if (p->mixed)                                   // BAND GRID: the planes of the two bindings, on the inner plan
         return mixed_mc_run_mv(p, q, base_seed, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, host_FG, host_FH, host_swap, host_xsrc,
                                host_ysrc, host_Fnorm, mv_weights, mv_wstride, nspec, host_a, host_b, ids_hc, nids, counts, norm, leg_cols, kappa_cols,
                                leg_rows, kappa_rows, mrow, n, S, C, st);
-    if (int rc = ensure_work(p, q)) return rc;
-    const size_t es = 2 * (p->dtype == OA_F32 ? 4 : 8), rs = es / 2, pb = plane_bytes(p);
-    long fn_moff = 0;
-    const bool engaged = mv_div_batched(q, nest, host_Fnorm, rs, &fn_moff);
-    // entry-owned pool, taken on the first call (and regrown when a call needs more): that call synchronises the device once
-    const size_t sb = (size_t)oa_bin_power_multi_scratch_bytes(nspec, nids), ub = (size_t)nspec * nids * sizeof(double);
-    const size_t need = (3 + (engaged ? 0 : (size_t)nest)) * pb + sb + ub;
-    if (q->mvmc_bytes < need) {
-        if (q->mvmc) { OA_HIP(hipDeviceSynchronize()); (void)hipFree(q->mvmc); q->mvmc = nullptr; q->mvmc_bytes = 0; }
-        OA_HIP(hipMalloc(&q->mvmc, need));
-        OA_HIP(hipMemset(q->mvmc, 0, need));
-        q->mvmc_bytes = need;
+    McMvLoop L;
+    if (int rc = mc_mv_pow2_loop(p, q, nest, host_Fnorm, mv_weights, mv_wstride, nspec, ids_hc, nids, mrow, &L)) return rc;
+    return mc_mv_loop(L, base_seed, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, host_FG, host_FH, host_swap, host_xsrc, host_ysrc,
+                      host_Fnorm, nspec, host_a, host_b, nids, counts, norm, leg_cols, kappa_cols, leg_rows, kappa_rows, n, S, C, st);
+}
+
+/* oa_mc_run_mv_windowed (include/orphics_amd.h): oa_mc_run_mv with a real-space window on T, Q, U and the mean-field stacks of the estimator
+ * set.  The window multiplies Q and U, not E and B -- a taper leaks E into B, which is what the EB and TB noise on an apodised patch is made
+ * of -- so the source stage of a windowed realisation is: full-plane draw of T, E, B rotated to T, Q, U in the same pass (the counters of the
+ * band draw) -> one batched inverse column launch -> one fused row launch over the three planes (C2R / Npix -> x window -> R2C, the real maps
+ * in LDS only, leg_cols columns stored at the compact pitch) -> one batched forward column launch onto the leg band of the loop's three
+ * source planes -> Q, U -> E, B on that band.  OA_OPT_WIN_FUSED = 0: oa_fft_c2r_windowed -> real maps in HBM (the column temporaries) ->
+ * oa_fft_r2c on the band.  Then mc_mv_loop's estimator, binning and moment steps, and one stack launch. */
+int oa_mc_run_mv_windowed(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest,
+                          const int* host_npieces, const double* host_signs, const void* const* host_FG, const void* const* host_FH,
+                          const int* host_swap, const int* host_xsrc, const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights,
+                          long mv_wstride, int nspec, const int* host_a, const int* host_b, const int32_t* ids_hc, int nids, const int64_t* counts,
+                          double norm, int leg_cols, int kappa_cols, int leg_rows, int kappa_rows, int mrow, const void* window_real,
+                          const void* rot_c, const void* rot_s, int64_t* n, double* S, double* C, double* const* host_meanfield, void* stream) {
+    OA_REQUIRE(p, "oa_mc_run_mv_windowed: bad argument");
+    if (int rc = mc_mv_check("oa_mc_run_mv_windowed", p->pow2,
+                             ": power-of-two map sides only (no band-grid version on sides 2^a 3^b 5^c yet, no one-call path on chirp-z sides); run "
+                             "the host loop of the existing entries (mc.GaussianN0MonteCarloPol with one_call=False: Engine.grf_mix, Engine.irfft with "
+                             "the window, Engine.rfft, Engine.rot2, reconstruct_hc per estimator, Engine.bin_power, Statistics.add)", p, sim_lo, sim_hi,
+                             host_covsqrt, nest, host_npieces, host_signs, host_FG, host_FH, host_xsrc, host_ysrc, host_Fnorm, mv_weights, nspec, host_a,
+                             host_b, ids_hc, nids, counts, leg_cols, kappa_cols, leg_rows, kappa_rows, n, S, C))
+        return rc;
+    OA_REQUIRE(!window_real || (rot_c && rot_s), "oa_mc_run_mv_windowed: a window acts on Q and U and needs both rotation planes rot_c, rot_s (cos / sin "
+               "2 phi_l on the half plane, oa_qe_mv_maps' convention: what mc.GaussianN0MonteCarloPol passes, and what its one_call=False host "
+               "loop rotates with)");
+    if (host_meanfield)
+        for (int e = 0; e < nest + (mv_weights ? 1 : 0); ++e) OA_REQUIRE(host_meanfield[e], "oa_mc_run_mv_windowed: NULL mean-field stack plane");
+    Pipeline* q = pipe_of(p);
+    hipStream_t st = (hipStream_t)stream;
+    McMvLoop L;
+    if (int rc = mc_mv_pow2_loop(p, q, nest, host_Fnorm, mv_weights, mv_wstride, nspec, ids_hc, nids, mrow, &L)) return rc;
+    if (host_meanfield) { L.mf = host_meanfield; L.mf_mv = mv_weights ? host_meanfield[nest] : nullptr; }
+    if (window_real) {
+        const size_t es = 2 * (p->dtype == OA_F32 ? 4 : 8), pb = plane_bytes(p);
+        const long pl = work_pitch(p, leg_cols);
+        const size_t lb = (size_t)pl * p->ny * es, need = 6 * pb + 3 * lb;
+        if (q->mvwin_bytes < need) {                // taken on first use (regrown when the leg band widens): one device synchronisation
+            OA_HIP(hipDeviceSynchronize());
+            if (q->mvwin) { (void)hipFree(q->mvwin); q->mvwin = nullptr; q->mvwin_bytes = 0; }
+            OA_HIP(hipMalloc(&q->mvwin, need));
+            q->mvwin_bytes = need;
+        }
+        char* const wb = (char*)q->mvwin;
+        char* const tmp = wb + 3 * pb;
+        char* const rowT = wb + 6 * pb;
+        const double inv = 1.0 / ((double)p->ny * p->nx);
+        const bool fused = q->opt_win_fused;
+        void* const* const dst = L.draw;
+        L.source = [=](long i) -> int {
+            void* tqu[3] = {wb, wb + pb, wb + 2 * pb};
+            int rc = grf_mix_teb_to_tqu(p, base_seed, 3 * (uint64_t)i, host_covsqrt, rot_c, rot_s, tqu, st);
+            if (rc) return rc;
+            if (fused) {
+                if ((rc = qe_windowed_rows_w(p, wb, tmp, window_real, leg_cols, pl, inv, st, rowT, 3, (long)(pb / es), (long)(lb / es)))) return rc;
+                if ((rc = qe_fwd_cols_batch_w(p, rowT, pl, dst[0], 3, (long)(lb / es), (long)(pb / es), leg_cols, leg_rows, st))) return rc;
+            } else {
+                for (int f = 0; f < 3; ++f) {       // A/B: the window at the C2R's store, the real map in HBM, the R2C on the leg band
+                    if ((rc = oa_fft_c2r_windowed(p, tqu[f], tmp + (size_t)f * pb, inv, window_real, st))) return rc;
+                    if ((rc = oa_fft_r2c(p, tmp + (size_t)f * pb, dst[f], 1.0, leg_cols, leg_rows, st))) return rc;
+                }
+            }
+            return band_rot2(p->dtype, rot_c, rot_s, dst[1], dst[2], p->ny, p->kp, leg_cols, leg_rows, st);
+        };
     }
-    char* const base = (char*)q->mvmc;
-    McMvLoop L{p, p, q, engaged, {base, base + pb, base + 2 * pb}, base + 3 * pb /* per-estimator kappa planes when the plan's are not used */,
-               base + q->mvmc_bytes - sb - ub, (double*)(base + q->mvmc_bytes - ub), mv_weights, mv_wstride, ids_hc, mrow};
     return mc_mv_loop(L, base_seed, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, host_FG, host_FH, host_swap, host_xsrc, host_ysrc,
                       host_Fnorm, nspec, host_a, host_b, nids, counts, norm, leg_cols, kappa_cols, leg_rows, kappa_rows, n, S, C, st);
 }

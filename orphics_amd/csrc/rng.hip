@@ -169,6 +169,7 @@ struct GrfMixArgs {
     int wpairs, width, rband;      // BAND launches (oa_grf_mix_band): column pairs / columns drawn, row band (0 = every row)
     int my;                        // INNER launches (oa_grf_mix_band_inner): rows and row pitch of the output planes
     long okp;
+    int rneg;                      // != 0: the rotation runs with -rs (E, B -> Q, U by the planes that take Q, U -> E, B: oa_mc_run_mv_windowed)
 };
 // NC and the input mode are compile-time: every loop unrolls, the pointer tables and the per-component values stay in registers
 // (with run-time indices they went through scratch: 400-660 us per call at 4096^2 float64 instead of 100-250).  A thread owns the
@@ -229,7 +230,10 @@ __global__ __launch_bounds__(256) void grf_mix_kernel(GrfMixArgs<T> a) {
 #pragma unroll
     for (int k = 0; k < NC * NC; ++k) { sv[k].a = (T)0; sv[k].b = (T)0; if (a.cs[k]) sv[k] = load_pair<VEC>(a.cs[k], i0, second); }
     R2 rc{(T)1, (T)1}, rs{(T)0, (T)0}, fl{(T)1, (T)1};
-    if (NC == 3 && a.rc) { rc = load_pair<VEC>(a.rc, i0, second); rs = load_pair<VEC>(a.rs, i0, second); }
+    if (NC == 3 && a.rc) {
+        rc = load_pair<VEC>(a.rc, i0, second); rs = load_pair<VEC>(a.rs, i0, second);
+        if (a.rneg) { rs.a = -rs.a; rs.b = -rs.b; }
+    }
     C2 u[NC];
     if constexpr (HAS_IN) {
         if (a.filt) fl = load_pair<VEC>(a.filt, i0, second);
@@ -356,9 +360,9 @@ __global__ __launch_bounds__(256) void moments_add_binned_kernel(const double* _
 
 template <typename T>
 static int grf_mix_launch(oa_plan* p, uint64_t seed, uint64_t sid0, int ncomp, const void* const* cs, const void* rc, const void* rs,
-                          const void* const* in, const void* filt, double scale, void* const* out, hipStream_t st) {
+                          const void* const* in, const void* filt, double scale, void* const* out, hipStream_t st, int rneg = 0) {
     GrfMixArgs<T> a;
-    a.seed = seed; a.sid0 = sid0;
+    a.seed = seed; a.sid0 = sid0; a.rneg = rneg;
     for (int i = 0; i < 9; ++i) a.cs[i] = i < ncomp * ncomp ? (const T*)cs[i] : nullptr;
     a.rc = (const T*)rc; a.rs = (const T*)rs;
     for (int i = 0; i < 3; ++i) { a.in[i] = (in && i < ncomp) ? (const cx<T>*)in[i] : nullptr; a.out[i] = i < ncomp ? (cx<T>*)out[i] : nullptr; }
@@ -403,7 +407,7 @@ static int grf_mix_band_launch(oa_plan* p, uint64_t seed, uint64_t sid0, int nco
     a.width = (width > 0 && width < hw) ? width : hw;
     a.wpairs = (a.width + 1) / 2;
     a.rband = (rband > 0 && 2L * rband - 1 < p->ny) ? rband : 0;
-    a.my = 0; a.okp = 0;
+    a.my = 0; a.okp = 0; a.rneg = 0;
     const int bs = a.wpairs >= 256 ? 256 : 64;
     const dim3 grid((a.wpairs + bs - 1) / bs, a.rband ? 2 * a.rband - 1 : p->ny);
     if (ncomp == 1) hipLaunchKernelGGL((grf_mix_kernel<T, 1, false, false, true>), grid, dim3(bs), 0, st, a);
@@ -425,7 +429,7 @@ static int grf_mix_band_inner_launch(oa_plan* p, uint64_t seed, uint64_t sid0, i
     a.scale = (T)scale;
     a.ncomp = ncomp; a.ny = p->ny; a.nx = p->nx; a.kp = p->kp;
     a.width = width; a.wpairs = (width + 1) / 2; a.rband = rband;
-    a.my = my; a.okp = okp;
+    a.my = my; a.okp = okp; a.rneg = 0;
     const int bs = a.wpairs >= 256 ? 256 : 64;
     const dim3 grid((a.wpairs + bs - 1) / bs, 2 * rband - 1);
     if (ncomp == 1) hipLaunchKernelGGL((grf_mix_kernel<T, 1, false, false, true, true>), grid, dim3(bs), 0, st, a);
@@ -433,6 +437,15 @@ static int grf_mix_band_inner_launch(oa_plan* p, uint64_t seed, uint64_t sid0, i
     else hipLaunchKernelGGL((grf_mix_kernel<T, 3, false, false, true, true>), grid, dim3(bs), 0, st, a);
     OA_LAUNCH_CHECK();
     return 0;
+}
+
+// oa_mc_run_mv_windowed: oa_grf_mix's full-plane T, E, B draw with E, B -> Q, U in the same pass -- Q = E c + B s, U = -E s + B c, the
+// inverse of oa_rot2's combination, by the caller's Q, U -> E, B planes (the sine enters negated: the values of
+// oa_grf_mix(rot_c = c, rot_s = -s) bit for bit)
+int grf_mix_teb_to_tqu(oa_plan* p, uint64_t seed, uint64_t sid0, const void* const* cs, const void* rot_c, const void* rot_s, void* const* out,
+                       hipStream_t st) {
+    return p->dtype == OA_F32 ? grf_mix_launch<float>(p, seed, sid0, 3, cs, rot_c, rot_s, nullptr, nullptr, 1.0, out, st, 1)
+                              : grf_mix_launch<double>(p, seed, sid0, 3, cs, rot_c, rot_s, nullptr, nullptr, 1.0, out, st, 1);
 }
 
 // x[s * d + j] = sums[s * nids + j + 1] / counts[j + 1], d = nids - 2 (the interior bins of nspec binned spectra, oa_bin_power_multi's

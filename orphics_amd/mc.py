@@ -306,10 +306,27 @@ class GaussianN0MonteCarloPol(object):
     call on sides 2^a 3^b 5^c as well: it runs on the band grid of the estimator set (``qest.one_call_pol(estimators,
     ext_norm=True)``; ``oa_qe_band_bind`` + ``oa_mc_mv_band_bind`` bind the planes, re-bound whenever anything else used the plan in
     between -- :meth:`sample_host` included, so the two paths may be interleaved), and raises where there is no such path (chirp-z
-    sides, unbounded filters, a band grid not smaller than the map): pass ``one_call=False`` there."""
+    sides, unbounded filters, a band grid not smaller than the map): pass ``one_call=False`` there.
+
+    ``window``: a (Ny, Nx) real-space apodisation (``maps.get_taper(shape, ...)[0]``) multiplied into the T, Q, U maps of every
+    realisation before their transforms, as the reference's analysis flow does.  The window acts on Q and U, not on E and B: a taper
+    leaks E into B, which the EB and TB filters do not expect, so the N0 and the mean field of EB, TB and MV on an apodised patch are
+    not those of the unwindowed run.  Realisations are then drawn over the full plane, rotated E, B -> Q, U, inverse-transformed,
+    windowed, transformed and rotated back Q, U -> E, B; both rotations use ``qest._qu_rot(False)`` -- the angle convention cancels
+    between them, so there is no ``iau`` argument.  ``window_moments`` = (mean w^2, mean w^4); bandpowers of kappa_hat (quadratic in the
+    maps) carry a factor mean(w^4) that :meth:`debiased_mean` divides out.
+
+    ``mean_field=True``: device stacks of every estimator's kappa_hat and -- with ``mv`` -- of the MV combination in ``self.acc`` under
+    the labels "mf_TT", ..., "mf_MV" (shape (ny, kp, 2), interleaved re / im, support = kappa's band, so the all-reduce moves the
+    band only).
+
+    With a window or a mean field the one call is ``oa_mc_run_mv_windowed``, on power-of-two sides only: ``one_call=None`` runs it
+    there and the host loop elsewhere, ``one_call=True`` on other sides raises.  The host loop (any side; the reference of the one
+    call) is then ``Engine.grf_mix(rot=(c, -s))`` on full planes, ``Engine.irfft(window=...)`` per field, ``Engine.rfft``,
+    ``Engine.rot2(c, s, ...)``, the per-estimator sequence above, and the stacks added with torch."""
 
     def __init__(self, qest, total_power_half, bin_edges, estimators=("TT", "TE", "EE", "EB", "TB"), cross=True, mv=True, comm=None,
-                 base_seed=1234, one_call=None):
+                 base_seed=1234, one_call=None, window=None, mean_field=False):
         torch = _torch()
         from .lensing import pol_bands
         self.q = qest
@@ -320,6 +337,25 @@ class GaussianN0MonteCarloPol(object):
         self.spectra, self.pairs = pol_spectrum_list(self.estimators, cross, mv)
         self.mv = bool(mv)
         self.one_call = e.pow2 if one_call is None else bool(one_call)
+        self.mean_field = bool(mean_field)
+        self.mf_labels = ["mf_" + XY for XY in self.estimators] + (["mf_MV"] if self.mv else [])
+        self.window = None
+        self.window_moments = (1.0, 1.0)
+        self.rot = None
+        self.host_maps = None         # host loop with a window: the windowed real T, Q, U maps of the last sample_host call
+        if (window is not None or self.mean_field) and self.one_call and not e.pow2:
+            from ._lib import OrphicsAmdError
+            raise OrphicsAmdError("GaussianN0MonteCarloPol: a window or a mean-field stack runs in one call (oa_mc_run_mv_windowed) on "
+                                  "power-of-two map sides only; %d x %d: construct the driver with one_call=False (host loop of the existing "
+                                  "entries, any side) or leave one_call=None" % (e.ny, e.nx))
+        if window is not None:
+            w = np.asarray(window, dtype=np.float64)
+            if w.shape != (e.ny, e.nx):
+                raise ValueError("window must be a (Ny, Nx) real-space array")
+            self.window = e.to_real(w)
+            self.window_moments = (float(np.mean(w ** 2)), float(np.mean(w ** 4)))
+            c, s_ = qest._qu_rot(False)
+            self.rot = (c, s_, -s_)   # Q, U -> E, B planes (oa_rot2's combination) and the negated sine of the inverse rotation
         geom = qest.geom
         nE = len(self.estimators)
         # unnormalised DFT of a unit-pixel-variance white map has |k|^2 = Npix; power p -> k = sqrt(p Npix^2/area) w
@@ -393,6 +429,17 @@ class GaussianN0MonteCarloPol(object):
                 e._pipe_owner = None
         wstride = self.w[0].numel() if self.w is not None else 0
         wl, wk, rl, rk = self._bands
+        if self.window is not None or self.mean_field:
+            import ctypes
+            mfs = self._stacks()
+            mfp = (ctypes.c_void_p * len(mfs))(*[t.data_ptr() for t in mfs]) if mfs else None
+            rot = self.rot if self.rot is not None else (None, None)
+            check(e.lib.oa_mc_run_mv_windowed(e.plan, self.base_seed, int(lo), int(hi), A["cs"], len(self.estimators), A["npieces"], A["signs"],
+                                              A["fgs"], A["fhs"], A["swaps"], A["xsrc"], A["ysrc"], A["fns"], _ptr(self.w), wstride,
+                                              len(self.spectra), A["a"], A["b"], _ptr(self.ids), self.nids, _ptr(self.counts), float(self.norm),
+                                              int(wl), int(wk), int(rl), int(rk), int(q.mrow), _ptr(self.window), _ptr(rot[0]), _ptr(rot[1]),
+                                              _ptr(n), _ptr(S), _ptr(C), mfp, _stream()))
+            return
         if e.mixed:
             # the estimator set with its pure normalisations in order, then the weights and bin ids, on the plan's inner grid; the plan
             # is shared: both are bound again whenever anything else bound it in between (sample_host's reconstruct_hc does)
@@ -410,26 +457,62 @@ class GaussianN0MonteCarloPol(object):
                                  _ptr(n), _ptr(S), _ptr(C), _stream()))
 
     # ---- the host loop of existing entries (every side the estimators run on; the reference of the one-call path) -------------------
-    def sample_host(self, i):
-        """realisation ``i``'s sample vector (device, float64) through the existing entries"""
+    def _stacks(self):
+        """the device mean-field stacks in label order (estimators, then MV); [] without ``mean_field``"""
+        if not self.mean_field:
+            return []
+        e = self.eng
+        sup = (self.rk, self.wk) if (self.wk and self.rk) else None
+        return [self.acc.device_stack(lab, (e.ny, e.kp, 2), support=sup) for lab in self.mf_labels]
+
+    def _host_fields(self, i):
+        """realisation ``i``'s kappa_hat planes through the existing entries: one per estimator, then -- ``mv`` -- the weighted sum"""
         torch = _torch()
         e, q = self.eng, self.q
         if self._host is None:
             t = torch.empty((3, e.ny, e.kp), dtype=e.cdt, device=e.device)
             self._host = ([t[j] for j in range(3)], [q.new_output() for _ in self.estimators], self.counts[1:-1].double())
+            if self.window is not None:
+                self.host_maps = [e.real() for _ in range(3)]
         draw, outs, cnt = self._host
-        e.grf_mix(self.base_seed, self.cs, out=draw, stream_id0=3 * int(i))
-        f = {"T": draw[0], "E": draw[1], "B": draw[2]}
+        if self.window is None:
+            e.grf_mix(self.base_seed, self.cs, out=draw, stream_id0=3 * int(i))
+            f = {"T": draw[0], "E": draw[1], "B": draw[2]}
+        else:
+            # T, E, B -> T, Q, U in the draw's pass, x window in real space, back to T, E, B: the window multiplies Q and U
+            c, s_, ms = self.rot
+            e.grf_mix(self.base_seed, self.cs, rot=(c, ms), out=draw, stream_id0=3 * int(i))
+            for j in range(3):
+                if e.pow2 or e.mixed:
+                    e.irfft(draw[j], out=self.host_maps[j], window=self.window)
+                else:
+                    e.irfft(draw[j], out=self.host_maps[j])
+                    self.host_maps[j].mul_(self.window)
+                e.rfft(self.host_maps[j], out=draw[j])
+            kE, kB = e.rot2(c, s_, draw[1], draw[2])
+            f = {"T": draw[0], "E": kE, "B": kB}
         fields = [q.reconstruct_hc(XY, f[XY[0]], f[XY[1]], out=outs[j]) for j, XY in enumerate(self.estimators)]
         if self.mv:
             kmv = self.w[0] * fields[0]
             for j in range(1, len(fields)):
                 kmv += self.w[j] * fields[j]
             fields = fields + [kmv]
+        return fields
+
+    def sample_host(self, i, stack=False):
+        """realisation ``i``'s sample vector (device, float64) through the existing entries; ``stack`` (with ``mean_field``): its
+        kappa_hat planes are added to the mean-field stacks as well"""
+        torch = _torch()
+        e = self.eng
+        fields = self._host_fields(i)
+        cnt = self._host[2]
         x = []
         for (a, b) in self.pairs:
             s, _ = e.bin_power(fields[a], fields[b], self.norm, self.ids, self.nids, herm=True, active_cols=self.wk, active_rows=self.rk)
             x.append(s[1:-1] / cnt)
+        if stack:
+            for t, k in zip(self._stacks(), fields):
+                t += torch.view_as_real(k).to(torch.float64)
         return torch.cat(x)
 
     def run_local(self, sims):
@@ -440,7 +523,8 @@ class GaussianN0MonteCarloPol(object):
             return self
         if not self.one_call:
             for i in sims:
-                self.acc.add("n0", self.sample_host(i))
+                self.acc.add("n0", self.sample_host(i, stack=self.mean_field))
+            self._note_stacked(len(sims))
             return self
         n, S, C = self.acc.device_moments("n0", self.D)
         start = prev = sims[0]
@@ -450,10 +534,18 @@ class GaussianN0MonteCarloPol(object):
                 start = i
             prev = i
         self.acc.note_samples("n0", len(sims))
+        self._note_stacked(len(sims))
         return self
 
+    def _note_stacked(self, k):
+        if self.mean_field:
+            self._stacks()
+            for lab in self.mf_labels:
+                self.acc.note_stacked(lab, k)
+
     def run(self, nsims):
-        """Shard ``nsims`` with mpi.mpi_distribute, run, reduce once; returns the reduced :class:`Statistics` (label "n0")."""
+        """Shard ``nsims`` with mpi.mpi_distribute, run, reduce once; returns the reduced :class:`Statistics` (label "n0"; with
+        ``mean_field`` the stacks "mf_TT", ..., "mf_MV")."""
         comm = self.comm
         size, rank = comm.Get_size(), comm.Get_rank()
         _, tasks = _mpi.mpi_distribute(nsims, size, allow_empty=True)
@@ -473,6 +565,10 @@ class GaussianN0MonteCarloPol(object):
     def mean(self, a, b=None):
         """N0^{ab} bandpowers of the (reduced) run: ``mean("EB")`` an auto, ``mean("TT", "TE")`` a cross, ``mean("MV")`` the MV auto"""
         return self.acc.mean("n0")[self._slot(a, b)]
+
+    def debiased_mean(self, a, b=None):
+        """:meth:`mean` divided by mean(w^4) of the window (1 without one)"""
+        return self.mean(a, b) / self.window_moments[1]
 
     def sem(self, a, b=None):
         """standard error of :meth:`mean` from the run's own covariance"""

@@ -8,7 +8,13 @@ crosses and the MV auto (16 spectra).
     is --iters consecutive realisations timed with HIP events; per path the median and the 10th .. 90th percentile of --reps blocks
     (at least 7), in ms per realisation.  One JSON line per (side, precision), appended to --out if given.  The two paths' moments of
     the timed realisations are compared as well (max relative difference of the mean sample vector).
---mode onecall N / --mode hostloop N: N realisations of one path and nothing else (the workload for a kernel trace)."""
+--mode onecall N / --mode hostloop N: N realisations of one path and nothing else (the workload for a kernel trace).
+--windowed [--mean-field]: every realisation's T, Q, U maps are multiplied by ``maps.get_taper(shape, g, 12.0, 3.0)[0]`` (12 % taper, 3 % pad)
+    before their transforms, and -- with --mean-field -- the six kappa_hat stacks are kept: the one call is then oa_mc_run_mv_windowed (full-plane
+    draw rotated to T, Q, U, batched inverse columns, one fused C2R x window -> R2C row launch over the three planes, batched forward
+    columns, band rotation), the baseline the host loop on the same library and plan (one_call=False: Engine.grf_mix with the rotation,
+    Engine.irfft(window=...), Engine.rfft and Engine.rot2, then the sequence above, the stacks added with torch).  The JSON line
+    carries "windowed" and "mean_field"; profiles/mc_pol_windowed.jsonl collects these lines."""
 import argparse
 import json
 import os
@@ -60,19 +66,24 @@ def main():
     ap.add_argument("--iters", type=int, default=8, help="realisations per timed block")
     ap.add_argument("--reps", type=int, default=9, help="timed blocks per path (>= 7)")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file")
+    ap.add_argument("--windowed", action="store_true", help="apply the 12 %% / 3 %% taper to T, Q, U (oa_mc_run_mv_windowed against its host loop)")
+    ap.add_argument("--mean-field", action="store_true", help="with --windowed: keep the mean-field stacks of every estimator and of MV")
     args = ap.parse_args()
     import torch
-    from orphics_amd import mc
+    from orphics_amd import maps, mc
     mode = args.mode[0]
+    if args.mean_field and not args.windowed:
+        ap.error("--mean-field goes with --windowed")
     if mode == "compare" and args.reps < 7:
         ap.error("--reps must be at least 7")
     edges = np.linspace(100, 2900, 12)
     for n in [int(s) for s in args.sides.split(",")]:
         q64, tot = setup(n, args.res)
+        extra = dict(window=maps.get_taper((n, n), q64.geom, 12.0, 3.0)[0], mean_field=args.mean_field) if args.windowed else {}
         for prec in args.precs.split(","):
             q = q64 if prec == "f64" else q64.astype("f32")
-            one = mc.GaussianN0MonteCarloPol(q, tot, edges, estimators=ESTS, base_seed=5, one_call=True)
-            host = mc.GaussianN0MonteCarloPol(q, tot, edges, estimators=ESTS, base_seed=5, one_call=False)
+            one = mc.GaussianN0MonteCarloPol(q, tot, edges, estimators=ESTS, base_seed=5, one_call=True, **extra)
+            host = mc.GaussianN0MonteCarloPol(q, tot, edges, estimators=ESTS, base_seed=5, one_call=False, **extra)
             if not one.one_call:
                 raise SystemExit("side %d has no one-call path" % n)
             if mode in ("onecall", "hostloop"):
@@ -90,7 +101,7 @@ def main():
                 t0.append(block_ms(host, lo, it))
             one.acc.allreduce(); host.acc.allreduce()
             m1, m0 = one.acc.mean("n0"), host.acc.mean("n0")
-            line = dict(tool="mc_pol_bench", side=n, prec=prec, res_arcmin=args.res, spectra=len(one.spectra), bins=int(one.d),
+            line = dict(tool="mc_pol_bench", side=n, prec=prec, windowed=bool(args.windowed), mean_field=bool(args.mean_field), res_arcmin=args.res, spectra=len(one.spectra), bins=int(one.d),
                         iters=it, reps=args.reps, leg_band=[int(one.wl), int(one.rl)], kappa_band=[int(one.wk), int(one.rk)],
                         onecall_ms=round(float(np.median(t1)), 4),
                         onecall_p10_p90=[round(float(np.percentile(t1, 10)), 4), round(float(np.percentile(t1, 90)), 4)],
