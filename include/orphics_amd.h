@@ -535,13 +535,15 @@ int oa_plan_release_pools(oa_plan* p);
  *               contraction (NumPy op order of enmap.modlmap).  `pitch`/`width`
  *               select the plane layout: full plane pitch=width=nx; hc plane
  *               pitch=kpitch,width=nx/2+1 (pad columns get id -1 = ignored).
- * oa_bin      : sums[id] += v, counts[id] += m over all i with ids[i] >= 0 where
- *                 v = data[i] (mode 0) | (data[i]-aux[id])^2 (mode 1), times
+ * oa_bin      : sums[id] += v, counts[id] += m over all i with 0 <= ids[i] < nids
+ *               (any other id, negative or >= nids, drops the element) where
+ *                 v = data[i] (mode 0) | (data[i]-aux[id])^2 (mode 1; no weights), times
  *                 weights[i] if weights != NULL, times the Hermitian multiplicity m,
- *                 m = 1 (herm_nxh < 0) or {1 for col 0 and col nxh, 2 for 0<col<nxh}
- *                 with col = i % herm_pitch;
+ *                 m = 1 (herm_nxh < 0) or {1 for col 0 and col nxh, 2 for 0<col<nxh,
+ *                 0 = dropped for col > nxh: the row padding} with col = i % herm_pitch
+ *                 (herm_pitch a positive multiple of 4, n a multiple of it);
  *               counts[] are exact int64 (unweighted) ; wsums[] = sum of weights*m (f64).
- *               skip_nan != 0 drops NaN data (mask_nan=True, stats.py:793).
+ *               skip_nan != 0 drops NaN data, with their weights (mask_nan=True, stats.py:793).
  *               Output arrays have nids = nedges+1 entries and are OVERWRITTEN.
  *               Deterministic: per-workgroup partials reduced in fixed order.
  *               `scratch` must hold oa_bin_scratch_bytes(nids) bytes. */
@@ -556,10 +558,13 @@ int oa_bin(int dtype, const void* data, const int32_t* ids, const void* weights,
 /* oa_bin_power: FourierCalc.f2power (maps.py:1620-1624) fused into oa_bin: the binned value is
  * Re(conj(k1[i]) k2[i]) * norm for complex planes k1, k2 (k1 == k2 for auto spectra); the 2-D power
  * plane is never written.  Same ids / multiplicity / determinism contract as oa_bin (mode 0).
- * active_cols > 0 (Hermitian mode only): only columns < active_cols of each row are visited (planes that
- * vanish beyond them): sums are unchanged, COUNTS then cover the visited columns only -- take the
+ * With weights != NULL the binned value is multiplied by weights[i] and wsums replaces counts, as in oa_bin.
+ * active_cols > 0 (Hermitian mode only): only columns < active_cols of each row are binned, exactly -- whatever
+ * the planes hold at columns >= active_cols never reaches sums or counts (for planes that vanish beyond them the
+ * sums are unchanged); COUNTS then cover the visited columns only -- take the
  * data-independent counts from one full oa_bin_power / oa_bin call at plan time.  active_rows > 0 (with
- * active_cols): additionally only the rows of the band y < active_rows or y > ny - active_rows. */
+ * active_cols): additionally only the rows of the band y < active_rows or y > ny - active_rows.  active_cols >=
+ * herm_pitch is no limit at all: whole planes are binned and active_rows is ignored. */
 int oa_bin_power(int dtype, const void* k1, const void* k2, double norm, const int32_t* ids, const void* weights, long n,
                  int nids, long herm_pitch, int herm_nxh, double* sums, int64_t* counts, double* wsums, void* scratch, int active_cols, int active_rows,
                  void* stream);

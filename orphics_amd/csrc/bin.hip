@@ -150,7 +150,7 @@ __global__ __launch_bounds__(BIN_BLOCK) void bin_kernel(const T* __restrict__ da
                                                         const int32_t* __restrict__ ids,
                                                         const T* __restrict__ w, const double* __restrict__ aux, long n,
                                                         int nids, int mode, int skip_nan, unsigned hp, int nxh, unsigned wq,
-                                                        unsigned rb, double* __restrict__ part_sum, double* __restrict__ part_w,
+                                                        int acols, unsigned rb, double* __restrict__ part_sum, double* __restrict__ part_w,
                                                         unsigned long long* __restrict__ part_cnt, long dstride, long pstride) {
     // grid y = plane of a batch (oa_mc_run): data planes dstride elements apart, partial arrays pstride apart
     data += (long)blockIdx.y * dstride; data2 += (long)blockIdx.y * dstride;
@@ -166,8 +166,9 @@ __global__ __launch_bounds__(BIN_BLOCK) void bin_kernel(const T* __restrict__ da
     double* row_w = s_w + wv * nids;
     unsigned long long* row_cnt = s_cnt + wv * nids;
 
-    // wq > 0: visit only the first wq 4-element chunks of every row of pitch hp (active columns); rb > 0: and
-    // only the rows of the band |ky index| < rb, i.e. y < rb or y > ny - rb  (2 rb - 1 rows)
+    // wq > 0: visit only the first wq 4-element chunks of every row of pitch hp (active columns; of the last chunk only
+    // the columns < acols count); rb > 0: and only the rows of the band |ky index| < rb, i.e. y < rb or y > ny - rb
+    // (2 rb - 1 rows)
     const long nyf = n / hp;
     const long nrows = (wq && rb && 2L * rb - 1 < nyf) ? 2L * rb - 1 : nyf;
     // Hermitian (row-structured) planes: the chunks of a visited row are padded to a whole number of waves in the
@@ -230,6 +231,7 @@ __global__ __launch_bounds__(BIN_BLOCK) void bin_kernel(const T* __restrict__ da
             if (nxh >= 0) {
                 const int col = (int)col0 + j;
                 m = (col == 0 || col == nxh) ? 1 : (col < nxh ? 2 : 0);
+                if (wq && col >= acols) m = 0;     // the column limit falls inside the last visited chunk
             }
             ok[j] = ok[j] && id[j] >= 0 && id[j] < nids && m > 0;
             if (skip_nan && v[j] != v[j]) ok[j] = false;
@@ -395,7 +397,7 @@ static int bin_impl(const void* data, const void* data2, double pnorm, bool powe
             OA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                        (int)smem));                                                                  \
         hipLaunchKernelGGL(k, dim3(G, nbatch), dim3(BIN_BLOCK), smem, st, (const T*)data, (const T*)data2, pnorm, ids, \
-                           (const T*)weights, aux, n, nids, mode, skip_nan, (unsigned)(hp > 0 ? hp : 4), nxh, wq, rb, \
+                           (const T*)weights, aux, n, nids, mode, skip_nan, (unsigned)(hp > 0 ? hp : 4), nxh, wq, active_cols, rb, \
                            part_sum, part_w, part_cnt, dstride, pstride);                                            \
     }
     if (weighted && power) OA_BIN_LAUNCH(true, true)

@@ -136,8 +136,10 @@ def dev_bin(data, ids, nids, weights=None, aux=None, mode=0, skip_nan=False, her
     return sums, (counts if weights is None else wsums)
 
 
-def dev_bin_power(k1, k2, norm, ids, nids, herm_pitch=0, herm_nxh=-1, active_cols=0, active_rows=0):
-    """Binned Re(conj k1 k2)*norm without materialising the 2-D power (oa_bin_power).
+def dev_bin_power(k1, k2, norm, ids, nids, herm_pitch=0, herm_nxh=-1, active_cols=0, active_rows=0, weights=None):
+    """Binned Re(conj k1 k2)*norm without materialising the 2-D power (oa_bin_power); returns (sums f64[nids],
+    counts int64[nids]) or, with ``weights`` (one real value of the planes' precision per mode, multiplying the binned value),
+    (sums, wsums f64[nids]) as :func:`dev_bin` does.
     ``active_cols`` > 0: visit only those leading columns of each row (planes that vanish beyond them);
     ``active_rows`` > 0: and only the rows y < active_rows or y > ny - active_rows;
     the returned counts then cover the visited region only."""
@@ -148,6 +150,8 @@ def dev_bin_power(k1, k2, norm, ids, nids, herm_pitch=0, herm_nxh=-1, active_col
     if k2.numel() != n or ids.numel() != n or ids.dtype != torch.int32 or not (ids.is_contiguous() and k1.is_contiguous() and k2.is_contiguous()):
         raise ValueError("bin_power: operands must be contiguous with one int32 id per mode")
     prec = precision_of(k1, default=None)
+    if weights is not None and (weights.dtype != _RDT[prec] or weights.numel() != n or not weights.is_cuda or not weights.is_contiguous()):
+        raise ValueError("bin_power: weights must be contiguous real values of the planes' precision, one per mode")
     need = int(lib.oa_bin_scratch_bytes(int(nids)))
     key = (k1.device.index, torch.cuda.current_stream().cuda_stream)
     scr = _BIN_SCRATCH.get(key)
@@ -155,10 +159,11 @@ def dev_bin_power(k1, k2, norm, ids, nids, herm_pitch=0, herm_nxh=-1, active_col
         scr = torch.empty(need, dtype=torch.uint8, device=k1.device)
         _BIN_SCRATCH[key] = scr
     sums = torch.empty(nids, dtype=torch.float64, device=k1.device)
-    counts = torch.empty(nids, dtype=torch.int64, device=k1.device)
-    check(lib.oa_bin_power(_CODE[prec], _ptr(k1), _ptr(k2), float(norm), _ptr(ids), None, n, int(nids), int(herm_pitch),
-                           int(herm_nxh), _ptr(sums), _ptr(counts), None, _ptr(scr), int(active_cols), int(active_rows), _stream()))
-    return sums, counts
+    counts = torch.empty(nids, dtype=torch.int64, device=k1.device) if weights is None else None
+    wsums = torch.empty(nids, dtype=torch.float64, device=k1.device) if weights is not None else None
+    check(lib.oa_bin_power(_CODE[prec], _ptr(k1), _ptr(k2), float(norm), _ptr(ids), _ptr(weights), n, int(nids), int(herm_pitch),
+                           int(herm_nxh), _ptr(sums), _ptr(counts), _ptr(wsums), _ptr(scr), int(active_cols), int(active_rows), _stream()))
+    return sums, (counts if weights is None else wsums)
 
 
 BAND_MIN = 128      # smallest side of a band grid (pipeline.hip BAND_MIN)
@@ -560,7 +565,7 @@ class Engine(object):
         return dev_bin(data, ids, nids, weights=weights, aux=aux, mode=mode, skip_nan=skip_nan,
                        herm_pitch=self.kp if herm else 0, herm_nxh=self.nxh if herm else -1)
 
-    def bin_power(self, k1, k2, norm, ids, nids, herm=True, active_cols=0, active_rows=0):
+    def bin_power(self, k1, k2, norm, ids, nids, herm=True, active_cols=0, active_rows=0, weights=None):
         if herm and self.kp % 4 and tuple(k1.shape) == tuple(k2.shape) == tuple(ids.shape) == (self.ny, self.kp):
             # oa_bin_power moves four columns per lane and refuses a row pitch that is no multiple of 4 (nx/2 odd: 750 -> 375 + 16):
             # such planes are binned from copies padded to the next multiple, the padding ignored (id -1)
@@ -572,10 +577,12 @@ class Engine(object):
                 return o
             p1 = padded(k1, 0)
             p2 = p1 if k2 is k1 else padded(k2, 0)
+            if weights is not None and tuple(weights.shape) != (self.ny, self.kp):
+                raise ValueError("bin_power: weights must have the planes' shape")
             return dev_bin_power(p1, p2, norm, padded(ids, -1), nids, herm_pitch=kp4, herm_nxh=self.nxh, active_cols=active_cols,
-                                 active_rows=active_rows)
+                                 active_rows=active_rows, weights=None if weights is None else padded(weights, 0))
         return dev_bin_power(k1, k2, norm, ids, nids, herm_pitch=self.kp if herm else 0, herm_nxh=self.nxh if herm else -1,
-                             active_cols=active_cols if herm else 0, active_rows=active_rows if herm else 0)
+                             active_cols=active_cols if herm else 0, active_rows=active_rows if herm else 0, weights=weights)
 
     # ---- random fields / accumulators ---------------------------------------------------
     def grf_hc(self, seed, stream_id, covsqrt_hc=None, out=None, width=0, rband=0):
