@@ -464,7 +464,13 @@ int oa_fullreal_to_hc(oa_plan* p, const void* fullreal_in, void* hcreal_out, voi
  *                                                   MapGen covsqrt*rand scalar case, maps.py:1579)
  * oa_cmul       : out = k * f (complex * complex)   (filter_map with a complex kfilter, maps.py:1923)
  * oa_mul_real   : out = a * b (real)                (QE real-space product)
- * oa_axpby_real : out = alpha*a + beta*b (real)     (observed = beamed + noise, lensing.py:516) */
+ * oa_axpby_real : out = alpha*a + beta*b (real)     (observed = beamed + noise, lensing.py:516)
+ * norm, alpha and beta are rounded to the planes' precision first.  n = 0 launches nothing that writes; elements at and beyond n are
+ * never touched.  ALIGNMENT: oa_f2power, oa_cmul_real, oa_mul_real and oa_axpby_real move 16 bytes per access, so each of their three
+ * pointers must be 16-byte aligned (any whole device allocation is; a view that starts at an odd element is not): a misaligned pointer
+ * is refused before anything is launched, oa_last_error set.  oa_cmul and oa_rot2 need only the natural alignment of an element.
+ * ALIASING: out may be one of the inputs (every element is read before it is written, by the same lane); partial overlaps are not
+ * supported. */
 int oa_f2power(int dtype, const void* k1, const void* k2, void* out_real, double norm, long n, void* stream);
 int oa_cmul_real(int dtype, const void* k_in, const void* filt_real, void* k_out, long n, void* stream);
 int oa_cmul(int dtype, const void* k_in, const void* filt_complex, void* k_out, long n, void* stream);
@@ -492,7 +498,11 @@ int oa_qe_div(oa_plan* p, const void* Px, const void* Py, const void* Fnorm, voi
  * oa_lens_split  : shift[i] = rint(alpha[i]/step), delta[i] = alpha[i] - shift[i]*step (nearest pixel +
  *                  sub-pixel remainder of a displacement component; lensing.py:420-424)
  * oa_lens_gather : out[y,x] (+)= coef * src[(y+sy) mod ny, (x+sx) mod nx] * dx^pow_x * dy^pow_y
- *                  (integer-pixel remap and one Taylor term, lensing.py:428-438) */
+ *                  (integer-pixel remap and one Taylor term, lensing.py:428-438)
+ * step is rounded to the planes' precision first; rint rounds ties to even.  VALID RANGE: oa_lens_split needs finite alpha with
+ * |alpha / step| < 2^31 (the shift is stored as int32; beyond that, and for NaN, it is undefined); oa_lens_gather / oa_lens_taylor /
+ * oa_lens_maps accept any shift with |shift| + max(ny, nx) < 2^31 (the index y + shift_y is formed in int32 before the wrap), of
+ * either sign and any number of wraps of the map.  0 <= pow_x, pow_y, pow_x + pow_y <= 16; src != out. */
 int oa_lens_split(int dtype, const void* alpha, double step, int32_t* shift, void* delta, long n, void* stream);
 int oa_lens_gather(oa_plan* p, const void* src, const int32_t* shift_x, const int32_t* shift_y, const void* dx, const void* dy,
                    int pow_x, int pow_y, double coef, void* out, int accumulate, void* stream);

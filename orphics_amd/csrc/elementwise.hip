@@ -27,9 +27,10 @@ __global__ __launch_bounds__(256) void f2power_kernel(const cx<T>* __restrict__ 
     if (t0 < n) out[t0] = (k1[t0].x * k2[t0].x + k1[t0].y * k2[t0].y) * norm;
 }
 
-// out = k * f, both complex (filter_map with a complex k-space filter, maps.py:1923)
+// out = k * f, both complex (filter_map with a complex k-space filter, maps.py:1923).  k and out carry no __restrict__: filter_map
+// runs this in place (out == k), every element read before it is written by the same lane
 template <typename T>
-__global__ __launch_bounds__(256) void cmul_kernel(const cx<T>* __restrict__ k, const cx<T>* __restrict__ f, cx<T>* __restrict__ out, long n) {
+__global__ __launch_bounds__(256) void cmul_kernel(const cx<T>* k, const cx<T>* __restrict__ f, cx<T>* out, long n) {
     const long stride = (long)gridDim.x * blockDim.x;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const cx<T> a = k[i], b = f[i];
@@ -37,9 +38,9 @@ __global__ __launch_bounds__(256) void cmul_kernel(const cx<T>* __restrict__ k, 
     }
 }
 
+// k and out carry no __restrict__: the library's filters run this in place (out == k)
 template <typename T>
-__global__ __launch_bounds__(256) void cmul_real_kernel(const cx<T>* __restrict__ k, const T* __restrict__ f,
-                                                        cx<T>* __restrict__ out, long n4, long n) {
+__global__ __launch_bounds__(256) void cmul_real_kernel(const cx<T>* k, const T* __restrict__ f, cx<T>* out, long n4, long n) {
     const long stride = (long)gridDim.x * blockDim.x;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         const Arr<T, 8> a = reinterpret_cast<const Arr<T, 8>*>(k)[i];
@@ -56,9 +57,9 @@ __global__ __launch_bounds__(256) void cmul_real_kernel(const cx<T>* __restrict_
     if (t0 < n) out[t0] = k[t0] * f[t0];
 }
 
+// no __restrict__: the estimators run this in place (out == a: mul_real(gx, h, out=gx); out == b: axpby(gx, ax, s, 1, out=ax))
 template <typename T>
-__global__ __launch_bounds__(256) void axpby_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ out,
-                                                    T alpha, T beta, int mul, long n4, long n) {
+__global__ __launch_bounds__(256) void axpby_kernel(const T* a, const T* b, T* out, T alpha, T beta, int mul, long n4, long n) {
     const long stride = (long)gridDim.x * blockDim.x;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         const Arr<T, 4> x = reinterpret_cast<const Arr<T, 4>*>(a)[i];
@@ -481,10 +482,16 @@ using namespace oa;
 #define DISPATCH(dtype, CALL_F, CALL_D) \
     if ((dtype) == OA_F32) { CALL_F; } else if ((dtype) == OA_F64) { CALL_D; } else return fail("bad dtype")
 
+// the vectorised flat kernels move 16 bytes per access (Arr<T, 4 / 8>)
+static inline bool aligned16(const void* a, const void* b, const void* c) {
+    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
+}
+
 extern "C" {
 
 int oa_f2power(int dtype, const void* k1, const void* k2, void* out, double norm, long n, void* stream) {
     OA_REQUIRE(k1 && k2 && out && n >= 0, "oa_f2power: bad argument");
+    OA_REQUIRE(aligned16(k1, k2, out), "oa_f2power: pointers must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const long n4 = n / EW;
     const int g = flat_grid(n4 > 0 ? n4 : 1);
@@ -516,6 +523,7 @@ int oa_split_cross_power(int dtype, int nsplits, const void* const* host_kappa, 
 
 int oa_cmul_real(int dtype, const void* k, const void* f, void* out, long n, void* stream) {
     OA_REQUIRE(k && f && out && n >= 0, "oa_cmul_real: bad argument");
+    OA_REQUIRE(aligned16(k, f, out), "oa_cmul_real: pointers must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const long n4 = n / EW;
     const int g = flat_grid(n4 > 0 ? n4 : 1);
@@ -541,6 +549,7 @@ int oa_cmul(int dtype, const void* k, const void* f, void* out, long n, void* st
 
 int oa_mul_real(int dtype, const void* a, const void* b, void* out, long n, void* stream) {
     OA_REQUIRE(a && b && out && n >= 0, "oa_mul_real: bad argument");
+    OA_REQUIRE(aligned16(a, b, out), "oa_mul_real: pointers must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const long n4 = n / EW;
     const int g = flat_grid(n4 > 0 ? n4 : 1);
@@ -555,6 +564,7 @@ int oa_mul_real(int dtype, const void* a, const void* b, void* out, long n, void
 
 int oa_axpby_real(int dtype, const void* a, const void* b, void* out, double alpha, double beta, long n, void* stream) {
     OA_REQUIRE(a && b && out && n >= 0, "oa_axpby_real: bad argument");
+    OA_REQUIRE(aligned16(a, b, out), "oa_axpby_real: pointers must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const long n4 = n / EW;
     const int g = flat_grid(n4 > 0 ? n4 : 1);

@@ -418,17 +418,28 @@ class Engine(object):
 
     # ---- flat elementwise ---------------------------------------------------------
     def _same(self, *ts):
+        for t in ts:
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous()):
+                raise ValueError("elementwise operands must be contiguous CUDA tensors of equal size")
         n = ts[0].numel()
         for t in ts:
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.numel() == n):
+            if t.numel() != n or t.device != ts[0].device:
                 raise ValueError("elementwise operands must be contiguous CUDA tensors of equal size")
         return n
+
+    def _out(self, out, like, dtype, what):
+        """an ``out=`` plane is written with ``like.numel()`` elements of ``dtype``: anything else is refused here, before the library
+        is called (a short plane would be written past its end)"""
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == like.device and out.is_contiguous()
+                and out.dtype == dtype and out.numel() == like.numel()):
+            raise ValueError("%s: out must be a contiguous %s CUDA tensor of %d elements on %s" % (what, dtype, like.numel(), like.device))
+        return _dirty(out)
 
     def f2power(self, k1, k2, norm, out=None):
         n = self._same(k1, k2)
         if k1.dtype != self.cdt or k2.dtype != self.cdt:
             raise ValueError("f2power: complex dtype mismatch")
-        out = torch.empty(k1.shape, dtype=self.rdt, device=self.device) if out is None else _dirty(out)
+        out = torch.empty(k1.shape, dtype=self.rdt, device=self.device) if out is None else self._out(out, k1, self.rdt, "f2power")
         check(self.lib.oa_f2power(self.code, _ptr(k1), _ptr(k2), _ptr(out), float(norm), n, _stream()))
         return out
 
@@ -436,7 +447,7 @@ class Engine(object):
         n = self._same(k, f)
         if k.dtype != self.cdt or f.dtype != self.rdt:
             raise ValueError("cmul_real: dtype mismatch")
-        out = torch.empty_like(k) if out is None else _dirty(out)
+        out = torch.empty_like(k) if out is None else self._out(out, k, self.cdt, "cmul_real")
         check(self.lib.oa_cmul_real(self.code, _ptr(k), _ptr(f), _ptr(out), n, _stream()))
         return out
 
@@ -445,7 +456,7 @@ class Engine(object):
         n = self._same(k, f)
         if k.dtype != self.cdt or f.dtype != self.cdt:
             raise ValueError("cmul: dtype mismatch")
-        out = torch.empty_like(k) if out is None else _dirty(out)
+        out = torch.empty_like(k) if out is None else self._out(out, k, self.cdt, "cmul")
         check(self.lib.oa_cmul(self.code, _ptr(k), _ptr(f), _ptr(out), n, _stream()))
         return out
 
@@ -453,7 +464,7 @@ class Engine(object):
         n = self._same(a, b)
         if a.dtype != self.rdt or b.dtype != self.rdt:
             raise ValueError("mul_real: dtype mismatch")
-        out = torch.empty_like(a) if out is None else _dirty(out)
+        out = torch.empty_like(a) if out is None else self._out(out, a, self.rdt, "mul_real")
         check(self.lib.oa_mul_real(self.code, _ptr(a), _ptr(b), _ptr(out), n, _stream()))
         return out
 
@@ -461,7 +472,7 @@ class Engine(object):
         n = self._same(a, b)
         if a.dtype != self.rdt or b.dtype != self.rdt:
             raise ValueError("axpby: dtype mismatch")
-        out = torch.empty_like(a) if out is None else _dirty(out)
+        out = torch.empty_like(a) if out is None else self._out(out, a, self.rdt, "axpby")
         check(self.lib.oa_axpby_real(self.code, _ptr(a), _ptr(b), _ptr(out), float(alpha), float(beta), n, _stream()))
         return out
 
@@ -538,9 +549,16 @@ class Engine(object):
         return shift, delta
 
     def lens_gather(self, src, sx, sy, dx, dy, px, py, coef, out, accumulate):
+        for t in (src, out, dx, dy):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == self.device):
+                raise ValueError("lens_gather: maps must be CUDA tensors on %s" % (self.device,))
         self._chk(src, "real"); _dirty(self._chk(out, "real")); self._chk(dx, "real"); self._chk(dy, "real")
-        if sx.dtype != torch.int32 or sy.dtype != torch.int32 or sx.numel() != src.numel() or sy.numel() != src.numel():
-            raise ValueError("lens_gather: shifts must be int32 planes")
+        for s in (sx, sy):
+            if not (isinstance(s, torch.Tensor) and s.is_cuda and s.device == src.device and s.is_contiguous() and s.dtype == torch.int32
+                    and s.numel() == src.numel()):
+                raise ValueError("lens_gather: shifts must be contiguous int32 CUDA planes of the map's size")
+        if out.data_ptr() == src.data_ptr():
+            raise ValueError("lens_gather: in-place not supported")
         check(self.lib.oa_lens_gather(self.plan, _ptr(src), _ptr(sx), _ptr(sy), _ptr(dx), _ptr(dy), int(px), int(py),
                                       float(coef), _ptr(out), 1 if accumulate else 0, _stream()))
         return out
