@@ -43,7 +43,7 @@ typedef struct oa_plan oa_plan;
 const char* oa_last_error(void);
 /* ABI version = 100 x the build round that last changed a signature in this header; bindings must refuse a library
  * that reports less than the version they were written against (OA_ABI_VERSION) */
-#define OA_ABI_VERSION 409
+#define OA_ABI_VERSION 410
 int oa_version(void);
 /* number of HIP devices visible; <0 on error (no compute) */
 int oa_device_count(void);
@@ -207,7 +207,7 @@ int oa_plan_col_grid(const oa_plan* p);
  * leg rows), the Monte-Carlo draw (the leg band of oa_grf_hc's N-grid draw, same Philox counters) and the scatter of kappa's band
  * into the N-grid output / mean-field stack see the map's grid.  oa_qe_tt_splits runs there too, and oa_qe_tt_split_power is the
  * split-based estimator evaluated on the inner grid (both below, at their declarations); oa_mc_run_windowed runs there behind a
- * full-plane N-grid front end (at its declaration); oa_qe_tt_stage and oa_mc_run_mv_windowed stay power-of-two only.  oa_plan_band_grid reports (My, Mx), or (0, 0) when no band grid is bound.
+ * full-plane N-grid front end (at its declaration); oa_mc_run_mv_windowed runs there behind oa_qe_band_bind + oa_mc_mv_band_bind (at its declaration); oa_qe_tt_stage stays power-of-two only.  oa_plan_band_grid reports (My, Mx), or (0, 0) when no band grid is bound.
  * oa_qe_pol / oa_qe_mv ON A BAND GRID.  The band-limit argument does not depend on the estimator (every separable piece is a product of
  * fields confined to the leg band; the cos / sin 2 phi_ell factors live on the same ell lattice, so a copy of their band is exact), but
  * these two entries take their planes per call, and a stream-ordered call may neither allocate nor synchronise.  oa_qe_band_bind is
@@ -398,8 +398,8 @@ int oa_mc_run_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const
  *   rot_c, rot_s    (ny, kpitch) hc-real planes cos / sin 2 phi_l, as oa_qe_mv_maps takes them (needed with a window);
  *   host_meanfield  NULL, or a host array of nest (+ 1 when mv_weights is given) device float64 planes (ny, kpitch, 2): the sums of the
  *                   per-estimator kappa_hat in estimator order, then of the MV combination sum_e w_e kappa_hat_e.
- * POWER-OF-TWO PLANS ONLY: a 2^a 3^b 5^c or chirp-z plan is refused before anything is launched (n, S, C and the stacks untouched), naming
- * this entry and the host loop mc.GaussianN0MonteCarloPol runs with one_call=False.
+ * POWER-OF-TWO PLANS, AND 2^a 3^b 5^c PLANS ON THEIR BAND GRID (below).  A chirp-z plan is refused before anything is launched (n, S, C and
+ * the stacks untouched), naming this entry and the host loop mc.GaussianN0MonteCarloPol runs with one_call=False.
  * The window multiplies Q and U, not E and B: a taper leaks E into B.  Per realisation i, stream-ordered, nothing leaving the device:
  * without a window, step 1 is oa_mc_run_mv's band draw (the moments are then oa_mc_run_mv's bit for bit); with one it is
  *   a. the full-plane oa_grf_mix draw of T, E, B (streams 3 i .. 3 i + 2: the counters of the band draw, so window == 1 reproduces the
@@ -417,7 +417,21 @@ int oa_mc_run_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const
  * Realisation i's contribution to n, S, C and the stacks does not depend on how a range is cut into calls.  The entry's planes (three draw
  * planes, one column temporary per plane, the compact row planes) are taken by the first windowed call, which synchronises the device
  * once; oa_plan_release_pools frees them.  Refused before anything is launched: a window without rot_c / rot_s, a NULL stack plane, and
- * every refusal of oa_mc_run_mv. */
+ * every refusal of oa_mc_run_mv.
+ * ON A BAND GRID (2^a 3^b 5^c plans): the two bindings of oa_mc_run_mv (oa_qe_band_bind, then oa_mc_mv_band_bind) and its lookups and
+ * refusals, every message naming this entry, mc.GaussianN0MonteCarloPol and one_call=False.  Steps 2-4 run on the inner plan.  The source
+ * stage of a windowed realisation runs on the N grid: a. as above (three N-grid hc planes the entry owns); then ONE inverse mixed-radix
+ * column launch over the three planes in place (grid y = plane), ONE fused row launch over them (C2R / Npix -> x window -> R2C, leg_cols
+ * columns stored), and the pruned column DFT of the three row planes with the fold that rotates Q, U -> E, B in double before the one
+ * rounding -- straight onto the three inner source planes.  OA_OPT_WIN_FUSED = 0: oa_fft_c2r_windowed per plane onto a real map in an
+ * entry-owned plane, then the batched band input transform of oa_qe_mv_maps over the three maps with the rotation.  Until the option is
+ * set (or after a value < 0) the plan takes oa_mc_run_windowed's rule: unfused for rows of up to 1200 points, fused for longer ones; rows
+ * of more than 8192 points are always unfused.  Without a window step 1 is oa_grf_mix_band_inner: oa_mc_run_mv's moments bit for bit.  The
+ * stacks stay N-grid planes: one launch per realisation reads the nest kappa_hat values of a mode of kappa's band from the inner planes
+ * (and the inner copies of the weights) and adds them at the N grid's row and pitch; one owner per mode, no atomics.  The first windowed
+ * call takes the N-grid planes (three draws, three real maps, the band input transform's scratch for three maps) with one device
+ * synchronisation; they are regrown when the band widens, dropped when the binding's inner plan is remade, and freed by
+ * oa_plan_release_pools.  After that the entry neither allocates nor synchronises. */
 int oa_mc_run_mv_windowed(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest,
                           const int* host_npieces, const double* host_signs, const void* const* host_FG, const void* const* host_FH,
                           const int* host_swap, const int* host_xsrc, const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights,

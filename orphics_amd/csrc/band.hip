@@ -227,7 +227,9 @@ static int maps_r2c_t(oa_plan* p, int nmaps, const void* const* maps, const void
 }
 // FRONT END of oa_mc_run_windowed on these sides (body: fft_band.hpp band_rows_win_body): the fused windowed row pass of B realisations in one
 // launch, then the pruned column DFT with the realisations in the place of maps and no rotation (batched: band_colsn_kernel +
-// band_cols_fold_kernel on the layout of band_maps_scratch_bytes; single: band_cols_kernel + band_cols_sum on band_map_scratch_bytes')
+// band_cols_fold_kernel on the layout of band_maps_scratch_bytes; single: band_cols_kernel + band_cols_sum on band_map_scratch_bytes').
+// oa_mc_run_mv_windowed passes the T, Q, U planes of ONE realisation as the batch (B = 3) and rot_c / rot_s: the fold then rotates the
+// pair (1, 2) Q, U -> E, B, as for band_maps_r2c.
 template <typename T>
 __global__ __launch_bounds__(BRW_NT, waves_per_eu<T>()) void band_rows_win_kernel(BandRowsWinArgs<T> a) {
     GpuCtx c{oa_dyn_smem};
@@ -235,7 +237,7 @@ __global__ __launch_bounds__(BRW_NT, waves_per_eu<T>()) void band_rows_win_kerne
 }
 template <typename T>
 static int win_r2c_t(oa_plan* p, int B, const void* hc_in, long in_bstride, const void* window, double scale, void* scratch, int single, int wl,
-                     int rl, void* dst, long dstride, int dny, long dkp, hipStream_t st) {
+                     int rl, const void* rot_c, const void* rot_s, void* dst, long dstride, int dny, long dkp, hipStream_t st) {
     const int N = p->nx / 2;
     int rc = 0;
     BandRowsWinArgs<T> ra{};
@@ -245,17 +247,18 @@ static int win_r2c_t(oa_plan* p, int B, const void* hc_in, long in_bstride, cons
     launch_go(rc, st, band_rows_win_kernel<T>, dim3(p->ny, B), BRW_NT, band_rows_lds<T>(N), ra);
     if (rc) return rc;
     if (single) return cols_single_t<T>(p, scratch, wl, rl, dst, dny, dkp, st);
-    return cols_batched_t<T>(p, B, scratch, wl, rl, nullptr, nullptr, dst, dstride, dny, dkp, st);
+    return cols_batched_t<T>(p, B, scratch, wl, rl, rot_c, rot_s, dst, dstride, dny, dkp, st);
 }
 bool band_rows_win_ok(const oa_plan* p) { return band_rows_win_fits(p->nx / 2); }
 int band_win_r2c(oa_plan* p, int B, const void* hc_in, long in_bstride, const void* window, double scale, void* scratch, int single, int wl, int rl,
-                 void* dst, long dstride, int dny, long dkp, hipStream_t st) {
+                 const void* rot_c, const void* rot_s, void* dst, long dstride, int dny, long dkp, hipStream_t st) {
     OA_REQUIRE(p->mixed && wl >= 1 && wl <= p->nx / 2 && rl >= 1 && 2 * rl - 1 <= std::min(p->ny, dny), "band windowed front end: bad band");
     OA_REQUIRE(B >= 1 && B <= BAND_MAPS_MAX && (!single || B == 1) && wl <= dkp && (B == 1 || (long)dny * dkp <= dstride) &&
                (B == 1 || (long)p->ny * p->kp <= in_bstride), "band windowed front end: bad planes");
     OA_REQUIRE(band_rows_win_fits(p->nx / 2), "band windowed front end: map rows longer than 8192 points");
-    return p->dtype == OA_F32 ? win_r2c_t<float>(p, B, hc_in, in_bstride, window, scale, scratch, single, wl, rl, dst, dstride, dny, dkp, st)
-                              : win_r2c_t<double>(p, B, hc_in, in_bstride, window, scale, scratch, single, wl, rl, dst, dstride, dny, dkp, st);
+    OA_REQUIRE((!rot_c && !rot_s) || (rot_c && rot_s && !single && (B == 3 || B == 6) && wl <= p->kp), "band windowed front end: bad rotation planes");
+    return p->dtype == OA_F32 ? win_r2c_t<float>(p, B, hc_in, in_bstride, window, scale, scratch, single, wl, rl, rot_c, rot_s, dst, dstride, dny, dkp, st)
+                              : win_r2c_t<double>(p, B, hc_in, in_bstride, window, scale, scratch, single, wl, rl, rot_c, rot_s, dst, dstride, dny, dkp, st);
 }
 int band_maps_r2c(oa_plan* p, int nmaps, const void* const* maps, const void* rot_c, const void* rot_s, void* scratch, int wl, int rl, void* dst,
                   long dstride, int dny, long dkp, hipStream_t st) {

@@ -126,6 +126,12 @@ int stack_add_region_multi(int dtype, const void* k, long kstride, const void* w
                            int ny, long kp, int w, int rb, hipStream_t st);
 int grf_mix_teb_to_tqu(oa_plan* p, uint64_t seed, uint64_t sid0, const void* const* cs, const void* rot_c, const void* rot_s, void* const* out,
                        hipStream_t st);
+// ... on a band grid: k and wt are inner-layout planes (iny rows, ipitch elements per row), the stacks N-grid planes (any rows, apitch
+// complex per row); band: columns < w, rows |ky| < r
+int band_stack_add_multi(int dtype, const void* k, long kstride, const void* wt, long wstride, int nest, double* const* acc, double* acc_mv,
+                         int iny, long ipitch, int any, long apitch, int w, int r, hipStream_t st);
+// the unscaled inverse column transform of nplanes hc planes pstride complex elements apart, in place, ONE launch (grid y = plane)
+int mixed_cols_inverse_batch(oa_plan* p, int nplanes, void* hc, long pstride, hipStream_t st);
 // my > 0: COLUMN GRID -- legs, row stage and divergence run on my < ny rows (plan_ensure_col_grid(p, my) first)
 int plan_ensure_col_grid(oa_plan* p, int my);
 // lr > 0 (qe_rsplit_lr): R-SPLIT path -- row R2C with the first radix-R column butterfly, then one single-pass column kernel;
@@ -203,9 +209,10 @@ size_t band_maps_scratch_bytes(const oa_plan* p, int nmaps, int wl, int rl);
 // FRONT END of oa_mc_run_windowed on these sides: B <= 6 inverse-column-transformed spectra (N-grid hc planes in_bstride elements apart)
 // -> fused C2R x window x scale -> R2C rows (the real map in LDS only) -> pruned column DFT onto B inner planes dstride elements apart.
 // single = 0: the batched kernels, scratch of band_maps_scratch_bytes(p, B, wl, rl); single != 0 (B = 1): band_map_r2c's column
-// kernels, scratch of band_map_scratch_bytes(p, wl, rl)
+// kernels, scratch of band_map_scratch_bytes(p, wl, rl).  rot_c / rot_s (both or neither; batched, B = 3 or 6): the planes are T, Q, U
+// and the fold rotates the pairs (1, 2) / (4, 5) Q, U -> E, B as band_maps_r2c does (oa_mc_run_mv_windowed)
 int band_win_r2c(oa_plan* p, int B, const void* hc_in, long in_bstride, const void* window, double scale, void* scratch, int single, int wl, int rl,
-                 void* dst, long dstride, int dny, long dkp, hipStream_t st);
+                 const void* rot_c, const void* rot_s, void* dst, long dstride, int dny, long dkp, hipStream_t st);
 bool band_rows_win_ok(const oa_plan* p);                 // the fused windowed row kernel holds a row of this plan (nx <= 8192)
 int band_copy(int kind, const void* src, long spitch, int sny, void* dst, long dpitch, int dny, int w, int r, double scale, hipStream_t st);
 int band_zero_outside(int dtype, void* out, int ny, long kp, int w, int r, hipStream_t st);

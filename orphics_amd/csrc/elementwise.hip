@@ -464,6 +464,32 @@ int stack_add_region_multi(int dtype, const void* k, long kstride, const void* w
     return dtype == OA_F32 ? stack_multi_t<float>(k, kstride, wt, wstride, nest, acc, acc_mv, ny, kp, w, rb, st)
                            : stack_multi_t<double>(k, kstride, wt, wstride, nest, acc, acc_mv, ny, kp, w, rb, st);
 }
+// the same stacks from the inner planes of a band grid (mc_pol.hpp band_stack_add_multi_body): k and wt in the inner layout (iny rows,
+// ipitch elements per row), the float64 stacks on the N grid (any rows, apitch complex per row); band: columns < w, rows |ky| < r
+template <typename T>
+__global__ __launch_bounds__(256) void band_stack_add_multi_kernel(BandStackMultiArgs<T> a) {
+    ModeCtx c;
+    band_stack_add_multi_body<T>(c, a);
+}
+template <typename T>
+static int band_stack_multi_t(const void* k, long kstride, const void* wt, long wstride, int nest, double* const* acc, double* acc_mv, int iny,
+                              long ipitch, int any, long apitch, int w, int r, hipStream_t st) {
+    BandStackMultiArgs<T> a{};
+    a.k = (const cx<T>*)k; a.kstride = kstride; a.wt = acc_mv ? (const T*)wt : nullptr; a.wstride = wstride;
+    for (int e = 0; e < nest; ++e) a.acc[e] = (cx<double>*)acc[e];
+    a.acc_mv = (cx<double>*)acc_mv;
+    a.ipitch = ipitch; a.iny = iny; a.apitch = apitch; a.any = any; a.nest = nest; a.w = w; a.r = r;
+    hipLaunchKernelGGL(band_stack_add_multi_kernel<T>, dim3((w + 255) / 256, 2 * r - 1), dim3(256), 0, st, a);
+    OA_LAUNCH_CHECK();
+    return 0;
+}
+int band_stack_add_multi(int dtype, const void* k, long kstride, const void* wt, long wstride, int nest, double* const* acc, double* acc_mv,
+                         int iny, long ipitch, int any, long apitch, int w, int r, hipStream_t st) {
+    OA_REQUIRE(k && acc && nest >= 1 && nest <= STACK_MULTI_MAX && (!acc_mv || wt), "band_stack_add_multi: bad argument");
+    OA_REQUIRE(w >= 1 && r >= 1 && 2L * r - 1 <= (iny < any ? iny : any) && w <= ipitch && w <= apitch, "band_stack_add_multi: bad band");
+    return dtype == OA_F32 ? band_stack_multi_t<float>(k, kstride, wt, wstride, nest, acc, acc_mv, iny, ipitch, any, apitch, w, r, st)
+                           : band_stack_multi_t<double>(k, kstride, wt, wstride, nest, acc, acc_mv, iny, ipitch, any, apitch, w, r, st);
+}
 // mean-field stack of the one-call Monte-Carlo driver (pipeline.hip)
 int stack_add_region(int dtype, const void* x, double* acc, int ny, long kp, int w, int rb, hipStream_t st, int nbatch, long xstride) {
     // xstride: real elements between the planes of a batch

@@ -291,9 +291,11 @@ struct MrColArgs {
     int inverse;
     const T* dly;                    // != nullptr: the input is multiplied by (i ly[n])^dpow at the load (y-derivative of a field's transform)
     int dpow;
+    long in_pstride, out_pstride;    // BATCH of planes on grid y: plane b at in + b * in_pstride -> out + b * out_pstride (0, grid y = 1: one plane)
 };
 
-// a tile of C adjacent columns per workgroup, transformed along y; IP: the in-place stages (one [N][C] buffer)
+// a tile of C adjacent columns per workgroup, transformed along y; IP: the in-place stages (one [N][C] buffer).  Grid y = plane of a
+// batch: a workgroup's LDS is that of the single-plane launch.
 template <typename T, bool IP = false, class Ctx>
 OA_HD void mr_col_body(Ctx& ctx, const MrColArgs<T>& a) {
     cx<T>* b0 = reinterpret_cast<cx<T>*>(ctx.smem());
@@ -301,13 +303,15 @@ OA_HD void mr_col_body(Ctx& ctx, const MrColArgs<T>& a) {
     cx<T>* b1 = IP ? b0 : b0 + (long)N * C;
     const int tid = ctx.tid(), NT = ctx.nthreads();
     const int c0 = ctx.bid_x() << a.logC;
+    const cx<T>* const in = a.in + ctx.bid_y() * a.in_pstride;
+    cx<T>* const out = a.out + ctx.bid_y() * a.out_pstride;
     int ncols = a.width - c0;
     if (ncols > C) ncols = C;
     const bool inv = a.inverse != 0;
     for (int i = tid; i < N * C; i += NT) {
         const int c = i & (C - 1), n = i >> a.logC;
         cx<T> v = mk<T>((T)0, (T)0);
-        if (c < ncols) v = a.in[(long)n * a.in_pitch + c0 + c];
+        if (c < ncols) v = in[(long)n * a.in_pitch + c0 + c];
         if (a.dly) {
             T f = (T)1;
             const T l = a.dly[n];
@@ -320,7 +324,7 @@ OA_HD void mr_col_body(Ctx& ctx, const MrColArgs<T>& a) {
     const cx<T>* r = mr_run<T, IP>(ctx, b0, b1, N, a.f, a.logC, a.tw, tid, NT);
     for (int i = tid; i < N * C; i += NT) {
         const int c = i & (C - 1), n = i >> a.logC;
-        if (c < ncols) { const cx<T> v = r[i] * a.scale; a.out[(long)n * a.out_pitch + c0 + c] = inv ? swp(v) : v; }
+        if (c < ncols) { const cx<T> v = r[i] * a.scale; out[(long)n * a.out_pitch + c0 + c] = inv ? swp(v) : v; }
     }
 }
 

@@ -1,5 +1,6 @@
 // Per-mode bodies of oa_mc_run_mv_windowed (pipeline.hip) that are not FFT passes: the Q,U -> E,B rotation on the leg band and the
-// mean-field stack of an estimator set.  Shared by the HIP launchers (elementwise.hip) and the CPU emulator (tests/emul/emul_win3.cpp).
+// mean-field stack of an estimator set, on the plan's own grid and from the inner planes of a band grid.  Shared by the HIP launchers
+// (elementwise.hip) and the CPU emulator (tests/emul/emul_win3.cpp, tests/emul/emul_band_mf.cpp).
 #pragma once
 #include "cx.hpp"
 
@@ -69,6 +70,47 @@ OA_HD void stack_add_region_multi_body(Ctx& ctx, const StackMultiArgs<T>& a) {
     if (a.wt) {
         const cx<double> s = a.acc_mv[at];
         a.acc_mv[at] = mk<double>(s.x + mr, s.y + mi);
+    }
+}
+
+// The same stacks when kappa_hat lives on the INNER grid of a band grid (oa_mc_run_mv_windowed on map sides 2^a 3^b 5^c): the nest
+// kappa_hat planes and the weights (the Monte-Carlo binding's inner-layout copies) are read at the inner pitch and row -- band row i of
+// 0 .. 2 r - 2 sits at row i (i < r) or i - (2 r - 1) + rows of either grid --, the float64 stacks are the N grid's.  One thread per mode
+// of kappa's band, lanes along columns; one owner per mode: no atomics, the same sums however a range of realisations is cut into calls.
+template <typename T>
+struct BandStackMultiArgs {
+    const cx<T>* k;  long kstride;     // nest inner kappa_hat planes, kstride complex elements apart
+    const T* wt;     long wstride;     // nest inner MV weight planes (real), wstride elements apart; nullptr: no MV stack
+    cx<double>* acc[STACK_MULTI_MAX];  // the estimators' N-grid stacks
+    cx<double>* acc_mv;                // the N-grid MV stack (with wt)
+    long ipitch;     int iny;          // inner planes: row pitch (elements of their own type), rows
+    long apitch;     int any;          // N-grid stacks: row pitch (complex elements), rows
+    int nest, w, r;                    // band: columns < w, rows |ky| < r (r >= 1)
+};
+template <typename T, class Ctx>
+OA_HD void band_stack_add_multi_body(Ctx& ctx, const BandStackMultiArgs<T>& a) {
+    const int x = ctx.bid_x() * ctx.nthreads() + ctx.tid();
+    if (x >= a.w) return;
+    const int i = ctx.bid_y();
+    const long src = (long)band_row_of(i, a.r, a.iny) * a.ipitch + x, dst = (long)band_row_of(i, a.r, a.any) * a.apitch + x;
+    double mr = 0.0, mi = 0.0;
+#pragma unroll
+    for (int e = 0; e < STACK_MULTI_MAX; ++e) {
+        if (e < a.nest) {
+            const cx<T> v = a.k[src + e * a.kstride];
+            const double vr = (double)v.x, vi = (double)v.y;
+            const cx<double> s = a.acc[e][dst];
+            a.acc[e][dst] = mk<double>(s.x + vr, s.y + vi);
+            if (a.wt) {
+                const double ww = (double)a.wt[src + e * a.wstride];
+                mr += ww * vr;
+                mi += ww * vi;
+            }
+        }
+    }
+    if (a.wt) {
+        const cx<double> s = a.acc_mv[dst];
+        a.acc_mv[dst] = mk<double>(s.x + mr, s.y + mi);
     }
 }
 

@@ -73,16 +73,16 @@ static int rows(oa_plan* p, int mode, const void* in, long ipitch, void* out, lo
 }
 template <typename T>
 static int cols(oa_plan* p, const void* in, long ipitch, void* out, long opitch, int width, bool inverse, double scale, hipStream_t st,
-                const T* dly = nullptr, int dpow = 0) {
+                const T* dly = nullptr, int dpow = 0, int nplanes = 1, long in_pstride = 0, long out_pstride = 0) {
     MrColArgs<T> a{};
-    a.dly = dly; a.dpow = dpow;
+    a.dly = dly; a.dpow = dpow; a.in_pstride = in_pstride; a.out_pstride = out_pstride;
     a.in = (const cx<T>*)in; a.out = (cx<T>*)out; a.in_pitch = ipitch; a.out_pitch = opitch; a.N = p->ny; a.width = width;
     a.logC = mr_col_logc<T>(p->ny); a.f = mixed_factor(p->ny); a.tw = (const cx<T>*)p->mr_twy; a.scale = (T)scale; a.inverse = inverse ? 1 : 0;
     const int C = 1 << a.logC;
     int rc = 0;
-    if (mr_col_lds<T>(p->ny, a.logC) <= LDS_MAX) launch_go(rc, st, mr_col_kernel<T>, dim3((width + C - 1) / C), 256, mr_col_lds<T>(p->ny, a.logC), a);
+    if (mr_col_lds<T>(p->ny, a.logC) <= LDS_MAX) launch_go(rc, st, mr_col_kernel<T>, dim3((width + C - 1) / C, nplanes), 256, mr_col_lds<T>(p->ny, a.logC), a);
     else if (a.logC == 0 && mr_ip_fits(a.f, p->ny, 0, MR_IP_NT))
-        launch_go(rc, st, mr_col_ip_kernel<T>, dim3(width), MR_IP_NT, (size_t)p->ny * sizeof(cx<T>), a);
+        launch_go(rc, st, mr_col_ip_kernel<T>, dim3(width, nplanes), MR_IP_NT, (size_t)p->ny * sizeof(cx<T>), a);
     else rc = fail("fft: transform size exceeds the LDS / workgroup budget for this dtype");
     return rc;
 }
@@ -147,6 +147,13 @@ int mixed_c2r_windowed(oa_plan* p, const void* hc_in, void* real_out, double sca
 int mixed_cols_inverse(oa_plan* p, const void* hc_in, void* hc_out, hipStream_t st) {
     return p->dtype == OA_F32 ? cols<float>(p, hc_in, p->kp, hc_out, p->kp, p->nx / 2 + 1, true, 1.0, st)
                               : cols<double>(p, hc_in, p->kp, hc_out, p->kp, p->nx / 2 + 1, true, 1.0, st);
+}
+// the same for nplanes planes pstride complex elements apart, in place, in ONE launch: the plane on grid y (fft_mixed.hpp MrColArgs), the
+// LDS of a workgroup that of the single-plane launch
+int mixed_cols_inverse_batch(oa_plan* p, int nplanes, void* hc, long pstride, hipStream_t st) {
+    OA_REQUIRE(nplanes >= 1 && nplanes <= 65535 && (nplanes == 1 || pstride >= (long)p->ny * p->kp), "batched inverse column transform: bad planes");
+    return p->dtype == OA_F32 ? cols<float>(p, hc, p->kp, hc, p->kp, p->nx / 2 + 1, true, 1.0, st, nullptr, 0, nplanes, pstride, pstride)
+                              : cols<double>(p, hc, p->kp, hc, p->kp, p->nx / 2 + 1, true, 1.0, st, nullptr, 0, nplanes, pstride, pstride);
 }
 int mixed_c2c(oa_plan* p, const void* in, void* out, int inverse, double scale, hipStream_t st) {
     return p->dtype == OA_F32 ? c2c_t<float>(p, in, out, inverse, scale, st) : c2c_t<double>(p, in, out, inverse, scale, st);

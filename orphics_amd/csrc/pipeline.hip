@@ -116,6 +116,8 @@ struct Pipeline {
         std::vector<const void*> skey;         // what it holds
         void* mrows = nullptr;                 // oa_qe_mv_maps: row planes + column partial sums of the batched band input transform
         size_t mrows_bytes = 0;                // (band_maps_scratch_bytes; taken on the first from-maps call, grown on demand)
+        void* mwin = nullptr;                  // oa_mc_run_mv_windowed: the three N-grid hc planes of a realisation's T, Q, U draw | three planes
+        size_t mwin_bytes = 0;                 // for the real maps of the unfused flow | band_maps_scratch_bytes(p, 3, wl, rl) (first windowed call)
         // oa_mc_run_mv on this binding (oa_mc_mv_band_bind; dropped by the next oa_qe_band_bind): what the caller's shard calls must
         // bring again (the key), and one pool in the inner layout: nest weight planes (real; none without weights) | bin ids (-1 outside
         // kappa's band) | the three drawn hc planes (zero outside the leg band) | nest kappa planes (for when the one-launch divergence
@@ -168,6 +170,7 @@ void pipeline_release(oa_plan* p) {
     if (q->pb.planes) (void)hipFree(q->pb.planes);
     if (q->pb.stab) (void)hipFree(q->pb.stab);
     if (q->pb.mrows) (void)hipFree(q->pb.mrows);
+    if (q->pb.mwin) (void)hipFree(q->pb.mwin);
     if (q->pb.mc.pool) (void)hipFree(q->pb.mc.pool);
     delete q;
     p->pipe = nullptr;
@@ -669,6 +672,8 @@ int oa_plan_release_pools(oa_plan* p) {
     if (q->bwin) { (void)hipFree(q->bwin); q->bwin = nullptr; q->bwin_bytes = 0; }
     // ... and the map-side scratch of oa_qe_mv_maps (retaken by the next from-maps call)
     if (q->pb.mrows) { (void)hipFree(q->pb.mrows); q->pb.mrows = nullptr; q->pb.mrows_bytes = 0; }
+    // ... and the N-grid planes of oa_mc_run_mv_windowed there (retaken by the next windowed call)
+    if (q->pb.mwin) { (void)hipFree(q->pb.mwin); q->pb.mwin = nullptr; q->pb.mwin_bytes = 0; }
     // ... and the Monte-Carlo binding's pool: oa_mc_mv_band_bind makes it again
     if (q->pb.mc.pool) { (void)hipFree(q->pb.mc.pool); q->pb.mc = Pipeline::PolBind::McBind(); }
     return 0;
@@ -1352,7 +1357,7 @@ static int mixed_mc_run_windowed(oa_plan* p, Pipeline* q, uint64_t base_seed, lo
             if ((rc = oa_grf_hc(p, base_seed, (uint64_t)(i + k), covsqrt_hc, pl, st))) return rc;
             if ((rc = mixed_cols_inverse(p, pl, pl, st))) return rc;
         }
-        if ((rc = band_win_r2c(p, B, draw, pne, window, inv, rows, 0, q->wl, q->rl, qb->mc_src, pbe, b->ny, b->kp, st))) return rc;
+        if ((rc = band_win_r2c(p, B, draw, pne, window, inv, rows, 0, q->wl, q->rl, nullptr, nullptr, qb->mc_src, pbe, b->ny, b->kp, st))) return rc;
         int fallback = 0;
         if ((rc = mc_batch_tail(b, qb, B, n, S, C, nullptr, st, &fallback, meanfield_acc != nullptr))) return rc;
         if (fallback) { batched = false; break; }
@@ -1365,7 +1370,7 @@ static int mixed_mc_run_windowed(oa_plan* p, Pipeline* q, uint64_t base_seed, lo
         if (rc) return rc;
         if (fused) {
             if ((rc = mixed_cols_inverse(p, draw, draw, st))) return rc;
-            rc = band_win_r2c(p, 1, draw, pne, window, inv, rows, 1, q->wl, q->rl, bx, 0, b->ny, b->kp, st);
+            rc = band_win_r2c(p, 1, draw, pne, window, inv, rows, 1, q->wl, q->rl, nullptr, nullptr, bx, 0, b->ny, b->kp, st);
         } else {
             void* tmap = draw + pb;                                              // ny x nx reals fit an hc plane
             if ((rc = oa_fft_c2r_windowed(p, draw, tmap, inv, window, st))) return rc;
@@ -1396,6 +1401,7 @@ static int pol_bind(oa_plan* p, Pipeline* q, int nf, const void* const* filters,
     if (!B.plan || B.my != my || B.mx != mx) {
         if (B.plan) { (void)oa_plan_destroy(B.plan); B.plan = nullptr; }
         if (B.mrows) { (void)hipFree(B.mrows); B.mrows = nullptr; B.mrows_bytes = 0; }      // (the from-maps calls' scratch: retaken on demand)
+        if (B.mwin) { (void)hipFree(B.mwin); B.mwin = nullptr; B.mwin_bytes = 0; }          // (the windowed Monte Carlo's planes: likewise)
         B.my = B.mx = 0;
         if (int rc = band_inner_plan(p, my, mx, &B.plan)) return rc;
         B.my = my; B.mx = mx;
@@ -1635,7 +1641,8 @@ static int mc_mv_bind(oa_plan* p, Pipeline* q, const void* w, long wstride, int 
  * layout.  Nothing here allocates or synchronises once the pools exist.
  * SOURCE STAGE HOOK: `source` (when set) replaces the band draw -- it leaves realisation i's T, E, B on the leg band of `draw`
  * (oa_mc_run_mv_windowed's windowed front end).  `mf` (when set): nest host-side pointers to float64 stack planes, and `mf_mv` the MV
- * stack or nullptr -- one stack_add_region_multi launch per realisation over kappa's band. */
+ * stack or nullptr -- one stack_add_region_multi launch per realisation over kappa's band (band_stack_add_multi when `run` is an inner
+ * plan: the stacks are always `grid`'s planes). */
 struct McMvLoop {
     oa_plan* grid; oa_plan* run; Pipeline* rq;
     bool engaged;                                   // the one-launch divergence: kappa planes = run's work planes c[0] + e
@@ -1674,8 +1681,13 @@ static int mc_mv_loop(const McMvLoop& L, uint64_t base_seed, long sim_lo, long s
         if ((rc = oa_bin_power_multi(r->dtype, nest, block, (long)(pb / es), L.w, L.wstride, nspec, host_a, host_b, norm, L.ids, nids,
                                      r->ny, r->kp, r->nx / 2, kappa_cols, kappa_rows, L.sums, L.scratch, st))) return rc;
         if ((rc = moments_add_binned_multi(L.sums, counts, nspec, nids, n, S, C, st))) return rc;
-        if (L.mf && (rc = stack_add_region_multi(r->dtype, block, (long)(pb / es), L.w, L.wstride, nest, L.mf, L.mf_mv, r->ny, r->kp, kappa_cols,
-                                                 kappa_rows, st))) return rc;
+        if (!L.mf) continue;
+        // the stacks are the map's planes: on a band grid kappa_hat's band goes from the inner rows and pitch to the N grid's
+        rc = L.grid == r ? stack_add_region_multi(r->dtype, block, (long)(pb / es), L.w, L.wstride, nest, L.mf, L.mf_mv, r->ny, r->kp, kappa_cols,
+                                                  kappa_rows, st)
+                         : band_stack_add_multi(r->dtype, block, (long)(pb / es), L.w, L.wstride, nest, L.mf, L.mf_mv, r->ny, r->kp, L.grid->ny,
+                                                L.grid->kp, kappa_cols, kappa_rows, st);
+        if (rc) return rc;
     }
     return 0;
 }
@@ -1684,21 +1696,29 @@ static int mc_mv_loop(const McMvLoop& L, uint64_t base_seed, long sim_lo, long s
  * first launch; then the loop above on the inner plan.  kappa_hat per mode is the same on both grids (the bound normalisations carry
  * My Mx / (ny nx)), the inner ids are the N grid's at the same mode, and since Mx >= 2 kappa_cols the inner Nyquist column is never
  * visited: column 0 is the only visited one of Hermitian multiplicity 1, as on the N grid.  The caller's counts are the N plane's. */
-static int mixed_mc_run_mv(oa_plan* p, Pipeline* q, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest,
-                           const int* host_npieces, const double* host_signs, const void* const* host_FG, const void* const* host_FH,
-                           const int* host_swap, const int* host_xsrc, const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights,
-                           long mv_wstride, int nspec, const int* host_a, const int* host_b, const int32_t* ids_hc, int nids, const int64_t* counts,
-                           double norm, int wl, int wk, int rl, int rk, int mrow, int64_t* n, double* S, double* C, hipStream_t st) {
+// what a band-grid shard call resolves before its first launch: the inner-layout planes of the call's pointers and the loop on them
+struct MixedMvCall {
+    std::vector<const void*> iFG, iFH, iFn;
+    McMvLoop L;
+};
+// `who`: the entry's name.  `how_all`: every refusal ends with the way out (oa_mc_run_mv_windowed names the driver and one_call=False in
+// each of its refusals); oa_mc_run_mv's messages are as they were.
+static int mixed_mc_mv_lookup(const std::string& who, bool how_all, oa_plan* p, Pipeline* q, int nest, const int* host_npieces,
+                              const void* const* host_FG, const void* const* host_FH, const int* host_swap, const int* host_xsrc,
+                              const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights, long mv_wstride, int nspec,
+                              const int32_t* ids_hc, int nids, int wl, int wk, int rl, int rk, int mrow, MixedMvCall* out) {
     static const char* const how = " -- bind the estimator set with oa_qe_band_bind, then oa_mc_mv_band_bind, or run the host loop of the "
                                    "existing entries (mc.GaussianN0MonteCarloPol with one_call=False)";
+    const std::string tail = how_all ? how : "";
     Pipeline::PolBind& B = q->pb;
     const Pipeline::PolBind::McBind& M = B.mc;
-    if (!B.bound) return fail(std::string("oa_mc_run_mv: on map sides 2^a 3^b 5^c the filter and normalisation planes are bound first") + how);
+    if (!B.bound) return fail(who + ": on map sides 2^a 3^b 5^c the filter and normalisation planes are bound first" + how);
     if (wl != B.wl || wk != B.wk || rl != B.rl || rk != B.rk || mrow != B.mrow)
-        return fail(std::string("oa_mc_run_mv: leg / kappa columns and rows or the row grid differ from the bound ones") + how);
-    if (!M.bound) return fail(std::string("oa_mc_run_mv: no Monte-Carlo binding on the current oa_qe_band_bind binding") + how);
+        return fail(who + ": leg / kappa columns and rows or the row grid differ from the bound ones" + how);
+    if (!M.bound) return fail(who + ": no Monte-Carlo binding on the current oa_qe_band_bind binding" + how);
     if (mv_weights != M.w || (mv_weights && mv_wstride != M.wstride) || ids_hc != M.ids || nids != M.nids || nest != M.nest || nspec > M.nspec_max)
-        return fail(std::string("oa_mc_run_mv: the weights, their stride, the bin ids, nids, nest or nspec differ from the Monte-Carlo binding's") + how);
+        return fail(who + ": the weights, their stride, the bin ids, nids, nest or nspec differ from the Monte-Carlo binding's" + how);
+    std::vector<const void*>&iFG = out->iFG, &iFH = out->iFH, &iFn = out->iFn;
     oa_plan* b = B.plan;
     Pipeline* qb = (Pipeline*)b->pipe;
     band_options(q);
@@ -1707,15 +1727,15 @@ static int mixed_mc_run_mv(oa_plan* p, Pipeline* q, uint64_t base_seed, long sim
     char* const nbase = fbase + B.fkey.size() * rb;
     int total = 0;
     for (int e = 0; e < nest; ++e) total += host_npieces[e];
-    std::vector<const void*> iFG(total), iFH(total), iFn(nest);
+    iFG.assign(total, nullptr); iFH.assign(total, nullptr); iFn.assign(nest, nullptr);
     for (int i = 0; i < total; ++i) {
         iFG[i] = pol_inner(B.fkey, host_FG[i], fbase, rb);
         iFH[i] = pol_inner(B.fkey, host_FH[i], fbase, rb);
-        if (!iFG[i] || !iFH[i]) return fail("oa_mc_run_mv: a filter plane of this call is not bound (oa_qe_band_bind binds every distinct plane)");
+        if (!iFG[i] || !iFH[i]) return fail(who + ": a filter plane of this call is not bound (oa_qe_band_bind binds every distinct plane)" + tail);
     }
     for (int e = 0; e < nest; ++e) {
         iFn[e] = pol_inner(B.nkey, host_Fnorm[e], nbase, rb);
-        if (!iFn[e]) return fail("oa_mc_run_mv: a normalisation plane of this call is not bound (oa_qe_band_bind)");
+        if (!iFn[e]) return fail(who + ": a normalisation plane of this call is not bound (oa_qe_band_bind)" + tail);
     }
     {                                               // the inner plan's leg pool: sized by oa_qe_band_bind, never grown here
         std::vector<std::pair<int, const void*>> grad, hpl;
@@ -1731,17 +1751,87 @@ static int mixed_mc_run_mv(oa_plan* p, Pipeline* q, uint64_t base_seed, long sim
             }
         const size_t lb = (size_t)work_pitch(b, wl) * b->ny * es, lbk = (size_t)work_pitch(b, wk) * b->ny * es;
         if ((2 * grad.size() + hpl.size()) * lb + 4 * (size_t)nest * lbk > qb->split_bytes)
-            return fail("oa_mc_run_mv: this call needs " + std::to_string(2 * grad.size() + hpl.size()) + " leg planes and " + std::to_string(nest) +
-                        " estimators, more than oa_qe_band_bind was told (max_leg_planes, normalisation planes)");
+            return fail(who + ": this call needs " + std::to_string(2 * grad.size() + hpl.size()) + " leg planes and " + std::to_string(nest) +
+                        " estimators, more than oa_qe_band_bind was told (max_leg_planes, normalisation planes)" + tail);
     }
     char* const base = (char*)M.pool;
     const size_t cb = plane_bytes(b);
     long fn_moff = 0;
-    McMvLoop L{p, b, qb, mv_div_batched(qb, nest, iFn.data(), es / 2, &fn_moff),
-               {base + M.off_draw, base + M.off_draw + cb, base + M.off_draw + 2 * cb}, base + M.off_kappa, base + M.off_scratch,
-               (double*)(base + M.off_sums), mv_weights ? (const void*)base : nullptr, (long)(rb / (es / 2)), (const int32_t*)(base + M.off_ids), -1};
-    return mc_mv_loop(L, base_seed, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, iFG.data(), iFH.data(), host_swap, host_xsrc,
-                      host_ysrc, iFn.data(), nspec, host_a, host_b, nids, counts, norm, wl, wk, rl, rk, n, S, C, st);
+    out->L = McMvLoop{p, b, qb, mv_div_batched(qb, nest, iFn.data(), es / 2, &fn_moff),
+                      {base + M.off_draw, base + M.off_draw + cb, base + M.off_draw + 2 * cb}, base + M.off_kappa, base + M.off_scratch,
+                      (double*)(base + M.off_sums), mv_weights ? (const void*)base : nullptr, (long)(rb / (es / 2)),
+                      (const int32_t*)(base + M.off_ids), -1};
+    return 0;
+}
+static int mixed_mc_run_mv(oa_plan* p, Pipeline* q, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest,
+                           const int* host_npieces, const double* host_signs, const void* const* host_FG, const void* const* host_FH,
+                           const int* host_swap, const int* host_xsrc, const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights,
+                           long mv_wstride, int nspec, const int* host_a, const int* host_b, const int32_t* ids_hc, int nids, const int64_t* counts,
+                           double norm, int wl, int wk, int rl, int rk, int mrow, int64_t* n, double* S, double* C, hipStream_t st) {
+    MixedMvCall c;
+    if (int rc = mixed_mc_mv_lookup("oa_mc_run_mv", false, p, q, nest, host_npieces, host_FG, host_FH, host_swap, host_xsrc, host_ysrc, host_Fnorm,
+                                    mv_weights, mv_wstride, nspec, ids_hc, nids, wl, wk, rl, rk, mrow, &c)) return rc;
+    return mc_mv_loop(c.L, base_seed, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, c.iFG.data(), c.iFH.data(), host_swap, host_xsrc,
+                      host_ysrc, c.iFn.data(), nspec, host_a, host_b, nids, counts, norm, wl, wk, rl, rk, n, S, C, st);
+}
+/* oa_mc_run_mv_windowed on a 2^a 3^b 5^c plan: the lookups and refusals above under this entry's name, then the same loop on the inner plan
+ * with the mean-field stacks on the N grid (band_stack_add_multi) and -- with a window -- the source stage replaced: per realisation the
+ * full-plane T, E, B draw rotated to T, Q, U on the N grid (grf_mix_teb_to_tqu), then
+ *   fused   : ONE batched inverse column launch over the three planes (in place), ONE fused row launch (C2R / Npix x window -> R2C, the
+ *             real rows in LDS only, leg columns stored), the pruned column DFT of the three planes and the fold with the Q, U -> E, B
+ *             rotation onto the loop's three inner source planes (band_win_r2c with rot_c / rot_s: mixed_mc_run_windowed's front end with
+ *             planes in the place of realisations);
+ *   unfused : oa_fft_c2r_windowed per plane onto a real map in an entry-owned plane, then ONE band_maps_r2c(3, rot_c, rot_s) -- what
+ *             oa_qe_mv_maps runs.
+ * Fused or unfused: OA_OPT_WIN_FUSED, until it is set mixed_mc_run_windowed's rule by row length; rows the fused kernel does not hold take
+ * the unfused flow.  The N-grid planes are taken on the first windowed call (one device synchronisation; regrown when the band widens). */
+static int mixed_mc_run_mv_windowed(oa_plan* p, Pipeline* q, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest,
+                                    const int* host_npieces, const double* host_signs, const void* const* host_FG, const void* const* host_FH,
+                                    const int* host_swap, const int* host_xsrc, const int* host_ysrc, const void* const* host_Fnorm,
+                                    const void* mv_weights, long mv_wstride, int nspec, const int* host_a, const int* host_b, const int32_t* ids_hc,
+                                    int nids, const int64_t* counts, double norm, int wl, int wk, int rl, int rk, int mrow, const void* window,
+                                    const void* rot_c, const void* rot_s, int64_t* n, double* S, double* C, double* const* host_meanfield,
+                                    hipStream_t st) {
+    MixedMvCall c;
+    if (int rc = mixed_mc_mv_lookup("oa_mc_run_mv_windowed", true, p, q, nest, host_npieces, host_FG, host_FH, host_swap, host_xsrc, host_ysrc,
+                                    host_Fnorm, mv_weights, mv_wstride, nspec, ids_hc, nids, wl, wk, rl, rk, mrow, &c)) return rc;
+    McMvLoop& L = c.L;
+    if (host_meanfield) { L.mf = host_meanfield; L.mf_mv = mv_weights ? host_meanfield[nest] : nullptr; }
+    if (window) {
+        Pipeline::PolBind& B = q->pb;
+        oa_plan* b = B.plan;
+        const size_t es = 2 * (p->dtype == OA_F32 ? 4 : 8), pb = plane_bytes(p), need = 6 * pb + band_maps_scratch_bytes(p, 3, wl, rl);
+        if (B.mwin_bytes < need) {                  // first windowed call on this binding's inner plan, or a wider band
+            OA_HIP(hipDeviceSynchronize());
+            if (B.mwin) { (void)hipFree(B.mwin); B.mwin = nullptr; B.mwin_bytes = 0; }
+            OA_HIP(hipMalloc(&B.mwin, need));
+            B.mwin_bytes = need;
+        }
+        char* const wb = (char*)B.mwin;
+        char* const tmp = wb + 3 * pb;              // ny x nx reals fit an hc plane
+        void* const rows = wb + 6 * pb;
+        const long pne = (long)(pb / es), pbe = (long)(plane_bytes(b) / es);
+        const double inv = 1.0 / ((double)p->ny * p->nx);
+        const bool fused = band_rows_win_ok(p) && (q->opt_win_fused_set ? q->opt_win_fused : p->nx > 1200);
+        void* const dst = L.draw[0];                // the three inner source planes are contiguous, one inner plane apart (oa_mc_mv_band_bind)
+        const int dny = b->ny;
+        const long dkp = b->kp;
+        L.source = [=](long i) -> int {
+            void* tqu[3] = {wb, wb + pb, wb + 2 * pb};
+            int rc = grf_mix_teb_to_tqu(p, base_seed, 3 * (uint64_t)i, host_covsqrt, rot_c, rot_s, tqu, st);
+            if (rc) return rc;
+            if (fused) {
+                if ((rc = mixed_cols_inverse_batch(p, 3, wb, pne, st))) return rc;
+                return band_win_r2c(p, 3, wb, pne, window, inv, rows, 0, wl, rl, rot_c, rot_s, dst, pbe, dny, dkp, st);
+            }
+            const void* maps[3] = {tmp, tmp + pb, tmp + 2 * pb};
+            for (int f = 0; f < 3; ++f)
+                if ((rc = oa_fft_c2r_windowed(p, tqu[f], tmp + (size_t)f * pb, inv, window, st))) return rc;
+            return band_maps_r2c(p, 3, maps, rot_c, rot_s, rows, wl, rl, dst, pbe, dny, dkp, st);
+        };
+    }
+    return mc_mv_loop(L, base_seed, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, c.iFG.data(), c.iFH.data(), host_swap, host_xsrc,
+                      host_ysrc, c.iFn.data(), nspec, host_a, host_b, nids, counts, norm, wl, wk, rl, rk, n, S, C, st);
 }
 }  // namespace oa
 
@@ -1906,7 +1996,9 @@ int oa_mc_run_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const
  * band draw) -> one batched inverse column launch -> one fused row launch over the three planes (C2R / Npix -> x window -> R2C, the real maps
  * in LDS only, leg_cols columns stored at the compact pitch) -> one batched forward column launch onto the leg band of the loop's three
  * source planes -> Q, U -> E, B on that band.  OA_OPT_WIN_FUSED = 0: oa_fft_c2r_windowed -> real maps in HBM (the column temporaries) ->
- * oa_fft_r2c on the band.  Then mc_mv_loop's estimator, binning and moment steps, and one stack launch. */
+ * oa_fft_r2c on the band.  Then mc_mv_loop's estimator, binning and moment steps, and one stack launch.
+ * On a 2^a 3^b 5^c plan the loop runs on the inner plan of the band grid behind oa_qe_band_bind + oa_mc_mv_band_bind, with the windowed
+ * source stage on the N grid in front of it and the stacks on the N grid behind it (mixed_mc_run_mv_windowed). */
 int oa_mc_run_mv_windowed(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest,
                           const int* host_npieces, const double* host_signs, const void* const* host_FG, const void* const* host_FH,
                           const int* host_swap, const int* host_xsrc, const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights,
@@ -1914,8 +2006,8 @@ int oa_mc_run_mv_windowed(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_
                           double norm, int leg_cols, int kappa_cols, int leg_rows, int kappa_rows, int mrow, const void* window_real,
                           const void* rot_c, const void* rot_s, int64_t* n, double* S, double* C, double* const* host_meanfield, void* stream) {
     OA_REQUIRE(p, "oa_mc_run_mv_windowed: bad argument");
-    if (int rc = mc_mv_check("oa_mc_run_mv_windowed", p->pow2,
-                             ": power-of-two map sides only (no band-grid version on sides 2^a 3^b 5^c yet, no one-call path on chirp-z sides); run "
+    if (int rc = mc_mv_check("oa_mc_run_mv_windowed", p->pow2 || p->mixed,
+                             ": map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path; run "
                              "the host loop of the existing entries (mc.GaussianN0MonteCarloPol with one_call=False: Engine.grf_mix, Engine.irfft with "
                              "the window, Engine.rfft, Engine.rot2, reconstruct_hc per estimator, Engine.bin_power, Statistics.add)", p, sim_lo, sim_hi,
                              host_covsqrt, nest, host_npieces, host_signs, host_FG, host_FH, host_xsrc, host_ysrc, host_Fnorm, mv_weights, nspec, host_a,
@@ -1928,6 +2020,10 @@ int oa_mc_run_mv_windowed(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_
         for (int e = 0; e < nest + (mv_weights ? 1 : 0); ++e) OA_REQUIRE(host_meanfield[e], "oa_mc_run_mv_windowed: NULL mean-field stack plane");
     Pipeline* q = pipe_of(p);
     hipStream_t st = (hipStream_t)stream;
+    if (p->mixed)                                   // BAND GRID: the planes of the two bindings, on the inner plan
+        return mixed_mc_run_mv_windowed(p, q, base_seed, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, host_FG, host_FH, host_swap,
+                                        host_xsrc, host_ysrc, host_Fnorm, mv_weights, mv_wstride, nspec, host_a, host_b, ids_hc, nids, counts, norm,
+                                        leg_cols, kappa_cols, leg_rows, kappa_rows, mrow, window_real, rot_c, rot_s, n, S, C, host_meanfield, st);
     McMvLoop L;
     if (int rc = mc_mv_pow2_loop(p, q, nest, host_Fnorm, mv_weights, mv_wstride, nspec, ids_hc, nids, mrow, &L)) return rc;
     if (host_meanfield) { L.mf = host_meanfield; L.mf_mv = mv_weights ? host_meanfield[nest] : nullptr; }

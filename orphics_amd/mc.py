@@ -320,10 +320,14 @@ class GaussianN0MonteCarloPol(object):
     the labels "mf_TT", ..., "mf_MV" (shape (ny, kp, 2), interleaved re / im, support = kappa's band, so the all-reduce moves the
     band only).
 
-    With a window or a mean field the one call is ``oa_mc_run_mv_windowed``, on power-of-two sides only: ``one_call=None`` runs it
-    there and the host loop elsewhere, ``one_call=True`` on other sides raises.  The host loop (any side; the reference of the one
-    call) is then ``Engine.grf_mix(rot=(c, -s))`` on full planes, ``Engine.irfft(window=...)`` per field, ``Engine.rfft``,
-    ``Engine.rot2(c, s, ...)``, the per-estimator sequence above, and the stacks added with torch."""
+    With a window or a mean field the one call is ``oa_mc_run_mv_windowed``: ``one_call=None`` runs it on power-of-two sides and the
+    host loop elsewhere, ``one_call=True`` on other sides raises.  ``one_call="band"`` behaves as ``True`` everywhere and, in addition,
+    runs that call on the band grid of sides 2^a 3^b 5^c (the bindings and bands of the unwindowed one call above; per realisation the
+    full-plane T, Q, U draw, one batched inverse column launch, the windowed row pass and the pruned column transform with the
+    Q, U -> E, B rotation on the map's grid, the estimators on the inner grid, the stacks on the map's grid with support = the kappa
+    mask's); it raises, naming ``one_call=False``, where there is no band grid.  Any other string is a ``ValueError``.  The host loop
+    (any side; the reference of the one call) is then ``Engine.grf_mix(rot=(c, -s))`` on full planes, ``Engine.irfft(window=...)`` per
+    field, ``Engine.rfft``, ``Engine.rot2(c, s, ...)``, the per-estimator sequence above, and the stacks added with torch."""
 
     def __init__(self, qest, total_power_half, bin_edges, estimators=("TT", "TE", "EE", "EB", "TB"), cross=True, mv=True, comm=None,
                  base_seed=1234, one_call=None, window=None, mean_field=False):
@@ -336,6 +340,9 @@ class GaussianN0MonteCarloPol(object):
         self.estimators = tuple(estimators)
         self.spectra, self.pairs = pol_spectrum_list(self.estimators, cross, mv)
         self.mv = bool(mv)
+        if isinstance(one_call, str) and one_call != "band":
+            raise ValueError("one_call must be None, True, False or \"band\", not %r" % (one_call,))
+        self.band_call = one_call == "band"   # True, and oa_mc_run_mv_windowed on the band grid of sides 2^a 3^b 5^c as well
         self.one_call = e.pow2 if one_call is None else bool(one_call)
         self.mean_field = bool(mean_field)
         self.mf_labels = ["mf_" + XY for XY in self.estimators] + (["mf_MV"] if self.mv else [])
@@ -343,11 +350,12 @@ class GaussianN0MonteCarloPol(object):
         self.window_moments = (1.0, 1.0)
         self.rot = None
         self.host_maps = None         # host loop with a window: the windowed real T, Q, U maps of the last sample_host call
-        if (window is not None or self.mean_field) and self.one_call and not e.pow2:
+        if (window is not None or self.mean_field) and self.one_call and not e.pow2 and not self.band_call:
             from ._lib import OrphicsAmdError
-            raise OrphicsAmdError("GaussianN0MonteCarloPol: a window or a mean-field stack runs in one call (oa_mc_run_mv_windowed) on "
-                                  "power-of-two map sides only; %d x %d: construct the driver with one_call=False (host loop of the existing "
-                                  "entries, any side) or leave one_call=None" % (e.ny, e.nx))
+            raise OrphicsAmdError("GaussianN0MonteCarloPol: with one_call=True a window or a mean-field stack runs in one call "
+                                  "(oa_mc_run_mv_windowed) on power-of-two map sides only; %d x %d: construct the driver with one_call=False "
+                                  "(host loop of the existing entries, any side), leave one_call=None, or opt in to the call on the band grid of "
+                                  "sides 2^a 3^b 5^c with one_call=\"band\"" % (e.ny, e.nx))
         if window is not None:
             w = np.asarray(window, dtype=np.float64)
             if w.shape != (e.ny, e.nx):
@@ -429,17 +437,6 @@ class GaussianN0MonteCarloPol(object):
                 e._pipe_owner = None
         wstride = self.w[0].numel() if self.w is not None else 0
         wl, wk, rl, rk = self._bands
-        if self.window is not None or self.mean_field:
-            import ctypes
-            mfs = self._stacks()
-            mfp = (ctypes.c_void_p * len(mfs))(*[t.data_ptr() for t in mfs]) if mfs else None
-            rot = self.rot if self.rot is not None else (None, None)
-            check(e.lib.oa_mc_run_mv_windowed(e.plan, self.base_seed, int(lo), int(hi), A["cs"], len(self.estimators), A["npieces"], A["signs"],
-                                              A["fgs"], A["fhs"], A["swaps"], A["xsrc"], A["ysrc"], A["fns"], _ptr(self.w), wstride,
-                                              len(self.spectra), A["a"], A["b"], _ptr(self.ids), self.nids, _ptr(self.counts), float(self.norm),
-                                              int(wl), int(wk), int(rl), int(rk), int(q.mrow), _ptr(self.window), _ptr(rot[0]), _ptr(rot[1]),
-                                              _ptr(n), _ptr(S), _ptr(C), mfp, _stream()))
-            return
         if e.mixed:
             # the estimator set with its pure normalisations in order, then the weights and bin ids, on the plan's inner grid; the plan
             # is shared: both are bound again whenever anything else bound it in between (sample_host's reconstruct_hc does)
@@ -451,6 +448,17 @@ class GaussianN0MonteCarloPol(object):
                 e._mc_owner = None
                 check(e.lib.oa_mc_mv_band_bind(e.plan, _ptr(self.w), wstride, nE, _ptr(self.ids), self.nids, nS))
                 e._mc_owner = (e._pol_owner, key)
+        if self.window is not None or self.mean_field:
+            import ctypes
+            mfs = self._stacks()
+            mfp = (ctypes.c_void_p * len(mfs))(*[t.data_ptr() for t in mfs]) if mfs else None
+            rot = self.rot if self.rot is not None else (None, None)
+            check(e.lib.oa_mc_run_mv_windowed(e.plan, self.base_seed, int(lo), int(hi), A["cs"], len(self.estimators), A["npieces"], A["signs"],
+                                              A["fgs"], A["fhs"], A["swaps"], A["xsrc"], A["ysrc"], A["fns"], _ptr(self.w), wstride,
+                                              len(self.spectra), A["a"], A["b"], _ptr(self.ids), self.nids, _ptr(self.counts), float(self.norm),
+                                              int(wl), int(wk), int(rl), int(rk), int(q.mrow), _ptr(self.window), _ptr(rot[0]), _ptr(rot[1]),
+                                              _ptr(n), _ptr(S), _ptr(C), mfp, _stream()))
+            return
         check(e.lib.oa_mc_run_mv(e.plan, self.base_seed, int(lo), int(hi), A["cs"], len(self.estimators), A["npieces"], A["signs"], A["fgs"],
                                  A["fhs"], A["swaps"], A["xsrc"], A["ysrc"], A["fns"], _ptr(self.w), wstride, len(self.spectra), A["a"], A["b"],
                                  _ptr(self.ids), self.nids, _ptr(self.counts), float(self.norm), int(wl), int(wk), int(rl), int(rk), int(q.mrow),
@@ -462,7 +470,9 @@ class GaussianN0MonteCarloPol(object):
         if not self.mean_field:
             return []
         e = self.eng
-        sup = (self.rk, self.wk) if (self.wk and self.rk) else None
+        # kappa's band of the path that writes the stacks: on a band grid the kappa mask's support (self._bands), what the kernel writes
+        wk, rk = (self._bands[1], self._bands[3]) if (self.one_call and e.mixed) else (self.wk, self.rk)
+        sup = (rk, wk) if (wk and rk) else None
         return [self.acc.device_stack(lab, (e.ny, e.kp, 2), support=sup) for lab in self.mf_labels]
 
     def _host_fields(self, i):

@@ -25,7 +25,12 @@ modular chain on the same plan, on the reference notebooks' patches (tutorials/t
     on the band grid) with the fused row pass (win_fused = 1) and with the unfused flow (win_fused = 0), against the one_call=False host loop
     of existing entries on the same plan -- the three paths ALTERNATED block by block in one process after a warm-up of each.  A block is
     --sims realisations (host loop: --loop-sims); per path the median and the 10th .. 90th percentile of --reps blocks, in sims/s.
-    --out appends the raw lines to a file.  With --only-onecall N: N realisations of the fused one call per cell and nothing else."""
+    --out appends the raw lines to a file.  With --only-onecall N: N realisations of the fused one call per cell and nothing else.
+--pol --windowed: the same for the polarisation set, GaussianN0MonteCarloPol(TT, TE, EE, EB, TB + MV, window=taper, mean_field=True: all
+    six stacks): one_call="band" (oa_mc_run_mv_windowed on the band grid) with win_fused = 1 and 0 against the one_call=False host loop on
+    the same library and plan, alternated block by block with HIP events.  speedup_vs_host_loop takes the flow the entry picks by itself
+    (auto_flow).  With --only-onecall N: per cell N realisations of the one call with win_fused = 1 (one batched inverse column launch
+    over three planes per realisation), then N with win_fused = 0 (three single-plane launches per realisation), and nothing else."""
 import argparse
 import json
 import os
@@ -242,6 +247,71 @@ def main_windowed(args):
             f.write("\n".join(lines) + "\n")
 
 
+def main_pol_windowed(args):
+    import torch
+    from orphics_amd import cosmology, lensing, maps, mc
+    from orphics_amd.geometry import FlatGeometry
+    ests = ("TT", "TE", "EE", "EB", "TB")
+    edges = np.linspace(100, 3000, 12)
+    lines = []
+    for n in [int(s) for s in args.sides.split(",")]:
+        shape = (n, n)
+        g = FlatGeometry.from_res(shape, 0.5)
+        th = cosmology.default_theory()
+        ml = g.modlmap()
+        beam = maps.gauss_beam(ml, 1.5)
+        nT = np.full(shape, cosmology.white_noise_power(1.0))
+        tmask = maps.mask_kspace(shape, g, lmin=300, lmax=2000)
+        kmask = maps.mask_kspace(shape, g, lmin=20, lmax=3500)
+        cl = {k: th.lCl(k, ml) for k in ("TT", "EE", "BB", "TE")}
+        tot = dict(TT=cl["TT"] * beam ** 2 + nT, EE=cl["EE"] * beam ** 2 + 2 * nT, BB=cl["BB"] * beam ** 2 + 2 * nT, TE=cl["TE"] * beam ** 2)
+        tot_h = {k: np.ascontiguousarray(v[:, :n // 2 + 1]) for k, v in tot.items()}
+        taper, _ = maps.get_taper(shape, g, taper_percent=12.0, pad_percent=3.0)
+        for prec in args.precs.split(","):
+            q = lensing.qest(shape, g, th, noise2d=nT, beam2d=beam, kmask=tmask, noise2d_P=2 * nT, kmask_P=tmask, kmask_K=kmask, pol=True,
+                             unlensed_equals_lensed=True, dtype=prec)
+            e = q.eng
+            kw = dict(estimators=ests, base_seed=3, mean_field=True, window=taper)
+            one = mc.GaussianN0MonteCarloPol(q, tot_h, edges, one_call="band", **kw)
+            host = mc.GaussianN0MonteCarloPol(q, tot_h, edges, one_call=False, **kw)
+            state = {"lo": 1000}
+
+            def block(drv, fused, count):
+                e.set_option("win_fused", fused)
+                drv.run_local(range(state["lo"], state["lo"] + count))
+                state["lo"] += count
+            if args.only_onecall:
+                for fused in (1, 0):
+                    block(one, fused, args.only_onecall)
+                torch.cuda.synchronize()
+                e.set_option("win_fused", -1)
+                continue
+            # a block of the one call binds the plan again after the host loop's per-estimator bindings: two set-up calls per block,
+            # inside its timed window
+            names = ("onecall_fused", "onecall_unfused", "host_loop")
+            counts = (args.sims, args.sims, args.loop_sims)
+            ms = timed_alternating(lambda: block(one, 1, args.sims), lambda: block(one, 0, args.sims), 1, args.reps,
+                                   lambda: block(host, 1, args.loop_sims))
+            rates = {name: [c / (t / 1e3) for t in (m[0], m[2], m[1])] for name, c, m in zip(names, counts, ms)}      # median, p10, p90 of the rate
+            e.set_option("win_fused", -1)
+            rec = dict(side=n, prec=prec, call="pol_windowed_n0_mean_field", estimators=list(ests), nstacks=len(one.mf_labels),
+                       band_grid=list(q.pol_band_grid(ests, ext_norm=True)), reps=args.reps, sims_per_block=args.sims, loop_sims_per_block=args.loop_sims)
+            for name, r in rates.items():
+                rec[name + "_sims_per_s"] = round(r[0], 2)
+                rec[name + "_p10_p90"] = [round(r[1], 2), round(r[2], 2)]
+            auto = "onecall_fused" if n > 1200 else "onecall_unfused"                  # what the entry runs until win_fused is set
+            rec["auto_flow"] = auto
+            rec["speedup_vs_host_loop"] = round(rec[auto + "_sims_per_s"] / rec["host_loop_sims_per_s"], 2)
+            rec["fused_vs_unfused"] = round(rec["onecall_fused_sims_per_s"] / rec["onecall_unfused_sims_per_s"], 3)
+            line = json.dumps(rec)
+            print(line, flush=True)
+            lines.append(line)
+            e.release_pools()
+    if args.out and lines:
+        with open(args.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 class _Duck(object):
     """a qest that is not this package's Estimator: SplitLensing takes the generic pairwise loop"""
 
@@ -315,6 +385,8 @@ def main():
     import torch
     from orphics_amd import mc
     torch.cuda.set_device(0)
+    if args.pol and args.windowed:
+        return main_pol_windowed(args)
     if args.pol:
         return main_pol(args)
     if args.splits:
