@@ -17,6 +17,25 @@ namespace oa {
 
 constexpr int MC_BATCH_MAX = 6;      // realisations per launch in oa_mc_run (kappa planes: the six plan-owned work planes in front of kk)
 
+// A grow-only device buffer.  reserve() on a buffer that is already large enough does NOTHING -- no HIP call: the steady-state one-call
+// entries stay free of allocation and synchronisation.  Otherwise it synchronises the device before it frees a live allocation (launches
+// in flight may still use it), allocates, and zero-fills when asked.  A plain value: nothing is freed implicitly, pipeline_release is
+// where a plan's device memory is returned.
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    int reserve(size_t need, bool zero = false) {
+        if (bytes >= need) return 0;
+        if (p) { OA_HIP(hipDeviceSynchronize()); release(); }
+        OA_HIP(hipMalloc(&p, need));
+        bytes = need;
+        if (zero) OA_HIP(hipMemset(p, 0, need));
+        return 0;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+    char* at(size_t off = 0) const { return (char*)p + off; }
+};
+
 struct Pipeline {
     // filters (caller-owned device planes) + active region of the TT estimator
     const void* FG = nullptr; const void* FH = nullptr; const void* Fn = nullptr;
@@ -40,24 +59,20 @@ struct Pipeline {
     int64_t* counts_full = nullptr;   // data-independent mode counts over the whole plane
     int64_t* counts_tmp = nullptr;
     unsigned* ticket = nullptr;       // last-workgroup ticket of the fused bin + moments launch (bin.hip, BinTail)
-    void* split_legs = nullptr;       // oa_qe_tt_splits / oa_qe_mv: pool of compact leg planes
-    size_t split_bytes = 0;
+    DevBuf split_legs;                // oa_qe_tt_splits / oa_qe_mv: pool of compact leg planes (grown on demand)
     void* mv_rtab = nullptr;          // oa_qe_mv: device table of per-piece row-stage operands (RowQeMap), 64 entries
     std::vector<unsigned long long> mv_rkey;
-    void* mc_src = nullptr;           // oa_mc_run: hc planes of a batch of realisations
-    int mc_cap = 0;
-    void* lens_pool = nullptr;        // oa_lens_maps: transforms + derivative planes (hc and real) of the maps of one call
-    size_t lens_bytes = 0;
-    void* mvmc = nullptr;             // oa_mc_run_mv: the three drawn hc planes | per-estimator kappa planes (only when the one-launch divergence
-    size_t mvmc_bytes = 0;            // is not engaged) | oa_bin_power_multi's partials | its sums
-    void* mvwin = nullptr;            // oa_mc_run_mv_windowed: the three full-plane T, Q, U draws | one column temporary per plane (the real maps of
-    size_t mvwin_bytes = 0;           // the unfused flow) | the three compact row-transformed planes
+    DevBuf mc_src;                    // oa_mc_run: MC_BATCH_MAX hc planes, a batch of realisations
+    DevBuf lens_pool;                 // oa_lens_maps: transforms + derivative planes (hc and real) of the maps of one call
+    DevBuf mvmc;                      // oa_mc_run_mv: the three drawn hc planes | per-estimator kappa planes (only when the one-launch divergence
+                                      // is not engaged) | oa_bin_power_multi's partials | its sums
+    DevBuf mvwin;                     // oa_mc_run_mv_windowed: the three full-plane T, Q, U draws | one column temporary per plane (the real maps of
+                                      // the unfused flow) | the three compact row-transformed planes
     // tile-major copies of Fnorm and of the bin ids on the coarse grid of the fused divergence + binning launch (what they were
     // made from: rebuilt when the filters / bins / column grid change)
     // (one set per grid a plan can carry: [0] the column grid `my`, [1] the from-map grid `my3`)
     struct DivTabs {
-        void* fn_t = nullptr; int32_t* ids_t = nullptr;
-        size_t fn_t_bytes = 0, ids_t_bytes = 0;
+        DevBuf fn_t, ids_t;
         unsigned long tab_gen = 0;
         int tab_rows = 0, tab_logc = 0, tab_wk = 0;
     } dt[2];
@@ -67,8 +82,7 @@ struct Pipeline {
     // allocator hands a new estimator the addresses of a freed one, and a caller may refill Fnorm or the ids in place
     unsigned long bind_gen = 1;
     // the packed (FG, FH) table of the R-split column stage (ColFBandArgs::fgh), same generation key
-    void* fb_t = nullptr;
-    size_t fb_t_bytes = 0;
+    DevBuf fb_t;
     unsigned long fb_gen = 0;
     int fb_my = 0, fb_wl = 0, fb_rl = 0;
     void** mv_ftab = nullptr;         // oa_qe_mv: device table of the distinct filter planes (gradient fields, then H fields)
@@ -85,22 +99,18 @@ struct Pipeline {
     // (bmy, bmx) points that holds inner-layout copies of the filters and bin ids; made by oa_plan_set_filters / oa_plan_set_col_grid
     oa_plan* band = nullptr;
     int bmy = 0, bmx = 0;
-    void* bplanes = nullptr;          // inner layout: FG, FH, Fnorm (real planes), then the two input-transform planes kX, kY (hc)
-    int32_t* bids = nullptr;          // inner-layout bin ids (-1 outside kappa's band)
-    void* brows = nullptr;            // band input transform: row pass (ny x leg_cols complex) + column-pass partial sums
-    size_t brows_bytes = 0;
+    DevBuf bplanes;                   // inner layout: FG, FH, Fnorm (real planes), then the two input-transform planes kX, kY (hc)
+    DevBuf bids;                      // inner-layout bin ids (int32, -1 outside kappa's band)
+    DevBuf brows;                     // band input transform: row pass (ny x leg_cols complex) + column-pass partial sums
     // ... oa_mc_run_windowed there: MC_BATCH_MAX N-grid hc planes (the full-plane draws, inverse-column-transformed in place; plane 1
     // holds the real map of the unfused flow) | the row planes and column partial sums of a batch (band_maps_scratch_bytes); taken on
     // the first windowed call, regrown when the band widens
-    void* bwin = nullptr;
-    size_t bwin_bytes = 0;
+    DevBuf bwin;
     // ... oa_qe_tt_splits / oa_qe_tt_split_power there: bs_cap inner source planes (hc, zero outside the leg band) | the evenly spaced
     // (n, n, My, kp_inner) block of the inner kappa planes; allocated on first use, grown when a call brings more splits
-    void* bsplit = nullptr;
-    size_t bsplit_bytes = 0;
+    DevBuf bsplit;
     int bs_cap = 0;
-    void** bs_tab = nullptr;          // device table: the n N-grid source planes, then the n^2 N-grid output planes of the batched scatter
-    int bs_tab_cap = 0;
+    DevBuf bs_tab;                    // device table (void*): the n N-grid source planes, then the n^2 N-grid output planes of the batched scatter
     std::vector<const void*> bs_key;  // what it holds
     // ... and oa_qe_pol / oa_qe_mv there: a PRIVATE inner plan (their bands differ from the TT binding's: kmask_P, the widest band of
     // an estimator set) with inner-layout copies of the planes handed to oa_qe_band_bind, looked up by their N-grid address
@@ -110,14 +120,14 @@ struct Pipeline {
         int my = 0, mx = 0;
         int wl = 0, wk = 0, rl = 0, rk = 0, mrow = -1;
         std::vector<const void*> fkey, nkey;   // the bound N-grid filter / normalisation planes; inner plane i belongs to key i
-        void* planes = nullptr;                // inner layout: nf filter planes | nn normalisation planes, stacked in the bound order |
-        size_t planes_bytes = 0;               //               POL_SRC_MAX source planes (hc)
-        void** stab = nullptr;                 // device table of the N-grid source planes of the batched embed
+        DevBuf planes;                         // inner layout: nf filter planes | nn normalisation planes, stacked in the bound order |
+                                               //               POL_SRC_MAX source planes (hc)
+        DevBuf stab;                           // device table (void*) of the N-grid source planes of the batched embed
         std::vector<const void*> skey;         // what it holds
-        void* mrows = nullptr;                 // oa_qe_mv_maps: row planes + column partial sums of the batched band input transform
-        size_t mrows_bytes = 0;                // (band_maps_scratch_bytes; taken on the first from-maps call, grown on demand)
-        void* mwin = nullptr;                  // oa_mc_run_mv_windowed: the three N-grid hc planes of a realisation's T, Q, U draw | three planes
-        size_t mwin_bytes = 0;                 // for the real maps of the unfused flow | band_maps_scratch_bytes(p, 3, wl, rl) (first windowed call)
+        DevBuf mrows;                          // oa_qe_mv_maps: row planes + column partial sums of the batched band input transform
+                                               // (band_maps_scratch_bytes; taken on the first from-maps call, grown on demand)
+        DevBuf mwin;                           // oa_mc_run_mv_windowed: the three N-grid hc planes of a realisation's T, Q, U draw | three planes
+                                               // for the real maps of the unfused flow | band_maps_scratch_bytes(p, 3, wl, rl) (first windowed call)
         // oa_mc_run_mv on this binding (oa_mc_mv_band_bind; dropped by the next oa_qe_band_bind): what the caller's shard calls must
         // bring again (the key), and one pool in the inner layout: nest weight planes (real; none without weights) | bin ids (-1 outside
         // kappa's band) | the three drawn hc planes (zero outside the leg band) | nest kappa planes (for when the one-launch divergence
@@ -127,14 +137,18 @@ struct Pipeline {
             const void* w = nullptr; long wstride = 0;
             const int32_t* ids = nullptr;
             int nids = 0, nest = 0, nspec_max = 0;
-            void* pool = nullptr;
-            size_t pool_bytes = 0, off_ids = 0, off_draw = 0, off_kappa = 0, off_scratch = 0, off_sums = 0;
+            DevBuf pool;
+            size_t off_ids = 0, off_draw = 0, off_kappa = 0, off_scratch = 0, off_sums = 0;
         } mc;
     } pb;
+    // what is sized by the band plan's planes: returned when the band grid changes (mixed_bind) and with the plan
+    void release_band() { for (DevBuf* b : {&bplanes, &bids, &bsplit, &bwin}) b->release(); bs_cap = 0; }
 };
 constexpr int POL_SRC_MAX = 6;                 // T, E, B and the Y-leg sources of a split call
 
-static size_t plane_bytes(const oa_plan* p) { return (size_t)p->ny * p->kp * 2 * (p->dtype == OA_F32 ? 4 : 8); }
+static size_t elem_bytes(const oa_plan* p) { return 2 * (size_t)(p->dtype == OA_F32 ? 4 : 8); }       // one complex element
+static size_t plane_bytes(const oa_plan* p) { return (size_t)p->ny * p->kp * elem_bytes(p); }
+static long plane_elems(const oa_plan* p) { return (long)p->ny * p->kp; }                               // complex elements per hc plane
 
 static Pipeline* pipe_of(oa_plan* p) {
     if (!p->pipe) p->pipe = new Pipeline();
@@ -150,28 +164,16 @@ void pipeline_release(oa_plan* p) {
     if (q->counts_full) (void)hipFree(q->counts_full);
     if (q->counts_tmp) (void)hipFree(q->counts_tmp);
     if (q->ticket) (void)hipFree(q->ticket);
-    if (q->split_legs) (void)hipFree(q->split_legs);
     if (q->mv_ftab) (void)hipFree(q->mv_ftab);
-    if (q->mc_src) (void)hipFree(q->mc_src);
     if (q->mv_rtab) (void)hipFree(q->mv_rtab);
-    if (q->lens_pool) (void)hipFree(q->lens_pool);
-    if (q->mvmc) (void)hipFree(q->mvmc);
-    if (q->mvwin) (void)hipFree(q->mvwin);
-    for (auto& t : q->dt) { if (t.fn_t) (void)hipFree(t.fn_t); if (t.ids_t) (void)hipFree(t.ids_t); }
-    if (q->fb_t) (void)hipFree(q->fb_t);
+    for (DevBuf* b : {&q->split_legs, &q->mc_src, &q->lens_pool, &q->mvmc, &q->mvwin, &q->dt[0].fn_t, &q->dt[0].ids_t, &q->dt[1].fn_t,
+                      &q->dt[1].ids_t, &q->fb_t}) b->release();
     if (q->band) (void)oa_plan_destroy(q->band);
-    if (q->bplanes) (void)hipFree(q->bplanes);
-    if (q->bids) (void)hipFree(q->bids);
-    if (q->brows) (void)hipFree(q->brows);
-    if (q->bwin) (void)hipFree(q->bwin);
-    if (q->bsplit) (void)hipFree(q->bsplit);
-    if (q->bs_tab) (void)hipFree(q->bs_tab);
+    q->release_band();
+    q->brows.release();
+    q->bs_tab.release();
     if (q->pb.plan) (void)oa_plan_destroy(q->pb.plan);
-    if (q->pb.planes) (void)hipFree(q->pb.planes);
-    if (q->pb.stab) (void)hipFree(q->pb.stab);
-    if (q->pb.mrows) (void)hipFree(q->pb.mrows);
-    if (q->pb.mwin) (void)hipFree(q->pb.mwin);
-    if (q->pb.mc.pool) (void)hipFree(q->pb.mc.pool);
+    for (DevBuf* b : {&q->pb.planes, &q->pb.stab, &q->pb.mrows, &q->pb.mwin, &q->pb.mc.pool}) b->release();
     delete q;
     p->pipe = nullptr;
 }
@@ -190,13 +192,7 @@ static int ensure_work(oa_plan* p, Pipeline* q) {
 }
 
 // pool of compact planes of the multi-map entries (grown on demand; growing synchronises the device once)
-static int ensure_pool(Pipeline* q, size_t bytes) {
-    if (q->split_bytes >= bytes) return 0;
-    if (q->split_legs) { OA_HIP(hipDeviceSynchronize()); (void)hipFree(q->split_legs); q->split_legs = nullptr; q->split_bytes = 0; }
-    OA_HIP(hipMalloc(&q->split_legs, bytes));
-    q->split_bytes = bytes;
-    return 0;
-}
+static int ensure_pool(Pipeline* q, size_t bytes) { return q->split_legs.reserve(bytes); }
 
 // zero the part of a caller-supplied output plane that the pruned divergence kernel never writes: every 16-byte unit of
 // the plane outside (columns < wk) x (band rows), in one streaming launch (two hipMemset2DAsync calls ran at 1.2 TB/s:
@@ -214,7 +210,7 @@ __global__ __launch_bounds__(256) void zero_complement_kernel(uint4* __restrict_
 }
 
 static int zero_complement(oa_plan* p, void* out, int wk, int rk, hipStream_t st) {
-    const size_t es = 2 * (p->dtype == OA_F32 ? 4 : 8);
+    const size_t es = elem_bytes(p);
     const int per16 = (int)(16 / es);                           // complex elements per 16-byte unit (2 in f32, 1 in f64)
     if (!(wk > 0 && wk < p->kp)) wk = (int)p->kp;
     if (!(rk > 0 && 2L * rk - 1 < p->ny)) rk = 0;
@@ -280,11 +276,6 @@ static int mixed_bind(oa_plan* p, Pipeline* q);
 static int mixed_bins(oa_plan* p, Pipeline* q, hipStream_t st);
 static int mixed_qe_tt(oa_plan* p, Pipeline* q, const void* map, const void* kX, const void* kY, void* out, int zero_outside, hipStream_t st);
 static int mixed_moments(oa_plan* p, Pipeline* q, const void* map, int64_t* n, double* S, double* C, hipStream_t st);
-static int mixed_mc_run(oa_plan* p, Pipeline* q, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, int64_t* n, double* S,
-                        double* C, double* meanfield_acc, hipStream_t st);
-static int mixed_mc_run_windowed(oa_plan* p, Pipeline* q, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, const void* window,
-                                 int64_t* n, double* S, double* C, double* meanfield_acc, hipStream_t st);
-static void band_options(Pipeline* q);
 struct MvCall {            // the arguments of oa_qe_mv (oa_qe_pol: nest = 1 and pol set)
     int nest; const int* npieces; const double* signs; const void* const* FG; const void* const* FH; const int* swap;
     const void* const* kX; const void* const* kY; const void* const* Fn; bool pol;
@@ -433,7 +424,7 @@ int oa_plan_set_bins(oa_plan* p, const int32_t* ids_hc, int nids, double norm, v
         // copies padded to the next multiple of 4, the padding ignored (id -1) -- what Engine.bin_power does.  Set-up call: the
         // temporaries are released after a stream synchronisation
         const long kp4 = (p->kp + 3) / 4 * 4;
-        const size_t es = 2 * (p->dtype == OA_F32 ? 4 : 8);
+        const size_t es = elem_bytes(p);
         int32_t* ids4 = nullptr;
         void* z4 = nullptr;
         OA_HIP(hipMalloc((void**)&ids4, (size_t)p->ny * kp4 * sizeof(int32_t)));
@@ -471,18 +462,10 @@ static int ensure_div_tables(oa_plan* p, Pipeline* q, hipStream_t st, int rows) 
     if (t->tab_gen == q->bind_gen && t->tab_rows == rows && t->tab_logc == logc && t->tab_wk == q->wk) return 0;
     const size_t rs = p->dtype == OA_F32 ? 4 : 8;
     const long tiles = ((long)q->wk + (1 << logc) - 1) >> logc, total = (tiles * rows) << logc;
-    if (t->fn_t_bytes < (size_t)total * rs) {
-        if (t->fn_t) { OA_HIP(hipDeviceSynchronize()); (void)hipFree(t->fn_t); t->fn_t = nullptr; }
-        OA_HIP(hipMalloc(&t->fn_t, (size_t)total * rs));
-        t->fn_t_bytes = (size_t)total * rs;
-    }
-    if (t->ids_t_bytes < (size_t)total * 4) {
-        if (t->ids_t) { OA_HIP(hipDeviceSynchronize()); (void)hipFree(t->ids_t); t->ids_t = nullptr; }
-        OA_HIP(hipMalloc((void**)&t->ids_t, (size_t)total * 4));
-        t->ids_t_bytes = (size_t)total * 4;
-    }
-    if (int rc = pack_tiles(p, q->Fn, t->fn_t, rows, logc, q->wk, (int)rs, st)) return rc;
-    if (int rc = pack_tiles(p, q->ids, t->ids_t, rows, logc, q->wk, 4, st)) return rc;
+    if (int rc = t->fn_t.reserve((size_t)total * rs)) return rc;
+    if (int rc = t->ids_t.reserve((size_t)total * 4)) return rc;
+    if (int rc = pack_tiles(p, q->Fn, t->fn_t.p, rows, logc, q->wk, (int)rs, st)) return rc;
+    if (int rc = pack_tiles(p, q->ids, t->ids_t.p, rows, logc, q->wk, 4, st)) return rc;
     t->tab_gen = q->bind_gen; t->tab_rows = rows; t->tab_logc = logc; t->tab_wk = q->wk;
     return 0;
 }
@@ -497,16 +480,11 @@ static const void* fband_table(oa_plan* p, Pipeline* q, hipStream_t st) {
     static const bool off = exp_env("OA_NO_FBAND_TABLE") != nullptr;        // A/B switch
     const int my = q->map_grid();                  // (the R-split column stage exists on the from-map path only)
     if (off || !q->FG || my <= 0 || !qe_rsplit_lr(p, my, q->wl, q->wk, q->mrow)) return nullptr;
-    if (q->fb_t && q->fb_gen == q->bind_gen && q->fb_my == my && q->fb_wl == q->wl && q->fb_rl == q->rl) return q->fb_t;
-    const size_t need = (size_t)qe_fband_table_entries(p, q->wl, my) * 2 * (p->dtype == OA_F32 ? 4 : 8);
-    if (q->fb_t_bytes < need) {
-        if (q->fb_t) { if (hipDeviceSynchronize() != hipSuccess) return nullptr; (void)hipFree(q->fb_t); q->fb_t = nullptr; q->fb_t_bytes = 0; }
-        if (hipMalloc(&q->fb_t, need) != hipSuccess) { q->fb_t = nullptr; (void)hipGetLastError(); return nullptr; }
-        q->fb_t_bytes = need;
-    }
-    if (qe_fband_pack_w(p, q->FG, q->FH, q->fb_t, q->wl, q->rl, my, st)) return nullptr;
+    if (q->fb_t.p && q->fb_gen == q->bind_gen && q->fb_my == my && q->fb_wl == q->wl && q->fb_rl == q->rl) return q->fb_t.p;
+    if (q->fb_t.reserve((size_t)qe_fband_table_entries(p, q->wl, my) * elem_bytes(p))) { (void)hipGetLastError(); return nullptr; }
+    if (qe_fband_pack_w(p, q->FG, q->FH, q->fb_t.p, q->wl, q->rl, my, st)) return nullptr;
     q->fb_gen = q->bind_gen; q->fb_my = my; q->fb_wl = q->wl; q->fb_rl = q->rl;
-    return q->fb_t;
+    return q->fb_t.p;
 }
 // rows: the grid of the divergence launch the request goes to (-1: the column grid `my`)
 static DivBinFuse make_fuse(const oa_plan* p, const Pipeline* q, int64_t* n, double* S, double* C, int store, int rows = -1) {
@@ -514,7 +492,7 @@ static DivBinFuse make_fuse(const oa_plan* p, const Pipeline* q, int64_t* n, dou
     if (rows < 0) rows = q->my;
     const Pipeline::DivTabs& t = q->tabs_of(rows);
     if (t.tab_rows && t.tab_gen == q->bind_gen && t.tab_rows == rows && t.tab_wk == q->wk) {
-        f.ids_t = t.ids_t; f.fn_t = t.fn_t; f.tab_logc = t.tab_logc; f.tab_rows = t.tab_rows;
+        f.ids_t = (const int32_t*)t.ids_t.p; f.fn_t = t.fn_t.p; f.tab_logc = t.tab_logc; f.tab_rows = t.tab_rows;
     }
     f.ids = q->ids; f.ipitch = p->kp; f.pnorm = q->norm; f.nids = q->nids; f.nxh = p->nx / 2;
     f.part = (double*)q->bin_scratch; f.part_cap = (long)(oa_bin_scratch_bytes(q->nids) / (long)sizeof(double)) * MC_BATCH_MAX;
@@ -608,13 +586,8 @@ static int lens_maps_impl(oa_plan* p, int nmaps, const void* real_in, long in_st
         const size_t hcb = plane_bytes(p), rb = (size_t)rplane * rs;
         const int chunk = 1;                      // ONE hc plane: the column-transformed field of the current (map, y-derivative order)
         const size_t nk0 = hc_in ? 0 : (size_t)nmaps;
-        const size_t need = nk0 * hcb + (size_t)chunk * hcb + (size_t)nmaps * (nd + d00) * rb;
-        if (q->lens_bytes < need) {
-            if (q->lens_pool) { OA_HIP(hipDeviceSynchronize()); (void)hipFree(q->lens_pool); q->lens_pool = nullptr; q->lens_bytes = 0; }
-            OA_HIP(hipMalloc(&q->lens_pool, need));
-            q->lens_bytes = need;
-        }
-        char* k0 = (char*)q->lens_pool;
+        if (int rc = q->lens_pool.reserve(nk0 * hcb + (size_t)chunk * hcb + (size_t)nmaps * (nd + d00) * rb)) return rc;
+        char* k0 = q->lens_pool.at();
         char* hcp = k0 + nk0 * hcb;
         realp = hcp + (size_t)chunk * hcb;
         if (int rc = qe_lens_derivs_w(p, nmaps, real_in, in_stride, k0, hcp, realp, nd, st, hc_in, hc_stride, hc_scale)) return rc;
@@ -657,25 +630,15 @@ int oa_plan_release_pools(oa_plan* p) {
     if (!p->pipe) return 0;
     Pipeline* q = (Pipeline*)p->pipe;
     OA_HIP(hipDeviceSynchronize());
-    if (q->lens_pool) { (void)hipFree(q->lens_pool); q->lens_pool = nullptr; q->lens_bytes = 0; }
-    if (q->split_legs) { (void)hipFree(q->split_legs); q->split_legs = nullptr; q->split_bytes = 0; }
-    if (q->mc_src) { (void)hipFree(q->mc_src); q->mc_src = nullptr; q->mc_cap = 0; }
-    if (q->mvmc) { (void)hipFree(q->mvmc); q->mvmc = nullptr; q->mvmc_bytes = 0; }
-    if (q->mvwin) { (void)hipFree(q->mvwin); q->mvwin = nullptr; q->mvwin_bytes = 0; }
-    // band grid: the split entries' inner source planes and kappa block, and the pool their inner call grew (regrown on demand)
-    if (q->bsplit) { (void)hipFree(q->bsplit); q->bsplit = nullptr; q->bsplit_bytes = 0; q->bs_cap = 0; }
-    if (q->band && q->band->pipe) {
-        Pipeline* qb = (Pipeline*)q->band->pipe;
-        if (qb->split_legs) { (void)hipFree(qb->split_legs); qb->split_legs = nullptr; qb->split_bytes = 0; }
-    }
-    // ... the draw planes and row planes of oa_mc_run_windowed there (retaken by the next windowed call)
-    if (q->bwin) { (void)hipFree(q->bwin); q->bwin = nullptr; q->bwin_bytes = 0; }
-    // ... and the map-side scratch of oa_qe_mv_maps (retaken by the next from-maps call)
-    if (q->pb.mrows) { (void)hipFree(q->pb.mrows); q->pb.mrows = nullptr; q->pb.mrows_bytes = 0; }
-    // ... and the N-grid planes of oa_mc_run_mv_windowed there (retaken by the next windowed call)
-    if (q->pb.mwin) { (void)hipFree(q->pb.mwin); q->pb.mwin = nullptr; q->pb.mwin_bytes = 0; }
-    // ... and the Monte-Carlo binding's pool: oa_mc_mv_band_bind makes it again
-    if (q->pb.mc.pool) { (void)hipFree(q->pb.mc.pool); q->pb.mc = Pipeline::PolBind::McBind(); }
+    // band grid: the split entries' inner source planes and kappa block (bsplit), the draw and row planes of oa_mc_run_windowed (bwin), the
+    // map-side scratch of oa_qe_mv_maps (mrows) and the N-grid planes of oa_mc_run_mv_windowed (mwin): all retaken by the next call
+    for (DevBuf* b : {&q->lens_pool, &q->split_legs, &q->mc_src, &q->mvmc, &q->mvwin, &q->bsplit, &q->bwin, &q->pb.mrows, &q->pb.mwin}) b->release();
+    q->bs_cap = 0;
+    // ... the pool the split entries' inner call grew (regrown on demand)
+    if (q->band && q->band->pipe) ((Pipeline*)q->band->pipe)->split_legs.release();
+    // ... and the Monte-Carlo binding with its pool: oa_mc_mv_band_bind makes it again
+    q->pb.mc.pool.release();
+    q->pb.mc = Pipeline::PolBind::McBind();
     return 0;
 }
 
@@ -804,14 +767,14 @@ static int qe_mv_pow2(oa_plan* p, Pipeline* q, const MvCall& c, void* out, int a
         }
     }
     const int ng = (int)grad.size(), nh = (int)hpl.size(), nplanes = 2 * ng + nh;
-    const size_t es = 2 * (p->dtype == OA_F32 ? 4 : 8);
+    const size_t es = elem_bytes(p);
     const size_t lb = (size_t)pl * p->ny * es;                      // one compact leg plane
     // pool: leg planes | 2 product planes per estimator | 2 pass-1 planes per estimator (two-pass divergence)
     const size_t lbk = (size_t)pk * p->ny * es;                     // one compact product plane
     if (int rc = ensure_pool(q, nplanes * lb + 4 * (size_t)nest * lbk)) return rc;
-    char* const prod = (char*)q->split_legs + nplanes * lb;
+    char* const prod = q->split_legs.at(nplanes * lb);
     char* const tmp = prod + 2 * (size_t)nest * lbk;
-    auto plane = [&](int k) { return (void*)((char*)q->split_legs + (size_t)k * lb); };      // gradient pair g: 2g, 2g + 1; H plane h: 2 ng + h
+    auto plane = [&](int k) { return (void*)q->split_legs.at((size_t)k * lb); };      // gradient pair g: 2g, 2g + 1; H plane h: 2 ng + h
     // all leg planes in ONE inverse pass-1 launch when the fields come from at most three sources (T, E, B)
     std::vector<const void*> srcs;
     unsigned long long srcsel = 0;
@@ -839,7 +802,7 @@ static int qe_mv_pow2(oa_plan* p, Pipeline* q, const MvCall& c, void* out, int a
         bool aligned = true;
         for (size_t k = 1; k < srcs.size(); ++k) aligned = aligned && (((const char*)srcs[k] - (const char*)srcs[0]) % (long)es == 0);
         if (aligned) {
-            if (int rc = qe_legs_batch_w(p, srcs[0], off1, off2, srcsel, (const void* const*)q->mv_ftab, ng, nh, q->split_legs, (long)(lb / es),
+            if (int rc = qe_legs_batch_w(p, srcs[0], off1, off2, srcsel, (const void* const*)q->mv_ftab, ng, nh, q->split_legs.p, (long)(lb / es),
                                          leg_cols, leg_rows, pl, st, my, 2, &legs_done)) return rc;
         } else batch = false;
     }
@@ -850,12 +813,12 @@ static int qe_mv_pow2(oa_plan* p, Pipeline* q, const MvCall& c, void* out, int a
             if (int rc = qe_legs_subset_w(p, hpl[h].src, hpl[h].f, plane(2 * ng + h), nullptr, 1, leg_cols, leg_rows, pl, st, my)) return rc;
     }
     if (!legs_done)                  // (single-pass leg kernel on 1024- / 2048-row column grids: nothing left to do)
-        if (int rc = qe_legs_pass2_w(p, q->split_legs, nplanes, (long)(lb / es), leg_cols, pl, st, my)) return rc;
+        if (int rc = qe_legs_pass2_w(p, q->split_legs.p, nplanes, (long)(lb / es), leg_cols, pl, st, my)) return rc;
     const double s = 1.0 / ((double)p->ny * p->nx), sy = my ? (double)p->ny / my : 1.0;
     // divergence of all estimators in ONE launch when their Fnorm planes are evenly spaced (one stacked allocation): each
     // estimator's weighted kappa goes to its own plan-owned plane (c[0..2], g[0..1], kT are contiguous and unused here),
     // then one pass sums them in estimator order
-    const size_t rs = es / 2, pb = plane_bytes(p);
+    const size_t rs = es / 2;
     long fn_moff = 0;
     bool dbatch = mv_div_batched(q, nest, host_Fnorm, rs, &fn_moff);
     // ROW STAGE: the k-th separable piece of every estimator in ONE launch (they write different product planes; a launch
@@ -941,12 +904,12 @@ static int qe_mv_pow2(oa_plan* p, Pipeline* q, const MvCall& c, void* out, int a
             if (int rc = qe_cols_div_w(p, g0, g1, host_Fnorm[e], out, (accumulate || e > 0) ? 1 : 0, kappa_cols, kappa_rows, pk, st, my)) return rc;
     }
     if (dbatch) {
-        if (int rc = qe_cols_div_batch_w(p, prod, prod + lbk, host_Fnorm[0], q->c[0], tmp, nest, (long)(2 * lbk / es), fn_moff, (long)(pb / es),
+        if (int rc = qe_cols_div_batch_w(p, prod, prod + lbk, host_Fnorm[0], q->c[0], tmp, nest, (long)(2 * lbk / es), fn_moff, plane_elems(p),
                                          kappa_cols, kappa_rows, pk, st, my)) return rc;
         if (keep_planes) return 0;
         // (the divergence writes columns <= nx/2 only: the planes' row padding beyond holds whatever the work planes held)
         const int wsum = (kappa_cols > 0 && kappa_cols <= p->nx / 2 + 1) ? kappa_cols : p->nx / 2 + 1;
-        return sum_region(p->dtype, q->c[0], (long)(pb / es), nest, out, accumulate ? 1 : 0, p->ny, p->kp, wsum, kappa_rows, st);
+        return sum_region(p->dtype, q->c[0], plane_elems(p), nest, out, accumulate ? 1 : 0, p->ny, p->kp, wsum, kappa_rows, st);
     }
     return 0;
 }
@@ -958,8 +921,8 @@ int oa_qe_tt_splits(oa_plan* p, int nsplits, const void* const* host_kmaps, void
     hipStream_t st = (hipStream_t)stream;
     if (p->mixed) return mixed_qe_tt_splits(p, q, "oa_qe_tt_splits", nsplits, host_kmaps, host_out, nullptr, 0.0, zero_outside, st);
     const long pl = work_pitch(p, q->wl), pk = work_pitch(p, q->wk);
-    const size_t lb = (size_t)pl * p->ny * 2 * (p->dtype == OA_F32 ? 4 : 8);      // one compact leg plane
-    const size_t es = 2 * (p->dtype == OA_F32 ? 4 : 8), lbk = (size_t)pk * p->ny * es;
+    const size_t lb = (size_t)pl * p->ny * elem_bytes(p);      // one compact leg plane
+    const size_t es = elem_bytes(p), lbk = (size_t)pk * p->ny * es;
     const int npairs = nsplits * nsplits;
     // evenly spaced output planes (one (n, n, Ny, kp) block): the divergence of all pairs runs as ONE launch
     bool dbatch = npairs >= 2 && q->opt_mv_batch;
@@ -972,9 +935,9 @@ int oa_qe_tt_splits(oa_plan* p, int nsplits, const void* const* host_kmaps, void
     }
     // pool: 3 leg planes per split | 2 product planes per pair | 2 pass-1 planes per pair (two-pass divergence)
     if (int rc = ensure_pool(q, 3 * lb * nsplits + (dbatch ? 4 * (size_t)npairs * lbk : 0))) return rc;
-    char* const prod = (char*)q->split_legs + 3 * lb * nsplits;
+    char* const prod = q->split_legs.at(3 * lb * nsplits);
     const int my = q->my;
-    auto leg = [&](int i, int c) { return (void*)((char*)q->split_legs + (3 * (size_t)i + c) * lb); };
+    auto leg = [&](int i, int c) { return (void*)q->split_legs.at((3 * (size_t)i + c) * lb); };
     for (int i = 0; i < nsplits; ++i) {
         OA_REQUIRE(host_kmaps[i], "oa_qe_tt_splits: NULL split plane");
         if (int rc = qe_legs_cols_w(p, host_kmaps[i], host_kmaps[i], q->FG, q->FH, leg(i, 0), leg(i, 1), leg(i, 2), q->wl, q->rl, pl, st, my)) return rc;
@@ -1035,7 +998,7 @@ int oa_qe_tt_moments2(oa_plan* p, const void* real_map0, const void* real_map1, 
     }
     // both kappa planes binned in one launch pair (grid y = map; kT sits one plane IN FRONT of kk: stride -1 plane), the moment
     // tail adds the two bandpower vectors in map order
-    const long es = 2 * (p->dtype == OA_F32 ? 4 : 8);
+    const long es = elem_bytes(p);
     const long back = ((const char*)q->kT - (const char*)q->kk) / es;
     return bin_power_moments(p->dtype, q->kk, q->norm, q->ids, (long)p->ny * p->kp, q->nids, p->kp, p->nx / 2, q->sums, q->counts_tmp,
                              q->bin_scratch, q->wk, q->rk, q->ticket, q->counts_full, n, S, C, (hipStream_t)stream, 2, back);
@@ -1083,16 +1046,10 @@ int oa_qe_tt_stage(oa_plan* p, int stage, const void* real_map, void* stream) {
 }  // extern "C"
 
 namespace oa {
-static int ensure_mc_src(oa_plan* p, Pipeline* q) {
-    if (q->mc_cap >= MC_BATCH_MAX) return 0;
-    if (q->mc_src) { OA_HIP(hipDeviceSynchronize()); (void)hipFree(q->mc_src); q->mc_src = nullptr; q->mc_cap = 0; }
-    OA_HIP(hipMalloc(&q->mc_src, (size_t)MC_BATCH_MAX * plane_bytes(p)));
-    q->mc_cap = MC_BATCH_MAX;
-    return 0;
-}
+static int ensure_mc_src(oa_plan* p, Pipeline* q, bool zero = false) { return q->mc_src.reserve((size_t)MC_BATCH_MAX * plane_bytes(p), zero); }
 // pool bytes of a batch of B realisations: 3 B leg planes (gx_b, gy_b at 2b, 2b + 1; h_b at 2B + b) | 2 B product planes | 2 B pass-1 planes
 static size_t mc_pool_bytes(const oa_plan* p, const Pipeline* q, int B) {
-    const size_t es = 2 * (p->dtype == OA_F32 ? 4 : 8);
+    const size_t es = elem_bytes(p);
     return 3 * (size_t)B * work_pitch(p, q->wl) * p->ny * es + 4 * (size_t)B * work_pitch(p, q->wk) * p->ny * es;
 }
 /* Everything behind the transforms of a BATCH of B realisations (q->mc_src: their hc planes, leg band filled): leg planes, row
@@ -1103,11 +1060,11 @@ static int mc_batch_tail(oa_plan* p, Pipeline* q, int B, int64_t* n, double* S, 
                          bool keep_kappa = false) {     // keep_kappa: the kappa planes are stored (c[0] ...) even without a stack here
     *fallback = 0;
     const long pl = work_pitch(p, q->wl), pk = work_pitch(p, q->wk);
-    const size_t es = 2 * (p->dtype == OA_F32 ? 4 : 8), pb = plane_bytes(p);
+    const size_t es = elem_bytes(p);
     const size_t lb = (size_t)pl * p->ny * es, lbk = (size_t)pk * p->ny * es;
     const int my = q->my;
     if (int rc = ensure_pool(q, mc_pool_bytes(p, q, B))) return rc;
-    char* const legs = (char*)q->split_legs;
+    char* const legs = q->split_legs.at();
     char* const prod = legs + 3 * (size_t)B * lb;
     char* const tmp = prod + 2 * (size_t)B * lbk;
     std::vector<const void*> key;
@@ -1123,7 +1080,7 @@ static int mc_batch_tail(oa_plan* p, Pipeline* q, int B, int64_t* n, double* S, 
     // (the row stage's geometry check first: nothing may have been launched when this batch falls back)
     const double s = 1.0 / ((double)p->ny * p->nx), sy = my ? (double)p->ny / my : 1.0;
     int legs_done = 0, rc;
-    if ((rc = qe_legs_batch_w(p, q->mc_src, (long)(pb / es), 0, sel, (const void* const*)q->mv_ftab, B, B, legs, (long)(lb / es), q->wl, q->rl,
+    if ((rc = qe_legs_batch_w(p, q->mc_src.p, plane_elems(p), 0, sel, (const void* const*)q->mv_ftab, B, B, legs, (long)(lb / es), q->wl, q->rl,
                               pl, st, my, 4, &legs_done))) return rc;
     if (!legs_done && (rc = qe_legs_pass2_w(p, legs, 3 * B, (long)(lb / es), q->wl, pl, st, my))) return rc;
     rc = qe_rows_batch_w(p, legs, legs + lb, legs + 2 * (size_t)B * lb, prod, prod + lbk, s * s * sy, q->wl, q->wk, q->mrow, pl, pk, st, my, B,
@@ -1132,14 +1089,14 @@ static int mc_batch_tail(oa_plan* p, Pipeline* q, int B, int64_t* n, double* S, 
     if (rc) return rc;
     if ((rc = ensure_div_tables(p, q, st))) return rc;
     DivBinFuse f = make_fuse(p, q, n, S, C, (meanfield_acc || keep_kappa) ? 1 : 0);
-    if ((rc = qe_cols_div_batch_w(p, prod, prod + lbk, q->Fn, q->c[0], tmp, B, (long)(2 * lbk / es), 0, (long)(pb / es), q->wk, q->rk, pk, st, my,
+    if ((rc = qe_cols_div_batch_w(p, prod, prod + lbk, q->Fn, q->c[0], tmp, B, (long)(2 * lbk / es), 0, plane_elems(p), q->wk, q->rk, pk, st, my,
                                   divbin_enabled(q) ? &f : nullptr)))
         return rc;
     // binned power of the B kappa planes + their moment updates in realisation order: in the divergence launch, else two
     // launches; the mean-field stack: one
     if (!f.done && (rc = bin_power_moments(p->dtype, q->c[0], q->norm, q->ids, (long)p->ny * p->kp, q->nids, p->kp, p->nx / 2, q->sums, q->counts_tmp,
-                                q->bin_scratch, q->wk, q->rk, q->ticket, q->counts_full, n, S, C, st, B, (long)(pb / es)))) return rc;
-    if (meanfield_acc && (rc = stack_add_region(p->dtype, q->c[0], meanfield_acc, p->ny, p->kp, q->wk, q->rk, st, B, (long)(2 * pb / es)))) return rc;
+                                q->bin_scratch, q->wk, q->rk, q->ticket, q->counts_full, n, S, C, st, B, plane_elems(p)))) return rc;
+    if (meanfield_acc && (rc = stack_add_region(p->dtype, q->c[0], meanfield_acc, p->ny, p->kp, q->wk, q->rk, st, B, 2 * plane_elems(p)))) return rc;
     return 0;
 }
 
@@ -1201,26 +1158,18 @@ static int mixed_bind(oa_plan* p, Pipeline* q) {
     OA_HIP(hipDeviceSynchronize());
     if (!q->band || q->bmy != my || q->bmx != mx) {
         if (q->band) { (void)oa_plan_destroy(q->band); q->band = nullptr; }
-        if (q->bplanes) { (void)hipFree(q->bplanes); q->bplanes = nullptr; }
-        if (q->bids) { (void)hipFree(q->bids); q->bids = nullptr; }
-        if (q->bsplit) { (void)hipFree(q->bsplit); q->bsplit = nullptr; q->bsplit_bytes = 0; q->bs_cap = 0; }     // (sized by the inner plane)
-        if (q->bwin) { (void)hipFree(q->bwin); q->bwin = nullptr; q->bwin_bytes = 0; }                            // (retaken by the next windowed call)
+        q->release_band();           // (bsplit, bwin: sized by the inner plane, retaken by the next call that needs them)
         q->bmy = q->bmx = 0;
         if (int rc = band_inner_plan(p, my, mx, &q->band)) return rc;
-        OA_HIP(hipMalloc(&q->bplanes, 3 * band_real_bytes(q->band) + 2 * plane_bytes(q->band)));
-        OA_HIP(hipMalloc((void**)&q->bids, (size_t)my * q->band->kp * sizeof(int32_t)));
+        if (int rc = q->bplanes.reserve(3 * band_real_bytes(q->band) + 2 * plane_bytes(q->band))) return rc;
+        if (int rc = q->bids.reserve((size_t)my * q->band->kp * sizeof(int32_t))) return rc;
         q->bmy = my; q->bmx = mx;
         band_options(q);
     }
     oa_plan* b = q->band;
     const size_t rb = band_real_bytes(b);
-    const size_t sb = band_map_scratch_bytes(p, q->wl, q->rl);
-    if (q->brows_bytes < sb) {
-        if (q->brows) { (void)hipFree(q->brows); q->brows = nullptr; q->brows_bytes = 0; }
-        OA_HIP(hipMalloc(&q->brows, sb));
-        q->brows_bytes = sb;
-    }
-    char* f = (char*)q->bplanes;
+    if (int rc = q->brows.reserve(band_map_scratch_bytes(p, q->wl, q->rl))) return rc;
+    char* f = q->bplanes.at();
     OA_HIP(hipMemset(f, 0, 3 * rb + 2 * plane_bytes(b)));          // zero outside the bands (the input planes: only their band is written)
     const int kind = p->dtype == OA_F32 ? 0 : 1;
     const double fscale = (double)b->ny * b->nx / ((double)p->ny * p->nx);
@@ -1240,18 +1189,15 @@ static int mixed_bind(oa_plan* p, Pipeline* q) {
 // by the full grid's count).  Also takes the band plan's Monte-Carlo planes now (set-up time), zero-filled
 static int mixed_bins(oa_plan* p, Pipeline* q, hipStream_t st) {
     oa_plan* b = q->band;
-    OA_HIP(hipMemsetAsync(q->bids, 0xFF, (size_t)b->ny * b->kp * sizeof(int32_t), st));
-    if (int rc = band_copy(2, q->ids, p->kp, p->ny, q->bids, b->kp, b->ny, q->wk, q->rk, 1.0, st)) return rc;
-    if (int rc = oa_plan_set_bins(b, q->bids, q->nids, q->norm, st)) return rc;
+    OA_HIP(hipMemsetAsync(q->bids.p, 0xFF, (size_t)b->ny * b->kp * sizeof(int32_t), st));
+    if (int rc = band_copy(2, q->ids, p->kp, p->ny, q->bids.p, b->kp, b->ny, q->wk, q->rk, 1.0, st)) return rc;
+    if (int rc = oa_plan_set_bins(b, (const int32_t*)q->bids.p, q->nids, q->norm, st)) return rc;
     Pipeline* qb = (Pipeline*)b->pipe;
     OA_HIP(hipMemcpyAsync(qb->counts_full, q->counts_full, q->nids * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-    if (!qb->mc_src) {
-        if (int rc = ensure_mc_src(b, qb)) return rc;
-        OA_HIP(hipMemset(qb->mc_src, 0, (size_t)MC_BATCH_MAX * plane_bytes(b)));
-    }
+    if (int rc = ensure_mc_src(b, qb, true)) return rc;
     return ensure_pool(qb, mc_pool_bytes(b, qb, MC_BATCH_MAX));
 }
-static void* band_in(const Pipeline* q, int which) { return (char*)q->bplanes + 3 * band_real_bytes(q->band) + which * plane_bytes(q->band); }
+static void* band_in(const Pipeline* q, int which) { return q->bplanes.at(3 * band_real_bytes(q->band) + which * plane_bytes(q->band)); }
 static int band_cx_kind(const oa_plan* p) { return p->dtype == OA_F32 ? 3 : 4; }
 
 // oa_qe_tt: input band -> band plan's fused pipeline (kappa on its plan-owned plane) -> scatter into the N-grid output
@@ -1260,7 +1206,7 @@ static int mixed_qe_tt(oa_plan* p, Pipeline* q, const void* map, const void* kX,
     void* bx = band_in(q, 0);
     void* by = nullptr;
     int rc;
-    if (map) rc = band_map_r2c(p, map, q->brows, q->wl, q->rl, bx, b->ny, b->kp, st);
+    if (map) rc = band_map_r2c(p, map, q->brows.p, q->wl, q->rl, bx, b->ny, b->kp, st);
     else {
         rc = band_copy(band_cx_kind(p), kX, p->kp, p->ny, bx, b->kp, b->ny, q->wl, q->rl, 1.0, st);
         if (!rc && kY && kY != kX) { by = band_in(q, 1); rc = band_copy(band_cx_kind(p), kY, p->kp, p->ny, by, b->kp, b->ny, q->wl, q->rl, 1.0, st); }
@@ -1277,111 +1223,124 @@ static int mixed_moments(oa_plan* p, Pipeline* q, const void* map, int64_t* n, d
     Pipeline* qb = (Pipeline*)b->pipe;
     band_options(q);
     void* bx = band_in(q, 0);
-    if (int rc = band_map_r2c(p, map, q->brows, q->wl, q->rl, bx, b->ny, b->kp, st)) return rc;
+    if (int rc = band_map_r2c(p, map, q->brows.p, q->wl, q->rl, bx, b->ny, b->kp, st)) return rc;
     if (int rc = ensure_div_tables(b, qb, st)) return rc;
     DivBinFuse f = make_fuse(b, qb, n, S, C, 0);
     if (int rc = qe_tt_impl(b, nullptr, bx, nullptr, nullptr, 0, st, divbin_enabled(qb) ? &f : nullptr)) return rc;
     if (f.done) return 0;
     return bandpower_moments(b, qb, n, S, C, st);
 }
-// oa_mc_run: the leg band of each realisation's N-grid draw straight into the band plan's layout, then oa_mc_run's batched launches there;
-// the mean-field stack is updated in the N-grid layout from the batch's kappa planes
+/* ---- the shard loop of oa_mc_run / oa_mc_run_windowed, both plan kinds --------------------------------------------------------------
+ * `grid` is the map's plan (Philox counters, the window and the mean-field stack are its), `run` the plan the estimator and the binning
+ * run on: `grid` itself (power of two) or the inner plan of its band grid; `rq` is run's Pipeline.
+ * BATCHES of realisations: at 4096^2 a realisation is ~60 MB of traffic behind ~10 launches, i.e. launch latency; with B realisations per
+ * launch (grid z) the column and row stages fill the chip (OA_OPT_MC_BATCH 1 / 2 / 4 / 6 per launch at 4096^2: 16.5 / 26.0 / 37.6 / 40.3 k
+ * realisations/s).  A batch of ONE goes through the same launches, so the moments do not depend on the batch size.  `source_batch(i, B)`
+ * leaves the leg bands of realisations i .. i + B - 1 in run's mc_src, mc_batch_tail does the rest.  A geometry whose row stage takes one
+ * map per launch reports `fallback` from its first batch, after the source stage and the leg launches (plan-owned planes only: harmless)
+ * have run; the one-by-one loop then starts from the same i and draws that realisation again with the same counters.
+ * ONE BY ONE: `source_one(i)` leaves realisation i in `one_map` (a real map; rows_done: its row transform on the plan's scratch plane
+ * instead, qe_windowed_rows_w) or on the leg band of `one_k` (Fourier plane); then the estimator -- with `fuse`, binning + moments in the
+ * divergence launch where the geometry has that kernel --, the bandpower moments, the stack. */
+struct McTtLoop {
+    oa_plan* grid; oa_plan* run; Pipeline* rq;
+    bool batched;                                   // whether batching may start
+    size_t pool_extra;                              // bytes per realisation of a batch behind the tail's region of run's pool
+    std::function<int(long, int)> source_batch;
+    std::function<int(long)> source_one;
+    const void* one_map; const void* one_k; int rows_done; bool fuse;
+};
+static int mc_tt_loop(const McTtLoop& T, long sim_lo, long sim_hi, int64_t* n, double* S, double* C, double* meanfield_acc, hipStream_t st) {
+    oa_plan* const r = T.run;
+    Pipeline* const rq = T.rq;
+    const bool inner = T.grid != r;                 // the stack is grid's plane: kappa's band goes from the inner rows and pitch to the N grid's
+    auto stack = [&](const void* kappa, int B, long stride) {
+        if (!meanfield_acc) return 0;
+        if (inner) return band_stack_add(T.grid->dtype, kappa, r->kp, r->ny, B, stride, meanfield_acc, T.grid->kp, T.grid->ny, rq->wk, rq->rk, st);
+        // kappa_hat vanishes outside its active region (the plan-owned plane was zero-filled once): stack only that
+        return stack_add_region(r->dtype, kappa, meanfield_acc, r->ny, r->kp, rq->wk, rq->rk, st);
+    };
+    const int BMAX = std::max(1, std::min(MC_BATCH_MAX, rq->opt_mc_batch));
+    long i = sim_lo;
+    bool batched = T.batched;
+    while (batched && i < sim_hi) {
+        const int B = (int)std::min<long>(BMAX, sim_hi - i);
+        // before the first draw: growing either synchronises the device (a band plan's were taken by oa_plan_set_bins: no allocation here)
+        if (int rc = ensure_mc_src(r, rq)) return rc;
+        if (int rc = ensure_pool(rq, mc_pool_bytes(r, rq, B) + (size_t)B * T.pool_extra)) return rc;
+        int rc = T.source_batch(i, B), fallback = 0;
+        if (rc) return rc;
+        // the power-of-two plans' stack is added inside the tail, in the batch's launch; a band plan's from the kappa planes it keeps
+        if ((rc = mc_batch_tail(r, rq, B, n, S, C, inner ? nullptr : meanfield_acc, st, &fallback, inner && meanfield_acc))) return rc;
+        if (fallback) break;
+        if (inner && (rc = stack(rq->c[0], B, plane_elems(r)))) return rc;
+        i += B;
+    }
+    for (; i < sim_hi; ++i) {
+        int rc = T.source_one(i);
+        if (rc) return rc;
+        DivBinFuse f = make_fuse(r, rq, n, S, C, meanfield_acc ? 1 : 0);     // (kappa_hat still stored when the stack needs it)
+        if ((rc = qe_tt_impl(r, T.one_map, T.one_k, nullptr, nullptr, 0, st, T.fuse && divbin_enabled(rq) ? &f : nullptr, T.rows_done))) return rc;
+        if (!f.done && (rc = bandpower_moments(r, rq, n, S, C, st))) return rc;
+        if ((rc = stack(rq->kk, 1, 0))) return rc;
+    }
+    return 0;
+}
+// oa_mc_run on a band grid: the leg band of each realisation's N-grid draw straight into the band plan's layout
 static int mixed_mc_run(oa_plan* p, Pipeline* q, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, int64_t* n, double* S,
                         double* C, double* meanfield_acc, hipStream_t st) {
     oa_plan* b = q->band;
     Pipeline* qb = (Pipeline*)b->pipe;
     band_options(q);
-    const int BMAX = std::max(1, std::min(MC_BATCH_MAX, qb->opt_mc_batch));
-    const long pbe = (long)(plane_bytes(b) / (2 * (b->dtype == OA_F32 ? 4 : 8)));     // complex elements per band plane
-    long i = sim_lo;
-    bool batched = true;
-    while (batched && i < sim_hi) {
-        const int B = (int)std::min<long>(BMAX, sim_hi - i);
-        if (int rc = ensure_mc_src(b, qb)) return rc;                            // (taken by oa_plan_set_bins: no allocation here)
-        if (int rc = ensure_pool(qb, mc_pool_bytes(b, qb, B))) return rc;
-        int rc = grf_band_inner(p, base_seed, (uint64_t)i, B, covsqrt_hc, qb->mc_src, b->ny, b->kp, pbe, q->wl, q->rl, st);
-        if (rc) return rc;
-        int fallback = 0;
-        if ((rc = mc_batch_tail(b, qb, B, n, S, C, nullptr, st, &fallback, meanfield_acc != nullptr))) return rc;
-        if (fallback) { batched = false; break; }
-        if (meanfield_acc && (rc = band_stack_add(p->dtype, qb->c[0], b->kp, b->ny, B, pbe, meanfield_acc, p->kp, p->ny, q->wk, q->rk, st))) return rc;
-        i += B;
-    }
-    void* bx = band_in(q, 0);
-    for (; i < sim_hi; ++i) {
-        int rc = grf_band_inner(p, base_seed, (uint64_t)i, 1, covsqrt_hc, bx, b->ny, b->kp, 0, q->wl, q->rl, st);
-        if (rc) return rc;
-        if ((rc = qe_tt_impl(b, nullptr, bx, nullptr, nullptr, 0, st, nullptr))) return rc;
-        if ((rc = bandpower_moments(b, qb, n, S, C, st))) return rc;
-        if (meanfield_acc && (rc = band_stack_add(p->dtype, qb->kk, b->kp, b->ny, 1, 0, meanfield_acc, p->kp, p->ny, q->wk, q->rk, st))) return rc;
-    }
-    return 0;
+    void* const bx = band_in(q, 0);
+    McTtLoop T{p, b, qb, true, 0, nullptr, nullptr, nullptr, bx, 0, false};
+    T.source_batch = [=](long i, int B) { return grf_band_inner(p, base_seed, (uint64_t)i, B, covsqrt_hc, qb->mc_src.p, b->ny, b->kp, plane_elems(b), q->wl, q->rl, st); };
+    T.source_one = [=](long i) { return grf_band_inner(p, base_seed, (uint64_t)i, 1, covsqrt_hc, bx, b->ny, b->kp, 0, q->wl, q->rl, st); };
+    return mc_tt_loop(T, sim_lo, sim_hi, n, S, C, meanfield_acc, st);
 }
-// oa_mc_run_windowed: per realisation the full-plane draw on the N grid and its inverse column transform (in place); per batch ONE fused
-// windowed row launch (C2R x window -> R2C, columns < wl stored: band_rows_win_kernel) and the pruned column DFT onto the band plan's
-// source planes, then oa_mc_run's batched launches there.  OA_OPT_WIN_FUSED = 0: one by one, C2R with the window at the row store -> real
-// map in HBM -> band_map_r2c.
+// oa_mc_run_windowed on a band grid: per realisation the full-plane draw on the N grid and its inverse column transform (in place); per
+// batch ONE fused windowed row launch (C2R x window -> R2C, columns < wl stored: band_rows_win_kernel) and the pruned column DFT onto the
+// band plan's source planes.  OA_OPT_WIN_FUSED = 0: one by one, C2R with the window at the row store -> real map in HBM -> band_map_r2c.
 static int mixed_mc_run_windowed(oa_plan* p, Pipeline* q, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, const void* window,
                                  int64_t* n, double* S, double* C, double* meanfield_acc, hipStream_t st) {
     oa_plan* b = q->band;
     Pipeline* qb = (Pipeline*)b->pipe;
     band_options(q);
-    const int BMAX = std::max(1, std::min(MC_BATCH_MAX, qb->opt_mc_batch));
-    const size_t pb = plane_bytes(p), es = 2 * (p->dtype == OA_F32 ? 4 : 8);
-    const long pbe = (long)(plane_bytes(b) / es), pne = (long)(pb / es);                // complex elements per band plane / per N-grid plane
+    const size_t pb = plane_bytes(p);
+    const long pbe = plane_elems(b), pne = plane_elems(p);
     // entry-owned planes, taken on the first windowed call (and regrown when the band widens): that call synchronises the device once
-    const size_t need = (size_t)MC_BATCH_MAX * pb + std::max(band_maps_scratch_bytes(p, MC_BATCH_MAX, q->wl, q->rl), band_map_scratch_bytes(p, q->wl, q->rl));
-    if (q->bwin_bytes < need) {
-        if (q->bwin) { OA_HIP(hipDeviceSynchronize()); (void)hipFree(q->bwin); q->bwin = nullptr; q->bwin_bytes = 0; }
-        OA_HIP(hipMalloc(&q->bwin, need));
-        q->bwin_bytes = need;
-    }
-    char* const draw = (char*)q->bwin;
+    if (int rc = q->bwin.reserve((size_t)MC_BATCH_MAX * pb + std::max(band_maps_scratch_bytes(p, MC_BATCH_MAX, q->wl, q->rl),
+                                                                      band_map_scratch_bytes(p, q->wl, q->rl)))) return rc;
+    char* const draw = q->bwin.at();
     void* const rows = draw + (size_t)MC_BATCH_MAX * pb;
+    void* const bx = band_in(q, 0);
     const double inv = 1.0 / ((double)p->ny * p->nx);
-    long i = sim_lo;
     // fused row pass or the unfused flow: the caller's OA_OPT_WIN_FUSED; until it is set, what measured faster (DESIGN 5a,
     // profiles/band_grid_windowed.jsonl): the unfused flow at 1200^2 (by 1 % f32, 5 % f64), the fused pass at 2400^2 (by up to 1 %)
     // (rows the fused kernel does not hold -- more than 8192 points -- take the unfused flow, whose row passes have an in-place form)
     const bool fused = q->opt_win_fused_set ? q->opt_win_fused : (p->nx > 1200 && band_rows_win_ok(p));
     // (an inner plan whose row stage takes one map per launch -- row grids below 1024 points -- abandons its first batch of every call
     // after the front end has run: about 1 % of a 300-realisation call)
-    bool batched = fused;
-    while (batched && i < sim_hi) {
-        const int B = (int)std::min<long>(BMAX, sim_hi - i);
-        if (int rc = ensure_mc_src(b, qb)) return rc;                            // (taken by oa_plan_set_bins: no allocation here)
-        if (int rc = ensure_pool(qb, mc_pool_bytes(b, qb, B))) return rc;
-        int rc = 0;
+    McTtLoop T{p, b, qb, fused, 0, nullptr, nullptr, nullptr, bx, 0, false};
+    T.source_batch = [=](long i, int B) {
         for (int k = 0; k < B; ++k) {
             void* pl = draw + (size_t)k * pb;
-            if ((rc = oa_grf_hc(p, base_seed, (uint64_t)(i + k), covsqrt_hc, pl, st))) return rc;
-            if ((rc = mixed_cols_inverse(p, pl, pl, st))) return rc;
+            if (int rc = oa_grf_hc(p, base_seed, (uint64_t)(i + k), covsqrt_hc, pl, st)) return rc;
+            if (int rc = mixed_cols_inverse(p, pl, pl, st)) return rc;
         }
-        if ((rc = band_win_r2c(p, B, draw, pne, window, inv, rows, 0, q->wl, q->rl, nullptr, nullptr, qb->mc_src, pbe, b->ny, b->kp, st))) return rc;
-        int fallback = 0;
-        if ((rc = mc_batch_tail(b, qb, B, n, S, C, nullptr, st, &fallback, meanfield_acc != nullptr))) return rc;
-        if (fallback) { batched = false; break; }
-        if (meanfield_acc && (rc = band_stack_add(p->dtype, qb->c[0], b->kp, b->ny, B, pbe, meanfield_acc, p->kp, p->ny, q->wk, q->rk, st))) return rc;
-        i += B;
-    }
-    void* bx = band_in(q, 0);
-    for (; i < sim_hi; ++i) {
-        int rc = oa_grf_hc(p, base_seed, (uint64_t)i, covsqrt_hc, draw, st);
-        if (rc) return rc;
+        return band_win_r2c(p, B, draw, pne, window, inv, rows, 0, q->wl, q->rl, nullptr, nullptr, qb->mc_src.p, pbe, b->ny, b->kp, st);
+    };
+    T.source_one = [=](long i) {
+        if (int rc = oa_grf_hc(p, base_seed, (uint64_t)i, covsqrt_hc, draw, st)) return rc;
         if (fused) {
-            if ((rc = mixed_cols_inverse(p, draw, draw, st))) return rc;
-            rc = band_win_r2c(p, 1, draw, pne, window, inv, rows, 1, q->wl, q->rl, nullptr, nullptr, bx, 0, b->ny, b->kp, st);
-        } else {
-            void* tmap = draw + pb;                                              // ny x nx reals fit an hc plane
-            if ((rc = oa_fft_c2r_windowed(p, draw, tmap, inv, window, st))) return rc;
-            rc = band_map_r2c(p, tmap, rows, q->wl, q->rl, bx, b->ny, b->kp, st);
+            if (int rc = mixed_cols_inverse(p, draw, draw, st)) return rc;
+            return band_win_r2c(p, 1, draw, pne, window, inv, rows, 1, q->wl, q->rl, nullptr, nullptr, bx, 0, b->ny, b->kp, st);
         }
-        if (rc) return rc;
-        if ((rc = qe_tt_impl(b, nullptr, bx, nullptr, nullptr, 0, st, nullptr))) return rc;
-        if ((rc = bandpower_moments(b, qb, n, S, C, st))) return rc;
-        if (meanfield_acc && (rc = band_stack_add(p->dtype, qb->kk, b->kp, b->ny, 1, 0, meanfield_acc, p->kp, p->ny, q->wk, q->rk, st))) return rc;
-    }
-    return 0;
+        void* tmap = draw + pb;                                                  // ny x nx reals fit an hc plane
+        if (int rc = oa_fft_c2r_windowed(p, draw, tmap, inv, window, st)) return rc;
+        return band_map_r2c(p, tmap, rows, q->wl, q->rl, bx, b->ny, b->kp, st);
+    };
+    return mc_tt_loop(T, sim_lo, sim_hi, n, S, C, meanfield_acc, st);
 }
 /* ---- oa_qe_pol / oa_qe_mv on the band grid -------------------------------------------------------------------------------------------
  * These entries take their filter planes per call, so the inner-layout copies are made by a set-up entry (oa_qe_band_bind, which may
@@ -1400,8 +1359,8 @@ static int pol_bind(oa_plan* p, Pipeline* q, int nf, const void* const* filters,
     OA_HIP(hipDeviceSynchronize());                 // the caller's planes may have been written on any stream; the old copies may be in use
     if (!B.plan || B.my != my || B.mx != mx) {
         if (B.plan) { (void)oa_plan_destroy(B.plan); B.plan = nullptr; }
-        if (B.mrows) { (void)hipFree(B.mrows); B.mrows = nullptr; B.mrows_bytes = 0; }      // (the from-maps calls' scratch: retaken on demand)
-        if (B.mwin) { (void)hipFree(B.mwin); B.mwin = nullptr; B.mwin_bytes = 0; }          // (the windowed Monte Carlo's planes: likewise)
+        B.mrows.release();                          // (the from-maps calls' scratch: retaken on demand)
+        B.mwin.release();                           // (the windowed Monte Carlo's planes: likewise)
         B.my = B.mx = 0;
         if (int rc = band_inner_plan(p, my, mx, &B.plan)) return rc;
         B.my = my; B.mx = mx;
@@ -1410,24 +1369,20 @@ static int pol_bind(oa_plan* p, Pipeline* q, int nf, const void* const* filters,
     Pipeline* qb = pipe_of(b);
     band_options(q);
     const size_t rb = band_real_bytes(b), cb = plane_bytes(b), need = (size_t)(nf + nn) * rb + (size_t)POL_SRC_MAX * cb;
-    if (B.planes_bytes < need) {
-        if (B.planes) { (void)hipFree(B.planes); B.planes = nullptr; B.planes_bytes = 0; }
-        OA_HIP(hipMalloc(&B.planes, need));
-        B.planes_bytes = need;
-    }
-    OA_HIP(hipMemset(B.planes, 0, need));           // zero outside the bands (source planes: only their band is ever written)
-    if (!B.stab) OA_HIP(hipMalloc((void**)&B.stab, POL_SRC_MAX * sizeof(void*)));
+    if (int rc = B.planes.reserve(need)) return rc;
+    OA_HIP(hipMemset(B.planes.p, 0, need));         // zero outside the bands (source planes: only their band is ever written)
+    if (int rc = B.stab.reserve(POL_SRC_MAX * sizeof(void*))) return rc;
     B.skey.clear();
     const int kind = p->dtype == OA_F32 ? 0 : 1;
     const double fscale = (double)b->ny * b->nx / ((double)p->ny * p->nx);
-    char* f = (char*)B.planes;
+    char* f = B.planes.at();
     for (int i = 0; i < nf; ++i)
         if (int rc = band_copy(kind, filters[i], p->kp, p->ny, f + (size_t)i * rb, b->kp, my, wl, rl, 1.0, nullptr)) return rc;
     for (int i = 0; i < nn; ++i)
         if (int rc = band_copy(kind, norms[i], p->kp, p->ny, f + (size_t)(nf + i) * rb, b->kp, my, wk, rk, fscale, nullptr)) return rc;
     // everything the inner entries would otherwise take on first use
     if (int rc = ensure_work(b, qb)) return rc;
-    const size_t es = 2 * (b->dtype == OA_F32 ? 4 : 8);
+    const size_t es = elem_bytes(b);
     const size_t lb = (size_t)work_pitch(b, wl) * b->ny * es, lbk = (size_t)work_pitch(b, wk) * b->ny * es;
     if (int rc = ensure_pool(qb, (size_t)(max_leg_planes > 0 ? max_leg_planes : 3 * nf) * lb + 4 * (size_t)nn * lbk)) return rc;
     if (!qb->mv_ftab) OA_HIP(hipMalloc((void**)&qb->mv_ftab, 32 * sizeof(void*)));
@@ -1450,12 +1405,11 @@ static void* pol_inner(const std::vector<const void*>& key, const void* ptr, cha
 static int mv_sources_embed(oa_plan* p, Pipeline::PolBind& B, const std::vector<const void*>& srcs, char* sbase, size_t cb, int wl, int rl,
                             hipStream_t st) {
     const oa_plan* b = B.plan;
-    const size_t es = 2 * (b->dtype == OA_F32 ? 4 : 8);
     if (srcs != B.skey) {                             // (pageable source: staged before the call returns; ordered on this stream)
-        OA_HIP(hipMemcpyAsync(B.stab, srcs.data(), srcs.size() * sizeof(void*), hipMemcpyHostToDevice, st));
+        OA_HIP(hipMemcpyAsync(B.stab.p, srcs.data(), srcs.size() * sizeof(void*), hipMemcpyHostToDevice, st));
         B.skey = srcs;
     }
-    return band_embed(p->dtype, (const void* const*)B.stab, (int)srcs.size(), p->kp, p->ny, sbase, (long)(cb / es), b->kp, b->ny, wl, rl, st);
+    return band_embed(p->dtype, (const void* const*)B.stab.p, (int)srcs.size(), p->kp, p->ny, sbase, plane_elems(b), b->kp, b->ny, wl, rl, st);
 }
 // SOURCE STAGE of oa_qe_mv_maps: the batched band input transform of the call's real maps (with the Q,U -> E,B rotation) straight into
 // the inner source planes -- no N-grid hc plane, no embed, no device table.  The map-side scratch belongs to the binding: taken on the
@@ -1463,14 +1417,8 @@ static int mv_sources_embed(oa_plan* p, Pipeline::PolBind& B, const std::vector<
 // once); later calls neither allocate nor synchronise
 static int mv_sources_maps(oa_plan* p, Pipeline::PolBind& B, const MvCall& c, char* sbase, size_t cb, int wl, int rl, hipStream_t st) {
     const oa_plan* b = B.plan;
-    const size_t es = 2 * (b->dtype == OA_F32 ? 4 : 8), need = band_maps_scratch_bytes(p, c.nmaps, wl, rl);
-    if (B.mrows_bytes < need) {
-        OA_HIP(hipDeviceSynchronize());
-        if (B.mrows) { (void)hipFree(B.mrows); B.mrows = nullptr; B.mrows_bytes = 0; }
-        OA_HIP(hipMalloc(&B.mrows, need));
-        B.mrows_bytes = need;
-    }
-    return band_maps_r2c(p, c.nmaps, c.maps, c.rot_c, c.rot_s, B.mrows, wl, rl, sbase, (long)(cb / es), b->ny, b->kp, st);
+    if (int rc = B.mrows.reserve(band_maps_scratch_bytes(p, c.nmaps, wl, rl))) return rc;
+    return band_maps_r2c(p, c.nmaps, c.maps, c.rot_c, c.rot_s, B.mrows.p, wl, rl, sbase, plane_elems(b), b->ny, b->kp, st);
 }
 static int mixed_qe_mv(oa_plan* p, Pipeline* q, const MvCall& c, void* out, int accumulate, int wl, int wk, int rl, int rk, int mrow, int zero_outside,
                        hipStream_t st) {
@@ -1484,8 +1432,8 @@ static int mixed_qe_mv(oa_plan* p, Pipeline* q, const MvCall& c, void* out, int 
     oa_plan* b = B.plan;
     Pipeline* qb = (Pipeline*)b->pipe;
     band_options(q);
-    const size_t rb = band_real_bytes(b), cb = plane_bytes(b), es = 2 * (b->dtype == OA_F32 ? 4 : 8);
-    char* const fbase = (char*)B.planes;
+    const size_t rb = band_real_bytes(b), cb = plane_bytes(b), es = elem_bytes(b);
+    char* const fbase = B.planes.at();
     char* const nbase = fbase + B.fkey.size() * rb;
     char* const sbase = nbase + B.nkey.size() * rb;
     int total = 0;
@@ -1531,7 +1479,7 @@ static int mixed_qe_mv(oa_plan* p, Pipeline* q, const MvCall& c, void* out, int 
                 add(hpl, sw ? ikX[e] : ikY[e], iFH[at]);
             }
         const size_t lb = (size_t)work_pitch(b, wl) * b->ny * es, lbk = (size_t)work_pitch(b, wk) * b->ny * es;
-        if ((2 * grad.size() + hpl.size()) * lb + 4 * (size_t)c.nest * lbk > qb->split_bytes)
+        if ((2 * grad.size() + hpl.size()) * lb + 4 * (size_t)c.nest * lbk > qb->split_legs.bytes)
             return fail(std::string(who) + ": this call needs " + std::to_string(2 * grad.size() + hpl.size()) + " leg planes and " + std::to_string(c.nest) +
                         " estimators, more than oa_qe_band_bind was told (max_leg_planes, normalisation planes)");
     }
@@ -1561,31 +1509,27 @@ static int mixed_qe_tt_splits(oa_plan* p, Pipeline* q, const char* who, int nspl
         if (!host_kmaps[i]) return fail(std::string(who) + ": NULL split plane");
     for (int k = 0; k < nout; ++k)
         if (!host_out[k]) return fail(std::string(who) + ": NULL output plane");
-    const size_t cb = plane_bytes(b), es = 2 * (b->dtype == OA_F32 ? 4 : 8);
+    const size_t cb = plane_bytes(b);
     if (n > q->bs_cap) {
-        if (q->bsplit) { OA_HIP(hipDeviceSynchronize()); (void)hipFree(q->bsplit); q->bsplit = nullptr; q->bsplit_bytes = 0; q->bs_cap = 0; }
-        const size_t need = ((size_t)n + (size_t)npairs) * cb;
-        OA_HIP(hipMalloc(&q->bsplit, need));
-        q->bsplit_bytes = need; q->bs_cap = n;
-        OA_HIP(hipMemsetAsync(q->bsplit, 0, (size_t)n * cb, st));    // source planes: zero outside the leg band (only the band is ever written)
+        q->bs_cap = 0;
+        if (int rc = q->bsplit.reserve(((size_t)n + (size_t)npairs) * cb)) return rc;
+        q->bs_cap = n;
+        OA_HIP(hipMemsetAsync(q->bsplit.p, 0, (size_t)n * cb, st));  // source planes: zero outside the leg band (only the band is ever written)
     }
-    if (n + nout > q->bs_tab_cap) {
-        if (q->bs_tab) { OA_HIP(hipDeviceSynchronize()); (void)hipFree(q->bs_tab); q->bs_tab = nullptr; q->bs_tab_cap = 0; }
-        const int cap = std::max(n + nout, 8 + 64);
-        OA_HIP(hipMalloc((void**)&q->bs_tab, (size_t)cap * sizeof(void*)));
-        q->bs_tab_cap = cap;
+    if ((size_t)(n + nout) * sizeof(void*) > q->bs_tab.bytes) {
+        if (int rc = q->bs_tab.reserve((size_t)std::max(n + nout, 8 + 64) * sizeof(void*))) return rc;
         q->bs_key.clear();
     }
     std::vector<const void*> key(host_kmaps, host_kmaps + n);
     if (nout) key.insert(key.end(), host_out, host_out + nout);
     if (key != q->bs_key) {                           // (pageable source: staged before the call returns; ordered on this stream)
         q->bs_key = key;
-        OA_HIP(hipMemcpyAsync(q->bs_tab, q->bs_key.data(), key.size() * sizeof(void*), hipMemcpyHostToDevice, st));
+        OA_HIP(hipMemcpyAsync(q->bs_tab.p, q->bs_key.data(), key.size() * sizeof(void*), hipMemcpyHostToDevice, st));
     }
-    char* const sbase = (char*)q->bsplit;
+    char* const sbase = q->bsplit.at();
     char* const kbase = sbase + (size_t)q->bs_cap * cb;
-    const long pe = (long)(cb / es);                  // complex elements per inner plane
-    int rc = band_embed(p->dtype, (const void* const*)q->bs_tab, n, p->kp, p->ny, sbase, pe, b->kp, b->ny, q->wl, q->rl, st);
+    const long pe = plane_elems(b);                   // complex elements per inner plane
+    int rc = band_embed(p->dtype, (const void* const*)q->bs_tab.p, n, p->kp, p->ny, sbase, pe, b->kp, b->ny, q->wl, q->rl, st);
     if (rc) return rc;
     std::vector<const void*> ins(n);
     std::vector<void*> outs(npairs);
@@ -1594,7 +1538,7 @@ static int mixed_qe_tt_splits(oa_plan* p, Pipeline* q, const char* who, int nspl
     if ((rc = oa_qe_tt_splits(b, n, ins.data(), outs.data(), 0, st))) return rc;
     if (out_power)
         return band_split_power(p->dtype, n, kbase, pe, b->kp, b->ny, out_power, p->kp, p->ny, q->wk, q->rk, norm, zero_outside, st);
-    return band_scatter_batch(p->dtype, kbase, pe, npairs, b->kp, b->ny, (void* const*)(q->bs_tab + n), p->kp, p->ny, q->wk, q->rk, zero_outside, st);
+    return band_scatter_batch(p->dtype, kbase, pe, npairs, b->kp, b->ny, (void* const*)q->bs_tab.p + n, p->kp, p->ny, q->wk, q->rk, zero_outside, st);
 }
 /* ---- oa_mc_run_mv on the band grid ----------------------------------------------------------------------------------------------------
  * The shard's per-call planes that are not filters -- the MV weights and the bin ids -- get their inner-layout copies from a second set-up
@@ -1615,12 +1559,8 @@ static int mc_mv_bind(oa_plan* p, Pipeline* q, const void* w, long wstride, int 
     const size_t off_ids = up256(w ? (size_t)nest * rb : 0), off_draw = up256(off_ids + ib), off_kappa = off_draw + 3 * cb;
     const size_t off_scratch = up256(off_kappa + (size_t)nest * cb), off_sums = up256(off_scratch + (size_t)sbl), need = off_sums + ub;
     OA_HIP(hipDeviceSynchronize());                 // the caller's planes may have been written on any stream; the old copies may be in use
-    if (M.pool_bytes < need) {
-        if (M.pool) { (void)hipFree(M.pool); M.pool = nullptr; M.pool_bytes = 0; }
-        OA_HIP(hipMalloc(&M.pool, need));
-        M.pool_bytes = need;
-    }
-    char* const base = (char*)M.pool;
+    if (int rc = M.pool.reserve(need)) return rc;
+    char* const base = M.pool.at();
     OA_HIP(hipMemset(base, 0, need));               // weights, draws and kappa planes: only their band is ever written
     OA_HIP(hipMemset(base + off_ids, 0xFF, ib));
     if (w)
@@ -1649,44 +1589,49 @@ struct McMvLoop {
     void* draw[3]; char* own; void* scratch; double* sums;
     const void* w; long wstride; const int32_t* ids;
     int mrow;
+    const void* const* FG; const void* const* FH; const void* const* Fn;    // the call's filter / normalisation planes in run's layout
     std::function<int(long)> source;
     double* const* mf = nullptr; double* mf_mv = nullptr;
 };
-static int mc_mv_loop(const McMvLoop& L, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest,
-                      const int* host_npieces, const double* host_signs, const void* const* FG, const void* const* FH, const int* host_swap,
-                      const int* host_xsrc, const int* host_ysrc, const void* const* Fn, int nspec, const int* host_a, const int* host_b, int nids,
-                      const int64_t* counts, double norm, int leg_cols, int kappa_cols, int leg_rows, int kappa_rows, int64_t* n, double* S,
-                      double* C, hipStream_t st) {
+// the arguments of oa_mc_run_mv and (the last four) oa_mc_run_mv_windowed, as the entries receive them (include/orphics_amd.h)
+struct McMvArgs {
+    uint64_t base_seed; long sim_lo, sim_hi; const void* const* covsqrt; int nest; const int* npieces; const double* signs;
+    const void* const* FG; const void* const* FH; const int* swap; const int* xsrc; const int* ysrc; const void* const* Fn;
+    const void* w; long wstride; int nspec; const int* a; const int* b; const int32_t* ids; int nids; const int64_t* counts; double norm;
+    int wl, wk, rl, rk, mrow; int64_t* n; double* S; double* C; hipStream_t st;
+    const void* window; const void* rot_c; const void* rot_s; double* const* mf;
+};
+static int mc_mv_loop(const McMvLoop& L, const McMvArgs& a) {
     oa_plan* r = L.run;
-    const size_t es = 2 * (r->dtype == OA_F32 ? 4 : 8), pb = plane_bytes(r);
+    hipStream_t st = a.st;
+    const size_t pb = plane_bytes(r);
+    const long pe = plane_elems(r);
     const void* const block = L.engaged ? L.rq->c[0] : (const void*)L.own;
-    std::vector<const void*> kX(nest), kY(nest);
-    for (int e = 0; e < nest; ++e) { kX[e] = L.draw[host_xsrc[e]]; kY[e] = L.draw[host_ysrc[e]]; }
-    for (long i = sim_lo; i < sim_hi; ++i) {
+    std::vector<const void*> kX(a.nest), kY(a.nest);
+    for (int e = 0; e < a.nest; ++e) { kX[e] = L.draw[a.xsrc[e]]; kY[e] = L.draw[a.ysrc[e]]; }
+    for (long i = a.sim_lo; i < a.sim_hi; ++i) {
         int rc = L.source    ? L.source(i)
-               : L.grid == r ? oa_grf_mix_band(r, base_seed, 3 * (uint64_t)i, 3, host_covsqrt, 1.0, L.draw, leg_cols, leg_rows, st)
-                             : oa_grf_mix_band_inner(L.grid, base_seed, 3 * (uint64_t)i, 3, host_covsqrt, 1.0, L.draw, r->ny, r->kp, leg_cols,
-                                                     leg_rows, st);
+               : L.grid == r ? oa_grf_mix_band(r, a.base_seed, 3 * (uint64_t)i, 3, a.covsqrt, 1.0, L.draw, a.wl, a.rl, st)
+                             : oa_grf_mix_band_inner(L.grid, a.base_seed, 3 * (uint64_t)i, 3, a.covsqrt, 1.0, L.draw, r->ny, r->kp, a.wl, a.rl, st);
         if (rc) return rc;
         if (L.engaged) {
-            const MvCall c{nest, host_npieces, host_signs, FG, FH, host_swap, kX.data(), kY.data(), Fn, false};
-            if ((rc = qe_mv_pow2(r, L.rq, c, nullptr, 0, leg_cols, kappa_cols, leg_rows, kappa_rows, L.mrow, 0, st, true))) return rc;
+            const MvCall c{a.nest, a.npieces, a.signs, L.FG, L.FH, a.swap, kX.data(), kY.data(), L.Fn, false};
+            if ((rc = qe_mv_pow2(r, L.rq, c, nullptr, 0, a.wl, a.wk, a.rl, a.rk, L.mrow, 0, st, true))) return rc;
         } else {
-            for (int e = 0, at = 0; e < nest; at += host_npieces[e], ++e) {      // one at a time, each into its plane of the entry's block
-                const MvCall c{1, host_npieces + e, host_signs + at, FG + at, FH + at, host_swap ? host_swap + at : nullptr,
-                               kX.data() + e, kY.data() + e, Fn + e, false};
-                if ((rc = qe_mv_pow2(r, L.rq, c, L.own + (size_t)e * pb, 0, leg_cols, kappa_cols, leg_rows, kappa_rows, L.mrow, 0, st, false))) return rc;
+            for (int e = 0, at = 0; e < a.nest; at += a.npieces[e], ++e) {       // one at a time, each into its plane of the entry's block
+                const MvCall c{1, a.npieces + e, a.signs + at, L.FG + at, L.FH + at, a.swap ? a.swap + at : nullptr,
+                               kX.data() + e, kY.data() + e, L.Fn + e, false};
+                if ((rc = qe_mv_pow2(r, L.rq, c, L.own + (size_t)e * pb, 0, a.wl, a.wk, a.rl, a.rk, L.mrow, 0, st, false))) return rc;
             }
         }
-        if ((rc = oa_bin_power_multi(r->dtype, nest, block, (long)(pb / es), L.w, L.wstride, nspec, host_a, host_b, norm, L.ids, nids,
-                                     r->ny, r->kp, r->nx / 2, kappa_cols, kappa_rows, L.sums, L.scratch, st))) return rc;
-        if ((rc = moments_add_binned_multi(L.sums, counts, nspec, nids, n, S, C, st))) return rc;
+        if ((rc = oa_bin_power_multi(r->dtype, a.nest, block, pe, L.w, L.wstride, a.nspec, a.a, a.b, a.norm, L.ids, a.nids,
+                                     r->ny, r->kp, r->nx / 2, a.wk, a.rk, L.sums, L.scratch, st))) return rc;
+        if ((rc = moments_add_binned_multi(L.sums, a.counts, a.nspec, a.nids, a.n, a.S, a.C, st))) return rc;
         if (!L.mf) continue;
         // the stacks are the map's planes: on a band grid kappa_hat's band goes from the inner rows and pitch to the N grid's
-        rc = L.grid == r ? stack_add_region_multi(r->dtype, block, (long)(pb / es), L.w, L.wstride, nest, L.mf, L.mf_mv, r->ny, r->kp, kappa_cols,
-                                                  kappa_rows, st)
-                         : band_stack_add_multi(r->dtype, block, (long)(pb / es), L.w, L.wstride, nest, L.mf, L.mf_mv, r->ny, r->kp, L.grid->ny,
-                                                L.grid->kp, kappa_cols, kappa_rows, st);
+        rc = L.grid == r ? stack_add_region_multi(r->dtype, block, pe, L.w, L.wstride, a.nest, L.mf, L.mf_mv, r->ny, r->kp, a.wk, a.rk, st)
+                         : band_stack_add_multi(r->dtype, block, pe, L.w, L.wstride, a.nest, L.mf, L.mf_mv, r->ny, r->kp, L.grid->ny,
+                                                L.grid->kp, a.wk, a.rk, st);
         if (rc) return rc;
     }
     return 0;
@@ -1696,45 +1641,42 @@ static int mc_mv_loop(const McMvLoop& L, uint64_t base_seed, long sim_lo, long s
  * first launch; then the loop above on the inner plan.  kappa_hat per mode is the same on both grids (the bound normalisations carry
  * My Mx / (ny nx)), the inner ids are the N grid's at the same mode, and since Mx >= 2 kappa_cols the inner Nyquist column is never
  * visited: column 0 is the only visited one of Hermitian multiplicity 1, as on the N grid.  The caller's counts are the N plane's. */
-// what a band-grid shard call resolves before its first launch: the inner-layout planes of the call's pointers and the loop on them
-struct MixedMvCall {
+// what a shard call resolves before its first launch: the loop's description and, on a band grid, the inner-layout planes of the call's pointers
+struct MvShard {
     std::vector<const void*> iFG, iFH, iFn;
     McMvLoop L;
 };
 // `who`: the entry's name.  `how_all`: every refusal ends with the way out (oa_mc_run_mv_windowed names the driver and one_call=False in
 // each of its refusals); oa_mc_run_mv's messages are as they were.
-static int mixed_mc_mv_lookup(const std::string& who, bool how_all, oa_plan* p, Pipeline* q, int nest, const int* host_npieces,
-                              const void* const* host_FG, const void* const* host_FH, const int* host_swap, const int* host_xsrc,
-                              const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights, long mv_wstride, int nspec,
-                              const int32_t* ids_hc, int nids, int wl, int wk, int rl, int rk, int mrow, MixedMvCall* out) {
+static int mixed_mc_mv_lookup(const std::string& who, bool how_all, oa_plan* p, Pipeline* q, const McMvArgs& a, MvShard* out) {
     static const char* const how = " -- bind the estimator set with oa_qe_band_bind, then oa_mc_mv_band_bind, or run the host loop of the "
                                    "existing entries (mc.GaussianN0MonteCarloPol with one_call=False)";
     const std::string tail = how_all ? how : "";
     Pipeline::PolBind& B = q->pb;
     const Pipeline::PolBind::McBind& M = B.mc;
     if (!B.bound) return fail(who + ": on map sides 2^a 3^b 5^c the filter and normalisation planes are bound first" + how);
-    if (wl != B.wl || wk != B.wk || rl != B.rl || rk != B.rk || mrow != B.mrow)
+    if (a.wl != B.wl || a.wk != B.wk || a.rl != B.rl || a.rk != B.rk || a.mrow != B.mrow)
         return fail(who + ": leg / kappa columns and rows or the row grid differ from the bound ones" + how);
     if (!M.bound) return fail(who + ": no Monte-Carlo binding on the current oa_qe_band_bind binding" + how);
-    if (mv_weights != M.w || (mv_weights && mv_wstride != M.wstride) || ids_hc != M.ids || nids != M.nids || nest != M.nest || nspec > M.nspec_max)
+    if (a.w != M.w || (a.w && a.wstride != M.wstride) || a.ids != M.ids || a.nids != M.nids || a.nest != M.nest || a.nspec > M.nspec_max)
         return fail(who + ": the weights, their stride, the bin ids, nids, nest or nspec differ from the Monte-Carlo binding's" + how);
     std::vector<const void*>&iFG = out->iFG, &iFH = out->iFH, &iFn = out->iFn;
     oa_plan* b = B.plan;
     Pipeline* qb = (Pipeline*)b->pipe;
     band_options(q);
-    const size_t rb = band_real_bytes(b), es = 2 * (b->dtype == OA_F32 ? 4 : 8);
-    char* const fbase = (char*)B.planes;
+    const size_t rb = band_real_bytes(b), es = elem_bytes(b);
+    char* const fbase = B.planes.at();
     char* const nbase = fbase + B.fkey.size() * rb;
     int total = 0;
-    for (int e = 0; e < nest; ++e) total += host_npieces[e];
-    iFG.assign(total, nullptr); iFH.assign(total, nullptr); iFn.assign(nest, nullptr);
+    for (int e = 0; e < a.nest; ++e) total += a.npieces[e];
+    iFG.assign(total, nullptr); iFH.assign(total, nullptr); iFn.assign(a.nest, nullptr);
     for (int i = 0; i < total; ++i) {
-        iFG[i] = pol_inner(B.fkey, host_FG[i], fbase, rb);
-        iFH[i] = pol_inner(B.fkey, host_FH[i], fbase, rb);
+        iFG[i] = pol_inner(B.fkey, a.FG[i], fbase, rb);
+        iFH[i] = pol_inner(B.fkey, a.FH[i], fbase, rb);
         if (!iFG[i] || !iFH[i]) return fail(who + ": a filter plane of this call is not bound (oa_qe_band_bind binds every distinct plane)" + tail);
     }
-    for (int e = 0; e < nest; ++e) {
-        iFn[e] = pol_inner(B.nkey, host_Fnorm[e], nbase, rb);
+    for (int e = 0; e < a.nest; ++e) {
+        iFn[e] = pol_inner(B.nkey, a.Fn[e], nbase, rb);
         if (!iFn[e]) return fail(who + ": a normalisation plane of this call is not bound (oa_qe_band_bind)" + tail);
     }
     {                                               // the inner plan's leg pool: sized by oa_qe_band_bind, never grown here
@@ -1743,95 +1685,140 @@ static int mixed_mc_mv_lookup(const std::string& who, bool how_all, oa_plan* p, 
             for (auto& k : v) if (k.first == s && k.second == f) return;
             v.emplace_back(s, f);
         };
-        for (int e = 0, at = 0; e < nest; ++e)
-            for (int i = 0; i < host_npieces[e]; ++i, ++at) {
-                const bool sw = host_swap && host_swap[at];
-                add(grad, sw ? host_ysrc[e] : host_xsrc[e], iFG[at]);
-                add(hpl, sw ? host_xsrc[e] : host_ysrc[e], iFH[at]);
+        for (int e = 0, at = 0; e < a.nest; ++e)
+            for (int i = 0; i < a.npieces[e]; ++i, ++at) {
+                const bool sw = a.swap && a.swap[at];
+                add(grad, sw ? a.ysrc[e] : a.xsrc[e], iFG[at]);
+                add(hpl, sw ? a.xsrc[e] : a.ysrc[e], iFH[at]);
             }
-        const size_t lb = (size_t)work_pitch(b, wl) * b->ny * es, lbk = (size_t)work_pitch(b, wk) * b->ny * es;
-        if ((2 * grad.size() + hpl.size()) * lb + 4 * (size_t)nest * lbk > qb->split_bytes)
-            return fail(who + ": this call needs " + std::to_string(2 * grad.size() + hpl.size()) + " leg planes and " + std::to_string(nest) +
+        const size_t lb = (size_t)work_pitch(b, a.wl) * b->ny * es, lbk = (size_t)work_pitch(b, a.wk) * b->ny * es;
+        if ((2 * grad.size() + hpl.size()) * lb + 4 * (size_t)a.nest * lbk > qb->split_legs.bytes)
+            return fail(who + ": this call needs " + std::to_string(2 * grad.size() + hpl.size()) + " leg planes and " + std::to_string(a.nest) +
                         " estimators, more than oa_qe_band_bind was told (max_leg_planes, normalisation planes)" + tail);
     }
-    char* const base = (char*)M.pool;
+    char* const base = M.pool.at();
     const size_t cb = plane_bytes(b);
     long fn_moff = 0;
-    out->L = McMvLoop{p, b, qb, mv_div_batched(qb, nest, iFn.data(), es / 2, &fn_moff),
+    out->L = McMvLoop{p, b, qb, mv_div_batched(qb, a.nest, iFn.data(), es / 2, &fn_moff),
                       {base + M.off_draw, base + M.off_draw + cb, base + M.off_draw + 2 * cb}, base + M.off_kappa, base + M.off_scratch,
-                      (double*)(base + M.off_sums), mv_weights ? (const void*)base : nullptr, (long)(rb / (es / 2)),
-                      (const int32_t*)(base + M.off_ids), -1};
+                      (double*)(base + M.off_sums), a.w ? (const void*)base : nullptr, (long)(rb / (es / 2)),
+                      (const int32_t*)(base + M.off_ids), -1, iFG.data(), iFH.data(), iFn.data()};
     return 0;
 }
-static int mixed_mc_run_mv(oa_plan* p, Pipeline* q, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest,
-                           const int* host_npieces, const double* host_signs, const void* const* host_FG, const void* const* host_FH,
-                           const int* host_swap, const int* host_xsrc, const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights,
-                           long mv_wstride, int nspec, const int* host_a, const int* host_b, const int32_t* ids_hc, int nids, const int64_t* counts,
-                           double norm, int wl, int wk, int rl, int rk, int mrow, int64_t* n, double* S, double* C, hipStream_t st) {
-    MixedMvCall c;
-    if (int rc = mixed_mc_mv_lookup("oa_mc_run_mv", false, p, q, nest, host_npieces, host_FG, host_FH, host_swap, host_xsrc, host_ysrc, host_Fnorm,
-                                    mv_weights, mv_wstride, nspec, ids_hc, nids, wl, wk, rl, rk, mrow, &c)) return rc;
-    return mc_mv_loop(c.L, base_seed, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, c.iFG.data(), c.iFH.data(), host_swap, host_xsrc,
-                      host_ysrc, c.iFn.data(), nspec, host_a, host_b, nids, counts, norm, wl, wk, rl, rk, n, S, C, st);
-}
-/* oa_mc_run_mv_windowed on a 2^a 3^b 5^c plan: the lookups and refusals above under this entry's name, then the same loop on the inner plan
- * with the mean-field stacks on the N grid (band_stack_add_multi) and -- with a window -- the source stage replaced: per realisation the
- * full-plane T, E, B draw rotated to T, Q, U on the N grid (grf_mix_teb_to_tqu), then
- *   fused   : ONE batched inverse column launch over the three planes (in place), ONE fused row launch (C2R / Npix x window -> R2C, the
- *             real rows in LDS only, leg columns stored), the pruned column DFT of the three planes and the fold with the Q, U -> E, B
- *             rotation onto the loop's three inner source planes (band_win_r2c with rot_c / rot_s: mixed_mc_run_windowed's front end with
- *             planes in the place of realisations);
- *   unfused : oa_fft_c2r_windowed per plane onto a real map in an entry-owned plane, then ONE band_maps_r2c(3, rot_c, rot_s) -- what
- *             oa_qe_mv_maps runs.
- * Fused or unfused: OA_OPT_WIN_FUSED, until it is set mixed_mc_run_windowed's rule by row length; rows the fused kernel does not hold take
- * the unfused flow.  The N-grid planes are taken on the first windowed call (one device synchronisation; regrown when the band widens). */
-static int mixed_mc_run_mv_windowed(oa_plan* p, Pipeline* q, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest,
-                                    const int* host_npieces, const double* host_signs, const void* const* host_FG, const void* const* host_FH,
-                                    const int* host_swap, const int* host_xsrc, const int* host_ysrc, const void* const* host_Fnorm,
-                                    const void* mv_weights, long mv_wstride, int nspec, const int* host_a, const int* host_b, const int32_t* ids_hc,
-                                    int nids, const int64_t* counts, double norm, int wl, int wk, int rl, int rk, int mrow, const void* window,
-                                    const void* rot_c, const void* rot_s, int64_t* n, double* S, double* C, double* const* host_meanfield,
-                                    hipStream_t st) {
-    MixedMvCall c;
-    if (int rc = mixed_mc_mv_lookup("oa_mc_run_mv_windowed", true, p, q, nest, host_npieces, host_FG, host_FH, host_swap, host_xsrc, host_ysrc,
-                                    host_Fnorm, mv_weights, mv_wstride, nspec, ids_hc, nids, wl, wk, rl, rk, mrow, &c)) return rc;
-    McMvLoop& L = c.L;
-    if (host_meanfield) { L.mf = host_meanfield; L.mf_mv = mv_weights ? host_meanfield[nest] : nullptr; }
-    if (window) {
-        Pipeline::PolBind& B = q->pb;
-        oa_plan* b = B.plan;
-        const size_t es = 2 * (p->dtype == OA_F32 ? 4 : 8), pb = plane_bytes(p), need = 6 * pb + band_maps_scratch_bytes(p, 3, wl, rl);
-        if (B.mwin_bytes < need) {                  // first windowed call on this binding's inner plan, or a wider band
-            OA_HIP(hipDeviceSynchronize());
-            if (B.mwin) { (void)hipFree(B.mwin); B.mwin = nullptr; B.mwin_bytes = 0; }
-            OA_HIP(hipMalloc(&B.mwin, need));
-            B.mwin_bytes = need;
-        }
-        char* const wb = (char*)B.mwin;
-        char* const tmp = wb + 3 * pb;              // ny x nx reals fit an hc plane
-        void* const rows = wb + 6 * pb;
-        const long pne = (long)(pb / es), pbe = (long)(plane_bytes(b) / es);
-        const double inv = 1.0 / ((double)p->ny * p->nx);
-        const bool fused = band_rows_win_ok(p) && (q->opt_win_fused_set ? q->opt_win_fused : p->nx > 1200);
-        void* const dst = L.draw[0];                // the three inner source planes are contiguous, one inner plane apart (oa_mc_mv_band_bind)
-        const int dny = b->ny;
-        const long dkp = b->kp;
-        L.source = [=](long i) -> int {
-            void* tqu[3] = {wb, wb + pb, wb + 2 * pb};
-            int rc = grf_mix_teb_to_tqu(p, base_seed, 3 * (uint64_t)i, host_covsqrt, rot_c, rot_s, tqu, st);
-            if (rc) return rc;
-            if (fused) {
-                if ((rc = mixed_cols_inverse_batch(p, 3, wb, pne, st))) return rc;
-                return band_win_r2c(p, 3, wb, pne, window, inv, rows, 0, wl, rl, rot_c, rot_s, dst, pbe, dny, dkp, st);
-            }
-            const void* maps[3] = {tmp, tmp + pb, tmp + 2 * pb};
-            for (int f = 0; f < 3; ++f)
-                if ((rc = oa_fft_c2r_windowed(p, tqu[f], tmp + (size_t)f * pb, inv, window, st))) return rc;
-            return band_maps_r2c(p, 3, maps, rot_c, rot_s, rows, wl, rl, dst, pbe, dny, dkp, st);
-        };
+// the argument checks oa_mc_run_mv and oa_mc_run_mv_windowed share, under the caller's name; `plan_msg`: what a chirp-z plan is told
+static int mc_mv_check(const std::string& who, const char* plan_msg, const oa_plan* p, const McMvArgs& a) {
+    OA_REQUIRE(p && a.covsqrt && a.npieces && a.signs && a.FG && a.FH && a.xsrc && a.ysrc && a.Fn && a.ids && a.counts &&
+               a.n && a.S && a.C && a.sim_hi >= a.sim_lo, who + ": bad argument");
+    OA_REQUIRE(p->pow2 || p->mixed, who + plan_msg);
+    OA_REQUIRE(a.nest >= 1 && a.nest <= 6, who + ": 1 <= nest <= 6 estimators");
+    OA_REQUIRE(a.nids >= 3, who + ": nids must be at least 3 (two outer bins around the bandpowers)");
+    if (int rc = bin_power_multi_check(who.c_str(), p->dtype, a.nest, a.w != nullptr, a.nspec, a.a, a.b, a.nids)) return rc;
+    const int hw = p->nx / 2 + 1;
+    OA_REQUIRE(a.wl >= 0 && a.wk >= 0 && a.rl >= 0 && a.rk >= 0 && a.wl <= hw && a.wk <= hw && 2L * a.rl - 1 <= p->ny && 2L * a.rk - 1 <= p->ny,
+               who + ": leg / kappa band beyond the hc plane");
+    int total = 0;
+    for (int e = 0; e < a.nest; ++e) {
+        OA_REQUIRE(a.npieces[e] >= 1 && a.Fn[e], who + ": bad estimator entry");
+        OA_REQUIRE(a.xsrc[e] >= 0 && a.xsrc[e] < 3 && a.ysrc[e] >= 0 && a.ysrc[e] < 3, who + ": source index outside [0, 3) (0 T, 1 E, 2 B)");
+        total += a.npieces[e];
     }
-    return mc_mv_loop(L, base_seed, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, c.iFG.data(), c.iFH.data(), host_swap, host_xsrc,
-                      host_ysrc, c.iFn.data(), nspec, host_a, host_b, nids, counts, norm, wl, wk, rl, rk, n, S, C, st);
+    for (int i = 0; i < total; ++i) OA_REQUIRE(a.FG[i] && a.FH[i], who + ": NULL filter plane");
+    return 0;
+}
+// the entry-owned pool of a power-of-two plan, taken on the first call (and regrown when a call needs more): that call synchronises the
+// device once; and the loop's description on it
+static int mc_mv_pow2_loop(oa_plan* p, Pipeline* q, const McMvArgs& a, McMvLoop* L) {
+    if (int rc = ensure_work(p, q)) return rc;
+    const size_t pb = plane_bytes(p);
+    long fn_moff = 0;
+    const bool engaged = mv_div_batched(q, a.nest, a.Fn, elem_bytes(p) / 2, &fn_moff);
+    const size_t sb = (size_t)oa_bin_power_multi_scratch_bytes(a.nspec, a.nids), ub = (size_t)a.nspec * a.nids * sizeof(double);
+    if (int rc = q->mvmc.reserve((3 + (engaged ? 0 : (size_t)a.nest)) * pb + sb + ub, true)) return rc;
+    char* const base = q->mvmc.at();
+    *L = McMvLoop{p, p, q, engaged, {base, base + pb, base + 2 * pb}, base + 3 * pb /* per-estimator kappa planes when the plan's are not used */,
+                  base + q->mvmc.bytes - sb - ub, (double*)(base + q->mvmc.bytes - ub), a.w, a.wstride, a.ids, a.mrow, a.FG, a.FH, a.Fn};
+    return 0;
+}
+/* SOURCE STAGE of a windowed realisation (oa_mc_run_mv_windowed; L->source): the full-plane T, E, B draw rotated to T, Q, U in the same
+ * pass (grf_mix_teb_to_tqu, the counters of the band draw), the window in real space, and T, E, B on the leg band of the loop's three
+ * source planes.  The planes of the front end are taken on the first windowed call (regrown when the leg band widens).
+ * POWER OF TWO, fused: one fused row launch over the three planes (inverse columns, C2R / Npix -> x window -> R2C, the real maps in LDS only,
+ * leg columns stored at the compact pitch), one batched forward column launch, Q, U -> E, B on the band.  Unfused (A/B): the window at
+ * the C2R's store, the real map in HBM, the R2C on the leg band. */
+static int mv_window_source_pow2(oa_plan* p, Pipeline* q, const McMvArgs& a, bool fused, McMvLoop* L) {
+    const size_t es = elem_bytes(p), pb = plane_bytes(p);
+    const long pl = work_pitch(p, a.wl);
+    const size_t lb = (size_t)pl * p->ny * es;
+    if (int rc = q->mvwin.reserve(6 * pb + 3 * lb)) return rc;
+    char* const wb = q->mvwin.at();
+    char* const tmp = wb + 3 * pb;
+    char* const rowT = wb + 6 * pb;
+    const double inv = 1.0 / ((double)p->ny * p->nx);
+    void* const* const dst = L->draw;
+    L->source = [=](long i) -> int {
+        void* tqu[3] = {wb, wb + pb, wb + 2 * pb};
+        int rc = grf_mix_teb_to_tqu(p, a.base_seed, 3 * (uint64_t)i, a.covsqrt, a.rot_c, a.rot_s, tqu, a.st);
+        if (rc) return rc;
+        if (fused) {
+            if ((rc = qe_windowed_rows_w(p, wb, tmp, a.window, a.wl, pl, inv, a.st, rowT, 3, plane_elems(p), (long)(lb / es)))) return rc;
+            if ((rc = qe_fwd_cols_batch_w(p, rowT, pl, dst[0], 3, (long)(lb / es), plane_elems(p), a.wl, a.rl, a.st))) return rc;
+        } else {
+            for (int f = 0; f < 3; ++f) {
+                if ((rc = oa_fft_c2r_windowed(p, tqu[f], tmp + (size_t)f * pb, inv, a.window, a.st))) return rc;
+                if ((rc = oa_fft_r2c(p, tmp + (size_t)f * pb, dst[f], 1.0, a.wl, a.rl, a.st))) return rc;
+            }
+        }
+        return band_rot2(p->dtype, a.rot_c, a.rot_s, dst[1], dst[2], p->ny, p->kp, a.wl, a.rl, a.st);
+    };
+    return 0;
+}
+/* BAND GRID, fused: ONE batched inverse column launch over the three N-grid planes (in place), ONE fused row launch, the pruned column DFT
+ * of the three planes and the fold with the Q, U -> E, B rotation onto the loop's three inner source planes (band_win_r2c with rot_c /
+ * rot_s: mixed_mc_run_windowed's front end with planes in the place of realisations).  Unfused: oa_fft_c2r_windowed per plane onto a real
+ * map in an entry-owned plane, then ONE band_maps_r2c(3, rot_c, rot_s) -- what oa_qe_mv_maps runs. */
+static int mv_window_source_band(oa_plan* p, Pipeline* q, const McMvArgs& a, bool fused, McMvLoop* L) {
+    Pipeline::PolBind& B = q->pb;
+    const size_t pb = plane_bytes(p);
+    if (int rc = B.mwin.reserve(6 * pb + band_maps_scratch_bytes(p, 3, a.wl, a.rl))) return rc;
+    char* const wb = B.mwin.at();
+    char* const tmp = wb + 3 * pb;                  // ny x nx reals fit an hc plane
+    void* const rows = wb + 6 * pb;
+    const long pne = plane_elems(p), pbe = plane_elems(B.plan);
+    const double inv = 1.0 / ((double)p->ny * p->nx);
+    void* const dst = L->draw[0];                   // the three inner source planes are contiguous, one inner plane apart (oa_mc_mv_band_bind)
+    const int dny = B.plan->ny;
+    const long dkp = B.plan->kp;
+    L->source = [=](long i) -> int {
+        void* tqu[3] = {wb, wb + pb, wb + 2 * pb};
+        int rc = grf_mix_teb_to_tqu(p, a.base_seed, 3 * (uint64_t)i, a.covsqrt, a.rot_c, a.rot_s, tqu, a.st);
+        if (rc) return rc;
+        if (fused) {
+            if ((rc = mixed_cols_inverse_batch(p, 3, wb, pne, a.st))) return rc;
+            return band_win_r2c(p, 3, wb, pne, a.window, inv, rows, 0, a.wl, a.rl, a.rot_c, a.rot_s, dst, pbe, dny, dkp, a.st);
+        }
+        const void* maps[3] = {tmp, tmp + pb, tmp + 2 * pb};
+        for (int f = 0; f < 3; ++f)
+            if ((rc = oa_fft_c2r_windowed(p, tqu[f], tmp + (size_t)f * pb, inv, a.window, a.st))) return rc;
+        return band_maps_r2c(p, 3, maps, a.rot_c, a.rot_s, rows, a.wl, a.rl, dst, pbe, dny, dkp, a.st);
+    };
+    return 0;
+}
+/* The body of oa_mc_run_mv and oa_mc_run_mv_windowed behind their argument checks.  Power of two: the loop on the plan itself, with the
+ * call's planes.  2^a 3^b 5^c: on the inner plan of the band grid behind oa_qe_band_bind + oa_mc_mv_band_bind, the windowed source stage on
+ * the N grid in front of it and the stacks on the N grid behind it. */
+static int mc_mv_shard(const std::string& who, bool how_all, oa_plan* p, const McMvArgs& a) {
+    Pipeline* q = pipe_of(p);
+    MvShard c;
+    McMvLoop& L = c.L;
+    if (int rc = p->mixed ? mixed_mc_mv_lookup(who, how_all, p, q, a, &c) : mc_mv_pow2_loop(p, q, a, &L)) return rc;
+    if (a.mf) { L.mf = a.mf; L.mf_mv = a.w ? a.mf[a.nest] : nullptr; }
+    if (a.window) {
+        // fused row pass or the unfused flow: OA_OPT_WIN_FUSED; a band-grid plan, until the option is set, picks by row length
+        // (mixed_mc_run_windowed's rule), and rows its fused kernel does not hold take the unfused flow
+        const bool fused = p->mixed ? band_rows_win_ok(p) && (q->opt_win_fused_set ? q->opt_win_fused : p->nx > 1200) : q->opt_win_fused;
+        if (int rc = p->mixed ? mv_window_source_band(p, q, a, fused, &L) : mv_window_source_pow2(p, q, a, fused, &L)) return rc;
+    }
+    return mc_mv_loop(L, a);
 }
 }  // namespace oa
 
@@ -1877,117 +1864,31 @@ int oa_mc_run(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const vo
     Pipeline* q = (Pipeline*)p->pipe;
     hipStream_t st = (hipStream_t)stream;
     if (p->mixed) return mixed_mc_run(p, q, base_seed, sim_lo, sim_hi, covsqrt_hc, n, S, C, meanfield_acc, st);
-    long i = sim_lo;
-    // BATCHES of realisations: at 4096^2 a realisation is ~60 MB of traffic behind ~10 launches, i.e. launch latency; with B
-    // realisations per launch (grid z) the column and row stages fill the chip.  Same kernels on the same operands in the same
-    // order per realisation as the one-by-one loop below: identical moments.
-    const int BMAX = std::max(1, std::min(MC_BATCH_MAX, q->opt_mc_batch));     // (OA_OPT_MC_BATCH) 1 / 2 / 4 / 6 per launch at 4096^2: 16.5 / 26.0 / 37.6 / 40.3 k realisations/s
-    const size_t es = 2 * (p->dtype == OA_F32 ? 4 : 8), pb = plane_bytes(p);
-    // (a batch of ONE goes through the same launches -- OA_OPT_MC_BATCH = 1 and the last realisation of an odd shard: the same kernels
-    // whatever the batch size, so the moments do not depend on it; the loop further down serves the geometries without them)
-    bool batched = p->pow2;
-    while (batched && i < sim_hi) {
-        const int B = (int)std::min<long>(BMAX, sim_hi - i);
-        if (int rc = ensure_mc_src(p, q)) return rc;
-        if (int rc = ensure_pool(q, mc_pool_bytes(p, q, B))) return rc;       // (before the draw: growing the pool synchronises the device)
-        // the first batch of a geometry without the batched row stage must not have drawn anything it then abandons: the tail checks
-        // before its first launch only AFTER the leg launches -- those write plan-owned planes only, harmless
-        int rc = grf_hc_band_batch(p, base_seed, (uint64_t)i, B, covsqrt_hc, q->mc_src, (long)(pb / es), q->wl, q->rl, st);
-        if (rc) return rc;
-        int fallback = 0;
-        if ((rc = mc_batch_tail(p, q, B, n, S, C, meanfield_acc, st, &fallback))) return rc;
-        if (fallback) { batched = false; break; }
-        i += B;
-    }
-    for (; i < sim_hi; ++i) {
-        // only the leg band of the realisation is ever read (col_legs: columns < wl, rows |ky index| < rl)
-        int rc = oa_grf_hc_band(p, base_seed, (uint64_t)i, covsqrt_hc, q->kT, q->wl, q->rl, stream);
-        if (rc) return rc;
-        if ((rc = oa_qe_tt(p, nullptr, q->kT, nullptr, nullptr, 0, stream))) return rc;
-        if ((rc = bandpower_moments(p, q, n, S, C, stream))) return rc;
-        // kappa_hat vanishes outside its active region (the plan-owned plane was zero-filled once): stack only that
-        if (meanfield_acc && (rc = stack_add_region(p->dtype, q->kk, meanfield_acc, p->ny, p->kp, q->wk, q->rk, (hipStream_t)stream))) return rc;
-    }
-    return 0;
+    // only the leg band of a realisation is ever read (col_legs: columns < wl, rows |ky index| < rl)
+    McTtLoop T{p, p, q, p->pow2, 0, nullptr, nullptr, nullptr, q->kT, 0, false};
+    T.source_batch = [=](long i, int B) { return grf_hc_band_batch(p, base_seed, (uint64_t)i, B, covsqrt_hc, q->mc_src.p, plane_elems(p), q->wl, q->rl, st); };
+    T.source_one = [=](long i) { return oa_grf_hc_band(p, base_seed, (uint64_t)i, covsqrt_hc, q->kT, q->wl, q->rl, st); };
+    return mc_tt_loop(T, sim_lo, sim_hi, n, S, C, meanfield_acc, st);
 }
-
-} // extern "C"
-namespace oa {
-// the argument checks oa_mc_run_mv and oa_mc_run_mv_windowed share (everything but the plan kind), under the caller's name
-static int mc_mv_check(const std::string& who, bool plan_ok, const char* plan_msg, oa_plan* p, long sim_lo, long sim_hi,
-                       const void* const* host_covsqrt, int nest, const int* host_npieces, const double* host_signs, const void* const* host_FG, const void* const* host_FH, const int* host_xsrc, const int* host_ysrc,
-                       const void* const* host_Fnorm, const void* mv_weights, int nspec, const int* host_a, const int* host_b, const int32_t* ids_hc,
-                       int nids, const int64_t* counts, int leg_cols, int kappa_cols, int leg_rows, int kappa_rows, const int64_t* n, const double* S,
-                       const double* C) {
-    OA_REQUIRE(p && host_covsqrt && host_npieces && host_signs && host_FG && host_FH && host_xsrc && host_ysrc && host_Fnorm && ids_hc && counts &&
-               n && S && C && sim_hi >= sim_lo, who + ": bad argument");
-    OA_REQUIRE(plan_ok, who + plan_msg);
-    OA_REQUIRE(nest >= 1 && nest <= 6, who + ": 1 <= nest <= 6 estimators");
-    OA_REQUIRE(nids >= 3, who + ": nids must be at least 3 (two outer bins around the bandpowers)");
-    if (int rc = bin_power_multi_check(who.c_str(), p->dtype, nest, mv_weights != nullptr, nspec, host_a, host_b, nids)) return rc;
-    const int hw = p->nx / 2 + 1;
-    OA_REQUIRE(leg_cols >= 0 && kappa_cols >= 0 && leg_rows >= 0 && kappa_rows >= 0 && leg_cols <= hw && kappa_cols <= hw &&
-               2L * leg_rows - 1 <= p->ny && 2L * kappa_rows - 1 <= p->ny, who + ": leg / kappa band beyond the hc plane");
-    int total = 0;
-    for (int e = 0; e < nest; ++e) {
-        OA_REQUIRE(host_npieces[e] >= 1 && host_Fnorm[e], who + ": bad estimator entry");
-        OA_REQUIRE(host_xsrc[e] >= 0 && host_xsrc[e] < 3 && host_ysrc[e] >= 0 && host_ysrc[e] < 3, who + ": source index outside [0, 3) (0 T, 1 E, 2 B)");
-        total += host_npieces[e];
-    }
-    for (int i = 0; i < total; ++i) OA_REQUIRE(host_FG[i] && host_FH[i], who + ": NULL filter plane");
-    return 0;
-}
-// the entry-owned pool of a power-of-two plan, taken on the first call (and regrown when a call needs more): that call synchronises the
-// device once; and the loop's description on it
-static int mc_mv_pow2_loop(oa_plan* p, Pipeline* q, int nest, const void* const* host_Fnorm, const void* mv_weights, long mv_wstride, int nspec,
-                           const int32_t* ids_hc, int nids, int mrow, McMvLoop* L) {
-    if (int rc = ensure_work(p, q)) return rc;
-    const size_t es = 2 * (p->dtype == OA_F32 ? 4 : 8), rs = es / 2, pb = plane_bytes(p);
-    long fn_moff = 0;
-    const bool engaged = mv_div_batched(q, nest, host_Fnorm, rs, &fn_moff);
-    const size_t sb = (size_t)oa_bin_power_multi_scratch_bytes(nspec, nids), ub = (size_t)nspec * nids * sizeof(double);
-    const size_t need = (3 + (engaged ? 0 : (size_t)nest)) * pb + sb + ub;
-    if (q->mvmc_bytes < need) {
-        if (q->mvmc) { OA_HIP(hipDeviceSynchronize()); (void)hipFree(q->mvmc); q->mvmc = nullptr; q->mvmc_bytes = 0; }
-        OA_HIP(hipMalloc(&q->mvmc, need));
-        OA_HIP(hipMemset(q->mvmc, 0, need));
-        q->mvmc_bytes = need;
-    }
-    char* const base = (char*)q->mvmc;
-    *L = McMvLoop{p, p, q, engaged, {base, base + pb, base + 2 * pb}, base + 3 * pb /* per-estimator kappa planes when the plan's are not used */,
-                  base + q->mvmc_bytes - sb - ub, (double*)(base + q->mvmc_bytes - ub), mv_weights, mv_wstride, ids_hc, mrow};
-    return 0;
-}
-}  // namespace oa
-extern "C" {
 
 /* oa_mc_run_mv (include/orphics_amd.h): the Gaussian N0 Monte-Carlo shard of an estimator SET.  Per realisation (mc_mv_loop): the leg band
  * of oa_grf_mix's T, E, B draw (streams 3 i, 3 i + 1, 3 i + 2) into three entry-owned planes -- not the plan's work planes: c[0..2], g[0..1]
  * and kT are where the one-launch divergence puts the per-estimator kappa_hat --, the launch sequence of oa_qe_mv with the sum left out
  * (qe_mv_pow2), one oa_bin_power_multi pass over the estimators' planes, one moment launch.  On a 2^a 3^b 5^c plan the same loop runs on
- * the inner plan of the band grid (mixed_mc_run_mv). */
+ * the inner plan of the band grid (mc_mv_shard). */
 int oa_mc_run_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest, const int* host_npieces,
                  const double* host_signs, const void* const* host_FG, const void* const* host_FH, const int* host_swap, const int* host_xsrc,
                  const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights, long mv_wstride, int nspec, const int* host_a,
                  const int* host_b, const int32_t* ids_hc, int nids, const int64_t* counts, double norm, int leg_cols, int kappa_cols,
                  int leg_rows, int kappa_rows, int mrow, int64_t* n, double* S, double* C, void* stream) {
-    OA_REQUIRE(p, "oa_mc_run_mv: bad argument");
-    if (int rc = mc_mv_check("oa_mc_run_mv", p->pow2 || p->mixed,
-                             ": map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path; "
+    const McMvArgs a{base_seed, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, host_FG, host_FH, host_swap, host_xsrc, host_ysrc,
+                     host_Fnorm, mv_weights, mv_wstride, nspec, host_a, host_b, ids_hc, nids, counts, norm, leg_cols, kappa_cols, leg_rows,
+                     kappa_rows, mrow, n, S, C, (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr};
+    if (int rc = mc_mv_check("oa_mc_run_mv", ": map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path; "
                              "run the host loop of the existing entries (mc.GaussianN0MonteCarloPol with one_call=False: Engine.grf_mix, reconstruct_hc per "
-                             "estimator, Engine.bin_power, Statistics.add)", p, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, host_FG, host_FH, host_xsrc, host_ysrc,
-                             host_Fnorm, mv_weights, nspec, host_a, host_b, ids_hc, nids, counts, leg_cols, kappa_cols, leg_rows, kappa_rows, n, S, C))
+                             "estimator, Engine.bin_power, Statistics.add)", p, a))
         return rc;
-    Pipeline* q = pipe_of(p);
-    hipStream_t st = (hipStream_t)stream;
-    if (p->mixed)                                   // BAND GRID: the planes of the two bindings, on the inner plan
-        return mixed_mc_run_mv(p, q, base_seed, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, host_FG, host_FH, host_swap, host_xsrc,
-                               host_ysrc, host_Fnorm, mv_weights, mv_wstride, nspec, host_a, host_b, ids_hc, nids, counts, norm, leg_cols, kappa_cols,
-                               leg_rows, kappa_rows, mrow, n, S, C, st);
-    McMvLoop L;
-    if (int rc = mc_mv_pow2_loop(p, q, nest, host_Fnorm, mv_weights, mv_wstride, nspec, ids_hc, nids, mrow, &L)) return rc;
-    return mc_mv_loop(L, base_seed, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, host_FG, host_FH, host_swap, host_xsrc, host_ysrc,
-                      host_Fnorm, nspec, host_a, host_b, nids, counts, norm, leg_cols, kappa_cols, leg_rows, kappa_rows, n, S, C, st);
+    return mc_mv_shard("oa_mc_run_mv", false, p, a);
 }
 
 /* oa_mc_run_mv_windowed (include/orphics_amd.h): oa_mc_run_mv with a real-space window on T, Q, U and the mean-field stacks of the estimator
@@ -1998,69 +1899,26 @@ int oa_mc_run_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const
  * source planes -> Q, U -> E, B on that band.  OA_OPT_WIN_FUSED = 0: oa_fft_c2r_windowed -> real maps in HBM (the column temporaries) ->
  * oa_fft_r2c on the band.  Then mc_mv_loop's estimator, binning and moment steps, and one stack launch.
  * On a 2^a 3^b 5^c plan the loop runs on the inner plan of the band grid behind oa_qe_band_bind + oa_mc_mv_band_bind, with the windowed
- * source stage on the N grid in front of it and the stacks on the N grid behind it (mixed_mc_run_mv_windowed). */
+ * source stage on the N grid in front of it and the stacks on the N grid behind it (mc_mv_shard, mv_window_source_band). */
 int oa_mc_run_mv_windowed(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest,
                           const int* host_npieces, const double* host_signs, const void* const* host_FG, const void* const* host_FH,
                           const int* host_swap, const int* host_xsrc, const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights,
                           long mv_wstride, int nspec, const int* host_a, const int* host_b, const int32_t* ids_hc, int nids, const int64_t* counts,
                           double norm, int leg_cols, int kappa_cols, int leg_rows, int kappa_rows, int mrow, const void* window_real,
                           const void* rot_c, const void* rot_s, int64_t* n, double* S, double* C, double* const* host_meanfield, void* stream) {
-    OA_REQUIRE(p, "oa_mc_run_mv_windowed: bad argument");
-    if (int rc = mc_mv_check("oa_mc_run_mv_windowed", p->pow2 || p->mixed,
-                             ": map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path; run "
+    const McMvArgs a{base_seed, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, host_FG, host_FH, host_swap, host_xsrc, host_ysrc,
+                     host_Fnorm, mv_weights, mv_wstride, nspec, host_a, host_b, ids_hc, nids, counts, norm, leg_cols, kappa_cols, leg_rows,
+                     kappa_rows, mrow, n, S, C, (hipStream_t)stream, window_real, rot_c, rot_s, host_meanfield};
+    if (int rc = mc_mv_check("oa_mc_run_mv_windowed", ": map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path; run "
                              "the host loop of the existing entries (mc.GaussianN0MonteCarloPol with one_call=False: Engine.grf_mix, Engine.irfft with "
-                             "the window, Engine.rfft, Engine.rot2, reconstruct_hc per estimator, Engine.bin_power, Statistics.add)", p, sim_lo, sim_hi,
-                             host_covsqrt, nest, host_npieces, host_signs, host_FG, host_FH, host_xsrc, host_ysrc, host_Fnorm, mv_weights, nspec, host_a,
-                             host_b, ids_hc, nids, counts, leg_cols, kappa_cols, leg_rows, kappa_rows, n, S, C))
+                             "the window, Engine.rfft, Engine.rot2, reconstruct_hc per estimator, Engine.bin_power, Statistics.add)", p, a))
         return rc;
     OA_REQUIRE(!window_real || (rot_c && rot_s), "oa_mc_run_mv_windowed: a window acts on Q and U and needs both rotation planes rot_c, rot_s (cos / sin "
                "2 phi_l on the half plane, oa_qe_mv_maps' convention: what mc.GaussianN0MonteCarloPol passes, and what its one_call=False host "
                "loop rotates with)");
     if (host_meanfield)
         for (int e = 0; e < nest + (mv_weights ? 1 : 0); ++e) OA_REQUIRE(host_meanfield[e], "oa_mc_run_mv_windowed: NULL mean-field stack plane");
-    Pipeline* q = pipe_of(p);
-    hipStream_t st = (hipStream_t)stream;
-    if (p->mixed)                                   // BAND GRID: the planes of the two bindings, on the inner plan
-        return mixed_mc_run_mv_windowed(p, q, base_seed, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, host_FG, host_FH, host_swap,
-                                        host_xsrc, host_ysrc, host_Fnorm, mv_weights, mv_wstride, nspec, host_a, host_b, ids_hc, nids, counts, norm,
-                                        leg_cols, kappa_cols, leg_rows, kappa_rows, mrow, window_real, rot_c, rot_s, n, S, C, host_meanfield, st);
-    McMvLoop L;
-    if (int rc = mc_mv_pow2_loop(p, q, nest, host_Fnorm, mv_weights, mv_wstride, nspec, ids_hc, nids, mrow, &L)) return rc;
-    if (host_meanfield) { L.mf = host_meanfield; L.mf_mv = mv_weights ? host_meanfield[nest] : nullptr; }
-    if (window_real) {
-        const size_t es = 2 * (p->dtype == OA_F32 ? 4 : 8), pb = plane_bytes(p);
-        const long pl = work_pitch(p, leg_cols);
-        const size_t lb = (size_t)pl * p->ny * es, need = 6 * pb + 3 * lb;
-        if (q->mvwin_bytes < need) {                // taken on first use (regrown when the leg band widens): one device synchronisation
-            OA_HIP(hipDeviceSynchronize());
-            if (q->mvwin) { (void)hipFree(q->mvwin); q->mvwin = nullptr; q->mvwin_bytes = 0; }
-            OA_HIP(hipMalloc(&q->mvwin, need));
-            q->mvwin_bytes = need;
-        }
-        char* const wb = (char*)q->mvwin;
-        char* const tmp = wb + 3 * pb;
-        char* const rowT = wb + 6 * pb;
-        const double inv = 1.0 / ((double)p->ny * p->nx);
-        const bool fused = q->opt_win_fused;
-        void* const* const dst = L.draw;
-        L.source = [=](long i) -> int {
-            void* tqu[3] = {wb, wb + pb, wb + 2 * pb};
-            int rc = grf_mix_teb_to_tqu(p, base_seed, 3 * (uint64_t)i, host_covsqrt, rot_c, rot_s, tqu, st);
-            if (rc) return rc;
-            if (fused) {
-                if ((rc = qe_windowed_rows_w(p, wb, tmp, window_real, leg_cols, pl, inv, st, rowT, 3, (long)(pb / es), (long)(lb / es)))) return rc;
-                if ((rc = qe_fwd_cols_batch_w(p, rowT, pl, dst[0], 3, (long)(lb / es), (long)(pb / es), leg_cols, leg_rows, st))) return rc;
-            } else {
-                for (int f = 0; f < 3; ++f) {       // A/B: the window at the C2R's store, the real map in HBM, the R2C on the leg band
-                    if ((rc = oa_fft_c2r_windowed(p, tqu[f], tmp + (size_t)f * pb, inv, window_real, st))) return rc;
-                    if ((rc = oa_fft_r2c(p, tmp + (size_t)f * pb, dst[f], 1.0, leg_cols, leg_rows, st))) return rc;
-                }
-            }
-            return band_rot2(p->dtype, rot_c, rot_s, dst[1], dst[2], p->ny, p->kp, leg_cols, leg_rows, st);
-        };
-    }
-    return mc_mv_loop(L, base_seed, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, host_FG, host_FH, host_swap, host_xsrc, host_ysrc,
-                      host_Fnorm, nspec, host_a, host_b, nids, counts, norm, leg_cols, kappa_cols, leg_rows, kappa_rows, n, S, C, st);
+    return mc_mv_shard("oa_mc_run_mv_windowed", true, p, a);
 }
 
 /* Monte-Carlo shard with a REAL-SPACE WINDOW (the reference's analysis flow multiplies every map by its apodisation taper
@@ -2079,60 +1937,38 @@ int oa_mc_run_windowed(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi,
     OA_REQUIRE(p->pipe && ((Pipeline*)p->pipe)->FG && ((Pipeline*)p->pipe)->ids, "oa_mc_run_windowed: call oa_plan_set_filters and oa_plan_set_bins first");
     OA_REQUIRE(covsqrt_hc && window_real && n && S && C && sim_hi >= sim_lo, "oa_mc_run_windowed: bad argument");
     Pipeline* q = (Pipeline*)p->pipe;
+    hipStream_t st = (hipStream_t)stream;
     if (p->mixed) {
         OA_REQUIRE(q->band && q->band->pipe, "oa_mc_run_windowed: the bound filters have no band grid on this plan (oa_plan_set_filters reports why)");
-        return mixed_mc_run_windowed(p, q, base_seed, sim_lo, sim_hi, covsqrt_hc, window_real, n, S, C, meanfield_acc, (hipStream_t)stream);
+        return mixed_mc_run_windowed(p, q, base_seed, sim_lo, sim_hi, covsqrt_hc, window_real, n, S, C, meanfield_acc, st);
     }
-    void* tmap = q->c[0];
+    void* const tmap = q->c[0];
     const double inv = 1.0 / ((double)p->ny * p->nx);
     const long pl = work_pitch(p, q->wl);
-    long i = sim_lo;
+    const size_t es = elem_bytes(p), lb = (size_t)pl * p->ny * es;
+    // FUSED ROW PASS (default): inverse columns of the drawn spectrum (into the first leg plane, free until the leg stage), then
+    // C2R x window -> R2C per row in ONE kernel -- the real map exists in LDS only -- onto the scratch plane the column stages
+    // read.  OA_OPT_WIN_FUSED = 0: C2R with the window at its store -> real map in HBM -> the from-map estimator path.
+    const bool fused = q->opt_win_fused;
     // BATCHES (fused row pass only): per realisation the full-plane part -- draw, inverse columns, C2R x window -> R2C rows onto a
-    // compact plane --, then for the batch ONE forward column transform onto the leg band of its hc planes and the launches of
-    // oa_mc_run's batches behind it (legs, row stage, divergence + binning + moments, stack): the latency-bound coarse-grid work of a
-    // realisation (70 of its 205 us at 4096^2 float) is shared by up to six
-    {
-        hipStream_t st = (hipStream_t)stream;
-        const size_t es = 2 * (p->dtype == OA_F32 ? 4 : 8), pb = plane_bytes(p), lb = (size_t)pl * p->ny * es;
-        const int BMAX = std::max(1, std::min(MC_BATCH_MAX, q->opt_mc_batch));
-        bool batched = q->opt_win_fused && p->pow2;
-        while (batched && i < sim_hi) {
-            const int B = (int)std::min<long>(BMAX, sim_hi - i);
-            if (int rc = ensure_mc_src(p, q)) return rc;
-            const size_t tail = mc_pool_bytes(p, q, B);
-            if (int rc = ensure_pool(q, tail + (size_t)B * lb)) return rc;      // the row-transformed planes sit behind the tail's region
-            char* const rowT = (char*)q->split_legs + tail;
-            for (int b = 0; b < B; ++b) {
-                int rc = oa_grf_hc(p, base_seed, (uint64_t)(i + b), covsqrt_hc, q->kT, stream);
-                if (rc) return rc;
-                if ((rc = qe_windowed_rows_w(p, q->kT, tmap, window_real, q->wl, pl, inv, st, rowT + (size_t)b * lb))) return rc;
-            }
-            int rc = qe_fwd_cols_batch_w(p, rowT, pl, q->mc_src, B, (long)(lb / es), (long)(pb / es), q->wl, q->rl, st);
-            if (rc) return rc;
-            int fallback = 0;
-            if ((rc = mc_batch_tail(p, q, B, n, S, C, meanfield_acc, st, &fallback))) return rc;
-            if (fallback) { batched = false; break; }         // (geometry without the batched row stage: one by one below)
-            i += B;
+    // compact plane behind the tail's region of the pool --, then for the batch ONE forward column transform onto the leg band of its hc
+    // planes and the launches of oa_mc_run's batches behind it: the latency-bound coarse-grid work of a realisation (70 of its 205 us at
+    // 4096^2 float) is shared by up to six
+    McTtLoop T{p, p, q, fused && p->pow2, lb, nullptr, nullptr, tmap, nullptr, fused ? 1 : 0, true};
+    T.source_batch = [=](long i, int B) {
+        char* const rowT = q->split_legs.at(mc_pool_bytes(p, q, B));
+        for (int b = 0; b < B; ++b) {
+            if (int rc = oa_grf_hc(p, base_seed, (uint64_t)(i + b), covsqrt_hc, q->kT, st)) return rc;
+            if (int rc = qe_windowed_rows_w(p, q->kT, tmap, window_real, q->wl, pl, inv, st, rowT + (size_t)b * lb)) return rc;
         }
-    }
-    for (; i < sim_hi; ++i) {
-        int rc = oa_grf_hc(p, base_seed, (uint64_t)i, covsqrt_hc, q->kT, stream);
-        if (rc) return rc;
-        // FUSED ROW PASS (default): inverse columns of the drawn spectrum (into the first leg plane, free until the leg stage), then
-        // C2R x window -> R2C per row in ONE kernel -- the real map exists in LDS only -- onto the scratch plane the column stages
-        // read.  OA_OPT_WIN_FUSED = 0: C2R with the window at its store -> real map in HBM -> the from-map estimator path.
-        const int fused_rows = q->opt_win_fused ? 1 : 0;
-        if (fused_rows) rc = qe_windowed_rows_w(p, q->kT, tmap, window_real, q->wl, pl, inv, (hipStream_t)stream);
-        else rc = oa_fft_c2r_windowed(p, q->kT, tmap, inv, window_real, stream);     // the window rides on the row pass's store
-        if (rc) return rc;
-        // binning + moments in the divergence launch where the geometry has that kernel (kappa_hat still stored when the mean-field
-        // stack needs it)
-        DivBinFuse f = make_fuse(p, q, n, S, C, meanfield_acc ? 1 : 0);
-        if ((rc = qe_tt_impl(p, tmap, nullptr, nullptr, nullptr, 0, stream, divbin_enabled(q) ? &f : nullptr, fused_rows))) return rc;
-        if (!f.done && (rc = bandpower_moments(p, q, n, S, C, stream))) return rc;
-        if (meanfield_acc && (rc = stack_add_region(p->dtype, q->kk, meanfield_acc, p->ny, p->kp, q->wk, q->rk, (hipStream_t)stream))) return rc;
-    }
-    return 0;
+        return qe_fwd_cols_batch_w(p, rowT, pl, q->mc_src.p, B, (long)(lb / es), plane_elems(p), q->wl, q->rl, st);
+    };
+    T.source_one = [=](long i) {
+        if (int rc = oa_grf_hc(p, base_seed, (uint64_t)i, covsqrt_hc, q->kT, st)) return rc;
+        if (fused) return qe_windowed_rows_w(p, q->kT, tmap, window_real, q->wl, pl, inv, st);
+        return oa_fft_c2r_windowed(p, q->kT, tmap, inv, window_real, st);           // the window rides on the row pass's store
+    };
+    return mc_tt_loop(T, sim_lo, sim_hi, n, S, C, meanfield_acc, st);
 }
 
 // ---- device memory for hosts that bring no GPU array library (the reference is NumPy) -----------------------------
