@@ -43,7 +43,7 @@ typedef struct oa_plan oa_plan;
 const char* oa_last_error(void);
 /* ABI version = 100 x the build round that last changed a signature in this header; bindings must refuse a library
  * that reports less than the version they were written against (OA_ABI_VERSION) */
-#define OA_ABI_VERSION 410
+#define OA_ABI_VERSION 411
 int oa_version(void);
 /* number of HIP devices visible; <0 on error (no compute) */
 int oa_device_count(void);
@@ -163,6 +163,10 @@ int oa_qe_cols_div(oa_plan* p, const void* px_rows, const void* py_rows, const v
  *                        tutorials/tt_verification.ipynb cell 4: Philox GRF (key = (base_seed, sim)) with per-mode
  *                        amplitude covsqrt_hc -> TT estimator -> bandpower moments (+ mean-field stack of kappa_hat,
  *                        interleaved re/im doubles, if meanfield_acc != NULL).  No host synchronisation.
+ *  oa_rdn0_set_data,
+ *  oa_mc_run_rdn0      : the realisation-dependent N0 shard of ONE data map: the data's three leg planes are cached by the
+ *                        set-up entry, then per realisation two draws s, s' -> A = QE(d, s) + QE(s, d), B = QE(s, s') + QE(s', s)
+ *                        -> x = [p(A) - p(B) / 2, p(B) / 2] -> moments of the 2 d-vector (at their declarations below).
  *  BINDING: the plan keeps the POINTERS handed to oa_plan_set_filters / oa_plan_set_bins and may keep derived copies of what they
  *  point to (tile-major Fnorm / ids of the fused divergence launch; the (FG, FH) values of the R-split column stage in thread order).  Every call of either entry invalidates those copies -- also
  *  when the addresses are the ones bound before -- so a caller that changes the contents of a bound plane calls the entry again. */
@@ -341,6 +345,36 @@ int oa_split_cross_power(int dtype, int nsplits, const void* const* host_kappa, 
  * synchronisation). */
 int oa_mc_run(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, int64_t* n, double* S,
               double* C, double* meanfield_acc, void* stream);
+/* REALISATION-DEPENDENT N0 (RDN0) of the TT estimator: the Monte Carlo that debiases the kappa_hat auto-spectrum of ONE given map d by
+ * pairing it with simulations through the two legs of the estimator.  With QE(X, Y) = oa_qe_tt(kX = X, kY = Y) of the bound filters and,
+ * for realisation i, s = the draw of Philox stream 2 i and s' = the draw of stream 2 i + 1 (key base_seed, amplitude covsqrt_hc: the very
+ * draws oa_mc_run makes for its realisations 2 i and 2 i + 1 -- the leg band of oa_grf_hc's plane, same counters):
+ *     A = QE(d, s) + QE(s, d),      B = QE(s, s') + QE(s', s),
+ *     p(Z)_b = binned |Z|^2 * norm over the mode counts of bin b (weights, ids and counts of oa_plan_set_bins, as oa_mc_run's bandpowers),
+ *     x_i = [ p(A) - p(B) / 2 ,  p(B) / 2 ]          (2 d numbers, d = nids - 2: "rdn0", then "mcn0"),
+ *     n += 1,  S += x_i,  C += x_i x_i^T             (Statistics.add of the 2 d-vector, float64, realisation order).
+ * |A|^2 is the four data-simulation terms of the usual six-term RDN0; p(B) / 2 has the expectation of its two simulation-simulation
+ * terms and a smaller variance.  The second half alone is the N0 of independent pairs (no data, no signal trispectrum); the debiased
+ * spectrum of the map is p(QE(d, d)) - mean(rdn0).  No window: simulations with the data's taper are not part of this entry.
+ *  oa_rdn0_set_data : set-up entry (needs oa_plan_set_filters; may allocate and synchronise).  kD_hc = the data map's transform; its three
+ *                     filtered leg planes are made on the plan's coarse grid, exactly as the leg stage of oa_qe_tt(kX = d) leaves them,
+ *                     and kept in a plan-owned buffer (on a band grid: the leg band of kD_hc is embedded into an inner plane first and
+ *                     the legs live on the inner plan).  Every later oa_plan_set_filters / oa_plan_set_bins / oa_plan_set_col_grid
+ *                     makes them stale (the binding generation is their key): call it after those.  oa_plan_release_pools frees them.
+ *  oa_mc_run_rdn0   : the shard [sim_lo, sim_hi); S holds 2 d doubles, C (2 d)^2.  Stream-ordered, no host work on data; it allocates
+ *                     nothing after the first call (nothing at all when oa_rdn0_set_data ran with the bins bound).  Refused by name
+ *                     before anything is launched: chirp-z sides, no filters, no bins, a binding without a band grid, no data set,
+ *                     stale data legs, more bins than the tail's fold workgroup holds.  Realisations are batched as in oa_mc_run
+ *                     (OA_OPT_MC_BATCH; a batch of B realisations holds 2 B draws); per batch: 1 draw launch, 2 leg launches (the
+ *                     data's legs are cached: only the simulations' 6 B fields are transformed) [+ 1 inverse pass 2], 1 chain row-stage
+ *                     launch (A_b, B_b: 2 B estimators of two pieces each, summed in real space), 1 divergence launch, and the 2
+ *                     launches of the combine -> bin -> moments tail (partial sums per group of band rows, then one fold workgroup:
+ *                     no ticket).  Where the row stage takes one map per launch the realisations run one by one.  Every sum has a
+ *                     fixed order: the moments are bit-reproducible and do not depend on the batch size nor on how a range is cut
+ *                     into calls. */
+int oa_rdn0_set_data(oa_plan* p, const void* kD_hc, void* stream);
+int oa_mc_run_rdn0(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, int64_t* n, double* S, double* C,
+                   void* stream);
 /* The same shard with a real-space window applied to every realisation before its transform (the reference's analysis
  * flow: maps.py:1873-1878 get_taper, maps.py:1350-1361): full-plane draw (same Philox counters as oa_mc_run) -> C2R / Npix
  * -> x window_real (ny x nx reals of the plan's dtype) -> TT estimator -> bandpower moments (+ mean-field stack).  With

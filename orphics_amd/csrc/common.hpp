@@ -130,6 +130,11 @@ int grf_mix_teb_to_tqu(oa_plan* p, uint64_t seed, uint64_t sid0, const void* con
 // complex per row); band: columns < w, rows |ky| < r
 int band_stack_add_multi(int dtype, const void* k, long kstride, const void* wt, long wstride, int nest, double* const* acc, double* acc_mv,
                          int iny, long ipitch, int any, long apitch, int w, int r, hipStream_t st);
+// oa_mc_run_rdn0's combine -> bin -> moments tail over the 2 B kappa_hat planes of a batch (elementwise.hip, rdn0.hpp): two launches
+size_t rdn0_part_bytes(int ny, int rb, int nids, int B);
+int rdn0_tail_check(const char* who, int nids, int B);
+int rdn0_tail(int dtype, const void* k, long kstride, int B, int ny, long kp, int nxh, const int32_t* ids, int nids, double pnorm, int w, int rb,
+              const int64_t* mcounts, double* part, int64_t* n, double* S, double* C, hipStream_t st);
 // the unscaled inverse column transform of nplanes hc planes pstride complex elements apart, in place, ONE launch (grid y = plane)
 int mixed_cols_inverse_batch(oa_plan* p, int nplanes, void* hc, long pstride, hipStream_t st);
 // my > 0: COLUMN GRID -- legs, row stage and divergence run on my < ny rows (plan_ensure_col_grid(p, my) first)

@@ -4,6 +4,7 @@
 #include "common.hpp"
 #include "split_power.hpp"
 #include "mc_pol.hpp"
+#include "rdn0.hpp"
 
 namespace oa {
 
@@ -489,6 +490,61 @@ int band_stack_add_multi(int dtype, const void* k, long kstride, const void* wt,
     OA_REQUIRE(w >= 1 && r >= 1 && 2L * r - 1 <= (iny < any ? iny : any) && w <= ipitch && w <= apitch, "band_stack_add_multi: bad band");
     return dtype == OA_F32 ? band_stack_multi_t<float>(k, kstride, wt, wstride, nest, acc, acc_mv, iny, ipitch, any, apitch, w, r, st)
                            : band_stack_multi_t<double>(k, kstride, wt, wstride, nest, acc, acc_mv, iny, ipitch, any, apitch, w, r, st);
+}
+// oa_mc_run_rdn0's tail (rdn0.hpp): partial sums per (row group, realisation), then ONE fold workgroup
+struct Rdn0Ctx {
+    char* sm;
+    OA_D int tid() const { return threadIdx.x; }
+    OA_D int nthreads() const { return blockDim.x; }
+    OA_D int bid_x() const { return blockIdx.x; }
+    OA_D int bid_z() const { return blockIdx.z; }
+    OA_D int grid_x() const { return gridDim.x; }
+    OA_D void sync() const { __syncthreads(); }
+    OA_D void* smem() const { return sm; }
+};
+extern __shared__ __attribute__((aligned(16))) char rdn0_smem[];
+template <typename T>
+__global__ __launch_bounds__(RDN0_NT) void rdn0_part_kernel(Rdn0PartArgs<T> a) {
+    Rdn0Ctx c{rdn0_smem};
+    rdn0_part_body<T>(c, a);
+}
+__global__ __launch_bounds__(RDN0_FOLD_NT) void rdn0_fold_kernel(Rdn0FoldArgs a) {
+    Rdn0Ctx c{rdn0_smem};
+    rdn0_fold_body(c, a);
+}
+size_t rdn0_part_bytes(int ny, int rb, int nids, int B) {
+    const int nrows = (rb > 0 && 2L * rb - 1 < ny) ? 2 * rb - 1 : ny;
+    return (size_t)B * rdn0_groups(nrows) * 2 * nids * sizeof(double);
+}
+// the checks of rdn0_tail that do not depend on the planes: 0, or the failure already reported (for an entry to refuse before its first launch)
+int rdn0_tail_check(const char* who, int nids, int B) {
+    OA_REQUIRE(nids >= 3 && B >= 1, std::string(who) + ": bad bins or batch");
+    OA_REQUIRE(rdn0_part_lds(nids) <= 48 * 1024 && rdn0_fold_lds(nids, B) <= 48 * 1024,
+               std::string(who) + ": too many bins for the combine / bin / moments tail (LDS of its fold workgroup); run the host loop "
+               "(mc.RDN0MonteCarlo with one_call=False)");
+    return 0;
+}
+// k: 2 B planes (ny, kp) kstride complex elements apart; ids: (ny, kp) int32; part: rdn0_part_bytes(ny, rb, nids, B); n, S, C as in rdn0.hpp
+int rdn0_tail(int dtype, const void* k, long kstride, int B, int ny, long kp, int nxh, const int32_t* ids, int nids, double pnorm, int w, int rb,
+              const int64_t* mcounts, double* part, int64_t* n, double* S, double* C, hipStream_t st) {
+    OA_REQUIRE(k && ids && mcounts && part && n && S && C, "rdn0 tail: NULL argument");
+    if (int rc = rdn0_tail_check("rdn0 tail", nids, B)) return rc;
+    if (w <= 0 || w > kp) w = (int)kp;
+    if (!(rb > 0 && 2L * rb - 1 < ny)) rb = 0;
+    const int nrows = rb ? 2 * rb - 1 : ny;
+    const int R = rdn0_rows_per_group(nrows), G = rdn0_groups(nrows);
+    if (dtype == OA_F32) {
+        Rdn0PartArgs<float> a{(const cx<float>*)k, kstride, kp, ny, ids, kp, nids, w, rb, nxh, pnorm, part, nrows, R};
+        hipLaunchKernelGGL(rdn0_part_kernel<float>, dim3(G, 1, B), dim3(RDN0_NT), rdn0_part_lds(nids), st, a);
+    } else {
+        Rdn0PartArgs<double> a{(const cx<double>*)k, kstride, kp, ny, ids, kp, nids, w, rb, nxh, pnorm, part, nrows, R};
+        hipLaunchKernelGGL(rdn0_part_kernel<double>, dim3(G, 1, B), dim3(RDN0_NT), rdn0_part_lds(nids), st, a);
+    }
+    OA_LAUNCH_CHECK();
+    Rdn0FoldArgs f{part, mcounts, B, G, nids, n, S, C};
+    hipLaunchKernelGGL(rdn0_fold_kernel, dim3(1), dim3(RDN0_FOLD_NT), rdn0_fold_lds(nids, B), st, f);
+    OA_LAUNCH_CHECK();
+    return 0;
 }
 // mean-field stack of the one-call Monte-Carlo driver (pipeline.hip)
 int stack_add_region(int dtype, const void* x, double* acc, int ny, long kp, int w, int rb, hipStream_t st, int nbatch, long xstride) {

@@ -68,6 +68,11 @@ struct Pipeline {
                                       // is not engaged) | oa_bin_power_multi's partials | its sums
     DevBuf mvwin;                     // oa_mc_run_mv_windowed: the three full-plane T, Q, U draws | one column temporary per plane (the real maps of
                                       // the unfused flow) | the three compact row-transformed planes
+    // oa_rdn0_set_data / oa_mc_run_rdn0.  On a band grid the two buffers are the inner plan's, the key is the map's plan's
+    DevBuf rdn0_legs;                 // the data map's three compact leg planes gx, gy, h, as the leg stage of oa_qe_tt(kX = d) leaves them
+    DevBuf rdn0_pool;                 // 2 MC_BATCH_MAX drawn hc planes | 2 MC_BATCH_MAX kappa planes | the partial sums of the tail (rdn0.hpp)
+    unsigned long rdn0_gen = 0;       // bind_gen the data legs were made under (0: no data set) ...
+    int rdn0_my = 0;                  // ... and the column grid
     // tile-major copies of Fnorm and of the bin ids on the coarse grid of the fused divergence + binning launch (what they were
     // made from: rebuilt when the filters / bins / column grid change)
     // (one set per grid a plan can carry: [0] the column grid `my`, [1] the from-map grid `my3`)
@@ -166,8 +171,8 @@ void pipeline_release(oa_plan* p) {
     if (q->ticket) (void)hipFree(q->ticket);
     if (q->mv_ftab) (void)hipFree(q->mv_ftab);
     if (q->mv_rtab) (void)hipFree(q->mv_rtab);
-    for (DevBuf* b : {&q->split_legs, &q->mc_src, &q->lens_pool, &q->mvmc, &q->mvwin, &q->dt[0].fn_t, &q->dt[0].ids_t, &q->dt[1].fn_t,
-                      &q->dt[1].ids_t, &q->fb_t}) b->release();
+    for (DevBuf* b : {&q->split_legs, &q->mc_src, &q->lens_pool, &q->mvmc, &q->mvwin, &q->rdn0_legs, &q->rdn0_pool, &q->dt[0].fn_t, &q->dt[0].ids_t,
+                      &q->dt[1].fn_t, &q->dt[1].ids_t, &q->fb_t}) b->release();
     if (q->band) (void)oa_plan_destroy(q->band);
     q->release_band();
     q->brows.release();
@@ -632,10 +637,13 @@ int oa_plan_release_pools(oa_plan* p) {
     OA_HIP(hipDeviceSynchronize());
     // band grid: the split entries' inner source planes and kappa block (bsplit), the draw and row planes of oa_mc_run_windowed (bwin), the
     // map-side scratch of oa_qe_mv_maps (mrows) and the N-grid planes of oa_mc_run_mv_windowed (mwin): all retaken by the next call
-    for (DevBuf* b : {&q->lens_pool, &q->split_legs, &q->mc_src, &q->mvmc, &q->mvwin, &q->bsplit, &q->bwin, &q->pb.mrows, &q->pb.mwin}) b->release();
+    for (DevBuf* b : {&q->lens_pool, &q->split_legs, &q->mc_src, &q->mvmc, &q->mvwin, &q->bsplit, &q->bwin, &q->pb.mrows, &q->pb.mwin, &q->rdn0_legs,
+                      &q->rdn0_pool}) b->release();
     q->bs_cap = 0;
-    // ... the pool the split entries' inner call grew (regrown on demand)
-    if (q->band && q->band->pipe) ((Pipeline*)q->band->pipe)->split_legs.release();
+    q->rdn0_gen = 0;                 // the data legs of oa_rdn0_set_data are gone: oa_mc_run_rdn0 asks for them again
+    // ... the pool the split entries' inner call grew (regrown on demand), and the inner planes of oa_rdn0_set_data / oa_mc_run_rdn0
+    if (q->band && q->band->pipe)
+        for (DevBuf* b : {&((Pipeline*)q->band->pipe)->split_legs, &((Pipeline*)q->band->pipe)->rdn0_legs, &((Pipeline*)q->band->pipe)->rdn0_pool}) b->release();
     // ... and the Monte-Carlo binding with its pool: oa_mc_mv_band_bind makes it again
     q->pb.mc.pool.release();
     q->pb.mc = Pipeline::PolBind::McBind();
@@ -1249,6 +1257,10 @@ struct McTtLoop {
     std::function<int(long, int)> source_batch;
     std::function<int(long)> source_one;
     const void* one_map; const void* one_k; int rows_done; bool fuse;
+    // oa_mc_run_rdn0: what stands in for mc_batch_tail (B realisations; *fallback as there) and for the estimator + binning of the
+    // one-by-one loop; the sources then leave 2 B draws in run's rdn0_pool, not in mc_src
+    std::function<int(int, int*)> tail_batch = nullptr;
+    std::function<int()> tail_one = nullptr;
 };
 static int mc_tt_loop(const McTtLoop& T, long sim_lo, long sim_hi, int64_t* n, double* S, double* C, double* meanfield_acc, hipStream_t st) {
     oa_plan* const r = T.run;
@@ -1266,12 +1278,14 @@ static int mc_tt_loop(const McTtLoop& T, long sim_lo, long sim_hi, int64_t* n, d
     while (batched && i < sim_hi) {
         const int B = (int)std::min<long>(BMAX, sim_hi - i);
         // before the first draw: growing either synchronises the device (a band plan's were taken by oa_plan_set_bins: no allocation here)
-        if (int rc = ensure_mc_src(r, rq)) return rc;
+        if (!T.tail_batch)
+            if (int rc = ensure_mc_src(r, rq)) return rc;
         if (int rc = ensure_pool(rq, mc_pool_bytes(r, rq, B) + (size_t)B * T.pool_extra)) return rc;
         int rc = T.source_batch(i, B), fallback = 0;
         if (rc) return rc;
         // the power-of-two plans' stack is added inside the tail, in the batch's launch; a band plan's from the kappa planes it keeps
-        if ((rc = mc_batch_tail(r, rq, B, n, S, C, inner ? nullptr : meanfield_acc, st, &fallback, inner && meanfield_acc))) return rc;
+        if ((rc = T.tail_batch ? T.tail_batch(B, &fallback)
+                               : mc_batch_tail(r, rq, B, n, S, C, inner ? nullptr : meanfield_acc, st, &fallback, inner && meanfield_acc))) return rc;
         if (fallback) break;
         if (inner && (rc = stack(rq->c[0], B, plane_elems(r)))) return rc;
         i += B;
@@ -1279,6 +1293,10 @@ static int mc_tt_loop(const McTtLoop& T, long sim_lo, long sim_hi, int64_t* n, d
     for (; i < sim_hi; ++i) {
         int rc = T.source_one(i);
         if (rc) return rc;
+        if (T.tail_one) {
+            if ((rc = T.tail_one())) return rc;
+            continue;
+        }
         DivBinFuse f = make_fuse(r, rq, n, S, C, meanfield_acc ? 1 : 0);     // (kappa_hat still stored when the stack needs it)
         if ((rc = qe_tt_impl(r, T.one_map, T.one_k, nullptr, nullptr, 0, st, T.fuse && divbin_enabled(rq) ? &f : nullptr, T.rows_done))) return rc;
         if (!f.done && (rc = bandpower_moments(r, rq, n, S, C, st))) return rc;
@@ -1341,6 +1359,123 @@ static int mixed_mc_run_windowed(oa_plan* p, Pipeline* q, uint64_t base_seed, lo
         return band_map_r2c(p, tmap, rows, q->wl, q->rl, bx, b->ny, b->kp, st);
     };
     return mc_tt_loop(T, sim_lo, sim_hi, n, S, C, meanfield_acc, st);
+}
+/* ---- oa_rdn0_set_data / oa_mc_run_rdn0: the realisation-dependent N0 shard (include/orphics_amd.h) ------------------------------------
+ * Realisation i pairs the data d with the draws s (Philox stream 2 i) and s' (stream 2 i + 1) through the two legs of the TT estimator:
+ *     A = QE(d, s) + QE(s, d),   B = QE(s, s') + QE(s', s)       (QE(X, Y): gradient leg from X, the other from Y).
+ * The real-space products are linear in the pieces, so A and B are two-piece estimators over the sources d, s, s' in oa_qe_mv's sense:
+ * (gx_d, gy_d, h_s) + (gx_s, gy_s, h_d) and (gx_s, gy_s, h_s') + (gx_s', gy_s', h_s), one divergence each.  d's three leg planes never
+ * change: oa_rdn0_set_data makes them once (rdn0_legs).  `r` is the plan the estimator runs on -- the map's plan, or the inner plan of
+ * its band grid -- and `rq` its Pipeline.  PER BATCH of B realisations (r's pool: 6 B leg planes | 4 B product planes | 4 B pass-1 planes;
+ * rdn0_pool: the 2 B draws, draw z = stream 2 i + z | the 2 B kappa planes, A_b and B_b at 2 b, 2 b + 1 | the tail's partials):
+ *   1 draw launch (2 B leg bands)  ->  2 leg launches (B gradient + B H fields each: the selector holds 16 fields) [+ 1 inverse pass 2 over
+ *   the 6 B planes where the leg kernel is not single-pass]  ->  1 chain row-stage launch (2 B estimators of two pieces)  ->  the batched
+ *   divergence of 2 B planes  ->  the tail's 2 launches (rdn0.hpp).
+ * ONE BY ONE, where the row stage takes one map per launch (rdn0_one): 1 draw launch (2 planes), 2 leg-stage calls, 4 row-stage launches
+ * (the second piece of an estimator accumulates), 2 divergences, the same tail with B = 1. */
+static size_t rdn0_pool_bytes(const oa_plan* r, const Pipeline* rq) {
+    return 4 * (size_t)MC_BATCH_MAX * plane_bytes(r) + rdn0_part_bytes(r->ny, rq->rk, rq->nids, MC_BATCH_MAX);
+}
+// everything a shard needs beyond the data legs; allocates (and synchronises) only when something is missing or too small
+static int rdn0_reserve(oa_plan* r, Pipeline* rq) {
+    if (int rc = ensure_work(r, rq)) return rc;
+    if (int rc = rq->rdn0_pool.reserve(rdn0_pool_bytes(r, rq), true)) return rc;          // draws and kappa planes: only their band is ever written
+    if (int rc = ensure_pool(rq, 2 * mc_pool_bytes(r, rq, MC_BATCH_MAX))) return rc;
+    if (!rq->mv_ftab) OA_HIP(hipMalloc((void**)&rq->mv_ftab, 32 * sizeof(void*)));
+    if (!rq->mv_rtab) OA_HIP(hipMalloc(&rq->mv_rtab, 64 * 64 + 1024));
+    return 0;
+}
+struct Rdn0Planes {                       // where a batch of B lives
+    char *legs, *prod, *tmp, *draw, *kappa; double* part; const char* data;
+    size_t lb, lbk, pb;
+};
+static Rdn0Planes rdn0_planes(const oa_plan* r, const Pipeline* rq, int B) {
+    Rdn0Planes P;
+    const size_t es = elem_bytes(r);
+    P.lb = (size_t)work_pitch(r, rq->wl) * r->ny * es; P.lbk = (size_t)work_pitch(r, rq->wk) * r->ny * es; P.pb = plane_bytes(r);
+    P.legs = rq->split_legs.at(); P.prod = P.legs + 6 * (size_t)B * P.lb; P.tmp = P.prod + 4 * (size_t)B * P.lbk;
+    P.draw = rq->rdn0_pool.at(); P.kappa = P.draw + 2 * (size_t)MC_BATCH_MAX * P.pb; P.part = (double*)(P.kappa + 2 * (size_t)MC_BATCH_MAX * P.pb);
+    P.data = rq->rdn0_legs.at();
+    return P;
+}
+static int rdn0_tail_of(oa_plan* r, Pipeline* rq, const Rdn0Planes& P, int B, int64_t* n, double* S, double* C, hipStream_t st) {
+    return rdn0_tail(r->dtype, P.kappa, plane_elems(r), B, r->ny, r->kp, r->nx / 2, rq->ids, rq->nids, rq->norm, rq->wk, rq->rk, rq->counts_full, P.part,
+                     n, S, C, st);
+}
+static int rdn0_batch(oa_plan* r, Pipeline* rq, int B, int64_t* n, double* S, double* C, hipStream_t st, int* fallback) {
+    *fallback = 0;
+    const Rdn0Planes P = rdn0_planes(r, rq, B);
+    const long pl = work_pitch(r, rq->wl), pk = work_pitch(r, rq->wk);
+    const size_t es = elem_bytes(r), lb = P.lb, lbk = P.lbk;
+    const int my = rq->my;
+    std::vector<const void*> fkey;
+    for (int b = 0; b < B; ++b) fkey.push_back(rq->FG);
+    for (int b = 0; b < B; ++b) fkey.push_back(rq->FH);
+    if (fkey != rq->mv_fkey) {
+        OA_HIP(hipMemcpyAsync(rq->mv_ftab, fkey.data(), fkey.size() * sizeof(void*), hipMemcpyHostToDevice, st));
+        rq->mv_fkey = fkey;
+    }
+    unsigned long long sel = 0;                       // field f of a leg launch (gradient fields 0..B-1, H fields B..2B-1) reads its draw f mod B
+    for (int f = 0; f < 2 * B; ++f) sel |= (unsigned long long)(f % B) << (4 * f);
+    int legs_done = 0, rc;
+    for (int c = 0; c < 2; ++c)                       // draws [c B, (c + 1) B) -> leg planes [3 c B, 3 (c + 1) B): gx, gy of draw z' at 2 z', 2 z' + 1, h at 2 B + z'
+        if ((rc = qe_legs_batch_w(r, P.draw + (size_t)c * B * P.pb, plane_elems(r), 0, sel, (const void* const*)rq->mv_ftab, B, B,
+                                  P.legs + 3 * (size_t)c * B * lb, (long)(lb / es), rq->wl, rq->rl, pl, st, my, 4, &legs_done))) return rc;
+    if (!legs_done && (rc = qe_legs_pass2_w(r, P.legs, 6 * B, (long)(lb / es), rq->wl, pl, st, my))) return rc;
+    auto gx = [&](int z) { return (const void*)(P.legs + (3 * (size_t)(z / B) * B + 2 * (size_t)(z % B)) * lb); };
+    auto hh = [&](int z) { return (const void*)(P.legs + (3 * (size_t)(z / B) * B + 2 * (size_t)B + (size_t)(z % B)) * lb); };
+    const double s = 1.0 / ((double)r->ny * r->nx), sy = my ? (double)r->ny / my : 1.0;
+    std::vector<const void*> cgx, cgy, chh;
+    std::vector<void*> cpx, cpy;
+    std::vector<double> csc(4 * B, s * s * sy);
+    std::vector<int> first(2 * B), cnt(2 * B, 2);
+    for (int b = 0; b < B; ++b) {
+        const int zs = 2 * b, zt = 2 * b + 1;         // s, s'
+        const void* const pg[4] = {P.data, gx(zs), gx(zs), gx(zt)};                 // A: (d, s) + (s, d);  B: (s, s') + (s', s)
+        const void* const ph[4] = {hh(zs), P.data + 2 * lb, hh(zt), hh(zs)};
+        for (int k = 0; k < 4; ++k) {
+            const int e = 2 * b + k / 2;
+            if (k % 2 == 0) first[e] = (int)cgx.size();
+            cgx.push_back(pg[k]); cgy.push_back((const char*)pg[k] + lb); chh.push_back(ph[k]);
+            cpx.push_back(P.prod + 2 * (size_t)e * lbk); cpy.push_back(P.prod + (2 * (size_t)e + 1) * lbk);
+        }
+    }
+    std::vector<unsigned long long> key;
+    for (size_t i = 0; i < cgx.size(); ++i)
+        key.insert(key.end(), {(unsigned long long)(uintptr_t)cgx[i], (unsigned long long)(uintptr_t)chh[i], (unsigned long long)(uintptr_t)cpx[i]});
+    unsigned long long bits;
+    memcpy(&bits, &csc[0], sizeof bits);
+    key.insert(key.end(), {bits, (unsigned long long)my, (unsigned long long)(unsigned)rq->mrow, (unsigned long long)r->dtype, 0x4D01ull});
+    rc = qe_rows_chain_w(r, 2 * B, 4 * B, cgx.data(), cgy.data(), chh.data(), cpx.data(), cpy.data(), csc.data(), first.data(), cnt.data(), rq->mv_rtab,
+                         key != rq->mv_rkey, rq->wl, rq->wk, rq->mrow, pl, pk, st, my);
+    if (rc < 0) { *fallback = 1; return 0; }          // this geometry's row stage takes one map per launch: one-by-one loop
+    if (rc) return rc;
+    rq->mv_rkey = key;
+    if ((rc = qe_cols_div_batch_w(r, P.prod, P.prod + lbk, rq->Fn, P.kappa, P.tmp, 2 * B, (long)(2 * lbk / es), 0, plane_elems(r), rq->wk, rq->rk, pk,
+                                  st, my))) return rc;
+    return rdn0_tail_of(r, rq, P, B, n, S, C, st);
+}
+// one realisation whose draws s, s' sit on the first two planes of rdn0_pool
+static int rdn0_one(oa_plan* r, Pipeline* rq, int64_t* n, double* S, double* C, hipStream_t st) {
+    const Rdn0Planes P = rdn0_planes(r, rq, 1);
+    const long pl = work_pitch(r, rq->wl), pk = work_pitch(r, rq->wk);
+    const size_t lb = P.lb;
+    const int my = rq->my;
+    char* const L = P.legs;                           // gx, gy, h of s, then of s'
+    int rc;
+    for (int z = 0; z < 2; ++z)
+        if ((rc = qe_legs_cols_w(r, P.draw + (size_t)z * P.pb, P.draw + (size_t)z * P.pb, rq->FG, rq->FH, L + 3 * (size_t)z * lb, L + (3 * (size_t)z + 1) * lb,
+                                 L + (3 * (size_t)z + 2) * lb, rq->wl, rq->rl, pl, st, my))) return rc;
+    const double s = 1.0 / ((double)r->ny * r->nx), sy = my ? (double)r->ny / my : 1.0, sc = s * s * sy;
+    const void* const pg[4] = {P.data, L, L, L + 3 * lb};
+    const void* const ph[4] = {L + 2 * lb, P.data + 2 * lb, L + 5 * lb, L + 2 * lb};
+    for (int e = 0; e < 2; ++e) {
+        for (int k = 0; k < 2; ++k)
+            if ((rc = qe_rows_w(r, pg[2 * e + k], (const char*)pg[2 * e + k] + lb, ph[2 * e + k], rq->g[0], rq->g[1], sc, k, rq->wl, rq->wk, rq->mrow, pl, pk,
+                                st, my))) return rc;
+        if ((rc = qe_cols_div_w(r, rq->g[0], rq->g[1], rq->Fn, P.kappa + (size_t)e * P.pb, 0, rq->wk, rq->rk, pk, st, my))) return rc;
+    }
+    return rdn0_tail_of(r, rq, P, 1, n, S, C, st);
 }
 /* ---- oa_qe_pol / oa_qe_mv on the band grid -------------------------------------------------------------------------------------------
  * These entries take their filter planes per call, so the inner-layout copies are made by a set-up entry (oa_qe_band_bind, which may
@@ -1869,6 +2004,74 @@ int oa_mc_run(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const vo
     T.source_batch = [=](long i, int B) { return grf_hc_band_batch(p, base_seed, (uint64_t)i, B, covsqrt_hc, q->mc_src.p, plane_elems(p), q->wl, q->rl, st); };
     T.source_one = [=](long i) { return oa_grf_hc_band(p, base_seed, (uint64_t)i, covsqrt_hc, q->kT, q->wl, q->rl, st); };
     return mc_tt_loop(T, sim_lo, sim_hi, n, S, C, meanfield_acc, st);
+}
+
+/* oa_rdn0_set_data (include/orphics_amd.h): the data map's three leg planes on the plan's coarse grid, kept for oa_mc_run_rdn0.  Set-up
+ * entry: may allocate and synchronise.  On a band grid the leg band of kD goes to the inner plan's first input plane first. */
+int oa_rdn0_set_data(oa_plan* p, const void* kD_hc, void* stream) {
+    OA_REQUIRE(p && kD_hc, "oa_rdn0_set_data: NULL argument");
+    OA_REQUIRE(p->pow2 || p->mixed, "oa_rdn0_set_data: map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path; "
+               "run the host loop of the existing entries (mc.RDN0MonteCarlo with one_call=False)");
+    OA_REQUIRE(p->pipe && ((Pipeline*)p->pipe)->FG, "oa_rdn0_set_data: call oa_plan_set_filters first");
+    Pipeline* q = (Pipeline*)p->pipe;
+    hipStream_t st = (hipStream_t)stream;
+    q->rdn0_gen = 0;
+    oa_plan* r = p;
+    const void* src = kD_hc;
+    if (p->mixed) {
+        OA_REQUIRE(q->band && q->band->pipe, "oa_rdn0_set_data: the bound filters have no band grid on this plan (oa_plan_set_filters reports why)");
+        band_options(q);
+        r = q->band;
+        void* bx = band_in(q, 0);
+        if (int rc = band_copy(band_cx_kind(p), kD_hc, p->kp, p->ny, bx, r->kp, r->ny, q->wl, q->rl, 1.0, st)) return rc;
+        src = bx;
+    }
+    Pipeline* rq = (Pipeline*)r->pipe;
+    const long pl = work_pitch(r, rq->wl);
+    const size_t lb = (size_t)pl * r->ny * elem_bytes(r);
+    if (int rc = ensure_work(r, rq)) return rc;
+    if (int rc = rq->rdn0_legs.reserve(3 * lb)) return rc;
+    if (rq->ids)                                   // the shard's planes now, where the bins are known: its first call then allocates nothing
+        if (int rc = rdn0_reserve(r, rq)) return rc;
+    char* const L = rq->rdn0_legs.at();
+    if (int rc = qe_legs_cols_w(r, src, src, rq->FG, rq->FH, L, L + lb, L + 2 * lb, rq->wl, rq->rl, pl, st, rq->my)) return rc;
+    q->rdn0_gen = q->bind_gen;
+    q->rdn0_my = rq->my;
+    return 0;
+}
+
+/* oa_mc_run_rdn0 (include/orphics_amd.h): the RDN0 shard [sim_lo, sim_hi) on oa_mc_run's loop (mc_tt_loop) with its own source stage
+ * (two draws per realisation) and its own tail (rdn0_batch / rdn0_one above).  Everything is refused before the first launch. */
+int oa_mc_run_rdn0(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, int64_t* n, double* S, double* C,
+                   void* stream) {
+    static const char* const how = "; or run the host loop of the existing entries (mc.RDN0MonteCarlo with one_call=False)";
+    OA_REQUIRE(p && covsqrt_hc && n && S && C && sim_hi >= sim_lo, "oa_mc_run_rdn0: bad argument");
+    OA_REQUIRE(p->pow2 || p->mixed, std::string("oa_mc_run_rdn0: map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path") + how);
+    OA_REQUIRE(p->pipe && ((Pipeline*)p->pipe)->FG, std::string("oa_mc_run_rdn0: no filters bound: call oa_plan_set_filters, oa_plan_set_bins and oa_rdn0_set_data first") + how);
+    Pipeline* q = (Pipeline*)p->pipe;
+    OA_REQUIRE(q->ids, std::string("oa_mc_run_rdn0: no bins bound: call oa_plan_set_bins, then oa_rdn0_set_data") + how);
+    OA_REQUIRE(!p->mixed || (q->band && q->band->pipe), std::string("oa_mc_run_rdn0: the bound filters have no band grid on this plan (oa_plan_set_filters reports why)") + how);
+    oa_plan* r = p->mixed ? q->band : p;
+    Pipeline* rq = (Pipeline*)r->pipe;
+    OA_REQUIRE(q->rdn0_gen, std::string("oa_mc_run_rdn0: no data set: call oa_rdn0_set_data (after oa_plan_set_filters and oa_plan_set_bins)") + how);
+    OA_REQUIRE(q->rdn0_gen == q->bind_gen && q->rdn0_my == rq->my && rq->rdn0_legs.p,
+               std::string("oa_mc_run_rdn0: the data legs are stale -- oa_plan_set_filters, oa_plan_set_bins or oa_plan_set_col_grid was called since "
+                           "they were made: call oa_rdn0_set_data again") + how);
+    if (int rc = rdn0_tail_check("oa_mc_run_rdn0", rq->nids, MC_BATCH_MAX)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (p->mixed) band_options(q);
+    if (int rc = rdn0_reserve(r, rq)) return rc;   // (nothing to do after the first call, or after oa_rdn0_set_data with bins bound)
+    void* const draw = rq->rdn0_pool.p;
+    McTtLoop T{p, r, rq, true, mc_pool_bytes(r, rq, 1), nullptr, nullptr, nullptr, nullptr, 0, false};
+    auto source = [=](long i, int nreal) {          // draws 2 i .. 2 i + nreal - 1: the leg band of oa_grf_hc's plane, oa_mc_run's counters
+        if (p->mixed) return grf_band_inner(p, base_seed, 2 * (uint64_t)i, nreal, covsqrt_hc, draw, r->ny, r->kp, plane_elems(r), q->wl, q->rl, st);
+        return grf_hc_band_batch(p, base_seed, 2 * (uint64_t)i, nreal, covsqrt_hc, draw, plane_elems(p), q->wl, q->rl, st);
+    };
+    T.source_batch = [=](long i, int B) { return source(i, 2 * B); };
+    T.source_one = [=](long i) { return source(i, 2); };
+    T.tail_batch = [=](int B, int* fallback) { return rdn0_batch(r, rq, B, n, S, C, st, fallback); };
+    T.tail_one = [=]() { return rdn0_one(r, rq, n, S, C, st); };
+    return mc_tt_loop(T, sim_lo, sim_hi, n, S, C, nullptr, st);
 }
 
 /* oa_mc_run_mv (include/orphics_amd.h): the Gaussian N0 Monte-Carlo shard of an estimator SET.  Per realisation (mc_mv_loop): the leg band

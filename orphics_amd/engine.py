@@ -515,6 +515,7 @@ class Engine(object):
         """free the plan-owned pools of the multi-map entries (oa_lens_maps, oa_qe_mv, oa_qe_tt_splits, oa_mc_run, oa_mc_run_mv, oa_mc_run_mv_windowed)"""
         check(self.lib.oa_plan_release_pools(self.plan))
         self._mc_owner = None             # the Monte-Carlo binding of a band grid went with its pool (mc.GaussianN0MonteCarloPol binds again)
+        self._rdn0_owner = None           # ... and the data legs of oa_rdn0_set_data (mc.RDN0MonteCarlo sets them again)
 
     def set_laxes(self, ly, lx):
         ly = np.ascontiguousarray(ly, dtype=np.float64)

@@ -370,6 +370,7 @@ class Estimator(object):
             check(e.lib.oa_plan_set_col_grid(e.plan, int(self.mcol)))
             e._pipe_owner = self._token
             e._bins_owner = None
+            e._rdn0_owner = None          # the data legs of oa_rdn0_set_data belong to the binding they were made under
         return e
 
     def bind_bins(self, ids_hc, nids, norm):
@@ -392,6 +393,7 @@ class Estimator(object):
             ids, nids, norm = self._bins
             check(e.lib.oa_plan_set_bins(e.plan, _ptr(ids), nids, norm, _stream()))
             e._bins_owner = self._token
+            e._rdn0_owner = None
         return e
 
     def tt_moments(self, tmap, n, S, C):
@@ -471,6 +473,22 @@ class Estimator(object):
         Px, Py = w["P"]
         e.rfft(gx, out=Px); e.rfft(gy, out=Py)
         return e.qe_div(Px, Py, Fn, out=out)
+
+    def reconstruct_tt_sym_hc(self, kA, kB, out=None):
+        """``QE(A, B) + QE(B, A)`` -- the TT reconstruction symmetrised over which of two maps feeds the gradient leg -- from the
+        transforms ``kA``, ``kB`` (hc tensors): two :meth:`reconstruct_tt_hc` calls and one sum, on any side.  It is the building
+        block of the realisation-dependent N0 (``mc.RDN0MonteCarlo``: data x simulation and simulation x simulation pairs).  ``out``
+        as in :meth:`reconstruct_tt_hc`; a plane from :meth:`new_output` keeps its zero-fill bookkeeping (the sum is zero where
+        both terms are)."""
+        from .engine import owned_clean_region, set_clean_region
+        if getattr(self, "_sym_tmp", None) is None or self._sym_tmp[0] is not self.eng:
+            self._sym_tmp = (self.eng, self.new_output())
+        out = self.reconstruct_tt_hc(kA, kB, out=out)
+        region = owned_clean_region(out)
+        out.add_(self.reconstruct_tt_hc(kB, kA, out=self._sym_tmp[1]))
+        if region is not None:
+            set_clean_region(out, region)
+        return out
 
     def reconstruct_tt_from_map(self, tmap, out=None):
         """TT reconstruction straight from a real device map (both legs from it) in ONE C-ABI call: the map's

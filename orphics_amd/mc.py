@@ -758,3 +758,177 @@ class LensedSimsMonteCarlo(object):
     @property
     def centers(self):
         return (self.edges[1:] + self.edges[:-1]) / 2.
+
+
+class RDN0MonteCarlo(object):
+    """Realisation-dependent N0 (RDN0) of the TT estimator: the Monte Carlo that debiases the kappa_hat auto-spectrum of ONE given map
+    by pairing that map with simulations through the two legs of the estimator.  It follows the fluctuation of the data's own power
+    and is insensitive, at first order, to a mis-modelled total power.
+
+    Definition.  ``QE(X, Y)`` is the unsymmetrised TT reconstruction of ``qest``'s filters, ``reconstruct_tt_hc(kX=X, kY=Y)``; ``d``
+    is the data map's transform.  Realisation ``i`` draws ``s`` with Philox stream ``2 i`` and ``s'`` with stream ``2 i + 1`` (key
+    ``base_seed``, total power ``total_power_half``) -- the very draws ``GaussianN0MonteCarlo`` makes for its realisations ``2 i`` and
+    ``2 i + 1``.  Then::
+
+        A   = QE(d, s)  + QE(s, d)
+        B   = QE(s, s') + QE(s', s)
+        p(Z)_b = bandpower b of |Z|^2 (the weights, bins and mode counts of GaussianN0MonteCarlo's bandpowers)
+        x_i = [ p(A) - p(B) / 2 ,  p(B) / 2 ]        # 2 d numbers: "rdn0", then "mcn0"
+
+    and ``x_i`` is one sample of the label ``"rdn0"`` (dimension ``2 d``, ``d = len(bin_edges) - 1``): n += 1, S += x_i,
+    C += x_i x_i^T.  ``|A|^2`` is exactly the four data-simulation terms of the usual six-term RDN0; ``p(B) / 2`` has the same expectation
+    as its two simulation-simulation terms ``C[ss', ss'] + C[ss', s's]`` and a smaller variance.  The second half, :meth:`mcn0`, is the
+    N0 of independent pairs: it carries no data and no signal trispectrum.  The debiased spectrum of the map is
+    ``p(QE(d, d)) - mean(rdn0)`` (:meth:`debiased`, :meth:`data_bandpowers`).
+
+    ``data``: a real ``(Ny, Nx)`` map (NumPy or device tensor) or its hc transform (complex device tensor of the engine's layout);
+    :meth:`set_data` binds another map on the same plan.
+
+    ``one_call``: ``None`` (default) runs the shard as ``oa_mc_run_rdn0`` calls wherever ``qest.one_call()`` holds (power-of-two sides
+    and the band grid of sides 2^a 3^b 5^c: the data's three leg planes are filtered and transformed once, by ``oa_rdn0_set_data``, a
+    batch of realisations shares every launch, and the combination, the binning and the moment update are one fused tail; nothing
+    leaves the device) and the host loop elsewhere.  ``one_call=False`` runs the host loop of existing entries on any side, with the
+    same seeds and streams: ``Engine.grf_hc`` (twice) -> :meth:`Estimator.reconstruct_tt_sym_hc` (twice) -> ``Engine.bin_power`` (twice)
+    -> ``Statistics.add``.  ``one_call=True`` raises where there is no one-call path (chirp-z sides, unbounded filters, a band grid not
+    smaller than the map).
+
+    There is no ``window`` argument: simulations that carry the data's apodisation taper (and the mean field that comes with it) are
+    not part of this driver yet; it serves periodic / untapered maps, as the unwindowed N0 drivers do."""
+
+    def __init__(self, qest, data, total_power_half, bin_edges, comm=None, base_seed=1234, one_call=None):
+        torch = _torch()
+        self.q = qest
+        self.eng = e = qest.eng
+        self.comm = comm if comm is not None else _mpi.get_world()
+        self.base_seed = int(base_seed)
+        geom = qest.geom
+        amp = np.sqrt(np.asarray(total_power_half, dtype=np.float64) * float(e.npix) ** 2 / geom.area)
+        self.cs = qest._hcreal(e, amp)
+        self.edges = np.asarray(bin_edges, dtype=np.float64)
+        self.ids = e.modl_digitize(torch.as_tensor(self.edges, device=e.device), half=True)
+        self.nids = self.edges.size + 1
+        self.d = self.nids - 2
+        self.norm = geom.area / float(e.npix) ** 2
+        self.acc = Statistics(comm=self.comm if hasattr(self.comm, "dist") else None, device=e.device)
+        avail = bool(qest.one_call())
+        if one_call and not avail:
+            from ._lib import OrphicsAmdError
+            raise OrphicsAmdError("RDN0MonteCarlo: no one-call path on this %d x %d geometry (chirp-z sides, unbounded filters or a band grid "
+                                  "not smaller than the map): construct the driver with one_call=False (host loop of the existing entries)"
+                                  % (e.ny, e.nx))
+        self.one_call = avail if one_call is None else bool(one_call)
+        self._host = None
+        self.set_data(data)
+
+    def set_data(self, data):
+        """Bind another data map (real ``(Ny, Nx)`` map or hc transform) on the same plan, bins and simulations; the accumulated
+        samples are NOT reset (use a new driver, or a fresh ``self.acc``, for an independent run)."""
+        torch = _torch()
+        e = self.eng
+        if isinstance(data, torch.Tensor) and data.is_complex():
+            kd = e._chk(data.to(e.cdt).contiguous(), "hc")
+        else:
+            a = data if isinstance(data, torch.Tensor) else np.asarray(data)
+            if tuple(a.shape) != (e.ny, e.nx):
+                raise ValueError("data must be a real (Ny, Nx) map or an hc transform of the engine's layout")
+            kd = e.rfft(e.to_real(a))
+        self.kd = kd
+        self._dtoken = object()           # the plan's cached data legs (oa_rdn0_set_data) belong to this token
+        return self
+
+    # ---- results (after run / allreduce) ------------------------------------------------------------------------------------------
+    def rdn0(self):
+        """mean of the first half of the sample vector: the realisation-dependent N0 bandpowers."""
+        return self.acc.mean("rdn0")[:self.d]
+
+    def mcn0(self):
+        """mean of the second half: the N0 of independent simulation pairs (no data)."""
+        return self.acc.mean("rdn0")[self.d:]
+
+    def sem(self):
+        """standard error of :meth:`rdn0`."""
+        return np.sqrt(self.acc.var("rdn0")[:self.d] / self.acc.count("rdn0"))
+
+    def cov(self):
+        """sample covariance of the whole ``2 d`` vector (rdn0 block, mcn0 block and their cross block)."""
+        return self.acc.cov("rdn0")
+
+    def data_bandpowers(self):
+        """``p(QE(d, d))``: the bandpowers of the data's own reconstruction, with the driver's bins."""
+        q, e = self.q, self.eng
+        kap = q.reconstruct_tt_hc(self.kd)
+        s, _ = e.bin_power(kap, kap, self.norm, self.ids, self.nids, herm=True, active_cols=q.kappa_cols, active_rows=q.kappa_rows)
+        return (s[1:-1] / self._counts()).cpu().numpy()
+
+    def debiased(self, data_bandpowers=None):
+        """``data_bandpowers - rdn0()`` (``data_bandpowers=None``: :meth:`data_bandpowers`)."""
+        p = self.data_bandpowers() if data_bandpowers is None else np.asarray(data_bandpowers, dtype=np.float64)
+        return p - self.rdn0()
+
+    @property
+    def centers(self):
+        return (self.edges[1:] + self.edges[:-1]) / 2.
+
+    # ---- the shard ----------------------------------------------------------------------------------------------------------------
+    def _counts(self):
+        """data-independent mode counts of the interior bins over the whole half plane (float64 device tensor)."""
+        if getattr(self, "_cnt", None) is None:
+            e = self.eng
+            zero = e.hc()
+            self._cnt = e.bin_power(zero, zero, self.norm, self.ids, self.nids, herm=True)[1][1:-1].double()
+        return self._cnt
+
+    def sample_host(self, i):
+        """x_i through the existing entries (the host loop's arithmetic): float64 device tensor of ``2 d`` numbers."""
+        torch = _torch()
+        q, e = self.q, self.eng
+        if self._host is None:
+            self._host = (e.hc(), e.hc(), q.new_output(), q.new_output())
+        s0, s1, ka, kb = self._host
+        wl, rl = (q.leg_cols, q.leg_rows) if (q.leg_cols and q.leg_rows) else (0, 0)
+        e.grf_hc(self.base_seed, 2 * i, self.cs, out=s0, width=wl, rband=rl)
+        e.grf_hc(self.base_seed, 2 * i + 1, self.cs, out=s1, width=wl, rband=rl)
+        ka = q.reconstruct_tt_sym_hc(self.kd, s0, out=ka)
+        kb = q.reconstruct_tt_sym_hc(s0, s1, out=kb)
+        region = dict(active_cols=q.kappa_cols, active_rows=q.kappa_rows)
+        pa = e.bin_power(ka, ka, self.norm, self.ids, self.nids, herm=True, **region)[0][1:-1] / self._counts()
+        half = 0.5 * (e.bin_power(kb, kb, self.norm, self.ids, self.nids, herm=True, **region)[0][1:-1] / self._counts())
+        return torch.cat((pa - half, half))
+
+    def run_local(self, sims):
+        """Process the given global realisation indices on this rank's GPU: every contiguous block of indices is ONE ``oa_mc_run_rdn0``
+        call (one-call path), or one :meth:`sample_host` + ``Statistics.add`` per index (host loop)."""
+        from ._lib import check
+        from .engine import _ptr, _stream
+        sims = [int(i) for i in sims]
+        if not sims:
+            return self
+        if not self.one_call:
+            for i in sims:
+                self.acc.add("rdn0", self.sample_host(i))
+            return self
+        q = self.q
+        q.bind_bins(self.ids, self.nids, self.norm)
+        e = q._bind_bins()
+        if getattr(e, "_rdn0_owner", None) is not self._dtoken:
+            check(e.lib.oa_rdn0_set_data(e.plan, _ptr(self.kd), _stream()))
+            e._rdn0_owner = self._dtoken
+        n, S, C = self.acc.device_moments("rdn0", 2 * self.d)
+        start = prev = sims[0]
+        for i in sims[1:] + [None]:
+            if i is None or i != prev + 1:
+                check(e.lib.oa_mc_run_rdn0(e.plan, self.base_seed, start, prev + 1, _ptr(self.cs), _ptr(n), _ptr(S), _ptr(C), _stream()))
+                start = i
+            prev = i
+        self.acc.note_samples("rdn0", len(sims))
+        return self
+
+    def run(self, nsims):
+        """Shard ``nsims`` realisations with mpi.mpi_distribute, run, reduce once; returns the reduced :class:`Statistics` (one label,
+        ``"rdn0"``, of dimension ``2 d``)."""
+        comm = self.comm
+        size, rank = comm.Get_size(), comm.Get_rank()
+        _, tasks = _mpi.mpi_distribute(nsims, size, allow_empty=True)
+        self.run_local(tasks[rank])
+        self.acc.allreduce()
+        return self.acc
