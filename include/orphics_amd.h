@@ -43,7 +43,7 @@ typedef struct oa_plan oa_plan;
 const char* oa_last_error(void);
 /* ABI version = 100 x the build round that last changed a signature in this header; bindings must refuse a library
  * that reports less than the version they were written against (OA_ABI_VERSION) */
-#define OA_ABI_VERSION 411
+#define OA_ABI_VERSION 412
 int oa_version(void);
 /* number of HIP devices visible; <0 on error (no compute) */
 int oa_device_count(void);
@@ -167,6 +167,10 @@ int oa_qe_cols_div(oa_plan* p, const void* px_rows, const void* py_rows, const v
  *  oa_mc_run_rdn0      : the realisation-dependent N0 shard of ONE data map: the data's three leg planes are cached by the
  *                        set-up entry, then per realisation two draws s, s' -> A = QE(d, s) + QE(s, d), B = QE(s, s') + QE(s', s)
  *                        -> x = [p(A) - p(B) / 2, p(B) / 2] -> moments of the 2 d-vector (at their declarations below).
+ *  oa_rdn0_set_data_mv,
+ *  oa_mc_run_rdn0_mv   : the same for an estimator SET (TT, TE, EE, EB, TB ...), its cross-spectra and its MV combination on
+ *                        power-of-two plans: the data triple's distinct leg planes are cached, then per realisation two T, E, B
+ *                        draws -> the 2 nest planes A_e, B_e -> one tail over all spectra (at their declarations below).
  *  BINDING: the plan keeps the POINTERS handed to oa_plan_set_filters / oa_plan_set_bins and may keep derived copies of what they
  *  point to (tile-major Fnorm / ids of the fused divergence launch; the (FG, FH) values of the R-split column stage in thread order).  Every call of either entry invalidates those copies -- also
  *  when the addresses are the ones bound before -- so a caller that changes the contents of a bound plane calls the entry again. */
@@ -426,6 +430,44 @@ int oa_mc_run_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const
                  const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights, long mv_wstride, int nspec, const int* host_a,
                  const int* host_b, const int32_t* ids_hc, int nids, const int64_t* counts, double norm, int leg_cols, int kappa_cols,
                  int leg_rows, int kappa_rows, int mrow, int64_t* n, double* S, double* C, void* stream);
+/* REALISATION-DEPENDENT N0 of an estimator SET and its MV combination (power-of-two plans): the RDN0 above for the estimators, crosses and MV
+ * field of oa_mc_run_mv.  The estimator set is oa_mc_run_mv's (nest <= 6, pieces flattened in estimator order: sign, FG, FH, swap; sources by
+ * index 0 T, 1 E, 2 B; pure normalisations host_Fnorm; optional MV weights) and so are the spectrum list (field nest = MV), the bins, the
+ * counts and the bands.  For field triples X = (X_T, X_E, X_B) and Y, QE_e(X; Y) is estimator e with kX = X[xsrc_e], kY = Y[ysrc_e].  With
+ * d the data triple and, for realisation i, s = the T, E, B draw of oa_grf_mix_band(seed = base_seed, stream_id0 = 6 i) and s' the draw of
+ * stream_id0 = 6 i + 3 (oa_mc_run_mv's draws of its realisations 2 i and 2 i + 1):
+ *     A_e = QE_e(d; s) + QE_e(s; d),    B_e = QE_e(s; s') + QE_e(s'; s),    A_MV = sum_e w_e A_e,    B_MV = sum_e w_e B_e,
+ *     p(Z_a, Z_b)_j = sum over the modes of bin j + 1 of m Re(Z_a conj Z_b) norm / counts[j + 1]   (m = Hermitian multiplicity),
+ *     x_i = [ p(A_a, A_b) - p(B_a, B_b) / 2 for every spectrum (a, b) in list order ] ("rdn0") ++ [ p(B_a, B_b) / 2 likewise ] ("mcn0"),
+ *     n += 1,  S += x_i,  C += x_i x_i^T          (D = 2 nspec d, d = nids - 2; S: D doubles, C: D x D).
+ * The debiased spectrum of the data is p(QE_a(d; d), QE_b(d; d)) - mean(rdn0_ab).  No window.
+ *  oa_rdn0_set_data_mv : set-up entry (may allocate and synchronise).  host_kD: the three hc transforms of the data (a plane no estimator
+ *                        reads may be NULL).  The data's DISTINCT leg planes -- one gradient pair per distinct (source, FG), one H plane
+ *                        per distinct (source, FH): oa_qe_mv's sharing rule -- are transformed once (one batched leg launch where that
+ *                        applies) on the column grid of the bands and kept in a plan-owned buffer; oa_plan_release_pools frees it.
+ *  oa_mc_run_rdn0_mv   : the shard [sim_lo, sim_hi), one realisation at a time.  Stream-ordered, no host work on data, no allocation after
+ *                        the first call (oa_plan_release_pools frees everything both entries took).  Per realisation: 2 band draws into entry-owned planes; the leg planes of s and of s' (one batched
+ *                        leg launch per triple [+ 1 inverse pass 2 over both]); the row stage of the 2 nest chains A_e, B_e (2 npieces_e
+ *                        pieces each over the leg planes of d, s, s': ONE chain launch where the row-stage table holds them, else two;
+ *                        where the chain kernel does not serve the geometry, or with OA_OPT_MV_CHAIN = 0, one launch per piece, the second
+ *                        and later pieces accumulating); the divergence of the nest A planes and of the nest B planes (one batched launch
+ *                        each where oa_qe_mv's one-launch divergence is engaged, else one per plane) into the entry's 2 nest kappa planes;
+ *                        and the 3 launches of the tail (partial sums per fixed group of band rows with A_MV, B_MV formed in registers, the
+ *                        fold to x_i, the moment update).  Every sum has an order fixed by the band, the bins and the spectrum list: the
+ *                        moments are the same bit for bit on every run and however a range is cut into calls.
+ * Refused by name before anything is launched, n, S, C untouched: a plan that is not power-of-two (band-grid and chirp-z sides: the
+ * message names mc.RDN0MonteCarloPol and one_call=False); no data set; stale data legs (another filter-plane list, other bands or mrow, a
+ * column grid changed by oa_plan_set_col_grid since oa_rdn0_set_data_mv); nest outside 1..6; a source index outside [0, 3); NULL planes;
+ * a (nspec, nids) beyond the tail's tables: it holds nspec <= 28, 3 <= nids <= 1024, nspec nids <= 4096 -- every (nspec, nids >= 3)
+ * oa_bin_power_multi accepts. */
+int oa_rdn0_set_data_mv(oa_plan* p, const void* const* host_kD, int nest, const int* host_npieces, const void* const* host_FG,
+                        const void* const* host_FH, const int* host_swap, const int* host_xsrc, const int* host_ysrc, int leg_cols, int kappa_cols,
+                        int leg_rows, int kappa_rows, int mrow, void* stream);
+int oa_mc_run_rdn0_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest, const int* host_npieces,
+                      const double* host_signs, const void* const* host_FG, const void* const* host_FH, const int* host_swap, const int* host_xsrc,
+                      const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights, long mv_wstride, int nspec, const int* host_a,
+                      const int* host_b, const int32_t* ids_hc, int nids, const int64_t* counts, double norm, int leg_cols, int kappa_cols,
+                      int leg_rows, int kappa_rows, int mrow, int64_t* n, double* S, double* C, void* stream);
 /* oa_mc_run_mv_windowed: oa_mc_run_mv with a real-space window on the T, Q, U maps of every realisation and with the mean-field stacks of the
  * estimator set.  The arguments are oa_mc_run_mv's, plus
  *   window_real     ny x nx reals of the plan's dtype (the apodisation every map is multiplied by before its transform), or NULL;

@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("ORPHICS_AMD_LIB", os.path.join(_HERE, "liborphics_amd
 
 OA_F32 = 0
 OA_F64 = 1
-ABI_VERSION = 411    # include/orphics_amd.h OA_ABI_VERSION: the signatures below are those of this version
+ABI_VERSION = 412   # include/orphics_amd.h OA_ABI_VERSION: the signatures below are those of this version
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
@@ -72,6 +72,11 @@ SIGNATURES = {
     # realisation-dependent N0 of the TT estimator: the data's cached leg planes (set-up entry), then the shard; S: 2 d, C: (2 d)^2
     "oa_rdn0_set_data": (c_int, [c_void_p, c_void_p, c_void_p]),
     "oa_mc_run_rdn0": (c_int, [c_void_p, c_u64, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # ... of an estimator set and its MV combination (power-of-two plans): host_kD[3] + the set's description and bands, then oa_mc_run_mv's
+    # arguments; S: 2 nspec d, C: (2 nspec d)^2
+    "oa_rdn0_set_data_mv": (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
+    "oa_mc_run_rdn0_mv": (c_int, [c_void_p, c_u64, c_long, c_long, c_void_p, c_int] + [c_void_p] * 9 + [c_long, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                  c_void_p, c_double] + [c_int] * 5 + [c_void_p] * 4),
     "oa_mc_run_mv": (c_int, [c_void_p, c_u64, c_long, c_long, c_void_p, c_int] + [c_void_p] * 9 + [c_long, c_int, c_void_p, c_void_p, c_void_p, c_int,
                              c_void_p, c_double] + [c_int] * 5 + [c_void_p] * 4),
     # oa_mc_run_mv's arguments + (window_real, rot_c, rot_s) behind mrow and host_meanfield in front of the stream; power-of-two plans only

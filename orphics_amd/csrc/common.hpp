@@ -135,6 +135,12 @@ size_t rdn0_part_bytes(int ny, int rb, int nids, int B);
 int rdn0_tail_check(const char* who, int nids, int B);
 int rdn0_tail(int dtype, const void* k, long kstride, int B, int ny, long kp, int nxh, const int32_t* ids, int nids, double pnorm, int w, int rb,
               const int64_t* mcounts, double* part, int64_t* n, double* S, double* C, hipStream_t st);
+// oa_mc_run_rdn0_mv's tail over the 2 nest kappa_hat planes of one realisation of an estimator set (elementwise.hip, rdn0_mv.hpp): three launches
+size_t rdn0mv_scratch_bytes(int ny, int rb, int nspec, int nids);
+int rdn0mv_tail_check(const char* who, int nest, bool have_w, int nspec, const int* host_a, const int* host_b, int nids);
+int rdn0mv_tail(int dtype, const void* k, long kstride, const void* wt, long wstride, int nest, int nspec, const int* host_a, const int* host_b, int ny,
+                long kp, int nxh, const int32_t* ids, int nids, double pnorm, int w, int rb, const int64_t* mcounts, void* scratch, int64_t* n, double* S,
+                double* C, hipStream_t st);
 // the unscaled inverse column transform of nplanes hc planes pstride complex elements apart, in place, ONE launch (grid y = plane)
 int mixed_cols_inverse_batch(oa_plan* p, int nplanes, void* hc, long pstride, hipStream_t st);
 // my > 0: COLUMN GRID -- legs, row stage and divergence run on my < ny rows (plan_ensure_col_grid(p, my) first)

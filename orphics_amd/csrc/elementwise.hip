@@ -5,6 +5,7 @@
 #include "split_power.hpp"
 #include "mc_pol.hpp"
 #include "rdn0.hpp"
+#include "rdn0_mv.hpp"
 
 namespace oa {
 
@@ -543,6 +544,74 @@ int rdn0_tail(int dtype, const void* k, long kstride, int B, int ny, long kp, in
     OA_LAUNCH_CHECK();
     Rdn0FoldArgs f{part, mcounts, B, G, nids, n, S, C};
     hipLaunchKernelGGL(rdn0_fold_kernel, dim3(1), dim3(RDN0_FOLD_NT), rdn0_fold_lds(nids, B), st, f);
+    OA_LAUNCH_CHECK();
+    return 0;
+}
+// oa_mc_run_rdn0_mv's tail (rdn0_mv.hpp): partial sums per row group, the fold to x_i, the moment update
+template <typename T>
+__global__ __launch_bounds__(RDN0MV_NT) void rdn0mv_part_kernel(Rdn0MvPartArgs<T> a) {
+    Rdn0Ctx c{rdn0_smem};
+    rdn0mv_part_body<T>(c, a);
+}
+__global__ __launch_bounds__(RDN0MV_FOLD_NT) void rdn0mv_fold_kernel(Rdn0MvFoldArgs a) {
+    Rdn0Ctx c{rdn0_smem};
+    rdn0mv_fold_body(c, a);
+}
+__global__ __launch_bounds__(RDN0MV_FOLD_NT) void rdn0mv_moments_kernel(Rdn0MvMomArgs a) {
+    Rdn0Ctx c{rdn0_smem};
+    rdn0mv_moments_body(c, a);
+}
+static size_t rdn0mv_x_bytes(int nspec, int nids) { return ((size_t)2 * nspec * (nids - 2) * sizeof(double) + 255) & ~(size_t)255; }
+// scratch of rdn0mv_tail: x_i (2 nspec (nids - 2) doubles, padded to 256 bytes) | the G partial tables
+size_t rdn0mv_scratch_bytes(int ny, int rb, int nspec, int nids) {
+    const int nrows = (rb > 0 && 2L * rb - 1 < ny) ? 2 * rb - 1 : ny;
+    return rdn0mv_x_bytes(nspec, nids) + (size_t)rdn0mv_groups(nrows) * 2 * nspec * nids * sizeof(double);
+}
+// the checks of rdn0mv_tail that do not depend on the planes: 0, or the failure already reported (for an entry to refuse before its first launch)
+int rdn0mv_tail_check(const char* who, int nest, bool have_w, int nspec, const int* host_a, const int* host_b, int nids) {
+    const std::string w(who);
+    OA_REQUIRE(nest >= 1 && nest <= STACK_MULTI_MAX, w + ": 1 <= nest <= 6 estimators");
+    OA_REQUIRE(nspec >= 1 && nspec <= RDN0MV_SPEC_MAX && nids >= 3 && nids <= RDN0MV_IDS_MAX && (long)nspec * nids <= RDN0MV_TABLE_MAX,
+               w + ": the tables of the combine / bin / moments tail hold 1 <= nspec <= 28 spectra and 3 <= nids <= 1024 bin ids with nspec * nids <= 4096 "
+               "(got nspec = " + std::to_string(nspec) + ", nids = " + std::to_string(nids) + "); run the host loop (mc.RDN0MonteCarloPol with one_call=False)");
+    OA_REQUIRE(host_a && host_b, w + ": NULL spectrum list");
+    for (int s = 0; s < nspec; ++s) {
+        OA_REQUIRE(host_a[s] >= 0 && host_a[s] <= nest && host_b[s] >= 0 && host_b[s] <= nest, w + ": field index outside [0, nest]");
+        OA_REQUIRE(have_w || (host_a[s] < nest && host_b[s] < nest), w + ": field index nest (the MV combination) needs weight planes");
+    }
+    return 0;
+}
+// k: 2 nest planes (ny, kp) kstride complex elements apart; wt: nest real planes wstride apart or nullptr; ids: (ny, kp) int32;
+// scratch: rdn0mv_scratch_bytes(ny, rb, nspec, nids); n, S, C as in rdn0_mv.hpp
+int rdn0mv_tail(int dtype, const void* k, long kstride, const void* wt, long wstride, int nest, int nspec, const int* host_a, const int* host_b, int ny,
+                long kp, int nxh, const int32_t* ids, int nids, double pnorm, int w, int rb, const int64_t* mcounts, void* scratch, int64_t* n, double* S,
+                double* C, hipStream_t st) {
+    OA_REQUIRE(k && ids && mcounts && scratch && n && S && C && ny > 0 && kp > 0 && nxh >= 0 && nxh < kp, "rdn0 mv tail: bad argument");
+    if (int rc = rdn0mv_tail_check("rdn0 mv tail", nest, wt != nullptr, nspec, host_a, host_b, nids)) return rc;
+    if (w <= 0 || w > kp) w = (int)kp;
+    if (!(rb > 0 && 2L * rb - 1 < ny)) rb = 0;
+    const int nrows = rb ? 2 * rb - 1 : ny;
+    const int R = rdn0mv_rows_per_group(nrows), G = rdn0mv_groups(nrows);
+    double* const x = (double*)scratch;
+    double* const part = (double*)((char*)scratch + rdn0mv_x_bytes(nspec, nids));
+    Rdn0MvSpec spec{};
+    spec.nspec = nspec;
+    for (int s = 0; s < nspec; ++s) { spec.a[s] = (unsigned char)host_a[s]; spec.b[s] = (unsigned char)host_b[s]; }
+    if (dtype == OA_F32) {
+        Rdn0MvPartArgs<float> a{(const cx<float>*)k, kstride, (const float*)wt, wstride, kp, ny, ids, kp, nest, nids, w, rb, nxh, pnorm, spec, part, nrows, R};
+        hipLaunchKernelGGL(rdn0mv_part_kernel<float>, dim3(G), dim3(RDN0MV_NT), rdn0mv_part_lds(), st, a);
+    } else {
+        Rdn0MvPartArgs<double> a{(const cx<double>*)k, kstride, (const double*)wt, wstride, kp, ny, ids, kp, nest, nids, w, rb, nxh, pnorm, spec, part, nrows, R};
+        hipLaunchKernelGGL(rdn0mv_part_kernel<double>, dim3(G), dim3(RDN0MV_NT), rdn0mv_part_lds(), st, a);
+    }
+    OA_LAUNCH_CHECK();
+    Rdn0MvFoldArgs f{part, mcounts, G, nspec, nids, x};
+    hipLaunchKernelGGL(rdn0mv_fold_kernel, dim3((nspec * nids + RDN0MV_FOLD_NT - 1) / RDN0MV_FOLD_NT), dim3(RDN0MV_FOLD_NT), 0, st, f);
+    OA_LAUNCH_CHECK();
+    const int D = 2 * nspec * (nids - 2);
+    Rdn0MvMomArgs m{x, D, n, S, C};
+    const long blocks = ((long)D * D + RDN0MV_FOLD_NT - 1) / RDN0MV_FOLD_NT;
+    hipLaunchKernelGGL(rdn0mv_moments_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(RDN0MV_FOLD_NT), 0, st, m);
     OA_LAUNCH_CHECK();
     return 0;
 }

@@ -73,6 +73,12 @@ struct Pipeline {
     DevBuf rdn0_pool;                 // 2 MC_BATCH_MAX drawn hc planes | 2 MC_BATCH_MAX kappa planes | the partial sums of the tail (rdn0.hpp)
     unsigned long rdn0_gen = 0;       // bind_gen the data legs were made under (0: no data set) ...
     int rdn0_my = 0;                  // ... and the column grid
+    // oa_rdn0_set_data_mv / oa_mc_run_rdn0_mv (power-of-two plans; the estimator set comes with every call, so the key is its description)
+    DevBuf rdn0mv_legs;               // the data triple's distinct leg planes in Rdn0MvSlots' numbering
+    DevBuf rdn0mv_pool;               // the 6 drawn hc planes (T, E, B of s, then of s') | the 2 nest kappa planes (A_e, then B_e) | the tail's scratch
+    std::vector<const void*> rdn0mv_key;   // Rdn0MvSlots::key() the data legs were made for (empty: no data set) ...
+    int rdn0mv_band[5] = {0, 0, 0, 0, 0};  // ... their leg_cols, kappa_cols, leg_rows, kappa_rows, mrow ...
+    int rdn0mv_my = 0;                     // ... and their column grid
     // tile-major copies of Fnorm and of the bin ids on the coarse grid of the fused divergence + binning launch (what they were
     // made from: rebuilt when the filters / bins / column grid change)
     // (one set per grid a plan can carry: [0] the column grid `my`, [1] the from-map grid `my3`)
@@ -171,7 +177,7 @@ void pipeline_release(oa_plan* p) {
     if (q->ticket) (void)hipFree(q->ticket);
     if (q->mv_ftab) (void)hipFree(q->mv_ftab);
     if (q->mv_rtab) (void)hipFree(q->mv_rtab);
-    for (DevBuf* b : {&q->split_legs, &q->mc_src, &q->lens_pool, &q->mvmc, &q->mvwin, &q->rdn0_legs, &q->rdn0_pool, &q->dt[0].fn_t, &q->dt[0].ids_t,
+    for (DevBuf* b : {&q->split_legs, &q->mc_src, &q->lens_pool, &q->mvmc, &q->mvwin, &q->rdn0_legs, &q->rdn0_pool, &q->rdn0mv_legs, &q->rdn0mv_pool, &q->dt[0].fn_t, &q->dt[0].ids_t,
                       &q->dt[1].fn_t, &q->dt[1].ids_t, &q->fb_t}) b->release();
     if (q->band) (void)oa_plan_destroy(q->band);
     q->release_band();
@@ -638,9 +644,10 @@ int oa_plan_release_pools(oa_plan* p) {
     // band grid: the split entries' inner source planes and kappa block (bsplit), the draw and row planes of oa_mc_run_windowed (bwin), the
     // map-side scratch of oa_qe_mv_maps (mrows) and the N-grid planes of oa_mc_run_mv_windowed (mwin): all retaken by the next call
     for (DevBuf* b : {&q->lens_pool, &q->split_legs, &q->mc_src, &q->mvmc, &q->mvwin, &q->bsplit, &q->bwin, &q->pb.mrows, &q->pb.mwin, &q->rdn0_legs,
-                      &q->rdn0_pool}) b->release();
+                      &q->rdn0_pool, &q->rdn0mv_legs, &q->rdn0mv_pool}) b->release();
     q->bs_cap = 0;
     q->rdn0_gen = 0;                 // the data legs of oa_rdn0_set_data are gone: oa_mc_run_rdn0 asks for them again
+    q->rdn0mv_key.clear();           // ... and those of oa_rdn0_set_data_mv
     // ... the pool the split entries' inner call grew (regrown on demand), and the inner planes of oa_rdn0_set_data / oa_mc_run_rdn0
     if (q->band && q->band->pipe)
         for (DevBuf* b : {&((Pipeline*)q->band->pipe)->split_legs, &((Pipeline*)q->band->pipe)->rdn0_legs, &((Pipeline*)q->band->pipe)->rdn0_pool}) b->release();
@@ -1955,6 +1962,200 @@ static int mc_mv_shard(const std::string& who, bool how_all, oa_plan* p, const M
     }
     return mc_mv_loop(L, a);
 }
+
+/* ---- oa_rdn0_set_data_mv / oa_mc_run_rdn0_mv: RDN0 of an estimator set (power-of-two plans) ----------------------------------------------
+ * SLOTS.  The distinct leg planes of a field triple X = (X_T, X_E, X_B) under an estimator set: one gradient pair per distinct
+ * (source index, FG), one H plane per distinct (source index, FH) -- qe_mv_pow2's sharing rule with source INDICES in the place of source
+ * pointers, so that the data triple d and the draws s, s' number their planes alike.  In a pool of compact planes gradient pair g sits at
+ * planes 2 g, 2 g + 1 and H plane h at 2 ng + h.  Piece idx of estimator e in QE_e(X; Y) reads its gradient pair from (swap ? Y : X) at
+ * gslot[idx] and its H plane from (swap ? X : Y) at hslot[idx].  BOTH entries number through rdn0mv_slots. */
+constexpr size_t MV_RTAB_BYTES = 64 * 64 + 1024;    // the device table mv_rtab of the table / chain row stage
+struct Rdn0MvSlots {
+    std::vector<std::pair<int, const void*>> grad, hpl;     // (source index, filter plane)
+    std::vector<int> gslot, hslot;                          // per piece
+    int total = 0;
+    int ng() const { return (int)grad.size(); }
+    int nh() const { return (int)hpl.size(); }
+    int nplanes() const { return 2 * ng() + nh(); }
+    std::vector<const void*> key() const {                  // what the data legs depend on besides the bands
+        std::vector<const void*> k;
+        for (const auto& g : grad) { k.push_back((const void*)(uintptr_t)(g.first + 1)); k.push_back(g.second); }
+        k.push_back(nullptr);
+        for (const auto& h : hpl) { k.push_back((const void*)(uintptr_t)(h.first + 1)); k.push_back(h.second); }
+        return k;
+    }
+};
+static Rdn0MvSlots rdn0mv_slots(int nest, const int* npieces, const void* const* FG, const void* const* FH, const int* swap, const int* xsrc,
+                                const int* ysrc) {
+    Rdn0MvSlots S;
+    auto slot_of = [](std::vector<std::pair<int, const void*>>& v, int src, const void* f) {
+        for (size_t i = 0; i < v.size(); ++i) if (v[i].first == src && v[i].second == f) return (int)i;
+        v.emplace_back(src, f);
+        return (int)v.size() - 1;
+    };
+    for (int e = 0; e < nest; ++e)
+        for (int i = 0; i < npieces[e]; ++i, ++S.total) {
+            const bool sw = swap && swap[S.total];
+            S.gslot.push_back(slot_of(S.grad, sw ? ysrc[e] : xsrc[e], FG[S.total]));
+            S.hslot.push_back(slot_of(S.hpl, sw ? xsrc[e] : ysrc[e], FH[S.total]));
+        }
+    return S;
+}
+// the checks of the estimator-set description both entries make, under the caller's name
+static int rdn0mv_set_check(const std::string& who, const oa_plan* p, int nest, const int* npieces, const void* const* FG, const void* const* FH,
+                            const int* xsrc, const int* ysrc, int wl, int wk, int rl, int rk) {
+    OA_REQUIRE(nest >= 1 && nest <= 6, who + ": 1 <= nest <= 6 estimators");
+    const int hw = p->nx / 2 + 1;
+    OA_REQUIRE(wl >= 0 && wk >= 0 && rl >= 0 && rk >= 0 && wl <= hw && wk <= hw && 2L * rl - 1 <= p->ny && 2L * rk - 1 <= p->ny,
+               who + ": leg / kappa band beyond the hc plane");
+    int total = 0;
+    for (int e = 0; e < nest; ++e) {
+        OA_REQUIRE(npieces[e] >= 1, who + ": bad estimator entry");
+        OA_REQUIRE(xsrc[e] >= 0 && xsrc[e] < 3 && ysrc[e] >= 0 && ysrc[e] < 3, who + ": source index outside [0, 3) (0 T, 1 E, 2 B)");
+        total += npieces[e];
+    }
+    for (int i = 0; i < total; ++i) OA_REQUIRE(FG[i] && FH[i], who + ": NULL filter plane");
+    return 0;
+}
+/* The leg planes of ONE field triple into `pool` (nplanes compact planes lb bytes apart): qe_mv_pow2's leg stage -- ONE inverse pass-1
+ * launch over all fields where it applies (at most 32 fields, sources a whole number of complex elements apart; OA_OPT_MV_BATCH), else one
+ * launch per field.  *done = 1: the planes need no inverse pass 2. */
+static int rdn0mv_legs_of(oa_plan* p, Pipeline* q, const Rdn0MvSlots& S, const void* const src[3], char* pool, size_t lb, int wl, int rl, long pl,
+                          int my, hipStream_t st, int* done) {
+    const size_t es = elem_bytes(p);
+    const int ng = S.ng(), nh = S.nh();
+    *done = 0;
+    std::vector<const void*> srcs;
+    unsigned long long srcsel = 0;
+    bool batch = ng + nh <= 32 && q->opt_mv_batch;
+    for (int f = 0; f < ng + nh; ++f) {
+        const void* sp = src[f < ng ? S.grad[f].first : S.hpl[f - ng].first];
+        size_t k = 0;
+        while (k < srcs.size() && srcs[k] != sp) ++k;
+        if (k == srcs.size()) srcs.push_back(sp);
+        if (f < 32) srcsel |= (unsigned long long)k << (2 * f);
+    }
+    for (size_t k = 1; k < srcs.size(); ++k) batch = batch && (((const char*)srcs[k] - (const char*)srcs[0]) % (long)es == 0);
+    if (batch) {
+        std::vector<const void*> key;
+        for (int g = 0; g < ng; ++g) key.push_back(S.grad[g].second);
+        for (int h = 0; h < nh; ++h) key.push_back(S.hpl[h].second);
+        if (key != q->mv_fkey) {       // (pageable source: staged before the call returns; ordered on this stream)
+            OA_HIP(hipMemcpyAsync(q->mv_ftab, key.data(), key.size() * sizeof(void*), hipMemcpyHostToDevice, st));
+            q->mv_fkey = key;
+        }
+        const long off1 = srcs.size() > 1 ? (long)(((const char*)srcs[1] - (const char*)srcs[0]) / (long)es) : 0;
+        const long off2 = srcs.size() > 2 ? (long)(((const char*)srcs[2] - (const char*)srcs[0]) / (long)es) : 0;
+        return qe_legs_batch_w(p, srcs[0], off1, off2, srcsel, (const void* const*)q->mv_ftab, ng, nh, pool, (long)(lb / es), wl, rl, pl, st, my, 2, done);
+    }
+    for (int g = 0; g < ng; ++g)
+        if (int rc = qe_legs_subset_w(p, src[S.grad[g].first], S.grad[g].second, pool + 2 * (size_t)g * lb, pool + (2 * (size_t)g + 1) * lb, 2, wl, rl, pl,
+                                      st, my)) return rc;
+    for (int h = 0; h < nh; ++h)
+        if (int rc = qe_legs_subset_w(p, src[S.hpl[h].first], S.hpl[h].second, pool + (2 * (size_t)ng + h) * lb, nullptr, 1, wl, rl, pl, st, my)) return rc;
+    return 0;
+}
+// where a shard lives: leg planes of s and s', product and pass-1 planes of the 2 nest chains in the plan's pool of compact planes
+// (split_legs); draws, kappa block and tail scratch in rdn0mv_pool
+struct Rdn0MvPlanes {
+    size_t lb, lbk, pb;
+    char *legs[3];                     // the leg pools of d, s, s'
+    char *prod, *tmp, *draw, *kappa, *scratch;
+};
+static size_t rdn0mv_split_bytes(const oa_plan* p, const Rdn0MvSlots& S, int nest, int wl, int wk) {
+    const size_t es = elem_bytes(p);
+    return 2 * (size_t)S.nplanes() * work_pitch(p, wl) * p->ny * es + 8 * (size_t)nest * work_pitch(p, wk) * p->ny * es;
+}
+static Rdn0MvPlanes rdn0mv_planes(const oa_plan* p, const Pipeline* q, const Rdn0MvSlots& S, int nest, int wl, int wk) {
+    Rdn0MvPlanes P;
+    const size_t es = elem_bytes(p);
+    P.lb = (size_t)work_pitch(p, wl) * p->ny * es; P.lbk = (size_t)work_pitch(p, wk) * p->ny * es; P.pb = plane_bytes(p);
+    P.legs[0] = q->rdn0mv_legs.at(); P.legs[1] = q->split_legs.at(); P.legs[2] = P.legs[1] + (size_t)S.nplanes() * P.lb;
+    P.prod = P.legs[2] + (size_t)S.nplanes() * P.lb; P.tmp = P.prod + 4 * (size_t)nest * P.lbk;
+    P.draw = q->rdn0mv_pool.at(); P.kappa = P.draw + 6 * P.pb; P.scratch = P.kappa + 2 * (size_t)nest * P.pb;
+    return P;
+}
+/* One realisation whose draws s, s' sit on the six planes of P.draw: leg planes of s and of s' (one batched launch per triple [+ ONE
+ * inverse pass 2 over both]), the row stage of the 2 nest chains -- A_e = pieces of QE_e(d; s), then of QE_e(s; d); B_e = pieces of
+ * QE_e(s; s'), then of QE_e(s'; s); chain e and nest + e --, their divergences into the kappa block, the tail. */
+static int rdn0mv_one(oa_plan* p, Pipeline* q, const McMvArgs& a, const Rdn0MvSlots& S, const Rdn0MvPlanes& P, int my) {
+    hipStream_t st = a.st;
+    const size_t es = elem_bytes(p), lb = P.lb, lbk = P.lbk;
+    const long pl = work_pitch(p, a.wl), pk = work_pitch(p, a.wk);
+    const int nest = a.nest, np = S.nplanes(), ng = S.ng();
+    int rc, done = 0;
+    for (int z = 0; z < 2; ++z) {
+        const void* const src[3] = {P.draw + 3 * (size_t)z * P.pb, P.draw + (3 * (size_t)z + 1) * P.pb, P.draw + (3 * (size_t)z + 2) * P.pb};
+        if ((rc = rdn0mv_legs_of(p, q, S, src, P.legs[1 + z], lb, a.wl, a.rl, pl, my, st, &done))) return rc;
+    }
+    if (!done && (rc = qe_legs_pass2_w(p, P.legs[1], 2 * np, (long)(lb / es), a.wl, pl, st, my))) return rc;
+    const double s = 1.0 / ((double)p->ny * p->nx), sy = my ? (double)p->ny / my : 1.0;
+    // the chains' pieces: triples 0 = d, 1 = s, 2 = s'
+    std::vector<const void*> cgx, cgy, chh;
+    std::vector<void*> cpx, cpy;
+    std::vector<double> csc;
+    std::vector<int> first(2 * nest), cnt(2 * nest);
+    static const int pairs[2][2][2] = {{{0, 1}, {1, 0}}, {{1, 2}, {2, 1}}};       // [A | B][half][X, Y]
+    for (int set = 0; set < 2; ++set)
+        for (int e = 0, base = 0; e < nest; base += a.npieces[e], ++e) {
+            const int c = set * nest + e;
+            first[c] = (int)cgx.size(); cnt[c] = 2 * a.npieces[e];
+            for (int half = 0; half < 2; ++half)
+                for (int i = 0; i < a.npieces[e]; ++i) {
+                    const int idx = base + i, X = pairs[set][half][0], Y = pairs[set][half][1];
+                    const bool sw = a.swap && a.swap[idx];
+                    const char* const G = P.legs[sw ? Y : X] + 2 * (size_t)S.gslot[idx] * lb;
+                    cgx.push_back(G); cgy.push_back(G + lb);
+                    chh.push_back(P.legs[sw ? X : Y] + (2 * (size_t)ng + S.hslot[idx]) * lb);
+                    cpx.push_back(P.prod + 2 * (size_t)c * lbk); cpy.push_back(P.prod + (2 * (size_t)c + 1) * lbk);
+                    csc.push_back(a.signs[idx] * s * s * sy);
+                }
+        }
+    const int total = (int)cgx.size();                                            // 4 x the set's pieces
+    const size_t eb = qe_rows_table_entry_bytes(p);
+    auto fits = [&](int pieces, int chains) { return ((size_t)pieces * eb + 15) / 16 * 16 + 2 * (size_t)chains * sizeof(int) <= MV_RTAB_BYTES; };
+    bool chained = false;
+    if (q->opt_mv_chain && fits(total / 2, nest)) {
+        // ONE launch over the 2 nest chains where the table holds them, else the A chains and the B chains in a launch each
+        const int nl = fits(total, 2 * nest) ? 1 : 2, nc = 2 * nest / nl;
+        for (int l = 0; l < nl; ++l) {
+            const int c0 = l * nc, p0 = first[c0], npc = (l + 1 < nl ? first[c0 + nc] : total) - p0;
+            std::vector<int> fl(nc);
+            for (int c = 0; c < nc; ++c) fl[c] = first[c0 + c] - p0;
+            std::vector<unsigned long long> key;
+            for (int i = p0; i < p0 + npc; ++i) {
+                unsigned long long bits;
+                memcpy(&bits, &csc[i], sizeof bits);
+                key.insert(key.end(), {(unsigned long long)(uintptr_t)cgx[i], (unsigned long long)(uintptr_t)chh[i], (unsigned long long)(uintptr_t)cpx[i], bits});
+            }
+            for (int c = 0; c < nc; ++c) key.push_back((unsigned long long)cnt[c0 + c]);
+            key.insert(key.end(), {(unsigned long long)my, (unsigned long long)(unsigned)a.mrow, (unsigned long long)p->dtype, 0x4D02ull});
+            rc = qe_rows_chain_w(p, nc, npc, cgx.data() + p0, cgy.data() + p0, chh.data() + p0, cpx.data() + p0, cpy.data() + p0, csc.data() + p0, fl.data(),
+                                 cnt.data() + c0, q->mv_rtab, key != q->mv_rkey, a.wl, a.wk, a.mrow, pl, pk, st, my);
+            if (rc < 0) break;                         // (only at l = 0, before anything is launched: this geometry's row stage is another kernel)
+            if (rc) return rc;
+            q->mv_rkey = key;
+            chained = l + 1 == nl;
+        }
+    }
+    if (!chained)                                      // piece by piece; the second and later pieces of a chain accumulate
+        for (int c = 0; c < 2 * nest; ++c)
+            for (int i = first[c]; i < first[c] + cnt[c]; ++i)
+                if ((rc = qe_rows_w(p, cgx[i], cgy[i], chh[i], cpx[i], cpy[i], csc[i], i > first[c], a.wl, a.wk, a.mrow, pl, pk, st, my))) return rc;
+    long fn_moff = 0;
+    if (mv_div_batched(q, nest, a.Fn, es / 2, &fn_moff)) {
+        for (int set = 0; set < 2; ++set)
+            if ((rc = qe_cols_div_batch_w(p, P.prod + 2 * (size_t)set * nest * lbk, P.prod + (2 * (size_t)set * nest + 1) * lbk, a.Fn[0],
+                                          P.kappa + (size_t)set * nest * P.pb, P.tmp + 2 * (size_t)set * nest * lbk, nest, (long)(2 * lbk / es), fn_moff,
+                                          plane_elems(p), a.wk, a.rk, pk, st, my))) return rc;
+    } else {
+        for (int c = 0; c < 2 * nest; ++c)
+            if ((rc = qe_cols_div_w(p, P.prod + 2 * (size_t)c * lbk, P.prod + (2 * (size_t)c + 1) * lbk, a.Fn[c % nest], P.kappa + (size_t)c * P.pb, 0, a.wk,
+                                    a.rk, pk, st, my))) return rc;
+    }
+    return rdn0mv_tail(p->dtype, P.kappa, plane_elems(p), a.w, a.wstride, nest, a.nspec, a.a, a.b, p->ny, p->kp, p->nx / 2, a.ids, a.nids, a.norm, a.wk,
+                       a.rk, a.counts, P.scratch, a.n, a.S, a.C, st);
+}
 }  // namespace oa
 
 extern "C" {
@@ -2122,6 +2323,89 @@ int oa_mc_run_mv_windowed(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_
     if (host_meanfield)
         for (int e = 0; e < nest + (mv_weights ? 1 : 0); ++e) OA_REQUIRE(host_meanfield[e], "oa_mc_run_mv_windowed: NULL mean-field stack plane");
     return mc_mv_shard("oa_mc_run_mv_windowed", true, p, a);
+}
+
+/* oa_rdn0_set_data_mv (include/orphics_amd.h): the data triple's distinct leg planes (rdn0mv_slots) on the column grid of the set's bands,
+ * transformed once and kept for oa_mc_run_rdn0_mv.  Set-up entry: may allocate and synchronise. */
+static const char* const RDN0MV_HOW = "; run the host loop of the existing entries (mc.RDN0MonteCarloPol with one_call=False)";
+int oa_rdn0_set_data_mv(oa_plan* p, const void* const* host_kD, int nest, const int* host_npieces, const void* const* host_FG,
+                        const void* const* host_FH, const int* host_swap, const int* host_xsrc, const int* host_ysrc, int leg_cols, int kappa_cols,
+                        int leg_rows, int kappa_rows, int mrow, void* stream) {
+    const std::string who = "oa_rdn0_set_data_mv";
+    OA_REQUIRE(p && host_kD && host_npieces && host_FG && host_FH && host_xsrc && host_ysrc, who + ": NULL argument");
+    OA_REQUIRE(p->pow2, who + ": the one-call RDN0 of an estimator set runs on power-of-two map sides only (not on the band grid of sides 2^a 3^b 5^c "
+               "yet, nor on chirp-z sides)" + RDN0MV_HOW);
+    if (int rc = rdn0mv_set_check(who, p, nest, host_npieces, host_FG, host_FH, host_xsrc, host_ysrc, leg_cols, kappa_cols, leg_rows, kappa_rows)) return rc;
+    OA_REQUIRE(p->have_laxes, who + ": call oa_plan_set_laxes first");
+    Pipeline* q = pipe_of(p);
+    hipStream_t st = (hipStream_t)stream;
+    q->rdn0mv_key.clear();
+    const Rdn0MvSlots S = rdn0mv_slots(nest, host_npieces, host_FG, host_FH, host_swap, host_xsrc, host_ysrc);
+    for (const auto& g : S.grad) OA_REQUIRE(host_kD[g.first], who + ": NULL data plane of a source an estimator reads");
+    for (const auto& h : S.hpl) OA_REQUIRE(host_kD[h.first], who + ": NULL data plane of a source an estimator reads");
+    if (int rc = ensure_work(p, q)) return rc;
+    int my = 0;
+    if (int rc = resolve_my(p, mrow == 0 ? 0 : q->mcol, leg_rows, kappa_rows, &my)) return rc;
+    const long pl = work_pitch(p, leg_cols);
+    const size_t es = elem_bytes(p), lb = (size_t)pl * p->ny * es;
+    if (int rc = q->rdn0mv_legs.reserve((size_t)S.nplanes() * lb)) return rc;
+    // the shard's planes that do not depend on the bins, now: its first call then takes the tail's scratch only
+    if (int rc = ensure_pool(q, rdn0mv_split_bytes(p, S, nest, leg_cols, kappa_cols))) return rc;
+    if (!q->mv_ftab) OA_HIP(hipMalloc((void**)&q->mv_ftab, 32 * sizeof(void*)));
+    if (!q->mv_rtab) OA_HIP(hipMalloc(&q->mv_rtab, MV_RTAB_BYTES));
+    int done = 0;
+    if (int rc = rdn0mv_legs_of(p, q, S, host_kD, q->rdn0mv_legs.at(), lb, leg_cols, leg_rows, pl, my, st, &done)) return rc;
+    if (!done)
+        if (int rc = qe_legs_pass2_w(p, q->rdn0mv_legs.p, S.nplanes(), (long)(lb / es), leg_cols, pl, st, my)) return rc;
+    q->rdn0mv_key = S.key();
+    const int band[5] = {leg_cols, kappa_cols, leg_rows, kappa_rows, mrow};
+    std::copy(band, band + 5, q->rdn0mv_band);
+    q->rdn0mv_my = my;
+    return 0;
+}
+
+/* oa_mc_run_rdn0_mv (include/orphics_amd.h): the RDN0 shard [sim_lo, sim_hi) of an estimator set, one realisation at a time (as mc_mv_loop):
+ * the two band draws (streams 6 i .. 6 i + 2 and 6 i + 3 .. 6 i + 5) into entry-owned planes, then rdn0mv_one.  Everything is refused before
+ * the first launch. */
+int oa_mc_run_rdn0_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest, const int* host_npieces,
+                      const double* host_signs, const void* const* host_FG, const void* const* host_FH, const int* host_swap, const int* host_xsrc,
+                      const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights, long mv_wstride, int nspec, const int* host_a,
+                      const int* host_b, const int32_t* ids_hc, int nids, const int64_t* counts, double norm, int leg_cols, int kappa_cols,
+                      int leg_rows, int kappa_rows, int mrow, int64_t* n, double* S, double* C, void* stream) {
+    const std::string who = "oa_mc_run_rdn0_mv";
+    const McMvArgs a{base_seed, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, host_FG, host_FH, host_swap, host_xsrc, host_ysrc,
+                     host_Fnorm, mv_weights, mv_wstride, nspec, host_a, host_b, ids_hc, nids, counts, norm, leg_cols, kappa_cols, leg_rows,
+                     kappa_rows, mrow, n, S, C, (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr};
+    OA_REQUIRE(p && a.covsqrt && a.npieces && a.signs && a.FG && a.FH && a.xsrc && a.ysrc && a.Fn && a.ids && a.counts && a.n && a.S && a.C &&
+               a.sim_hi >= a.sim_lo, who + ": bad argument");
+    OA_REQUIRE(p->pow2, who + ": the one-call RDN0 of an estimator set runs on power-of-two map sides only (not on the band grid of sides 2^a 3^b 5^c "
+               "yet, nor on chirp-z sides)" + RDN0MV_HOW);
+    if (int rc = rdn0mv_set_check(who, p, nest, host_npieces, host_FG, host_FH, host_xsrc, host_ysrc, leg_cols, kappa_cols, leg_rows, kappa_rows)) return rc;
+    for (int e = 0; e < nest; ++e) OA_REQUIRE(host_Fnorm[e], who + ": NULL normalisation plane");
+    OA_REQUIRE(!mv_weights || mv_wstride >= (long)p->ny * p->kp, who + ": weight planes closer than one hc-real plane");
+    if (int rc = rdn0mv_tail_check(who.c_str(), nest, mv_weights != nullptr, nspec, host_a, host_b, nids)) return rc;
+    Pipeline* q = pipe_of(p);
+    OA_REQUIRE(!q->rdn0mv_key.empty() && q->rdn0mv_legs.p, who + ": no data set: call oa_rdn0_set_data_mv with this estimator set first" + RDN0MV_HOW);
+    const Rdn0MvSlots SL = rdn0mv_slots(nest, host_npieces, host_FG, host_FH, host_swap, host_xsrc, host_ysrc);
+    const int band[5] = {leg_cols, kappa_cols, leg_rows, kappa_rows, mrow};
+    int my = 0;
+    if (int rc = resolve_my(p, mrow == 0 ? 0 : q->mcol, leg_rows, kappa_rows, &my)) return rc;
+    OA_REQUIRE(SL.key() == q->rdn0mv_key && std::equal(band, band + 5, q->rdn0mv_band) && my == q->rdn0mv_my,
+               who + ": the data legs are stale -- the filter planes, the bands, the row grid or the column grid (oa_plan_set_col_grid) differ from those "
+               "of oa_rdn0_set_data_mv: call it again" + RDN0MV_HOW);
+    if (int rc = ensure_work(p, q)) return rc;     // (nothing to do after oa_rdn0_set_data_mv)
+    const size_t pb = plane_bytes(p);
+    if (int rc = q->rdn0mv_pool.reserve((6 + 2 * (size_t)nest) * pb + rdn0mv_scratch_bytes(p->ny, kappa_rows, nspec, nids), true)) return rc;
+    if (int rc = ensure_pool(q, rdn0mv_split_bytes(p, SL, nest, leg_cols, kappa_cols))) return rc;
+    const Rdn0MvPlanes P = rdn0mv_planes(p, q, SL, nest, leg_cols, kappa_cols);
+    for (long i = sim_lo; i < sim_hi; ++i) {
+        for (int z = 0; z < 2; ++z) {
+            void* const out[3] = {P.draw + 3 * (size_t)z * pb, P.draw + (3 * (size_t)z + 1) * pb, P.draw + (3 * (size_t)z + 2) * pb};
+            if (int rc = oa_grf_mix_band(p, base_seed, 6 * (uint64_t)i + 3 * z, 3, host_covsqrt, 1.0, out, leg_cols, leg_rows, a.st)) return rc;
+        }
+        if (int rc = rdn0mv_one(p, q, a, SL, P, my)) return rc;
+    }
+    return 0;
 }
 
 /* Monte-Carlo shard with a REAL-SPACE WINDOW (the reference's analysis flow multiplies every map by its apodisation taper

@@ -516,6 +516,7 @@ class Engine(object):
         check(self.lib.oa_plan_release_pools(self.plan))
         self._mc_owner = None             # the Monte-Carlo binding of a band grid went with its pool (mc.GaussianN0MonteCarloPol binds again)
         self._rdn0_owner = None           # ... and the data legs of oa_rdn0_set_data (mc.RDN0MonteCarlo sets them again)
+        self._rdn0mv_owner = None         # ... and of oa_rdn0_set_data_mv (mc.RDN0MonteCarloPol)
 
     def set_laxes(self, ly, lx):
         ly = np.ascontiguousarray(ly, dtype=np.float64)

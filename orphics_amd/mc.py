@@ -932,3 +932,213 @@ class RDN0MonteCarlo(object):
         self.run_local(tasks[rank])
         self.acc.allreduce()
         return self.acc
+
+
+class RDN0MonteCarloPol(object):
+    """Realisation-dependent N0 (RDN0) of an estimator set (TT, TE, EE, EB, TB), its cross-spectra and its minimum-variance (MV)
+    combination: the bias a real analysis subtracts from the kappa_hat spectra of ONE observed T, E, B (or T, Q, U) triple.
+
+    Definition.  For field triples ``X = (X_T, X_E, X_B)`` and ``Y``, ``QE_e(X; Y)`` is estimator ``e`` of the set with
+    ``kX = X[XY[0]]`` and ``kY = Y[XY[1]]`` -- ``Estimator.reconstruct_hc(XY, X[XY[0]], Y[XY[1]])``.  ``d`` is the data triple.
+    Realisation ``i`` draws ``s`` = ``Engine.grf_mix(stream_id0 = 6 i)`` (Philox streams ``6 i .. 6 i + 2`` for T, E, B) and ``s'`` =
+    ``Engine.grf_mix(stream_id0 = 6 i + 3)`` (streams ``6 i + 3 .. 6 i + 5``), key ``base_seed``, total powers ``total_power_half``:
+    the draws :class:`GaussianN0MonteCarloPol` makes for its realisations ``2 i`` and ``2 i + 1``.  Then, for every estimator ``e``::
+
+        A_e  = QE_e(d; s)  + QE_e(s; d)            B_e  = QE_e(s; s') + QE_e(s'; s)
+        A_MV = sum_e w_e A_e                       B_MV = sum_e w_e B_e                 (w = qest.mv_weights(estimators))
+        p(Z_a, Z_b)_j = bandpower j of Re(Z_a conj Z_b)      (weights, bins, mode counts of GaussianN0MonteCarloPol's bandpowers)
+        x_i = [ p(A_a, A_b) - p(B_a, B_b) / 2  for every spectrum (a, b) of ``spectra`` ]       # "rdn0": nspec * d numbers
+           ++ [ p(B_a, B_b) / 2                for every spectrum (a, b) of ``spectra`` ]       # "mcn0": nspec * d numbers
+
+    and ``x_i`` is one sample of the label ``"rdn0"`` (dimension ``2 * nspec * d``, ``d = len(bin_edges) - 1``): n += 1, S += x_i,
+    C += x_i x_i^T.  ``spectra`` is :func:`pol_spectrum_list` ``(estimators, cross, mv)``.  ``p(A_a, A_b)`` is the sum of the four
+    data-simulation terms of the six-term RDN0 of the cross-spectrum (a, b); the mcn0 half carries no data.  The debiased spectrum of
+    the data is ``p(QE_a(d; d), QE_b(d; d)) - mean(rdn0_ab)`` (:meth:`debiased`, :meth:`data_bandpowers`).  For
+    ``estimators=("TT",)`` this is :class:`RDN0MonteCarlo`'s definition with other Philox streams.
+
+    ``data``: three hc transforms (T, E, B) of the engine's layout, or -- ``qu=True`` -- three real ``(Ny, Nx)`` maps T, Q, U, converted
+    once with ``Engine.rfft`` and the per-mode rotation ``reconstruct_mv_from_maps(qu=True)`` uses (``iau``: the angle convention).
+    :meth:`set_data` binds another triple on the same plan.
+
+    ``one_call``: ``True`` runs the shard as ``oa_mc_run_rdn0_mv`` calls on power-of-two sides (the data's distinct leg planes are
+    transformed once by ``oa_rdn0_set_data_mv``; per realisation two band draws, the leg planes of s and s', the row stage of the
+    2 nest chains, their divergences and one combine / bin / moments tail; nothing leaves the device) and raises elsewhere: band-grid
+    sides (2^a 3^b 5^c) run the host loop for now, as do chirp-z sides.  ``one_call=False`` runs the host loop of existing entries on
+    any side with the same seeds and streams: ``Engine.grf_mix`` (twice), per estimator four ``reconstruct_hc`` calls (the second of
+    each pair with ``accumulate=True``), the weighted sums in torch, ``Engine.bin_power`` per spectrum for A and for B,
+    ``Statistics.add``.  ``one_call=None`` (default): the one call on power-of-two sides, the host loop elsewhere.
+
+    There is no window: simulations that carry the data's apodisation taper (and the mean field that comes with it) are not part of
+    this driver yet, exactly as for :class:`RDN0MonteCarlo`."""
+
+    def __init__(self, qest, data, total_power_half, bin_edges, estimators=("TT", "TE", "EE", "EB", "TB"), cross=True, mv=True, comm=None,
+                 base_seed=1234, one_call=None, qu=False, iau=False):
+        # covsqrt, pure normalisations in one allocation, weights, bands, ids, counts: GaussianN0MonteCarloPol's set-up, host-loop flavour
+        g = self._set = GaussianN0MonteCarloPol(qest, total_power_half, bin_edges, estimators=estimators, cross=cross, mv=mv, comm=comm,
+                                                base_seed=base_seed, one_call=False)
+        self.q, self.eng, self.comm, self.base_seed = qest, g.eng, g.comm, g.base_seed
+        e = self.eng
+        self.estimators, self.spectra, self.pairs, self.mv = g.estimators, g.spectra, g.pairs, g.mv
+        self.edges, self.ids, self.nids, self.d, self.norm = g.edges, g.ids, g.nids, g.d, g.norm
+        self.cs, self.w, self.counts = g.cs, g.w, g.counts
+        self.nspec = len(self.spectra)
+        self.D = 2 * self.nspec * self.d
+        if one_call and not e.pow2:
+            from ._lib import OrphicsAmdError
+            raise OrphicsAmdError("RDN0MonteCarloPol: the one call (oa_mc_run_rdn0_mv) runs on power-of-two map sides only; %d x %d: construct the "
+                                  "driver with one_call=False (host loop of the existing entries, any side) or leave one_call=None"
+                                  % (e.ny, e.nx))
+        self.one_call = bool(e.pow2) if one_call is None else bool(one_call)
+        self.qu, self.iau = bool(qu), bool(iau)
+        self.acc = Statistics(comm=self.comm if hasattr(self.comm, "dist") else None, device=e.device)
+        self._host = None
+        self.set_data(data)
+
+    def set_data(self, data):
+        """Bind another data triple (hc transforms T, E, B, or real maps T, Q, U with ``qu=True``) on the same plan, bins and
+        simulations; the accumulated samples are NOT reset."""
+        e = self.eng
+        data = list(data)
+        if len(data) != 3:
+            raise ValueError("data must be three planes: hc transforms (T, E, B), or real maps (T, Q, U) with qu=True")
+        if self.qu:
+            self.kd = list(self.q._maps_to_hc([tuple(e.to_real(m) for m in data)], True, self.iau)[0])
+        else:
+            self.kd = [e._chk(k.to(e.cdt).contiguous(), "hc") for k in data]
+        self._dtoken = object()           # the plan's cached data legs (oa_rdn0_set_data_mv) belong to this token
+        self._pd = None
+        return self
+
+    # ---- results (after run / allreduce) ------------------------------------------------------------------------------------------
+    def _slot(self, a, b=None, half=0):
+        sl = self._set._slot(a, b)
+        off = half * self.nspec * self.d
+        return slice(sl.start + off, sl.stop + off)
+
+    def rdn0(self, a, b=None):
+        """mean of the rdn0 block of spectrum (a, b): ``rdn0("EB")`` an auto, ``rdn0("TT", "TE")`` a cross, ``rdn0("MV")`` the MV auto."""
+        return self.acc.mean("rdn0")[self._slot(a, b)]
+
+    def mcn0(self, a, b=None):
+        """mean of the mcn0 block of spectrum (a, b): the N0 of independent simulation pairs (no data)."""
+        return self.acc.mean("rdn0")[self._slot(a, b, 1)]
+
+    def sem(self, a, b=None):
+        """standard error of :meth:`rdn0` from the run's own covariance."""
+        return np.sqrt(np.diag(self.acc.cov("rdn0"))[self._slot(a, b)] / self.acc.count("rdn0"))
+
+    def cov(self):
+        """D x D covariance of the sample vector (D = 2 * nspec * d: the rdn0 blocks, then the mcn0 blocks)."""
+        return self.acc.cov("rdn0")
+
+    def data_bandpowers(self, a, b=None):
+        """``p(QE_a(d; d), QE_b(d; d))``: the bandpowers of the data's own reconstructions, with the driver's bins."""
+        if self._pd is None:
+            torch = _torch()
+            e, q, g = self.eng, self.q, self._set
+            f = dict(zip("TEB", self.kd))
+            fields = [q.reconstruct_hc(XY, f[XY[0]], f[XY[1]]) for XY in self.estimators]
+            if self.mv:
+                kmv = g.w[0] * fields[0]
+                for j in range(1, len(self.estimators)):
+                    kmv += g.w[j] * fields[j]
+                fields.append(kmv)
+            cnt = g.counts[1:-1].double()
+            self._pd = torch.cat([e.bin_power(fields[i], fields[j], self.norm, self.ids, self.nids, herm=True, active_cols=g.wk,
+                                              active_rows=g.rk)[0][1:-1] / cnt for (i, j) in self.pairs]).cpu().numpy()
+        return self._pd[self._set._slot(a, b)]
+
+    def debiased(self, a, b=None):
+        """``data_bandpowers(a, b) - rdn0(a, b)``."""
+        return self.data_bandpowers(a, b) - self.rdn0(a, b)
+
+    @property
+    def centers(self):
+        return (self.edges[1:] + self.edges[:-1]) / 2.
+
+    # ---- the shard ----------------------------------------------------------------------------------------------------------------
+    def sample_host(self, i):
+        """x_i through the existing entries (the host loop's arithmetic): float64 device tensor of ``2 * nspec * d`` numbers."""
+        torch = _torch()
+        e, q, g = self.eng, self.q, self._set
+        nE = len(self.estimators)
+        if self._host is None:
+            t = torch.empty((6, e.ny, e.kp), dtype=e.cdt, device=e.device)
+            self._host = ([t[j] for j in range(3)], [t[3 + j] for j in range(3)], [q.new_output() for _ in range(2 * nE)],
+                          g.counts[1:-1].double())
+        s0, s1, outs, cnt = self._host
+        e.grf_mix(self.base_seed, g.cs, out=s0, stream_id0=6 * int(i))
+        e.grf_mix(self.base_seed, g.cs, out=s1, stream_id0=6 * int(i) + 3)
+        idx = {"T": 0, "E": 1, "B": 2}
+        sets = []
+        for k, (X, Y) in enumerate(((self.kd, s0), (s0, s1))):        # A = (d, s) + (s, d); B = (s, s') + (s', s)
+            fields = []
+            for j, XY in enumerate(self.estimators):
+                x, y = idx[XY[0]], idx[XY[1]]
+                out = q.reconstruct_hc(XY, X[x], Y[y], out=outs[k * nE + j])
+                fields.append(q.reconstruct_hc(XY, Y[x], X[y], out=out, accumulate=True))
+            if self.mv:
+                kmv = g.w[0] * fields[0]
+                for j in range(1, nE):
+                    kmv += g.w[j] * fields[j]
+                fields.append(kmv)
+            sets.append(fields)
+        region = dict(active_cols=g.wk, active_rows=g.rk)
+        p = [[e.bin_power(f[a], f[b], self.norm, self.ids, self.nids, herm=True, **region)[0][1:-1] / cnt for (a, b) in self.pairs] for f in sets]
+        half = [0.5 * pb for pb in p[1]]
+        return torch.cat([pa - h for pa, h in zip(p[0], half)] + half)
+
+    def _run_block(self, lo, hi, n, S, C):
+        import ctypes
+        from ._lib import check
+        from .engine import _ptr, _stream
+        e, q, g = self.eng, self.q, self._set
+        A = g._entry_args()
+        e._ordered()
+        check(e.lib.oa_plan_set_col_grid(e.plan, int(q.mcol)))       # plans are shared per geometry: policy per call
+        if getattr(e, "_pipe_owner", None) is not q._token:
+            e._pipe_owner = None
+        nE = len(self.estimators)
+        wl, wk, rl, rk = g._bands
+        own = (self._dtoken, int(q.mcol), int(q.mrow))
+        if getattr(e, "_rdn0mv_owner", None) != own:
+            e._rdn0mv_owner = None
+            kd = (ctypes.c_void_p * 3)(*[k.data_ptr() for k in self.kd])
+            check(e.lib.oa_rdn0_set_data_mv(e.plan, kd, nE, A["npieces"], A["fgs"], A["fhs"], A["swaps"], A["xsrc"], A["ysrc"], int(wl), int(wk),
+                                            int(rl), int(rk), int(q.mrow), _stream()))
+            e._rdn0mv_owner = own
+        wstride = g.w[0].numel() if g.w is not None else 0
+        check(e.lib.oa_mc_run_rdn0_mv(e.plan, self.base_seed, int(lo), int(hi), A["cs"], nE, A["npieces"], A["signs"], A["fgs"], A["fhs"], A["swaps"],
+                                      A["xsrc"], A["ysrc"], A["fns"], _ptr(g.w), wstride, self.nspec, A["a"], A["b"], _ptr(self.ids), self.nids,
+                                      _ptr(g.counts), float(self.norm), int(wl), int(wk), int(rl), int(rk), int(q.mrow), _ptr(n), _ptr(S), _ptr(C),
+                                      _stream()))
+
+    def run_local(self, sims):
+        """Process the given global realisation indices on this rank's GPU: every contiguous block of indices is ONE
+        ``oa_mc_run_rdn0_mv`` call (one-call path), or one :meth:`sample_host` + ``Statistics.add`` per index (host loop)."""
+        sims = [int(i) for i in sims]
+        if not sims:
+            return self
+        if not self.one_call:
+            for i in sims:
+                self.acc.add("rdn0", self.sample_host(i))
+            return self
+        n, S, C = self.acc.device_moments("rdn0", self.D)
+        start = prev = sims[0]
+        for i in sims[1:] + [None]:
+            if i is None or i != prev + 1:
+                self._run_block(start, prev + 1, n, S, C)
+                start = i
+            prev = i
+        self.acc.note_samples("rdn0", len(sims))
+        return self
+
+    def run(self, nsims):
+        """Shard ``nsims`` realisations with mpi.mpi_distribute, run, reduce once; returns the reduced :class:`Statistics` (one label,
+        ``"rdn0"``, of dimension ``2 * nspec * d``)."""
+        comm = self.comm
+        size, rank = comm.Get_size(), comm.Get_rank()
+        _, tasks = _mpi.mpi_distribute(nsims, size, allow_empty=True)
+        self.run_local(tasks[rank])
+        self.acc.allreduce()
+        return self.acc

@@ -335,6 +335,12 @@ class _Moments(object):
         self.cell = None        # device mode: the int64 counter the accumulation kernels increment
 
 
+def _host(a):
+    """a reduced moment as a NumPy array: second moments with more than Statistics.PACK_LIMIT elements are reduced in place and stay
+    device tensors"""
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else a
+
+
 class _Stack(object):
     __slots__ = ("shape", "count", "total", "support")
 
@@ -693,13 +699,13 @@ class Statistics(object):
         g = self._reduced("vec", label)
         if g.count <= ddof:
             return np.full((g.dim, g.dim), np.nan, dtype=self.dtype)
-        return (g.second - np.outer(g.first, g.first) / g.count) / (g.count - ddof)
+        return (_host(g.second) - np.outer(_host(g.first), _host(g.first)) / g.count) / (g.count - ddof)
 
     def var(self, label, ddof=1):
         g = self._reduced("vec", label)
         if g.count <= ddof:
             return np.full(g.dim, np.nan, dtype=self.dtype)
-        return (np.diagonal(g.second) - g.first ** 2 / g.count) / (g.count - ddof)
+        return (np.diagonal(_host(g.second)) - _host(g.first) ** 2 / g.count) / (g.count - ddof)
 
     # -- on-disk format (interoperable with the reference's post-processing, stats.py:1455-1530) ------------------
     def save_reduced(self, path, compressed=False, root_rank=0):
