@@ -43,7 +43,7 @@ typedef struct oa_plan oa_plan;
 const char* oa_last_error(void);
 /* ABI version = 100 x the build round that last changed a signature in this header; bindings must refuse a library
  * that reports less than the version they were written against (OA_ABI_VERSION) */
-#define OA_ABI_VERSION 412
+#define OA_ABI_VERSION 413
 int oa_version(void);
 /* number of HIP devices visible; <0 on error (no compute) */
 int oa_device_count(void);
@@ -167,6 +167,7 @@ int oa_qe_cols_div(oa_plan* p, const void* px_rows, const void* py_rows, const v
  *  oa_mc_run_rdn0      : the realisation-dependent N0 shard of ONE data map: the data's three leg planes are cached by the
  *                        set-up entry, then per realisation two draws s, s' -> A = QE(d, s) + QE(s, d), B = QE(s, s') + QE(s', s)
  *                        -> x = [p(A) - p(B) / 2, p(B) / 2] -> moments of the 2 d-vector (at their declarations below).
+ *  oa_mc_run_rdn0_windowed : the same with s, s' multiplied by a real-space window (the simulations of an apodised data map).
  *  oa_rdn0_set_data_mv,
  *  oa_mc_run_rdn0_mv   : the same for an estimator SET (TT, TE, EE, EB, TB ...), its cross-spectra and its MV combination on
  *                        power-of-two plans: the data triple's distinct leg planes are cached, then per realisation two T, E, B
@@ -266,8 +267,14 @@ int oa_plan_div_fused(const oa_plan* p);
  *                      real map exists in LDS only); 0: C2R with the window at its store, real map in HBM, from-map estimator path
  *                      (sides 2^a 3^b 5^c: the band input transform; until the option is set, or after a value < 0, such a plan takes
  *                      what measured faster: the unfused flow for rows of up to 1200 points, the fused pass for longer ones up to
- *                      the 8192 points its kernel holds) */
-enum { OA_OPT_MC_BATCH = 1, OA_OPT_MV_BATCH = 2, OA_OPT_MV_ROWBATCH = 3, OA_OPT_MV_CHAIN = 4, OA_OPT_DIV_BIN = 5, OA_OPT_WIN_FUSED = 6 };
+ *                      the 8192 points its kernel holds)
+ *   OA_OPT_DRAW_FUSED  oa_mc_run_rdn0_windowed on power-of-two plans (with OA_OPT_WIN_FUSED = 1): 1 = the draws of up to three
+ *                      realisations are evaluated inside ONE inverse column pass-1 launch (oa_grf_hc_icols: the drawn planes never
+ *                      exist); 0 = ONE BY ONE: per draw oa_grf_hc, the column transform and the row pass (24 launches per six draws
+ *                      against 3); unset or < 0 = what measured faster: 1.  The kernel alone saves 5 - 14 us per drawn plane at 2048^2
+ *                      and 4096^2, beyond the spreads; a realisation is 9 - 25 % faster, most of that from the batched launches
+ *                      (profiles/rdn0_windowed.jsonl).  The moments are bit-equal between 0 and 1. */
+enum { OA_OPT_MC_BATCH = 1, OA_OPT_MV_BATCH = 2, OA_OPT_MV_ROWBATCH = 3, OA_OPT_MV_CHAIN = 4, OA_OPT_DIV_BIN = 5, OA_OPT_WIN_FUSED = 6, OA_OPT_DRAW_FUSED = 7 };
 int oa_plan_set_option(oa_plan* p, int option, int value);
 int oa_plan_set_bins(oa_plan* p, const int32_t* ids_hc, int nids, double norm, void* stream);
 void* oa_plan_kappa(oa_plan* p);
@@ -359,7 +366,7 @@ int oa_mc_run(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const vo
  *     n += 1,  S += x_i,  C += x_i x_i^T             (Statistics.add of the 2 d-vector, float64, realisation order).
  * |A|^2 is the four data-simulation terms of the usual six-term RDN0; p(B) / 2 has the expectation of its two simulation-simulation
  * terms and a smaller variance.  The second half alone is the N0 of independent pairs (no data, no signal trispectrum); the debiased
- * spectrum of the map is p(QE(d, d)) - mean(rdn0).  No window: simulations with the data's taper are not part of this entry.
+ * spectrum of the map is p(QE(d, d)) - mean(rdn0).  No window here: oa_mc_run_rdn0_windowed (below) is the entry for an apodised map.
  *  oa_rdn0_set_data : set-up entry (needs oa_plan_set_filters; may allocate and synchronise).  kD_hc = the data map's transform; its three
  *                     filtered leg planes are made on the plan's coarse grid, exactly as the leg stage of oa_qe_tt(kX = d) leaves them,
  *                     and kept in a plan-owned buffer (on a band grid: the leg band of kD_hc is embedded into an inner plane first and
@@ -379,6 +386,30 @@ int oa_mc_run(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const vo
 int oa_rdn0_set_data(oa_plan* p, const void* kD_hc, void* stream);
 int oa_mc_run_rdn0(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, int64_t* n, double* S, double* C,
                    void* stream);
+/* oa_mc_run_rdn0_windowed: oa_mc_run_rdn0's definition with ONE change -- s and s' are the WINDOWED draws
+ *     s = R2C(window_real . C2R(oa_grf_hc(base_seed, 2 i)) / Npix),      s' = the same from stream 2 i + 1,
+ * the full-plane draws oa_mc_run_windowed makes for its realisations 2 i and 2 i + 1 (window_real: ny x nx reals of the plan's dtype).
+ * The data legs are those cached by the unchanged oa_rdn0_set_data: its kD_hc is the transform of the map AS ANALYSED, i.e. already
+ * apodised by the caller.  A, B, x_i, the tail, its fixed summation order and its bit-reproducibility are oa_mc_run_rdn0's.  There is NO
+ * mean-field argument: s, s' and d are independent and zero-mean, so A and B carry no mean field (the mean field of the data's own
+ * reconstruction QE(d, d) is the caller's to subtract; mc.RDN0MonteCarlo.data_bandpowers(mean_field=...)).
+ * Power-of-two plans, per batch of B realisations: the full-plane part of its 2 B draws in groups of up to six -- OA_OPT_DRAW_FUSED = 1:
+ * one pass-1 launch with the draw at its load + pass 2 (oa_grf_hc_icols), one fused row launch C2R x window -> R2C; 0: oa_grf_hc,
+ * inverse columns and the row pass per draw -- onto compact row planes, then the forward column transform onto the leg band of the
+ * entry's draw planes (six planes per launch), then oa_mc_run_rdn0's launches.  OA_OPT_WIN_FUSED = 0: one by one, per draw oa_grf_hc ->
+ * oa_fft_c2r_windowed -> oa_fft_r2c.  Band grid (sides 2^a 3^b 5^c): oa_mc_run_windowed's front end there, the 2 B draws through its six
+ * N-grid planes in two halves, the pruned column DFT onto the inner plan's draw planes; the fused / unfused rule by row length is that entry's.
+ * Refused by name before anything is launched: a NULL window and everything oa_mc_run_rdn0 refuses.  Nothing is allocated after the
+ * first call; oa_plan_release_pools frees what the entry took.
+ * A batch is started only where the chain row stage serves the geometry; elsewhere the realisations run one at a time from the start.
+ * Measured per realisation against the host loop of existing entries (profiles/rdn0_windowed.jsonl): 0.11 against 0.40 ms at 2048^2 f32,
+ * 0.52 against 1.28 ms at 4096^2 f64; band grid (one at a time) 0.31 against 0.40 ms at 1200^2 f32, 0.51 against 0.69 ms at 2400^2 f32. */
+/* Which path the LAST oa_mc_run_rdn0 / oa_mc_run_rdn0_windowed call on this plan took: 1 when it ran realisations in batches (a batch
+ * reached the tail), 0 when it ran them one at a time (the row stage takes one map per launch, or OA_OPT_WIN_FUSED = 0 / the unfused
+ * rule of a band grid), was refused, or was never made. */
+int oa_plan_rdn0_batched(const oa_plan* p);
+int oa_mc_run_rdn0_windowed(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, const void* window_real, int64_t* n,
+                            double* S, double* C, void* stream);
 /* The same shard with a real-space window applied to every realisation before its transform (the reference's analysis
  * flow: maps.py:1873-1878 get_taper, maps.py:1350-1361): full-plane draw (same Philox counters as oa_mc_run) -> C2R / Npix
  * -> x window_real (ny x nx reals of the plan's dtype) -> TT estimator -> bandpower moments (+ mean-field stack).  With
@@ -693,6 +724,12 @@ int oa_bin_power_multi(int dtype, int nfields, const void* k0, long fstride, con
  * enmap.ifft(covsqrt*rand_gauss_harm).real.  Counter-based Philox4x32-10,
  * key = (seed, stream_id), so realisations are independent of launch geometry. */
 int oa_grf_hc(oa_plan* p, uint64_t seed, uint64_t stream_id, const void* covsqrt_hc, void* hc_out, void* stream);
+/* The draw INSIDE the inverse column transform: plane z (z < nreal, zstride complex elements apart) of hc_out is bit for bit
+ * oa_fft_cols(inverse = 1, scale = 1, width = nx/2 + 1) of oa_grf_hc(seed, stream_id + z, covsqrt_hc) -- the load of column pass 1
+ * evaluates the modes (same Philox counters, same self-conjugate rules at columns 0 and nx/2, same product with the amplitude), so the
+ * drawn planes are never stored; pass 2 is the in-place launch.  A lane pair shares each counter (columns 2 p, 2 p + 1): as many Philox
+ * evaluations as oa_grf_hc.  Power-of-two plans only (ny >= 32); other plans are refused by name. */
+int oa_grf_hc_icols(oa_plan* p, uint64_t seed, uint64_t stream_id, int nreal, const void* covsqrt_hc, void* hc_out, long zstride, void* stream);
 /* The same draw restricted to the ACTIVE region (columns < width, rows y < rband or y > ny - rband; 0 = all): a
  * bit-identical subset of oa_grf_hc's plane (every mode keeps its Philox counter), the rest of hc_out is not written.
  * A Monte-Carlo loop whose estimator reads only its leg band (oa_mc_run does this itself) draws ~1 % of the modes. */

@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("ORPHICS_AMD_LIB", os.path.join(_HERE, "liborphics_amd
 
 OA_F32 = 0
 OA_F64 = 1
-ABI_VERSION = 412   # include/orphics_amd.h OA_ABI_VERSION: the signatures below are those of this version
+ABI_VERSION = 413   # include/orphics_amd.h OA_ABI_VERSION: the signatures below are those of this version
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
@@ -72,6 +72,8 @@ SIGNATURES = {
     # realisation-dependent N0 of the TT estimator: the data's cached leg planes (set-up entry), then the shard; S: 2 d, C: (2 d)^2
     "oa_rdn0_set_data": (c_int, [c_void_p, c_void_p, c_void_p]),
     "oa_mc_run_rdn0": (c_int, [c_void_p, c_u64, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "oa_plan_rdn0_batched": (c_int, [c_void_p]),
+    "oa_mc_run_rdn0_windowed": (c_int, [c_void_p, c_u64, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # ... of an estimator set and its MV combination (power-of-two plans): host_kD[3] + the set's description and bands, then oa_mc_run_mv's
     # arguments; S: 2 nspec d, C: (2 nspec d)^2
     "oa_rdn0_set_data_mv": (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
@@ -122,6 +124,7 @@ SIGNATURES = {
     "oa_bin_power_multi": (c_int, [c_int, c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_void_p, c_void_p, c_double, c_void_p, c_int, c_int,
                                    c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "oa_grf_hc": (c_int, [c_void_p, c_u64, c_u64, c_void_p, c_void_p, c_void_p]),
+    "oa_grf_hc_icols": (c_int, [c_void_p, c_u64, c_u64, c_int, c_void_p, c_void_p, c_long, c_void_p]),
     "oa_grf_hc_band": (c_int, [c_void_p, c_u64, c_u64, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "oa_grf_mix": (c_int, [c_void_p, c_u64, c_u64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
     "oa_grf_mix_band": (c_int, [c_void_p, c_u64, c_u64, c_int, c_void_p, c_double, c_void_p, c_int, c_int, c_void_p]),

@@ -169,6 +169,8 @@ int qe_lens_derivs_w(oa_plan* p, int nmaps, const void* real_in, long in_stride,
 // plane z of hc_in and of cols_tmp sits z * in_moff, its row-transformed plane z * out_moff complex elements behind the first
 int qe_windowed_rows_w(oa_plan* p, const void* hc_in, void* cols_tmp, const void* window, int width, long pl, double scale, hipStream_t st,
                        void* out = nullptr, int nz = 0, long in_moff = 0, long out_moff = 0);
+int qe_win_rows_w(oa_plan* p, const void* cols_in, const void* window, int width, long pl, double scale, hipStream_t st, void* out, int nz,
+                  long in_moff, long out_moff);
 int qe_fwd_cols_batch_w(oa_plan* p, const void* in, long pin, void* out, int B, long in_moff, long out_moff, int width, int rband, hipStream_t st);
 // one filtered field (subset 1: H plane into a; 2: gradient pair into a, b), inverse pass 1 only; then pass 2 over a pool of planes
 int qe_legs_subset_w(oa_plan* p, const void* src, const void* F, void* a, void* b, int subset, int width, int rband, long pl,
@@ -193,6 +195,9 @@ size_t qe_rows_table_entry_bytes(const oa_plan* p);
 int qe_rows_chain_w(oa_plan* p, int nest, int total, const void* const* gx, const void* const* gy, const void* const* h, void* const* px,
                     void* const* py, const double* scales, const int* first, const int* count, void* dev_tab, int upload, int win, int wout, int mrow,
                     long pl, long pk, hipStream_t st, int my);
+// nreal full-plane draws (streams stream_id ...) straight into their inverse column transform: oa_grf_hc_icols without its checks (fft.hip)
+int grf_icols_w(oa_plan* p, uint64_t seed, uint64_t stream_id, int nreal, const void* cs, void* out, long zstride, hipStream_t st);
+bool qe_rows_chain_ok(const oa_plan* p, int win, int wout, int mrow, int my);
 int grf_hc_band_batch(oa_plan* p, uint64_t seed, uint64_t stream_id, int nreal, const void* covsqrt_hc, void* hc_out, long zstride,
                       int width, int rband, hipStream_t stream);
 // oa_mc_run_mv: the interior bins of nspec binned spectra (oa_bin_power_multi's layout) over the mode counts -> n += 1, S += x, C += x x^T (rng.hip);

@@ -211,6 +211,14 @@ __global__ __launch_bounds__(col_maxnt<SEQ>(), waves_per_eu<T>()) void col_fft_k
     col_fft_body<T, SEQ>(c, a);
 }
 
+// inverse column pass 1 whose load is the Gaussian draw (col_grf_body): the Philox / Box-Muller arithmetic sits in front of the first
+// butterfly, so it gets the fused column kernels' register budget
+template <typename T, class SEQ>
+__global__ __launch_bounds__(col_maxnt<SEQ>(), fused_col_waves_per_eu<T>()) void col_grf_kernel(GrfColArgs<T> a) {
+    GpuCtx c{oa_dyn_smem};
+    col_grf_body<T, SEQ>(c, a);
+}
+
 // resident workgroups per CU of a persistent kernel, with its dynamic-LDS attribute set: asked of the runtime ONCE per (kernel,
 // workgroup size, LDS bytes) -- both are driver calls of several microseconds, more than a 4096^2 launch leaves the host
 static int resident_per_cu(const void* kern, int nt, size_t smem, std::string* err) {
@@ -580,6 +588,17 @@ struct HipLauncher {
             if constexpr (seq_logl<S>() <= 8) {
                 if (nt > col_maxnt<S>()) { if (!rc) rc = fail("fft: column workgroup size exceeds its launch bound"); return; }
                 go(col_deriv_kernel<T, S>, dim3(gx, gy, nz), nt, smem, a);
+            } else if (!rc) rc = fail("fft: unsupported column sub-length");
+        });
+        if (!ok && !rc) rc = fail("fft: unsupported column length");
+    }
+    template <typename T>
+    void col_grf(int gx, int gy, int nt, size_t smem, const GrfColArgs<T>& a, int nz) {
+        const bool ok = dispatch_seq(a.logL, [&](auto seq) {
+            using S = decltype(seq);
+            if constexpr (seq_logl<S>() <= 8) {
+                if (nt > col_maxnt<S>()) { if (!rc) rc = fail("fft: column workgroup size exceeds its launch bound"); return; }
+                go(col_grf_kernel<T, S>, dim3(gx, gy, nz), nt, smem, a);
             } else if (!rc) rc = fail("fft: unsupported column sub-length");
         });
         if (!ok && !rc) rc = fail("fft: unsupported column length");
@@ -957,6 +976,21 @@ int qe_windowed_rows_w(oa_plan* p, const void* hc_in, void* cols_tmp, const void
     return p->dtype == OA_F32 ? windowed_rows_impl<float>(p, hc_in, cols_tmp, window, width, pl, scale, st, out, nz, in_moff, out_moff)
                               : windowed_rows_impl<double>(p, hc_in, cols_tmp, window, width, pl, scale, st, out, nz, in_moff, out_moff);
 }
+// the fused row pass alone, over nz (>= 1) planes whose inverse column transform is already done (oa_grf_hc_icols leaves it): planes
+// in_moff apart -> compact row planes of pitch pl, out_moff apart
+template <typename T>
+static int win_rows_impl(oa_plan* p, const void* cols_in, const void* window, int width, long pl, double scale, hipStream_t st, void* out, int nz,
+                         long in_moff, long out_moff) {
+    HipLauncher q{st};
+    auto f = view<T>(p);
+    f.rows(q, ROW_WIN, cols_in, p->kp, out, pl > 0 ? pl : p->kp, (T)scale, f.clampw(width), window, nz > 1 ? nz : 0, in_moff, out_moff);
+    return q.rc;
+}
+int qe_win_rows_w(oa_plan* p, const void* cols_in, const void* window, int width, long pl, double scale, hipStream_t st, void* out, int nz,
+                  long in_moff, long out_moff) {
+    return p->dtype == OA_F32 ? win_rows_impl<float>(p, cols_in, window, width, pl, scale, st, out, nz, in_moff, out_moff)
+                              : win_rows_impl<double>(p, cols_in, window, width, pl, scale, st, out, nz, in_moff, out_moff);
+}
 // forward column transform of B row-transformed compact planes (pitch pin, in_moff apart) onto the leg band (columns < width, rows
 // |ky index| < rband, natural order) of B full-pitch hc planes out_moff apart: two launches for the batch
 template <typename T>
@@ -969,6 +1003,17 @@ static int fwd_cols_batch_impl(oa_plan* p, const void* in, long pin, void* out, 
 int qe_fwd_cols_batch_w(oa_plan* p, const void* in, long pin, void* out, int B, long in_moff, long out_moff, int width, int rband, hipStream_t st) {
     return p->dtype == OA_F32 ? fwd_cols_batch_impl<float>(p, in, pin, out, B, in_moff, out_moff, width, rband, st)
                               : fwd_cols_batch_impl<double>(p, in, pin, out, B, in_moff, out_moff, width, rband, st);
+}
+// nreal draws (streams stream_id ...) and their inverse column transform, the drawn planes never stored (oa_grf_hc_icols)
+template <typename T>
+static int grf_icols_impl(oa_plan* p, uint64_t seed, uint64_t stream_id, int nreal, const void* cs, void* out, long zstride, hipStream_t st) {
+    HipLauncher q{st};
+    view<T>(p).grf_icols(q, seed, stream_id, nreal, (const T*)cs, (cx<T>*)out, zstride);
+    return q.rc;
+}
+int grf_icols_w(oa_plan* p, uint64_t seed, uint64_t stream_id, int nreal, const void* cs, void* out, long zstride, hipStream_t st) {
+    return p->dtype == OA_F32 ? grf_icols_impl<float>(p, seed, stream_id, nreal, cs, out, zstride, st)
+                              : grf_icols_impl<double>(p, seed, stream_id, nreal, cs, out, zstride, st);
 }
 // flat-sky Taylor lensing, FFT part (oa_lens_maps): nmaps real maps -> their transforms (k0: nmaps hc planes) -> the nd derivative
 // fields of each, inverse-transformed: ONE pass-1 launch with the derivative factor at the load, ONE pass-2 launch, ONE row C2R
@@ -1111,6 +1156,17 @@ int qe_rows_table_w(oa_plan* p, int n, const void* const* gx, const void* const*
                               : qe_rows_table_impl<double>(p, n, gx, gy, h, px, py, scales, dev_tab, upload, accumulate, win, wout, mrow, st, pl, pk, my);
 }
 size_t qe_rows_table_entry_bytes(const oa_plan* p) { return p->dtype == OA_F32 ? sizeof(RowQeMap<float>) : sizeof(RowQeMap<double>); }
+// whether qe_rows_chain_w serves this geometry (it returns -1 where it does not: the callers then run one map per launch)
+template <typename T>
+static bool qe_rows_chain_ok_impl(const oa_plan* p, int win, int wout, int mrow, int my) {
+    auto f = coarse_view<T>(p, my);
+    const int wi = f.clampw(win), wo = f.clampw(wout);
+    if (mrow < 0) { mrow = Fft2dPlan<T>::row_grid_min(p->nx, wi, wo); if (2L * wi + wo > mrow) mrow = 0; }
+    return f.rows_qe_is_pair(wi, wo, mrow) && !(mrow > 0 && ilog2(mrow) > 12);
+}
+bool qe_rows_chain_ok(const oa_plan* p, int win, int wout, int mrow, int my) {
+    return p->dtype == OA_F32 ? qe_rows_chain_ok_impl<float>(p, win, wout, mrow, my) : qe_rows_chain_ok_impl<double>(p, win, wout, mrow, my);
+}
 // estimator chains: `total` pieces (planes, scales as in qe_rows_table_w) grouped into nest estimators (first[e], count[e]); the
 // device table holds the pieces followed by the 2 nest chain integers.  -1: this geometry's row stage is another kernel
 template <typename T>
@@ -1121,7 +1177,7 @@ static int qe_rows_chain_impl(oa_plan* p, int nest, int total, const void* const
     auto f = coarse_view<T>(p, my);
     const int wi = f.clampw(win), wo = f.clampw(wout);
     if (mrow < 0) { mrow = Fft2dPlan<T>::row_grid_min(p->nx, wi, wo); if (2L * wi + wo > mrow) mrow = 0; }
-    if (!f.rows_qe_is_pair(wi, wo, mrow) || (mrow > 0 && ilog2(mrow) > 12)) return -1;
+    if (!qe_rows_chain_ok_impl<T>(p, win, wout, mrow, my)) return -1;
     const size_t tb = ((size_t)total * sizeof(RowQeMap<T>) + 15) / 16 * 16;
     if (upload) {
         std::vector<char> buf(tb + 2 * (size_t)nest * sizeof(int));
@@ -1204,6 +1260,16 @@ int oa_fft_cols(oa_plan* p, const void* hc_in, void* hc_out, int inverse, double
     OA_REQUIRE(hc_in != hc_out, "oa_fft_cols: in-place not supported");
     return p->dtype == OA_F32 ? cols_impl<float>(p, hc_in, hc_out, inverse, scale, width, (hipStream_t)stream)
                               : cols_impl<double>(p, hc_in, hc_out, inverse, scale, width, (hipStream_t)stream);
+}
+
+int oa_grf_hc_icols(oa_plan* p, uint64_t seed, uint64_t stream_id, int nreal, const void* covsqrt_hc, void* hc_out, long zstride, void* stream) {
+    OA_REQUIRE(p && hc_out, "oa_grf_hc_icols: NULL argument");
+    OA_REQUIRE(p->pow2, "oa_grf_hc_icols: the draw is fused into the power-of-two inverse column pass; this plan's sides are not powers of two "
+               "(run oa_grf_hc, then the plan's own column transform)");
+    OA_REQUIRE(nreal >= 1 && nreal <= 65535, "oa_grf_hc_icols: 1 <= nreal <= 65535 (grid z)");
+    OA_REQUIRE(nreal == 1 || zstride >= (long)p->ny * p->kp, "oa_grf_hc_icols: zstride must be at least one plane (ny * pitch elements)");
+    OA_REQUIRE(p->ny >= 32 && p->nx >= 4, "oa_grf_hc_icols: needs ny >= 32 and nx >= 4");
+    return oa::grf_icols_w(p, seed, stream_id, nreal, covsqrt_hc, hc_out, zstride, (hipStream_t)stream);
 }
 
 int oa_qe_rows(oa_plan* p, const void* gx, const void* gy, const void* h, void* px, void* py, double scale,

@@ -26,6 +26,7 @@
 #pragma once
 #include <type_traits>
 #include "cx.hpp"
+#include "philox.hpp"
 
 namespace oa {
 
@@ -2179,6 +2180,146 @@ OA_HD void col_fft_body(Ctx& ctx, const ColArgs<T>& a) {
     const ColStore<T> st{out + g * a.out_gs * a.out_pitch + c0, (unsigned)(a.out_ks * a.out_pitch), ncols, a.inverse != 0,
                          a.twiddle ? ti : nullptr, (unsigned)g, a.scale, a.rband, (int)(g * a.out_gs), (int)a.out_ks, a.ny};
     fft_pipeline<T, false, true, true, SEQ>(ctx, s, tid, CNT, logL, CLC, 0, twl, logL, ld, st);
+}
+
+// ===========================================================================
+// The Gaussian draw INSIDE inverse column pass 1 (oa_grf_hc_icols): the load functor evaluates grf_hc_kernel's mode (rng.hip) where
+// col_fft_body's ColLoad reads it from a plane, so the drawn spectrum never exists in memory.  Same Philox counter ys * npair + x / 2,
+// same self-conjugate rules at columns 0 and nx/2 (mirrored row, real modes), same 1 / sqrt 2 and the same product with the amplitude:
+// with pass 2 behind it the plane is bit for bit oa_fft_cols(inverse) of oa_grf_hc's draw (-ffp-contract=off).
+// ===========================================================================
+template <typename T>
+struct GrfColArgs {
+    uint64_t seed, sid;        // Philox key; grid z = realisation: stream sid + z into the plane z * out_zstride elements behind `out`
+    const T* cs;               // amplitude plane (row pitch `pitch`), or nullptr for the white draw
+    cx<T>* out;
+    long out_zstride, pitch;   // complex elements
+    int width, ny, nxh;        // width = nxh + 1 columns
+    int logL, NT;
+    const cx<T>* tw;           // master table of length 2^logTw (= Ny)
+    int logTw;
+    long in_ns, out_gs;        // N2, N1: input row of point n in group g = g + n N2, output row of bin k = g N1 + k
+    int twiddle;               // multiply bin k of group g by W_{Ny}^{g k}
+};
+
+template <typename T>
+struct GrfColLoad {
+    static constexpr bool reads_lds = false;
+    uint64_t seed, sid;
+    const T* cs;
+    long kp;
+    int ny, nxh, npair;
+    int y0, ystep;      // row of point n: y0 + n * ystep
+    int x0, ncols;      // first column and valid columns of this tile (x0 is even)
+    // the counter of (row y, column x): the mirrored row at a self-conjugate column's upper half
+    OA_HD int counter_row(int y, int x) const { return ((x == 0 || x == nxh) && y > ny / 2) ? ny - y : y; }
+    OA_HD void normals(int ys, int x, float* n) const { normals4(seed, sid, (uint64_t)ys * (uint64_t)npair + (uint64_t)(x >> 1), n); }
+    // the mode of (y, x) from the four normals of ITS counter, as the inverse pass reads it (real and imaginary part swapped)
+    template <typename U> OA_HD cx<U> mode(const float* n, int y, int x) const {
+        const U rs2 = (U)0.70710678118654752440;
+        const int j = x & 1;
+        const bool edgecol = (x == 0 || x == nxh);
+        const bool cj = edgecol && y > ny / 2;
+        const int ys = cj ? ny - y : y;
+        U re = (U)n[2 * j], im = (U)n[2 * j + 1];
+        if (edgecol && (ys == 0 || ys == ny / 2)) { im = (U)0; }
+        else { re *= rs2; im *= rs2; }
+        if (cj) im = -im;
+        const U s = cs ? cs[(long)y * kp + x] : (U)1;
+        return mk<U>(im * s, re * s);
+    }
+    // one element (the statement; the kernel fills a thread's points through grf_col_fill, one counter evaluation per column PAIR)
+    template <typename U> OA_HD cx<U> get(int n, int c) const {
+        if (c >= ncols) return mk<U>((U)0, (U)0);
+        const int y = y0 + n * ystep, x = x0 + c;
+        float nn[4];
+        normals(counter_row(y, x), x, nn);
+        return mode<U>(nn, y, x);
+    }
+};
+
+// swap a value with the neighbouring lane (lane ^ 1): DPP quad_perm [1, 0, 3, 2], no LDS
+#if defined(__HIP_DEVICE_COMPILE__)
+OA_D float lane_swap1(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true)); }
+OA_D double lane_swap1(double v) {
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)b, 0xB1, 0xF, 0xF, true);
+    const unsigned hi = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(b >> 32), 0xB1, 0xF, 0xF, true);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+#endif
+
+// v[u * R + t] = ld.get(j_u + t * L / R, c_u): the first-stage inputs of stage_in's mapping (column tiles).  One counter yields the
+// modes of columns 2 p and 2 p + 1, which are the adjacent lanes tid, tid ^ 1 at the same points: the even lane evaluates the counters
+// of the first eight of the sixteen points, the odd lane those of the last eight, each forms both columns' modes, keeps its own column's
+// and hands the other's to its neighbour in ONE exchange of eight values (DPP; through the tile under the thread emulator, which has no
+// lanes).  Philox evaluations per thread: eight, plus one per point where column 0 / nx/2 reads the mirrored row -- grf_hc_kernel's count
+// for the same modes.  `s`: the (still unused) column tile.
+template <typename T, int R, class Ctx>
+OA_HD void grf_col_fill(Ctx& ctx, cx<T>* s, cx<T>* v, int tid, int NT, int logL, const GrfColLoad<T>& ld) {
+    constexpr int LR = Log2c<R>::v;
+    constexpr int logC = COL_LOGC;
+    const int logLR = logL - LR;
+    const int odd = tid & 1;
+    cx<T> mine[EPT / 2], send[EPT / 2];
+#pragma unroll
+    for (int i = 0; i < EPT / 2; ++i) {
+        const int slot = i + odd * (EPT / 2), u = slot >> LR, t = slot & (R - 1);
+        const int b = tid + u * NT, c = b & ((1 << logC) - 1), j = b >> logC;
+        const int y = ld.y0 + (j + (t << logLR)) * ld.ystep;
+        const int xe = ld.x0 + (c & ~1);                 // the pair's even column; xe + 1 is the odd one
+        cx<T> m0 = mk<T>((T)0, (T)0), m1 = m0;
+        if (xe <= ld.nxh) {
+            float n[4];
+            ld.normals(y, xe, n);
+            if (xe + 1 <= ld.nxh) m1 = ld.template mode<T>(n, y, xe + 1);
+            const int ys = ld.counter_row(y, xe);
+            if (ys != y) ld.normals(ys, xe, n);          // (columns 0 and nx/2 above the middle row: the mirrored row's counter)
+            m0 = ld.template mode<T>(n, y, xe);
+        }
+        mine[i] = odd ? m1 : m0;
+        send[i] = odd ? m0 : m1;
+    }
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+    for (int i = 0; i < EPT / 2; ++i) send[i] = mk<T>(lane_swap1(send[i].x), lane_swap1(send[i].y));
+#else
+    for (int i = 0; i < EPT / 2; ++i) s[tid * (EPT / 2) + i] = send[i];
+    ctx.sync();
+    for (int i = 0; i < EPT / 2; ++i) send[i] = s[(tid ^ 1) * (EPT / 2) + i];
+    ctx.sync();
+#endif
+#pragma unroll
+    for (int i = 0; i < EPT / 2; ++i) {
+        v[i] = odd ? send[i] : mine[i];
+        v[i + EPT / 2] = odd ? mine[i] : send[i];
+    }
+}
+
+template <typename T, class SEQ, class Ctx>
+OA_HD void col_grf_body(Ctx& ctx, const GrfColArgs<T>& a) {
+    cx<T>* s = reinterpret_cast<cx<T>*>(ctx.smem());
+    const int tid = ctx.tid();
+    constexpr int CLC = COL_LOGC;
+    constexpr int CNT = ((1 << (seq_total_log<SEQ>() + COL_LOGC)) / EPT) > 0 ? ((1 << (seq_total_log<SEQ>() + COL_LOGC)) / EPT) : 1;
+    const int c0 = ctx.bid_x() << CLC;
+    const long g = ctx.bid_y();
+    int ncols = a.width - c0;
+    if (ncols > (1 << CLC)) ncols = 1 << CLC;
+    constexpr int logL = seq_total_log<SEQ>();
+    cx<T>* twl = s + (1 << (logL + CLC));
+    cx<T>* ti = twl + tw_lds_size(logL);
+    tw_lds_fill<T>(ctx, twl, a.tw, a.logTw, logL, CNT);
+    if (a.twiddle)
+        for (int i = tid; i < (1 << logL); i += CNT) ti[i] = a.tw[(unsigned)g * (unsigned)i];
+    const int z = ctx.bid_z();
+    const GrfColLoad<T> ld{a.seed, a.sid + (uint64_t)z, a.cs, a.pitch, a.ny, a.nxh, a.nxh / 2 + 1, (int)g, (int)a.in_ns, c0, ncols};
+    const ColStore<T> st{a.out + (long)z * a.out_zstride + g * a.out_gs * a.pitch + c0, (unsigned)a.pitch, ncols, true, a.twiddle ? ti : nullptr,
+                         (unsigned)g, (T)1, 0, 0, 0, 0};
+    cx<T> v[EPT];
+    grf_col_fill<T, SEQ::get(0)>(ctx, s, v, tid, CNT, logL, ld);
+    ctx.sync();                                         // the twiddle tables are in LDS
+    col_pipeline_from_regs<T, SEQ>(ctx, s, v, tid, CNT, CLC, twl, logL, st);
 }
 
 }  // namespace oa

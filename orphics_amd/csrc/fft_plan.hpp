@@ -344,6 +344,20 @@ struct Fft2dPlan {
         q.col(tiles, (int)N1, a.NT, ((size_t)N2 * C + tw_lds_size(logN2) + N2) * sizeof(cx<T>), a, nb * nmaps);
     }
 
+    // ---- nreal Gaussian draws (streams sid .. sid + nreal - 1) straight into their inverse column transform (oa_grf_hc_icols): pass 1
+    //      evaluates the modes at its load (col_grf_body), pass 2 is the in-place launch of cols() over the nreal planes
+    template <class Launcher>
+    void grf_icols(Launcher& q, uint64_t seed, uint64_t sid, int nreal, const T* cs, cx<T>* out, long zstride) const {
+        const int logN1 = (logNy + 1) / 2, logN2 = logNy - logN1;
+        const long N1 = 1L << logN1, N2 = 1L << logN2;
+        const int C = 1 << COLC, width = nx / 2 + 1, tiles = (width + C - 1) / C;
+        GrfColArgs<T> a{};
+        a.seed = seed; a.sid = sid; a.cs = cs; a.out = out; a.out_zstride = zstride; a.pitch = kp; a.width = width; a.ny = ny; a.nxh = nx / 2;
+        a.logL = logN1; a.NT = (int)((N1 * C) / EPT); a.tw = tw_y; a.logTw = logNy; a.in_ns = N2; a.out_gs = N1; a.twiddle = (logN2 > 0) ? 1 : 0;
+        q.col_grf(tiles, (int)N2, a.NT, ((size_t)N1 * C + tw_lds_size(logN1) + N1) * sizeof(cx<T>), a, nreal);
+        cols(q, out, kp, out, kp, width, true, (T)1, 2, 1, nullptr, nullptr, 0, false, -1, nreal, zstride, zstride);
+    }
+
     // (A) legs + inverse column transform of the three leg planes (outputs ready for rows_qe)
     template <class Launcher>
     void legs_cols(Launcher& q, const cx<T>* kX, const cx<T>* kY, const T* FG, const T* FH, const T* lxd, const T* lyd,

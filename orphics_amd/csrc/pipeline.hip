@@ -73,6 +73,7 @@ struct Pipeline {
     DevBuf rdn0_pool;                 // 2 MC_BATCH_MAX drawn hc planes | 2 MC_BATCH_MAX kappa planes | the partial sums of the tail (rdn0.hpp)
     unsigned long rdn0_gen = 0;       // bind_gen the data legs were made under (0: no data set) ...
     int rdn0_my = 0;                  // ... and the column grid
+    int rdn0_ran_batched = 0;         // whether the last oa_mc_run_rdn0 / oa_mc_run_rdn0_windowed call ran a batch to its tail (oa_plan_rdn0_batched)
     // oa_rdn0_set_data_mv / oa_mc_run_rdn0_mv (power-of-two plans; the estimator set comes with every call, so the key is its description)
     DevBuf rdn0mv_legs;               // the data triple's distinct leg planes in Rdn0MvSlots' numbering
     DevBuf rdn0mv_pool;               // the 6 drawn hc planes (T, E, B of s, then of s') | the 2 nest kappa planes (A_e, then B_e) | the tail's scratch
@@ -106,6 +107,8 @@ struct Pipeline {
     bool opt_divbin = true;           // moment entries: radial binning + moments in the tail of the single-pass divergence launch
     bool opt_win_fused = true;        // oa_mc_run_windowed: C2R x window -> R2C as one row pass (the real map stays in LDS)
     bool opt_win_fused_set = false;   // ... set by the caller (until then a band-grid plan picks by row length: mixed_mc_run_windowed)
+    int opt_draw_fused = -1;          // oa_mc_run_rdn0_windowed (power-of-two plans): the draws inside inverse column pass 1 (1), oa_grf_hc and
+                                      // the column transform (0), or the measured default (< 0: DRAW_FUSED_DEFAULT)
     // BAND GRID (map sides 2^a 3^b 5^c, p->mixed; include/orphics_amd.h): the one-call TT entries run on an inner power-of-two plan of
     // (bmy, bmx) points that holds inner-layout copies of the filters and bin ids; made by oa_plan_set_filters / oa_plan_set_col_grid
     oa_plan* band = nullptr;
@@ -346,6 +349,7 @@ int oa_plan_set_option(oa_plan* p, int option, int value) {
         case OA_OPT_DIV_BIN: q->opt_divbin = value != 0; return 0;
         case OA_OPT_WIN_FUSED:                     // (< 0: back to the automatic choice of a band-grid plan; pow2 plans: the fused pass)
             q->opt_win_fused = value != 0; q->opt_win_fused_set = value >= 0; return 0;
+        case OA_OPT_DRAW_FUSED: q->opt_draw_fused = value < 0 ? -1 : (value != 0); return 0;
         default: return fail("oa_plan_set_option: unknown option");
     }
 }
@@ -362,6 +366,7 @@ static void band_options(Pipeline* q) {
 }
 }  // namespace oa
 extern "C" {
+int oa_plan_rdn0_batched(const oa_plan* p) { return (p && p->pipe) ? ((const Pipeline*)p->pipe)->rdn0_ran_batched : 0; }
 int oa_plan_rsplit(const oa_plan* p) {
     if (!p || !p->pipe) return 0;
     const Pipeline* q = (const Pipeline*)p->pipe;
@@ -2270,8 +2275,136 @@ int oa_mc_run_rdn0(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, con
     };
     T.source_batch = [=](long i, int B) { return source(i, 2 * B); };
     T.source_one = [=](long i) { return source(i, 2); };
-    T.tail_batch = [=](int B, int* fallback) { return rdn0_batch(r, rq, B, n, S, C, st, fallback); };
+    q->rdn0_ran_batched = 0;
+    T.tail_batch = [=](int B, int* fallback) {
+        const int rc = rdn0_batch(r, rq, B, n, S, C, st, fallback);
+        if (!rc && !*fallback) q->rdn0_ran_batched = 1;
+        return rc;
+    };
     T.tail_one = [=]() { return rdn0_one(r, rq, n, S, C, st); };
+    return mc_tt_loop(T, sim_lo, sim_hi, n, S, C, nullptr, st);
+}
+
+/* oa_mc_run_rdn0_windowed (include/orphics_amd.h): oa_mc_run_rdn0 with the WINDOWED draws of oa_mc_run_windowed as s and s' -- the shard
+ * loop and the tail are oa_mc_run_rdn0's (mc_tt_loop with rdn0_batch / rdn0_one), the source stage is new.  No mean field: s, s' and d are
+ * independent and zero-mean, so neither A nor B has an ensemble mean to subtract.
+ * POWER-OF-TWO PLANS, per batch of B realisations (2 B draws, draw z = stream 2 i + z): the full-plane part in groups of up to six draws
+ * (three realisations) on the plan's six contiguous work planes -- OA_OPT_DRAW_FUSED = 1: ONE pass-1 launch that evaluates the draws at
+ * its load + the in-place pass 2 (oa_grf_hc_icols), then ONE fused row launch C2R x window -> R2C (grid y = draw); 0: per draw oa_grf_hc,
+ * inverse columns, the row pass -- onto compact row planes behind the tail's region of the pool; then the forward column transform of the
+ * 2 B row planes onto the leg band of rdn0_pool's draw planes (six planes per launch).  OA_OPT_WIN_FUSED = 0: one by one, per draw
+ * oa_grf_hc -> oa_fft_c2r_windowed (real map in HBM) -> oa_fft_r2c onto the draw plane.
+ * BAND GRID: mixed_mc_run_windowed's source stage, the 2 B draws through the six N-grid planes of bwin in two halves, the pruned column
+ * DFT onto the inner plan's rdn0_pool draw planes. */
+// the default of OA_OPT_DRAW_FUSED: oa_grf_hc_icols alone measured 5 - 14 us per plane below oa_grf_hc + oa_fft_cols, beyond both 10th - 90th
+// spreads at every measured geometry (profiles/rdn0_windowed.jsonl); the 0 arm is also one by one, so a realisation differs by more
+constexpr bool DRAW_FUSED_DEFAULT = true;
+int oa_mc_run_rdn0_windowed(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, const void* window_real, int64_t* n,
+                            double* S, double* C, void* stream) {
+    static const char* const how = "; or run the host loop of the existing entries (mc.RDN0MonteCarlo with one_call=False)";
+    const std::string who = "oa_mc_run_rdn0_windowed";
+    OA_REQUIRE(p && covsqrt_hc && n && S && C && sim_hi >= sim_lo, who + ": bad argument");
+    OA_REQUIRE(window_real, who + ": NULL window (oa_mc_run_rdn0 is the entry without one)");
+    OA_REQUIRE(p->pow2 || p->mixed, who + ": map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path" + how);
+    OA_REQUIRE(p->pipe && ((Pipeline*)p->pipe)->FG, who + ": no filters bound: call oa_plan_set_filters, oa_plan_set_bins and oa_rdn0_set_data first" + how);
+    Pipeline* q = (Pipeline*)p->pipe;
+    OA_REQUIRE(q->ids, who + ": no bins bound: call oa_plan_set_bins, then oa_rdn0_set_data" + how);
+    OA_REQUIRE(!p->mixed || (q->band && q->band->pipe), who + ": the bound filters have no band grid on this plan (oa_plan_set_filters reports why)" + how);
+    oa_plan* r = p->mixed ? q->band : p;
+    Pipeline* rq = (Pipeline*)r->pipe;
+    OA_REQUIRE(q->rdn0_gen, who + ": no data set: call oa_rdn0_set_data (after oa_plan_set_filters and oa_plan_set_bins)" + how);
+    OA_REQUIRE(q->rdn0_gen == q->bind_gen && q->rdn0_my == rq->my && rq->rdn0_legs.p,
+               who + ": the data legs are stale -- oa_plan_set_filters, oa_plan_set_bins or oa_plan_set_col_grid was called since they were made: "
+                     "call oa_rdn0_set_data again" + how);
+    if (int rc = rdn0_tail_check(who.c_str(), rq->nids, MC_BATCH_MAX)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (p->mixed) band_options(q);
+    if (int rc = rdn0_reserve(r, rq)) return rc;   // (nothing to do after the first call, or after oa_rdn0_set_data with bins bound)
+    char* const draw = rq->rdn0_pool.at();
+    const double inv = 1.0 / ((double)p->ny * p->nx);
+    // a batch is started only where the chain row stage finishes it: with a window the source stage is most of a realisation, and a batch
+    // abandoned at the row stage (mc_tt_loop's fallback) would have run it for up to six realisations in vain
+    const bool chain = qe_rows_chain_ok(r, rq->wl, rq->wk, rq->mrow, rq->my);
+    McTtLoop T{p, r, rq, true, mc_pool_bytes(r, rq, 1), nullptr, nullptr, nullptr, nullptr, 0, false};
+    q->rdn0_ran_batched = 0;
+    T.tail_batch = [=](int B, int* fallback) {
+        const int rc = rdn0_batch(r, rq, B, n, S, C, st, fallback);
+        if (!rc && !*fallback) q->rdn0_ran_batched = 1;
+        return rc;
+    };
+    T.tail_one = [=]() { return rdn0_one(r, rq, n, S, C, st); };
+    if (p->mixed) {
+        const size_t pb = plane_bytes(p), pbi = plane_bytes(r);
+        const long pbe = plane_elems(r), pne = plane_elems(p);
+        // the N-grid planes of oa_mc_run_windowed on this plan (taken on the first windowed call of either entry: one synchronisation)
+        if (int rc = q->bwin.reserve((size_t)MC_BATCH_MAX * pb + std::max(band_maps_scratch_bytes(p, MC_BATCH_MAX, q->wl, q->rl),
+                                                                          band_map_scratch_bytes(p, q->wl, q->rl)))) return rc;
+        char* const full = q->bwin.at();
+        void* const rows = full + (size_t)MC_BATCH_MAX * pb;
+        const bool fused = q->opt_win_fused_set ? q->opt_win_fused : (p->nx > 1200 && band_rows_win_ok(p));     // (mixed_mc_run_windowed's rule)
+        T.batched = fused && chain;
+        auto half = [=](long i, int z0, int nz) {       // draws z0 .. z0 + nz - 1 (nz <= 6) of the batch that starts at realisation i
+            for (int k = 0; k < nz; ++k) {
+                void* pl = full + (size_t)k * pb;
+                if (int rc = oa_grf_hc(p, base_seed, 2 * (uint64_t)i + (uint64_t)(z0 + k), covsqrt_hc, pl, st)) return rc;
+                if (int rc = mixed_cols_inverse(p, pl, pl, st)) return rc;
+            }
+            return band_win_r2c(p, nz, full, pne, window_real, inv, rows, 0, q->wl, q->rl, nullptr, nullptr, draw + (size_t)z0 * pbi, pbe, r->ny, r->kp, st);
+        };
+        T.source_batch = [=](long i, int B) {
+            if (int rc = half(i, 0, B)) return rc;
+            return half(i, B, B);
+        };
+        T.source_one = [=](long i) {
+            if (fused) return half(i, 0, 2);
+            void* tmap = full + pb;                                                  // ny x nx reals fit an hc plane
+            for (int z = 0; z < 2; ++z) {
+                if (int rc = oa_grf_hc(p, base_seed, 2 * (uint64_t)i + (uint64_t)z, covsqrt_hc, full, st)) return rc;
+                if (int rc = oa_fft_c2r_windowed(p, full, tmap, inv, window_real, st)) return rc;
+                if (int rc = band_map_r2c(p, tmap, rows, q->wl, q->rl, draw + (size_t)z * pbi, r->ny, r->kp, st)) return rc;
+            }
+            return 0;
+        };
+        return mc_tt_loop(T, sim_lo, sim_hi, n, S, C, nullptr, st);
+    }
+    const long pl = work_pitch(p, q->wl);
+    const size_t es = elem_bytes(p), lb = (size_t)pl * p->ny * es, pb = plane_bytes(p);
+    const bool fused = q->opt_win_fused;
+    const bool dfused = fused && (q->opt_draw_fused < 0 ? DRAW_FUSED_DEFAULT : q->opt_draw_fused != 0);
+    T.batched = fused && chain;
+    T.pool_extra = mc_pool_bytes(p, q, 1) + 2 * lb;        // the tail's region, then the 2 B compact row planes of the batch
+    if (int rc = ensure_pool(q, (size_t)MC_BATCH_MAX * T.pool_extra + mc_pool_bytes(p, q, MC_BATCH_MAX))) return rc;      // (first call only)
+    char* const full = (char*)q->c[0];                     // c[0..2], g[0..1], kT: six contiguous hc planes, free until the tail
+    auto source = [=](long i, int B) {
+        char* const rowT = q->split_legs.at(2 * mc_pool_bytes(p, q, B));
+        const int nd = 2 * B;
+        for (int z0 = 0; z0 < nd; z0 += MC_BATCH_MAX) {
+            const int nz = std::min(MC_BATCH_MAX, nd - z0);
+            const uint64_t sid = 2 * (uint64_t)i + (uint64_t)z0;
+            if (dfused) {
+                if (int rc = grf_icols_w(p, base_seed, sid, nz, covsqrt_hc, full, plane_elems(p), st)) return rc;
+                if (int rc = qe_win_rows_w(p, full, window_real, q->wl, pl, inv, st, rowT + (size_t)z0 * lb, nz, plane_elems(p), (long)(lb / es))) return rc;
+            } else {
+                for (int k = 0; k < nz; ++k) {
+                    if (int rc = oa_grf_hc(p, base_seed, sid + (uint64_t)k, covsqrt_hc, q->kT, st)) return rc;
+                    if (int rc = qe_windowed_rows_w(p, q->kT, full, window_real, q->wl, pl, inv, st, rowT + (size_t)(z0 + k) * lb)) return rc;
+                }
+            }
+            if (int rc = qe_fwd_cols_batch_w(p, rowT + (size_t)z0 * lb, pl, draw + (size_t)z0 * pb, nz, (long)(lb / es), plane_elems(p), q->wl, q->rl, st)) return rc;
+        }
+        return 0;
+    };
+    T.source_batch = source;
+    T.source_one = [=](long i) {
+        if (fused) return source(i, 1);
+        void* tmap = q->c[0];
+        for (int z = 0; z < 2; ++z) {
+            if (int rc = oa_grf_hc(p, base_seed, 2 * (uint64_t)i + (uint64_t)z, covsqrt_hc, q->kT, st)) return rc;
+            if (int rc = oa_fft_c2r_windowed(p, q->kT, tmap, inv, window_real, st)) return rc;
+            if (int rc = oa_fft_r2c(p, tmap, draw + (size_t)z * pb, 1.0, q->wl, q->rl, st)) return rc;
+        }
+        return 0;
+    };
     return mc_tt_loop(T, sim_lo, sim_hi, n, S, C, nullptr, st);
 }
 

@@ -486,7 +486,7 @@ class Engine(object):
 
     # ---- QE legs --------------------------------------------------------------------
     # oa_plan_set_option (include/orphics_amd.h): equivalent launch sequences of the one-call entries of THIS plan
-    OPTIONS = {"mc_batch": 1, "mv_batch": 2, "mv_rowbatch": 3, "mv_chain": 4, "div_bin": 5, "win_fused": 6}
+    OPTIONS = {"mc_batch": 1, "mv_batch": 2, "mv_rowbatch": 3, "mv_chain": 4, "div_bin": 5, "win_fused": 6, "draw_fused": 7}
 
     def set_option(self, name, value):
         if name not in self.OPTIONS:
@@ -616,6 +616,25 @@ class Engine(object):
         else:
             _dirty(self._chk(out, "hc"))
         check(self.lib.oa_grf_hc_band(self.plan, int(seed), int(stream_id), _ptr(covsqrt_hc), _ptr(out), int(width), int(rband), _stream()))
+        return out
+
+    def grf_hc_icols(self, seed, stream_id, covsqrt_hc=None, nreal=1, out=None):
+        """``oa_grf_hc_icols``: ``nreal`` draws (streams ``stream_id`` .. ``stream_id + nreal - 1``) evaluated inside the load of the
+        inverse column pass -- plane z of the ``(nreal, Ny, kp)`` result is bit for bit ``fft_cols(grf_hc(seed, stream_id + z, covsqrt_hc),
+        inverse=True, width=nx/2 + 1)``, and the drawn planes are never stored.  Power-of-two plans only."""
+        if covsqrt_hc is not None:
+            self._chk(covsqrt_hc, "hcreal")
+        nreal = int(nreal)
+        if nreal < 1:
+            raise ValueError("grf_hc_icols: nreal >= 1")
+        shp = (nreal, self.ny, self.kp)
+        if out is None:
+            out = torch.zeros(shp, dtype=self.cdt, device=self.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and tuple(out.shape) == shp and out.dtype == self.cdt and out.is_contiguous()):
+            raise ValueError("grf_hc_icols: out must be a contiguous %s CUDA tensor of shape %s" % (self.cdt, shp))
+        else:
+            _dirty(out)
+        check(self.lib.oa_grf_hc_icols(self.plan, int(seed), int(stream_id), nreal, _ptr(covsqrt_hc), _ptr(out), self.ny * self.kp, _stream()))
         return out
 
     def grf_mix(self, seed, covsqrt_hc, rot=None, inputs=None, filt=None, scale=1.0, out=None, stream_id0=0):

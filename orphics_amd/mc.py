@@ -792,10 +792,22 @@ class RDN0MonteCarlo(object):
     -> ``Statistics.add``.  ``one_call=True`` raises where there is no one-call path (chirp-z sides, unbounded filters, a band grid not
     smaller than the map).
 
-    There is no ``window`` argument: simulations that carry the data's apodisation taper (and the mean field that comes with it) are
-    not part of this driver yet; it serves periodic / untapered maps, as the unwindowed N0 drivers do."""
+    ``window``: an ``(Ny, Nx)`` real-space apodisation applied to every SIMULATION before its transform, as ``GaussianN0MonteCarlo``'s:
+    ``s = R2C(window . C2R(draw) / Npix)`` from the full-plane draw of stream ``2 i``, ``s'`` the same from stream ``2 i + 1``.  ``data``
+    is taken as given -- the map as analysed, i.e. ALREADY apodised by the caller; the driver never multiplies it by the window.
+    ``window_moments`` = (mean w^2, mean w^4): the bandpowers of kappa_hat are quadratic in two maps and carry mean(w^4), which
+    :meth:`debiased` divides out.  With a window the data's own reconstruction has a mean field; the simulations' ``A`` and ``B`` have
+    none (``s``, ``s'`` and ``d`` are independent and zero-mean), so it enters only :meth:`data_bandpowers` (``mean_field=``).
+    With a window ``one_call=None`` takes the one call (``oa_mc_run_rdn0_windowed``) on both classes of sides that have one --
+    power-of-two sides and the band grid of sides 2^a 3^b 5^c -- because it measured faster than the host loop at every measured geometry
+    of either (2.5 to 3.5 times at 2048^2 and 4096^2, 1.3 to 1.5 times at 1200^2 and 2400^2: profiles/rdn0_windowed.jsonl), and the host
+    loop elsewhere (chirp-z sides, no band grid);
+    ``one_call=False`` is the host loop on any side -- ``Engine.grf_hc`` (full plane) -> ``Engine.irfft`` ->
+    x window -> ``Engine.rfft`` for both draws, then the sequence above; ``one_call=True`` raises where there is no one-call path.
+    Without ``window`` the class behaves exactly as before it had the argument.  The polarisation / MV driver,
+    :class:`RDN0MonteCarloPol`, has no ``window`` argument yet."""
 
-    def __init__(self, qest, data, total_power_half, bin_edges, comm=None, base_seed=1234, one_call=None):
+    def __init__(self, qest, data, total_power_half, bin_edges, comm=None, base_seed=1234, one_call=None, window=None):
         torch = _torch()
         self.q = qest
         self.eng = e = qest.eng
@@ -818,6 +830,15 @@ class RDN0MonteCarlo(object):
                                   % (e.ny, e.nx))
         self.one_call = avail if one_call is None else bool(one_call)
         self._host = None
+        self._hostw = None                    # (the full-plane draw and the real map of the windowed host loop)
+        self.window = None
+        self.window_moments = (1.0, 1.0)
+        if window is not None:
+            w = np.asarray(window, dtype=np.float64)
+            if w.shape != (e.ny, e.nx):
+                raise ValueError("window must be a (Ny, Nx) real-space array")
+            self.window = e.to_real(w)
+            self.window_moments = (float(np.mean(w ** 2)), float(np.mean(w ** 4)))
         self.set_data(data)
 
     def set_data(self, data):
@@ -853,17 +874,31 @@ class RDN0MonteCarlo(object):
         """sample covariance of the whole ``2 d`` vector (rdn0 block, mcn0 block and their cross block)."""
         return self.acc.cov("rdn0")
 
-    def data_bandpowers(self):
-        """``p(QE(d, d))``: the bandpowers of the data's own reconstruction, with the driver's bins."""
+    def data_bandpowers(self, mean_field=None):
+        """``p(QE(d, d) - mean_field)``: the bandpowers of the data's own reconstruction, with the driver's bins.  ``mean_field``: a
+        complex hc tensor of kappa_hat's layout, or the ``(Ny, kp, 2)`` interleaved (re, im) stack mean that
+        ``GaussianN0MonteCarlo(window=..., mean_field=True)`` accumulates (``acc.stack_mean("mf")``); None subtracts nothing."""
+        torch = _torch()
         q, e = self.q, self.eng
         kap = q.reconstruct_tt_hc(self.kd)
+        if mean_field is not None:
+            m = mean_field if isinstance(mean_field, torch.Tensor) else torch.as_tensor(np.asarray(mean_field))
+            m = m.to(e.device)
+            if not m.is_complex():
+                if tuple(m.shape) != (e.ny, e.kp, 2):
+                    raise ValueError("mean_field must be a complex (Ny, kp) hc tensor or a real (Ny, kp, 2) stack mean")
+                m = torch.view_as_complex(m.to(torch.float64).contiguous())
+            if tuple(m.shape) != (e.ny, e.kp):
+                raise ValueError("mean_field must be a complex (Ny, kp) hc tensor or a real (Ny, kp, 2) stack mean")
+            kap = kap - m.to(e.cdt)
         s, _ = e.bin_power(kap, kap, self.norm, self.ids, self.nids, herm=True, active_cols=q.kappa_cols, active_rows=q.kappa_rows)
         return (s[1:-1] / self._counts()).cpu().numpy()
 
-    def debiased(self, data_bandpowers=None):
-        """``data_bandpowers - rdn0()`` (``data_bandpowers=None``: :meth:`data_bandpowers`)."""
-        p = self.data_bandpowers() if data_bandpowers is None else np.asarray(data_bandpowers, dtype=np.float64)
-        return p - self.rdn0()
+    def debiased(self, data_bandpowers=None, mean_field=None):
+        """``(data_bandpowers - rdn0()) / window_moments[1]`` (``data_bandpowers=None``: :meth:`data_bandpowers` with ``mean_field``); the
+        divisor mean(w^4) is 1 without a window."""
+        p = self.data_bandpowers(mean_field) if data_bandpowers is None else np.asarray(data_bandpowers, dtype=np.float64)
+        return (p - self.rdn0()) / self.window_moments[1]
 
     @property
     def centers(self):
@@ -886,8 +921,18 @@ class RDN0MonteCarlo(object):
             self._host = (e.hc(), e.hc(), q.new_output(), q.new_output())
         s0, s1, ka, kb = self._host
         wl, rl = (q.leg_cols, q.leg_rows) if (q.leg_cols and q.leg_rows) else (0, 0)
-        e.grf_hc(self.base_seed, 2 * i, self.cs, out=s0, width=wl, rband=rl)
-        e.grf_hc(self.base_seed, 2 * i + 1, self.cs, out=s1, width=wl, rband=rl)
+        if self.window is not None:            # the full-plane draws of oa_mc_run_windowed, windowed in real space
+            if self._hostw is None:
+                self._hostw = (e.hc(), e.real())
+            draw, tmap = self._hostw
+            for z, dst in ((0, s0), (1, s1)):
+                e.grf_hc(self.base_seed, 2 * i + z, self.cs, out=draw)
+                e.irfft(draw, out=tmap)
+                tmap.mul_(self.window)
+                e.rfft(tmap, out=dst)
+        else:
+            e.grf_hc(self.base_seed, 2 * i, self.cs, out=s0, width=wl, rband=rl)
+            e.grf_hc(self.base_seed, 2 * i + 1, self.cs, out=s1, width=wl, rband=rl)
         ka = q.reconstruct_tt_sym_hc(self.kd, s0, out=ka)
         kb = q.reconstruct_tt_sym_hc(s0, s1, out=kb)
         region = dict(active_cols=q.kappa_cols, active_rows=q.kappa_rows)
@@ -897,7 +942,7 @@ class RDN0MonteCarlo(object):
 
     def run_local(self, sims):
         """Process the given global realisation indices on this rank's GPU: every contiguous block of indices is ONE ``oa_mc_run_rdn0``
-        call (one-call path), or one :meth:`sample_host` + ``Statistics.add`` per index (host loop)."""
+        call (``oa_mc_run_rdn0_windowed`` with a window; one-call path), or one :meth:`sample_host` + ``Statistics.add`` per index (host loop)."""
         from ._lib import check
         from .engine import _ptr, _stream
         sims = [int(i) for i in sims]
@@ -917,7 +962,11 @@ class RDN0MonteCarlo(object):
         start = prev = sims[0]
         for i in sims[1:] + [None]:
             if i is None or i != prev + 1:
-                check(e.lib.oa_mc_run_rdn0(e.plan, self.base_seed, start, prev + 1, _ptr(self.cs), _ptr(n), _ptr(S), _ptr(C), _stream()))
+                if self.window is not None:
+                    check(e.lib.oa_mc_run_rdn0_windowed(e.plan, self.base_seed, start, prev + 1, _ptr(self.cs), _ptr(self.window), _ptr(n), _ptr(S),
+                                                        _ptr(C), _stream()))
+                else:
+                    check(e.lib.oa_mc_run_rdn0(e.plan, self.base_seed, start, prev + 1, _ptr(self.cs), _ptr(n), _ptr(S), _ptr(C), _stream()))
                 start = i
             prev = i
         self.acc.note_samples("rdn0", len(sims))
