@@ -1072,6 +1072,19 @@ static size_t mc_pool_bytes(const oa_plan* p, const Pipeline* q, int B) {
     const size_t es = elem_bytes(p);
     return 3 * (size_t)B * work_pitch(p, q->wl) * p->ny * es + 4 * (size_t)B * work_pitch(p, q->wk) * p->ny * es;
 }
+// B realisations through the bound (FG, FH) in one qe_legs_batch_w launch: its filter pointer table (FG x B, FH x B in q->mv_ftab, which the
+// caller has allocated; uploaded when it differs from the table there) and its field selector
+static int batch_filters(Pipeline* q, int B, hipStream_t st, unsigned long long* sel) {
+    std::vector<const void*> key(2 * (size_t)B, q->FH);
+    std::fill_n(key.begin(), B, q->FG);
+    if (key != q->mv_fkey) {
+        OA_HIP(hipMemcpyAsync(q->mv_ftab, key.data(), key.size() * sizeof(void*), hipMemcpyHostToDevice, st));
+        q->mv_fkey = key;
+    }
+    *sel = 0;                                         // field f (gradient fields 0..B-1, H fields B..2B-1) reads source plane f mod B
+    for (int f = 0; f < 2 * B; ++f) *sel |= (unsigned long long)(f % B) << (4 * f);
+    return 0;
+}
 /* Everything behind the transforms of a BATCH of B realisations (q->mc_src: their hc planes, leg band filled): leg planes, row
  * stage, divergence, binned power + moments in realisation order, mean-field stack -- each ONE launch for the batch (oa_mc_run and,
  * behind its windowed front end, oa_mc_run_windowed).  *fallback = 1: this geometry's row stage takes one map per launch (nothing
@@ -1087,16 +1100,9 @@ static int mc_batch_tail(oa_plan* p, Pipeline* q, int B, int64_t* n, double* S, 
     char* const legs = q->split_legs.at();
     char* const prod = legs + 3 * (size_t)B * lb;
     char* const tmp = prod + 2 * (size_t)B * lbk;
-    std::vector<const void*> key;
-    for (int b = 0; b < B; ++b) key.push_back(q->FG);
-    for (int b = 0; b < B; ++b) key.push_back(q->FH);
+    unsigned long long sel;
     if (!q->mv_ftab) OA_HIP(hipMalloc((void**)&q->mv_ftab, 32 * sizeof(void*)));
-    if (key != q->mv_fkey) {
-        OA_HIP(hipMemcpyAsync(q->mv_ftab, key.data(), key.size() * sizeof(void*), hipMemcpyHostToDevice, st));
-        q->mv_fkey = key;
-    }
-    unsigned long long sel = 0;                       // field f (gradient fields 0..B-1, H fields B..2B-1) reads realisation f mod B
-    for (int f = 0; f < 2 * B; ++f) sel |= (unsigned long long)(f % B) << (4 * f);
+    if (int rc = batch_filters(q, B, st, &sel)) return rc;
     // (the row stage's geometry check first: nothing may have been launched when this batch falls back)
     const double s = 1.0 / ((double)p->ny * p->nx), sy = my ? (double)p->ny / my : 1.0;
     int legs_done = 0, rc;
@@ -1328,48 +1334,106 @@ static int mixed_mc_run(oa_plan* p, Pipeline* q, uint64_t base_seed, long sim_lo
     T.source_one = [=](long i) { return grf_band_inner(p, base_seed, (uint64_t)i, 1, covsqrt_hc, bx, b->ny, b->kp, 0, q->wl, q->rl, st); };
     return mc_tt_loop(T, sim_lo, sim_hi, n, S, C, meanfield_acc, st);
 }
-// oa_mc_run_windowed on a band grid: per realisation the full-plane draw on the N grid and its inverse column transform (in place); per
-// batch ONE fused windowed row launch (C2R x window -> R2C, columns < wl stored: band_rows_win_kernel) and the pruned column DFT onto the
-// band plan's source planes.  OA_OPT_WIN_FUSED = 0: one by one, C2R with the window at the row store -> real map in HBM -> band_map_r2c.
+/* ---- WINDOWED TT DRAWS: the source stage of oa_mc_run_windowed (realisation i = Philox stream i) and of oa_mc_run_rdn0_windowed (s, s' of
+ * realisation i = streams 2 i, 2 i + 1).  A draw is the full-plane draw of its stream on the map's grid (oa_grf_hc: key (seed, stream), the
+ * counters of every other draw) -> C2R / Npix -> x window -> R2C, of which only the leg band is kept, on a plane of the plan the estimator
+ * runs on.  FUSED (one method per plan kind, `nd` consecutive streams onto planes a fixed stride apart, the full-plane part in groups of
+ * at most MC_BATCH_MAX = the work planes there are): the real map exists in LDS only.
+ *   band():  per draw oa_grf_hc into an N-grid plane of bwin + its inverse column transform in place (mixed_cols_inverse); per group ONE
+ *     fused row launch (C2R x window -> R2C, columns < wl stored: band_rows_win_kernel) and the pruned column DFT onto the inner planes
+ *     (band_win_r2c).  band_open() first: it owns bwin and the fused / unfused rule.
+ *   pow2():  on c[0..2], g[0..1], kT, the plan's six contiguous work planes, free until the tail -- dfused: ONE inverse pass-1 launch that
+ *     evaluates the group's draws at its load + the in-place pass 2 (oa_grf_hc_icols), then ONE fused row launch (grid y = draw); else per
+ *     draw oa_grf_hc into kT, inverse columns into c[0], the fused row pass -- onto compact row planes at `rowT` (the caller's place in the
+ *     pool); then per group ONE forward column transform onto the leg band of the destination planes.
+ * UNFUSED (band_map(), pow2_map(): one draw): oa_grf_hc -> C2R with the window at the row store -> real map in HBM -> its transform. */
+// the default of OA_OPT_DRAW_FUSED: oa_grf_hc_icols alone measured 5 - 14 us per plane below oa_grf_hc + oa_fft_cols, beyond both 10th - 90th
+// spreads at every measured geometry (profiles/rdn0_windowed.jsonl, DESIGN 5b); the 0 arm is also one by one, so a realisation differs by more
+constexpr bool DRAW_FUSED_DEFAULT = true;
+struct WinDraws {
+    oa_plan* p; Pipeline* q; uint64_t seed; const void* cs; const void* window; hipStream_t st;
+    bool fused = false, dfused = false;             // the fused row pass; the draw inside the column pass (pow2() only)
+    double inv() const { return 1.0 / ((double)p->ny * p->nx); }
+    char* rows() const { return q->bwin.at((size_t)MC_BATCH_MAX * plane_bytes(p)); }      // bwin: MC_BATCH_MAX N-grid planes | row scratch
+
+    int band_open() {
+        // entry-owned planes, taken on the first windowed call of either entry (and regrown when the band widens): that call synchronises
+        // the device once
+        if (int rc = q->bwin.reserve((size_t)MC_BATCH_MAX * plane_bytes(p) + std::max(band_maps_scratch_bytes(p, MC_BATCH_MAX, q->wl, q->rl),
+                                                                                     band_map_scratch_bytes(p, q->wl, q->rl)))) return rc;
+        // fused row pass or the unfused flow: the caller's OA_OPT_WIN_FUSED; until it is set, what measured faster (DESIGN 5a,
+        // profiles/band_grid_windowed.jsonl): the unfused flow at 1200^2 (by 1 % f32, 5 % f64), the fused pass at 2400^2 (by up to 1 %)
+        // (rows the fused kernel does not hold -- more than 8192 points -- take the unfused flow, whose row passes have an in-place form)
+        fused = q->opt_win_fused_set ? q->opt_win_fused : (p->nx > 1200 && band_rows_win_ok(p));
+        return 0;
+    }
+    // `single` (nd = 1): band_win_r2c's column kernels of one map
+    int band(uint64_t s0, int nd, void* dst, long dstride, int single = 0) const {
+        const oa_plan* b = q->band;
+        const size_t pb = plane_bytes(p);
+        char* const full = q->bwin.at();
+        for (int z0 = 0; z0 < nd; z0 += MC_BATCH_MAX) {
+            const int nz = std::min(MC_BATCH_MAX, nd - z0);
+            for (int k = 0; k < nz; ++k) {
+                void* pl = full + (size_t)k * pb;
+                if (int rc = oa_grf_hc(p, seed, s0 + (uint64_t)(z0 + k), cs, pl, st)) return rc;
+                if (int rc = mixed_cols_inverse(p, pl, pl, st)) return rc;
+            }
+            if (int rc = band_win_r2c(p, nz, full, plane_elems(p), window, inv(), rows(), single, q->wl, q->rl, nullptr, nullptr,
+                                      (char*)dst + (size_t)z0 * dstride * elem_bytes(b), dstride, b->ny, b->kp, st)) return rc;
+        }
+        return 0;
+    }
+    int band_map(uint64_t s, void* dst) const {
+        char* const full = q->bwin.at();
+        void* tmap = full + plane_bytes(p);                                      // ny x nx reals fit an hc plane
+        if (int rc = oa_grf_hc(p, seed, s, cs, full, st)) return rc;
+        if (int rc = oa_fft_c2r_windowed(p, full, tmap, inv(), window, st)) return rc;
+        return band_map_r2c(p, tmap, rows(), q->wl, q->rl, dst, q->band->ny, q->band->kp, st);
+    }
+    // dst = nullptr (one draw, not dfused): no Fourier plane -- the row transform stays on the plan's scratch plane, for qe_tt_impl(rows_done)
+    int pow2(uint64_t s0, int nd, char* rowT, void* dst) const {
+        const long pl = work_pitch(p, q->wl), pe = plane_elems(p);
+        const size_t es = elem_bytes(p), lb = (size_t)pl * p->ny * es;
+        char* const full = (char*)q->c[0];
+        for (int z0 = 0; z0 < nd; z0 += MC_BATCH_MAX) {
+            const int nz = std::min(MC_BATCH_MAX, nd - z0);
+            if (dfused) {
+                if (int rc = grf_icols_w(p, seed, s0 + (uint64_t)z0, nz, cs, full, pe, st)) return rc;
+                if (int rc = qe_win_rows_w(p, full, window, q->wl, pl, inv(), st, rowT + (size_t)z0 * lb, nz, pe, (long)(lb / es))) return rc;
+            } else {
+                for (int k = 0; k < nz; ++k) {
+                    if (int rc = oa_grf_hc(p, seed, s0 + (uint64_t)(z0 + k), cs, q->kT, st)) return rc;
+                    if (int rc = qe_windowed_rows_w(p, q->kT, full, window, q->wl, pl, inv(), st, dst ? rowT + (size_t)(z0 + k) * lb : nullptr)) return rc;
+                }
+            }
+            if (!dst) continue;
+            if (int rc = qe_fwd_cols_batch_w(p, rowT + (size_t)z0 * lb, pl, (char*)dst + (size_t)z0 * pe * es, nz, (long)(lb / es), pe, q->wl, q->rl, st))
+                return rc;
+        }
+        return 0;
+    }
+    // dst = nullptr: the real map stays in c[0] (the first leg plane, which the from-map estimator overwrites only after its row pass)
+    int pow2_map(uint64_t s, void* dst) const {
+        if (int rc = oa_grf_hc(p, seed, s, cs, q->kT, st)) return rc;
+        if (int rc = oa_fft_c2r_windowed(p, q->kT, q->c[0], inv(), window, st)) return rc;
+        return dst ? oa_fft_r2c(p, q->c[0], dst, 1.0, q->wl, q->rl, st) : 0;
+    }
+};
+// oa_mc_run_windowed on a band grid: WinDraws::band onto the band plan's source planes, batched where the row pass is fused
 static int mixed_mc_run_windowed(oa_plan* p, Pipeline* q, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, const void* window,
                                  int64_t* n, double* S, double* C, double* meanfield_acc, hipStream_t st) {
     oa_plan* b = q->band;
     Pipeline* qb = (Pipeline*)b->pipe;
     band_options(q);
-    const size_t pb = plane_bytes(p);
-    const long pbe = plane_elems(b), pne = plane_elems(p);
-    // entry-owned planes, taken on the first windowed call (and regrown when the band widens): that call synchronises the device once
-    if (int rc = q->bwin.reserve((size_t)MC_BATCH_MAX * pb + std::max(band_maps_scratch_bytes(p, MC_BATCH_MAX, q->wl, q->rl),
-                                                                      band_map_scratch_bytes(p, q->wl, q->rl)))) return rc;
-    char* const draw = q->bwin.at();
-    void* const rows = draw + (size_t)MC_BATCH_MAX * pb;
+    WinDraws W{p, q, base_seed, covsqrt_hc, window, st};
+    if (int rc = W.band_open()) return rc;
     void* const bx = band_in(q, 0);
-    const double inv = 1.0 / ((double)p->ny * p->nx);
-    // fused row pass or the unfused flow: the caller's OA_OPT_WIN_FUSED; until it is set, what measured faster (DESIGN 5a,
-    // profiles/band_grid_windowed.jsonl): the unfused flow at 1200^2 (by 1 % f32, 5 % f64), the fused pass at 2400^2 (by up to 1 %)
-    // (rows the fused kernel does not hold -- more than 8192 points -- take the unfused flow, whose row passes have an in-place form)
-    const bool fused = q->opt_win_fused_set ? q->opt_win_fused : (p->nx > 1200 && band_rows_win_ok(p));
     // (an inner plan whose row stage takes one map per launch -- row grids below 1024 points -- abandons its first batch of every call
     // after the front end has run: about 1 % of a 300-realisation call)
-    McTtLoop T{p, b, qb, fused, 0, nullptr, nullptr, nullptr, bx, 0, false};
-    T.source_batch = [=](long i, int B) {
-        for (int k = 0; k < B; ++k) {
-            void* pl = draw + (size_t)k * pb;
-            if (int rc = oa_grf_hc(p, base_seed, (uint64_t)(i + k), covsqrt_hc, pl, st)) return rc;
-            if (int rc = mixed_cols_inverse(p, pl, pl, st)) return rc;
-        }
-        return band_win_r2c(p, B, draw, pne, window, inv, rows, 0, q->wl, q->rl, nullptr, nullptr, qb->mc_src.p, pbe, b->ny, b->kp, st);
-    };
-    T.source_one = [=](long i) {
-        if (int rc = oa_grf_hc(p, base_seed, (uint64_t)i, covsqrt_hc, draw, st)) return rc;
-        if (fused) {
-            if (int rc = mixed_cols_inverse(p, draw, draw, st)) return rc;
-            return band_win_r2c(p, 1, draw, pne, window, inv, rows, 1, q->wl, q->rl, nullptr, nullptr, bx, 0, b->ny, b->kp, st);
-        }
-        void* tmap = draw + pb;                                                  // ny x nx reals fit an hc plane
-        if (int rc = oa_fft_c2r_windowed(p, draw, tmap, inv, window, st)) return rc;
-        return band_map_r2c(p, tmap, rows, q->wl, q->rl, bx, b->ny, b->kp, st);
-    };
+    McTtLoop T{p, b, qb, W.fused, 0, nullptr, nullptr, nullptr, bx, 0, false};
+    T.source_batch = [=](long i, int B) { return W.band((uint64_t)i, B, qb->mc_src.p, plane_elems(b)); };
+    T.source_one = [=](long i) { return W.fused ? W.band((uint64_t)i, 1, bx, 0, 1) : W.band_map((uint64_t)i, bx); };
     return mc_tt_loop(T, sim_lo, sim_hi, n, S, C, meanfield_acc, st);
 }
 /* ---- oa_rdn0_set_data / oa_mc_run_rdn0: the realisation-dependent N0 shard (include/orphics_amd.h) ------------------------------------
@@ -1420,17 +1484,10 @@ static int rdn0_batch(oa_plan* r, Pipeline* rq, int B, int64_t* n, double* S, do
     const long pl = work_pitch(r, rq->wl), pk = work_pitch(r, rq->wk);
     const size_t es = elem_bytes(r), lb = P.lb, lbk = P.lbk;
     const int my = rq->my;
-    std::vector<const void*> fkey;
-    for (int b = 0; b < B; ++b) fkey.push_back(rq->FG);
-    for (int b = 0; b < B; ++b) fkey.push_back(rq->FH);
-    if (fkey != rq->mv_fkey) {
-        OA_HIP(hipMemcpyAsync(rq->mv_ftab, fkey.data(), fkey.size() * sizeof(void*), hipMemcpyHostToDevice, st));
-        rq->mv_fkey = fkey;
-    }
-    unsigned long long sel = 0;                       // field f of a leg launch (gradient fields 0..B-1, H fields B..2B-1) reads its draw f mod B
-    for (int f = 0; f < 2 * B; ++f) sel |= (unsigned long long)(f % B) << (4 * f);
+    unsigned long long sel;                           // (the table itself is rdn0_reserve's)
     int legs_done = 0, rc;
-    for (int c = 0; c < 2; ++c)                       // draws [c B, (c + 1) B) -> leg planes [3 c B, 3 (c + 1) B): gx, gy of draw z' at 2 z', 2 z' + 1, h at 2 B + z'
+    if ((rc = batch_filters(rq, B, st, &sel))) return rc;
+    for (int c = 0; c < 2; ++c)                      // draws [c B, (c + 1) B) -> leg planes [3 c B, 3 (c + 1) B): gx, gy of draw z' at 2 z', 2 z' + 1, h at 2 B + z'
         if ((rc = qe_legs_batch_w(r, P.draw + (size_t)c * B * P.pb, plane_elems(r), 0, sel, (const void* const*)rq->mv_ftab, B, B,
                                   P.legs + 3 * (size_t)c * B * lb, (long)(lb / es), rq->wl, rq->rl, pl, st, my, 4, &legs_done))) return rc;
     if (!legs_done && (rc = qe_legs_pass2_w(r, P.legs, 6 * B, (long)(lb / es), rq->wl, pl, st, my))) return rc;
@@ -1488,6 +1545,40 @@ static int rdn0_one(oa_plan* r, Pipeline* rq, int64_t* n, double* S, double* C, 
         if ((rc = qe_cols_div_w(r, rq->g[0], rq->g[1], rq->Fn, P.kappa + (size_t)e * P.pb, 0, rq->wk, rq->rk, pk, st, my))) return rc;
     }
     return rdn0_tail_of(r, rq, P, 1, n, S, C, st);
+}
+static const char* const RDN0_HOW = "run the host loop of the existing entries (mc.RDN0MonteCarlo with one_call=False)";
+/* The opening of entry `who` (oa_mc_run_rdn0, oa_mc_run_rdn0_windowed): every refusal -- `refuse`, where not NULL, is the entry's own, said
+ * right after the argument check --, then the plan the estimator runs on and its planes (rdn0_reserve: nothing to do after the first call, or
+ * after oa_rdn0_set_data with bins bound), and *T = a batched McTtLoop on that plan with rdn0_batch / rdn0_one as its tail; the entry adds
+ * its source stage.  Nothing has been launched when it refuses. */
+static int rdn0_tt_open(const char* who, const char* refuse, oa_plan* p, long sim_lo, long sim_hi, const void* covsqrt_hc, int64_t* n, double* S,
+                        double* C, hipStream_t st, McTtLoop* T) {
+    auto msg = [who](const char* what, bool how = true) { return std::string(who) + ": " + what + (how ? std::string("; or ") + RDN0_HOW : ""); };
+    OA_REQUIRE(p && covsqrt_hc && n && S && C && sim_hi >= sim_lo, msg("bad argument", false));
+    OA_REQUIRE(!refuse, msg(refuse, false));
+    OA_REQUIRE(p->pow2 || p->mixed, msg("map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path"));
+    OA_REQUIRE(p->pipe && ((Pipeline*)p->pipe)->FG, msg("no filters bound: call oa_plan_set_filters, oa_plan_set_bins and oa_rdn0_set_data first"));
+    Pipeline* q = (Pipeline*)p->pipe;
+    OA_REQUIRE(q->ids, msg("no bins bound: call oa_plan_set_bins, then oa_rdn0_set_data"));
+    OA_REQUIRE(!p->mixed || (q->band && q->band->pipe), msg("the bound filters have no band grid on this plan (oa_plan_set_filters reports why)"));
+    oa_plan* r = p->mixed ? q->band : p;
+    Pipeline* rq = (Pipeline*)r->pipe;
+    OA_REQUIRE(q->rdn0_gen, msg("no data set: call oa_rdn0_set_data (after oa_plan_set_filters and oa_plan_set_bins)"));
+    OA_REQUIRE(q->rdn0_gen == q->bind_gen && q->rdn0_my == rq->my && rq->rdn0_legs.p,
+               msg("the data legs are stale -- oa_plan_set_filters, oa_plan_set_bins or oa_plan_set_col_grid was called since they were made: "
+                   "call oa_rdn0_set_data again"));
+    if (int rc = rdn0_tail_check(who, rq->nids, MC_BATCH_MAX)) return rc;
+    if (p->mixed) band_options(q);
+    if (int rc = rdn0_reserve(r, rq)) return rc;
+    *T = McTtLoop{p, r, rq, true, mc_pool_bytes(r, rq, 1), nullptr, nullptr, nullptr, nullptr, 0, false};
+    q->rdn0_ran_batched = 0;
+    T->tail_batch = [=](int B, int* fallback) {
+        const int rc = rdn0_batch(r, rq, B, n, S, C, st, fallback);
+        if (!rc && !*fallback) q->rdn0_ran_batched = 1;
+        return rc;
+    };
+    T->tail_one = [=]() { return rdn0_one(r, rq, n, S, C, st); };
+    return 0;
 }
 /* ---- oa_qe_pol / oa_qe_mv on the band grid -------------------------------------------------------------------------------------------
  * These entries take their filter planes per call, so the inner-layout copies are made by a set-up entry (oa_qe_band_bind, which may
@@ -2216,8 +2307,8 @@ int oa_mc_run(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const vo
  * entry: may allocate and synchronise.  On a band grid the leg band of kD goes to the inner plan's first input plane first. */
 int oa_rdn0_set_data(oa_plan* p, const void* kD_hc, void* stream) {
     OA_REQUIRE(p && kD_hc, "oa_rdn0_set_data: NULL argument");
-    OA_REQUIRE(p->pow2 || p->mixed, "oa_rdn0_set_data: map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path; "
-               "run the host loop of the existing entries (mc.RDN0MonteCarlo with one_call=False)");
+    OA_REQUIRE(p->pow2 || p->mixed, std::string("oa_rdn0_set_data: map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no "
+                                                "one-call path; ") + RDN0_HOW);
     OA_REQUIRE(p->pipe && ((Pipeline*)p->pipe)->FG, "oa_rdn0_set_data: call oa_plan_set_filters first");
     Pipeline* q = (Pipeline*)p->pipe;
     hipStream_t st = (hipStream_t)stream;
@@ -2250,160 +2341,68 @@ int oa_rdn0_set_data(oa_plan* p, const void* kD_hc, void* stream) {
  * (two draws per realisation) and its own tail (rdn0_batch / rdn0_one above).  Everything is refused before the first launch. */
 int oa_mc_run_rdn0(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, int64_t* n, double* S, double* C,
                    void* stream) {
-    static const char* const how = "; or run the host loop of the existing entries (mc.RDN0MonteCarlo with one_call=False)";
-    OA_REQUIRE(p && covsqrt_hc && n && S && C && sim_hi >= sim_lo, "oa_mc_run_rdn0: bad argument");
-    OA_REQUIRE(p->pow2 || p->mixed, std::string("oa_mc_run_rdn0: map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path") + how);
-    OA_REQUIRE(p->pipe && ((Pipeline*)p->pipe)->FG, std::string("oa_mc_run_rdn0: no filters bound: call oa_plan_set_filters, oa_plan_set_bins and oa_rdn0_set_data first") + how);
-    Pipeline* q = (Pipeline*)p->pipe;
-    OA_REQUIRE(q->ids, std::string("oa_mc_run_rdn0: no bins bound: call oa_plan_set_bins, then oa_rdn0_set_data") + how);
-    OA_REQUIRE(!p->mixed || (q->band && q->band->pipe), std::string("oa_mc_run_rdn0: the bound filters have no band grid on this plan (oa_plan_set_filters reports why)") + how);
-    oa_plan* r = p->mixed ? q->band : p;
-    Pipeline* rq = (Pipeline*)r->pipe;
-    OA_REQUIRE(q->rdn0_gen, std::string("oa_mc_run_rdn0: no data set: call oa_rdn0_set_data (after oa_plan_set_filters and oa_plan_set_bins)") + how);
-    OA_REQUIRE(q->rdn0_gen == q->bind_gen && q->rdn0_my == rq->my && rq->rdn0_legs.p,
-               std::string("oa_mc_run_rdn0: the data legs are stale -- oa_plan_set_filters, oa_plan_set_bins or oa_plan_set_col_grid was called since "
-                           "they were made: call oa_rdn0_set_data again") + how);
-    if (int rc = rdn0_tail_check("oa_mc_run_rdn0", rq->nids, MC_BATCH_MAX)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (p->mixed) band_options(q);
-    if (int rc = rdn0_reserve(r, rq)) return rc;   // (nothing to do after the first call, or after oa_rdn0_set_data with bins bound)
-    void* const draw = rq->rdn0_pool.p;
-    McTtLoop T{p, r, rq, true, mc_pool_bytes(r, rq, 1), nullptr, nullptr, nullptr, nullptr, 0, false};
+    McTtLoop T;
+    if (int rc = rdn0_tt_open("oa_mc_run_rdn0", nullptr, p, sim_lo, sim_hi, covsqrt_hc, n, S, C, st, &T)) return rc;
+    Pipeline* q = (Pipeline*)p->pipe;
+    oa_plan* r = T.run;
+    void* const draw = T.rq->rdn0_pool.p;
     auto source = [=](long i, int nreal) {          // draws 2 i .. 2 i + nreal - 1: the leg band of oa_grf_hc's plane, oa_mc_run's counters
         if (p->mixed) return grf_band_inner(p, base_seed, 2 * (uint64_t)i, nreal, covsqrt_hc, draw, r->ny, r->kp, plane_elems(r), q->wl, q->rl, st);
         return grf_hc_band_batch(p, base_seed, 2 * (uint64_t)i, nreal, covsqrt_hc, draw, plane_elems(p), q->wl, q->rl, st);
     };
     T.source_batch = [=](long i, int B) { return source(i, 2 * B); };
     T.source_one = [=](long i) { return source(i, 2); };
-    q->rdn0_ran_batched = 0;
-    T.tail_batch = [=](int B, int* fallback) {
-        const int rc = rdn0_batch(r, rq, B, n, S, C, st, fallback);
-        if (!rc && !*fallback) q->rdn0_ran_batched = 1;
-        return rc;
-    };
-    T.tail_one = [=]() { return rdn0_one(r, rq, n, S, C, st); };
     return mc_tt_loop(T, sim_lo, sim_hi, n, S, C, nullptr, st);
 }
 
 /* oa_mc_run_rdn0_windowed (include/orphics_amd.h): oa_mc_run_rdn0 with the WINDOWED draws of oa_mc_run_windowed as s and s' -- the shard
- * loop and the tail are oa_mc_run_rdn0's (mc_tt_loop with rdn0_batch / rdn0_one), the source stage is new.  No mean field: s, s' and d are
- * independent and zero-mean, so neither A nor B has an ensemble mean to subtract.
- * POWER-OF-TWO PLANS, per batch of B realisations (2 B draws, draw z = stream 2 i + z): the full-plane part in groups of up to six draws
- * (three realisations) on the plan's six contiguous work planes -- OA_OPT_DRAW_FUSED = 1: ONE pass-1 launch that evaluates the draws at
- * its load + the in-place pass 2 (oa_grf_hc_icols), then ONE fused row launch C2R x window -> R2C (grid y = draw); 0: per draw oa_grf_hc,
- * inverse columns, the row pass -- onto compact row planes behind the tail's region of the pool; then the forward column transform of the
- * 2 B row planes onto the leg band of rdn0_pool's draw planes (six planes per launch).  OA_OPT_WIN_FUSED = 0: one by one, per draw
- * oa_grf_hc -> oa_fft_c2r_windowed (real map in HBM) -> oa_fft_r2c onto the draw plane.
- * BAND GRID: mixed_mc_run_windowed's source stage, the 2 B draws through the six N-grid planes of bwin in two halves, the pruned column
- * DFT onto the inner plan's rdn0_pool draw planes. */
-// the default of OA_OPT_DRAW_FUSED: oa_grf_hc_icols alone measured 5 - 14 us per plane below oa_grf_hc + oa_fft_cols, beyond both 10th - 90th
-// spreads at every measured geometry (profiles/rdn0_windowed.jsonl, DESIGN 5b); the 0 arm is also one by one, so a realisation differs by more
-constexpr bool DRAW_FUSED_DEFAULT = true;
+ * loop and the tail are oa_mc_run_rdn0's (rdn0_tt_open), the source stage is that entry's (WinDraws above) with streams 2 i .. 2 i + 2 B - 1
+ * of a batch onto the draw planes of rdn0_pool.  No mean field: s, s' and d are independent and zero-mean, so neither A nor B has an
+ * ensemble mean to subtract.
+ * POWER-OF-TWO PLANS: WinDraws::pow2 with OA_OPT_DRAW_FUSED (default: on), the 2 B compact row planes behind the tail's region of the pool.
+ * BAND GRID: WinDraws::band, the batch's two halves of B draws each through the six N-grid planes of bwin.
+ * OA_OPT_WIN_FUSED = 0 (on a band grid: also its rule by row length): one by one, both draws through the unfused flow. */
 int oa_mc_run_rdn0_windowed(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* covsqrt_hc, const void* window_real, int64_t* n,
                             double* S, double* C, void* stream) {
-    static const char* const how = "; or run the host loop of the existing entries (mc.RDN0MonteCarlo with one_call=False)";
-    const std::string who = "oa_mc_run_rdn0_windowed";
-    OA_REQUIRE(p && covsqrt_hc && n && S && C && sim_hi >= sim_lo, who + ": bad argument");
-    OA_REQUIRE(window_real, who + ": NULL window (oa_mc_run_rdn0 is the entry without one)");
-    OA_REQUIRE(p->pow2 || p->mixed, who + ": map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path" + how);
-    OA_REQUIRE(p->pipe && ((Pipeline*)p->pipe)->FG, who + ": no filters bound: call oa_plan_set_filters, oa_plan_set_bins and oa_rdn0_set_data first" + how);
-    Pipeline* q = (Pipeline*)p->pipe;
-    OA_REQUIRE(q->ids, who + ": no bins bound: call oa_plan_set_bins, then oa_rdn0_set_data" + how);
-    OA_REQUIRE(!p->mixed || (q->band && q->band->pipe), who + ": the bound filters have no band grid on this plan (oa_plan_set_filters reports why)" + how);
-    oa_plan* r = p->mixed ? q->band : p;
-    Pipeline* rq = (Pipeline*)r->pipe;
-    OA_REQUIRE(q->rdn0_gen, who + ": no data set: call oa_rdn0_set_data (after oa_plan_set_filters and oa_plan_set_bins)" + how);
-    OA_REQUIRE(q->rdn0_gen == q->bind_gen && q->rdn0_my == rq->my && rq->rdn0_legs.p,
-               who + ": the data legs are stale -- oa_plan_set_filters, oa_plan_set_bins or oa_plan_set_col_grid was called since they were made: "
-                     "call oa_rdn0_set_data again" + how);
-    if (int rc = rdn0_tail_check(who.c_str(), rq->nids, MC_BATCH_MAX)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (p->mixed) band_options(q);
-    if (int rc = rdn0_reserve(r, rq)) return rc;   // (nothing to do after the first call, or after oa_rdn0_set_data with bins bound)
+    McTtLoop T;
+    if (int rc = rdn0_tt_open("oa_mc_run_rdn0_windowed", window_real ? nullptr : "NULL window (oa_mc_run_rdn0 is the entry without one)", p, sim_lo,
+                              sim_hi, covsqrt_hc, n, S, C, st, &T)) return rc;
+    Pipeline* q = (Pipeline*)p->pipe;
+    oa_plan* r = T.run;
+    Pipeline* rq = T.rq;
     char* const draw = rq->rdn0_pool.at();
-    const double inv = 1.0 / ((double)p->ny * p->nx);
+    const size_t pbr = plane_bytes(r);
+    WinDraws W{p, q, base_seed, covsqrt_hc, window_real, st};
     // a batch is started only where the chain row stage finishes it: with a window the source stage is most of a realisation, and a batch
     // abandoned at the row stage (mc_tt_loop's fallback) would have run it for up to six realisations in vain
     const bool chain = qe_rows_chain_ok(r, rq->wl, rq->wk, rq->mrow, rq->my);
-    McTtLoop T{p, r, rq, true, mc_pool_bytes(r, rq, 1), nullptr, nullptr, nullptr, nullptr, 0, false};
-    q->rdn0_ran_batched = 0;
-    T.tail_batch = [=](int B, int* fallback) {
-        const int rc = rdn0_batch(r, rq, B, n, S, C, st, fallback);
-        if (!rc && !*fallback) q->rdn0_ran_batched = 1;
-        return rc;
-    };
-    T.tail_one = [=]() { return rdn0_one(r, rq, n, S, C, st); };
     if (p->mixed) {
-        const size_t pb = plane_bytes(p), pbi = plane_bytes(r);
-        const long pbe = plane_elems(r), pne = plane_elems(p);
-        // the N-grid planes of oa_mc_run_windowed on this plan (taken on the first windowed call of either entry: one synchronisation)
-        if (int rc = q->bwin.reserve((size_t)MC_BATCH_MAX * pb + std::max(band_maps_scratch_bytes(p, MC_BATCH_MAX, q->wl, q->rl),
-                                                                          band_map_scratch_bytes(p, q->wl, q->rl)))) return rc;
-        char* const full = q->bwin.at();
-        void* const rows = full + (size_t)MC_BATCH_MAX * pb;
-        const bool fused = q->opt_win_fused_set ? q->opt_win_fused : (p->nx > 1200 && band_rows_win_ok(p));     // (mixed_mc_run_windowed's rule)
-        T.batched = fused && chain;
-        auto half = [=](long i, int z0, int nz) {       // draws z0 .. z0 + nz - 1 (nz <= 6) of the batch that starts at realisation i
-            for (int k = 0; k < nz; ++k) {
-                void* pl = full + (size_t)k * pb;
-                if (int rc = oa_grf_hc(p, base_seed, 2 * (uint64_t)i + (uint64_t)(z0 + k), covsqrt_hc, pl, st)) return rc;
-                if (int rc = mixed_cols_inverse(p, pl, pl, st)) return rc;
-            }
-            return band_win_r2c(p, nz, full, pne, window_real, inv, rows, 0, q->wl, q->rl, nullptr, nullptr, draw + (size_t)z0 * pbi, pbe, r->ny, r->kp, st);
-        };
-        T.source_batch = [=](long i, int B) {
-            if (int rc = half(i, 0, B)) return rc;
-            return half(i, B, B);
+        if (int rc = W.band_open()) return rc;
+        T.batched = W.fused && chain;
+        T.source_batch = [=](long i, int B) {           // (a launch of its own for each half, B <= 6 planes)
+            if (int rc = W.band(2 * (uint64_t)i, B, draw, plane_elems(r))) return rc;
+            return W.band(2 * (uint64_t)i + B, B, draw + (size_t)B * pbr, plane_elems(r));
         };
         T.source_one = [=](long i) {
-            if (fused) return half(i, 0, 2);
-            void* tmap = full + pb;                                                  // ny x nx reals fit an hc plane
-            for (int z = 0; z < 2; ++z) {
-                if (int rc = oa_grf_hc(p, base_seed, 2 * (uint64_t)i + (uint64_t)z, covsqrt_hc, full, st)) return rc;
-                if (int rc = oa_fft_c2r_windowed(p, full, tmap, inv, window_real, st)) return rc;
-                if (int rc = band_map_r2c(p, tmap, rows, q->wl, q->rl, draw + (size_t)z * pbi, r->ny, r->kp, st)) return rc;
-            }
-            return 0;
+            if (W.fused) return W.band(2 * (uint64_t)i, 2, draw, plane_elems(r));
+            if (int rc = W.band_map(2 * (uint64_t)i, draw)) return rc;
+            return W.band_map(2 * (uint64_t)i + 1, draw + pbr);
         };
         return mc_tt_loop(T, sim_lo, sim_hi, n, S, C, nullptr, st);
     }
-    const long pl = work_pitch(p, q->wl);
-    const size_t es = elem_bytes(p), lb = (size_t)pl * p->ny * es, pb = plane_bytes(p);
-    const bool fused = q->opt_win_fused;
-    const bool dfused = fused && (q->opt_draw_fused < 0 ? DRAW_FUSED_DEFAULT : q->opt_draw_fused != 0);
-    T.batched = fused && chain;
-    T.pool_extra = mc_pool_bytes(p, q, 1) + 2 * lb;        // the tail's region, then the 2 B compact row planes of the batch
+    W.fused = q->opt_win_fused;
+    W.dfused = W.fused && (q->opt_draw_fused < 0 ? DRAW_FUSED_DEFAULT : q->opt_draw_fused != 0);
+    T.batched = W.fused && chain;
+    T.pool_extra = mc_pool_bytes(p, q, 1) + 2 * work_pitch(p, q->wl) * p->ny * elem_bytes(p);      // the tail's region, then the batch's 2 B compact row planes
     if (int rc = ensure_pool(q, (size_t)MC_BATCH_MAX * T.pool_extra + mc_pool_bytes(p, q, MC_BATCH_MAX))) return rc;      // (first call only)
-    char* const full = (char*)q->c[0];                     // c[0..2], g[0..1], kT: six contiguous hc planes, free until the tail
-    auto source = [=](long i, int B) {
-        char* const rowT = q->split_legs.at(2 * mc_pool_bytes(p, q, B));
-        const int nd = 2 * B;
-        for (int z0 = 0; z0 < nd; z0 += MC_BATCH_MAX) {
-            const int nz = std::min(MC_BATCH_MAX, nd - z0);
-            const uint64_t sid = 2 * (uint64_t)i + (uint64_t)z0;
-            if (dfused) {
-                if (int rc = grf_icols_w(p, base_seed, sid, nz, covsqrt_hc, full, plane_elems(p), st)) return rc;
-                if (int rc = qe_win_rows_w(p, full, window_real, q->wl, pl, inv, st, rowT + (size_t)z0 * lb, nz, plane_elems(p), (long)(lb / es))) return rc;
-            } else {
-                for (int k = 0; k < nz; ++k) {
-                    if (int rc = oa_grf_hc(p, base_seed, sid + (uint64_t)k, covsqrt_hc, q->kT, st)) return rc;
-                    if (int rc = qe_windowed_rows_w(p, q->kT, full, window_real, q->wl, pl, inv, st, rowT + (size_t)(z0 + k) * lb)) return rc;
-                }
-            }
-            if (int rc = qe_fwd_cols_batch_w(p, rowT + (size_t)z0 * lb, pl, draw + (size_t)z0 * pb, nz, (long)(lb / es), plane_elems(p), q->wl, q->rl, st)) return rc;
-        }
-        return 0;
-    };
+    auto source = [=](long i, int B) { return W.pow2(2 * (uint64_t)i, 2 * B, q->split_legs.at(2 * mc_pool_bytes(p, q, B)), draw); };
     T.source_batch = source;
     T.source_one = [=](long i) {
-        if (fused) return source(i, 1);
-        void* tmap = q->c[0];
-        for (int z = 0; z < 2; ++z) {
-            if (int rc = oa_grf_hc(p, base_seed, 2 * (uint64_t)i + (uint64_t)z, covsqrt_hc, q->kT, st)) return rc;
-            if (int rc = oa_fft_c2r_windowed(p, q->kT, tmap, inv, window_real, st)) return rc;
-            if (int rc = oa_fft_r2c(p, tmap, draw + (size_t)z * pb, 1.0, q->wl, q->rl, st)) return rc;
-        }
-        return 0;
+        if (W.fused) return source(i, 1);
+        if (int rc = W.pow2_map(2 * (uint64_t)i, draw)) return rc;
+        return W.pow2_map(2 * (uint64_t)i + 1, draw + pbr);
     };
     return mc_tt_loop(T, sim_lo, sim_hi, n, S, C, nullptr, st);
 }
@@ -2562,32 +2561,18 @@ int oa_mc_run_windowed(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi,
         OA_REQUIRE(q->band && q->band->pipe, "oa_mc_run_windowed: the bound filters have no band grid on this plan (oa_plan_set_filters reports why)");
         return mixed_mc_run_windowed(p, q, base_seed, sim_lo, sim_hi, covsqrt_hc, window_real, n, S, C, meanfield_acc, st);
     }
-    void* const tmap = q->c[0];
-    const double inv = 1.0 / ((double)p->ny * p->nx);
-    const long pl = work_pitch(p, q->wl);
-    const size_t es = elem_bytes(p), lb = (size_t)pl * p->ny * es;
-    // FUSED ROW PASS (default): inverse columns of the drawn spectrum (into the first leg plane, free until the leg stage), then
-    // C2R x window -> R2C per row in ONE kernel -- the real map exists in LDS only -- onto the scratch plane the column stages
-    // read.  OA_OPT_WIN_FUSED = 0: C2R with the window at its store -> real map in HBM -> the from-map estimator path.
-    const bool fused = q->opt_win_fused;
-    // BATCHES (fused row pass only): per realisation the full-plane part -- draw, inverse columns, C2R x window -> R2C rows onto a
-    // compact plane behind the tail's region of the pool --, then for the batch ONE forward column transform onto the leg band of its hc
-    // planes and the launches of oa_mc_run's batches behind it: the latency-bound coarse-grid work of a realisation (70 of its 205 us at
-    // 4096^2 float) is shared by up to six
-    McTtLoop T{p, p, q, fused && p->pow2, lb, nullptr, nullptr, tmap, nullptr, fused ? 1 : 0, true};
-    T.source_batch = [=](long i, int B) {
-        char* const rowT = q->split_legs.at(mc_pool_bytes(p, q, B));
-        for (int b = 0; b < B; ++b) {
-            if (int rc = oa_grf_hc(p, base_seed, (uint64_t)(i + b), covsqrt_hc, q->kT, st)) return rc;
-            if (int rc = qe_windowed_rows_w(p, q->kT, tmap, window_real, q->wl, pl, inv, st, rowT + (size_t)b * lb)) return rc;
-        }
-        return qe_fwd_cols_batch_w(p, rowT, pl, q->mc_src.p, B, (long)(lb / es), plane_elems(p), q->wl, q->rl, st);
-    };
-    T.source_one = [=](long i) {
-        if (int rc = oa_grf_hc(p, base_seed, (uint64_t)i, covsqrt_hc, q->kT, st)) return rc;
-        if (fused) return qe_windowed_rows_w(p, q->kT, tmap, window_real, q->wl, pl, inv, st);
-        return oa_fft_c2r_windowed(p, q->kT, tmap, inv, window_real, st);           // the window rides on the row pass's store
-    };
+    // FUSED ROW PASS (default; WinDraws::pow2 without the draw inside the column pass): inverse columns of the drawn spectrum (into the
+    // first leg plane, free until the leg stage), then C2R x window -> R2C per row in ONE kernel -- the real map exists in LDS only.
+    // OA_OPT_WIN_FUSED = 0: C2R with the window at its store -> real map in HBM -> the from-map estimator path.
+    WinDraws W{p, q, base_seed, covsqrt_hc, window_real, st, (bool)q->opt_win_fused};
+    const size_t lb = (size_t)work_pitch(p, q->wl) * p->ny * elem_bytes(p);
+    // BATCHES (fused row pass only): per realisation the full-plane part onto a compact row plane behind the tail's region of the pool,
+    // then for the batch ONE forward column transform onto the leg band of its hc planes and the launches of oa_mc_run's batches behind
+    // it: the latency-bound coarse-grid work of a realisation (70 of its 205 us at 4096^2 float) is shared by up to six.  ONE BY ONE: the
+    // row transform on the scratch plane the column stages read (rows_done), or the real map in c[0].
+    McTtLoop T{p, p, q, W.fused && p->pow2, lb, nullptr, nullptr, q->c[0], nullptr, W.fused ? 1 : 0, true};
+    T.source_batch = [=](long i, int B) { return W.pow2((uint64_t)i, B, q->split_legs.at(mc_pool_bytes(p, q, B)), q->mc_src.p); };
+    T.source_one = [=](long i) { return W.fused ? W.pow2((uint64_t)i, 1, nullptr, nullptr) : W.pow2_map((uint64_t)i, nullptr); };
     return mc_tt_loop(T, sim_lo, sim_hi, n, S, C, meanfield_acc, st);
 }
 

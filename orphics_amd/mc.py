@@ -28,6 +28,25 @@ def allreduce_tensors(tensors, comm):
     return tensors
 
 
+def _blocks(sims):
+    """The non-empty list of indices ``sims`` cut where it stops being consecutive: [(lo, hi), ...], each block lo .. hi - 1."""
+    out, lo = [], sims[0]
+    for prev, i in zip(sims, sims[1:] + [None]):
+        if i != prev + 1:
+            out.append((lo, prev + 1))
+            lo = i
+    return out
+
+
+def _run_sharded(driver, nsims, **kw):
+    """Every driver's ``run``: this rank's share of ``nsims`` (mpi.mpi_distribute) through ``run_local``, ONE all-reduce, the Statistics."""
+    comm = driver.comm
+    _, tasks = _mpi.mpi_distribute(nsims, comm.Get_size(), allow_empty=True)
+    driver.run_local(tasks[comm.Get_rank()], **kw)
+    driver.acc.allreduce()
+    return driver.acc
+
+
 class GaussianN0MonteCarlo(object):
     """N0 bias / mean-field Monte Carlo on Gaussian maps with total power
     C_l^TT B_l^2 + N_l, generated on the device in harmonic space
@@ -112,13 +131,7 @@ class GaussianN0MonteCarlo(object):
         # kappa_hat vanishes outside its active region: the stack declares it, the all-reduce moves only that region
         sup = (q.kappa_rows, q.kappa_cols) if (q.kappa_cols and q.kappa_rows) else None
         mf = self.acc.device_stack("mf", (e.ny, e.kp, 2), support=sup) if self.mean_field else None
-        start = prev = sims[0]
-        blocks = []
-        for i in sims[1:] + [None]:
-            if i is None or i != prev + 1:
-                blocks.append((start, prev + 1))
-                start = i
-            prev = i
+        blocks = _blocks(sims)
         # (with the mean-field stack the one-stream loop measured faster -- 16.0k vs 14.1k sims/s at 4096^2 -- so the
         # lanes are used for the bandpower moments only)
         if self.window is not None and self.streams > 1 and len(sims) >= 4 * self.streams:
@@ -213,17 +226,13 @@ class GaussianN0MonteCarlo(object):
             with torch.cuda.stream(stream):
                 qj.bind_bins(self.ids, self.nids, self.norm)
                 ej = qj._bind_bins()
-                lo = prev = mine[0]
-                for i in mine[1:] + [None]:
-                    if i is None or i != prev + 1:
-                        if self.window is not None:
-                            check(ej.lib.oa_mc_run_windowed(ej.plan, self.base_seed, lo, prev + 1, _ptr(self.cs), _ptr(self.window), _ptr(nj),
-                                                            _ptr(Sj), _ptr(Cj), _ptr(mfj), stream.cuda_stream))
-                        else:
-                            check(ej.lib.oa_mc_run(ej.plan, self.base_seed, lo, prev + 1, _ptr(self.cs), _ptr(nj), _ptr(Sj), _ptr(Cj),
-                                                   _ptr(mfj), stream.cuda_stream))
-                        lo = i
-                    prev = i
+                for lo, hi in _blocks(mine):
+                    if self.window is not None:
+                        check(ej.lib.oa_mc_run_windowed(ej.plan, self.base_seed, lo, hi, _ptr(self.cs), _ptr(self.window), _ptr(nj),
+                                                        _ptr(Sj), _ptr(Cj), _ptr(mfj), stream.cuda_stream))
+                    else:
+                        check(ej.lib.oa_mc_run(ej.plan, self.base_seed, lo, hi, _ptr(self.cs), _ptr(nj), _ptr(Sj), _ptr(Cj),
+                                               _ptr(mfj), stream.cuda_stream))
             if j:
                 parts.append((stream, nj, Sj, Cj, mfj))
         for stream, nj, Sj, Cj, mfj in parts:
@@ -238,12 +247,7 @@ class GaussianN0MonteCarlo(object):
         """Shard ``nsims`` with mpi.mpi_distribute (mpi.py:78-91), run, reduce once; returns the reduced
         :class:`Statistics` (label 'n0' = kappa auto bandpowers, stack 'mf' = interleaved (re, im) sum of the
         kappa_hat DFTs if mean_field; ``stack_sum('mf', on_device=True)`` keeps it on the GPU)."""
-        comm = self.comm
-        size, rank = comm.Get_size(), comm.Get_rank()
-        _, tasks = _mpi.mpi_distribute(nsims, size, allow_empty=True)
-        self.run_local(tasks[rank])
-        self.acc.allreduce()
-        return self.acc
+        return _run_sharded(self, nsims)
 
     def debiased_mean(self):
         """mean kappa auto bandpowers of the (reduced) run divided by mean(w^4) of the window (1 without one)."""
@@ -537,12 +541,8 @@ class GaussianN0MonteCarloPol(object):
             self._note_stacked(len(sims))
             return self
         n, S, C = self.acc.device_moments("n0", self.D)
-        start = prev = sims[0]
-        for i in sims[1:] + [None]:
-            if i is None or i != prev + 1:
-                self._run_block(start, prev + 1, n, S, C)
-                start = i
-            prev = i
+        for lo, hi in _blocks(sims):
+            self._run_block(lo, hi, n, S, C)
         self.acc.note_samples("n0", len(sims))
         self._note_stacked(len(sims))
         return self
@@ -556,12 +556,7 @@ class GaussianN0MonteCarloPol(object):
     def run(self, nsims):
         """Shard ``nsims`` with mpi.mpi_distribute, run, reduce once; returns the reduced :class:`Statistics` (label "n0"; with
         ``mean_field`` the stacks "mf_TT", ..., "mf_MV")."""
-        comm = self.comm
-        size, rank = comm.Get_size(), comm.Get_rank()
-        _, tasks = _mpi.mpi_distribute(nsims, size, allow_empty=True)
-        self.run_local(tasks[rank])
-        self.acc.allreduce()
-        return self.acc
+        return _run_sharded(self, nsims)
 
     def _slot(self, a, b=None):
         key = (a, a if b is None else b)
@@ -737,12 +732,7 @@ class LensedSimsMonteCarlo(object):
             self.acc.add("cross_" + XY, cross)
 
     def run(self, nsims, stage_times=False):
-        comm = self.comm
-        size, rank = comm.Get_size(), comm.Get_rank()
-        _, tasks = _mpi.mpi_distribute(nsims, size, allow_empty=True)
-        self.run_local(tasks[rank], stage_times=stage_times)
-        self.acc.allreduce()
-        return self.acc
+        return _run_sharded(self, nsims, stage_times=stage_times)
 
     def table(self):
         """per estimator: (mean bias per band, its standard error, chi^2 of the pulls, weighted mean bias +- error)"""
@@ -959,28 +949,19 @@ class RDN0MonteCarlo(object):
             check(e.lib.oa_rdn0_set_data(e.plan, _ptr(self.kd), _stream()))
             e._rdn0_owner = self._dtoken
         n, S, C = self.acc.device_moments("rdn0", 2 * self.d)
-        start = prev = sims[0]
-        for i in sims[1:] + [None]:
-            if i is None or i != prev + 1:
-                if self.window is not None:
-                    check(e.lib.oa_mc_run_rdn0_windowed(e.plan, self.base_seed, start, prev + 1, _ptr(self.cs), _ptr(self.window), _ptr(n), _ptr(S),
-                                                        _ptr(C), _stream()))
-                else:
-                    check(e.lib.oa_mc_run_rdn0(e.plan, self.base_seed, start, prev + 1, _ptr(self.cs), _ptr(n), _ptr(S), _ptr(C), _stream()))
-                start = i
-            prev = i
+        for lo, hi in _blocks(sims):
+            if self.window is not None:
+                check(e.lib.oa_mc_run_rdn0_windowed(e.plan, self.base_seed, lo, hi, _ptr(self.cs), _ptr(self.window), _ptr(n), _ptr(S), _ptr(C),
+                                                    _stream()))
+            else:
+                check(e.lib.oa_mc_run_rdn0(e.plan, self.base_seed, lo, hi, _ptr(self.cs), _ptr(n), _ptr(S), _ptr(C), _stream()))
         self.acc.note_samples("rdn0", len(sims))
         return self
 
     def run(self, nsims):
         """Shard ``nsims`` realisations with mpi.mpi_distribute, run, reduce once; returns the reduced :class:`Statistics` (one label,
         ``"rdn0"``, of dimension ``2 d``)."""
-        comm = self.comm
-        size, rank = comm.Get_size(), comm.Get_rank()
-        _, tasks = _mpi.mpi_distribute(nsims, size, allow_empty=True)
-        self.run_local(tasks[rank])
-        self.acc.allreduce()
-        return self.acc
+        return _run_sharded(self, nsims)
 
 
 class RDN0MonteCarloPol(object):
@@ -1173,21 +1154,12 @@ class RDN0MonteCarloPol(object):
                 self.acc.add("rdn0", self.sample_host(i))
             return self
         n, S, C = self.acc.device_moments("rdn0", self.D)
-        start = prev = sims[0]
-        for i in sims[1:] + [None]:
-            if i is None or i != prev + 1:
-                self._run_block(start, prev + 1, n, S, C)
-                start = i
-            prev = i
+        for lo, hi in _blocks(sims):
+            self._run_block(lo, hi, n, S, C)
         self.acc.note_samples("rdn0", len(sims))
         return self
 
     def run(self, nsims):
         """Shard ``nsims`` realisations with mpi.mpi_distribute, run, reduce once; returns the reduced :class:`Statistics` (one label,
         ``"rdn0"``, of dimension ``2 * nspec * d``)."""
-        comm = self.comm
-        size, rank = comm.Get_size(), comm.Get_rank()
-        _, tasks = _mpi.mpi_distribute(nsims, size, allow_empty=True)
-        self.run_local(tasks[rank])
-        self.acc.allreduce()
-        return self.acc
+        return _run_sharded(self, nsims)
