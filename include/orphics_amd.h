@@ -43,7 +43,7 @@ typedef struct oa_plan oa_plan;
 const char* oa_last_error(void);
 /* ABI version = 100 x the build round that last changed a signature in this header; bindings must refuse a library
  * that reports less than the version they were written against (OA_ABI_VERSION) */
-#define OA_ABI_VERSION 413
+#define OA_ABI_VERSION 414
 int oa_version(void);
 /* number of HIP devices visible; <0 on error (no compute) */
 int oa_device_count(void);
@@ -273,7 +273,12 @@ int oa_plan_div_fused(const oa_plan* p);
  *                      exist); 0 = ONE BY ONE: per draw oa_grf_hc, the column transform and the row pass (24 launches per six draws
  *                      against 3); unset or < 0 = what measured faster: 1.  The kernel alone saves 5 - 14 us per drawn plane at 2048^2
  *                      and 4096^2, beyond the spreads; a realisation is 9 - 25 % faster, most of that from the batched launches
- *                      (profiles/rdn0_windowed.jsonl).  The moments are bit-equal between 0 and 1. */
+ *                      (profiles/rdn0_windowed.jsonl).  The moments are bit-equal between 0 and 1.
+ *                      oa_mc_run_rdn0_mv_windowed on power-of-two plans (with OA_OPT_WIN_FUSED = 1): 1 = both triples of a realisation are
+ *                      drawn inside ONE inverse column pass-1 launch (oa_grf_mix_icols) and the six planes share every later launch;
+ *                      0 = oa_mc_run_mv_windowed's source stage per triple; unset or < 0 = that entry's own default: 0 until the fused kernel
+ *                      has been timed against the per-triple draw.
+ *                      The moments are bit-equal between 0 and 1. */
 enum { OA_OPT_MC_BATCH = 1, OA_OPT_MV_BATCH = 2, OA_OPT_MV_ROWBATCH = 3, OA_OPT_MV_CHAIN = 4, OA_OPT_DIV_BIN = 5, OA_OPT_WIN_FUSED = 6, OA_OPT_DRAW_FUSED = 7 };
 int oa_plan_set_option(oa_plan* p, int option, int value);
 int oa_plan_set_bins(oa_plan* p, const int32_t* ids_hc, int nids, double norm, void* stream);
@@ -471,7 +476,8 @@ int oa_mc_run_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const
  *     p(Z_a, Z_b)_j = sum over the modes of bin j + 1 of m Re(Z_a conj Z_b) norm / counts[j + 1]   (m = Hermitian multiplicity),
  *     x_i = [ p(A_a, A_b) - p(B_a, B_b) / 2 for every spectrum (a, b) in list order ] ("rdn0") ++ [ p(B_a, B_b) / 2 likewise ] ("mcn0"),
  *     n += 1,  S += x_i,  C += x_i x_i^T          (D = 2 nspec d, d = nids - 2; S: D doubles, C: D x D).
- * The debiased spectrum of the data is p(QE_a(d; d), QE_b(d; d)) - mean(rdn0_ab).  No window.
+ * The debiased spectrum of the data is p(QE_a(d; d), QE_b(d; d)) - mean(rdn0_ab).  No window here: oa_mc_run_rdn0_mv_windowed (below) is
+ * the entry for an apodised triple.
  *  oa_rdn0_set_data_mv : set-up entry (may allocate and synchronise).  host_kD: the three hc transforms of the data (a plane no estimator
  *                        reads may be NULL).  The data's DISTINCT leg planes -- one gradient pair per distinct (source, FG), one H plane
  *                        per distinct (source, FH): oa_qe_mv's sharing rule -- are transformed once (one batched leg launch where that
@@ -499,6 +505,34 @@ int oa_mc_run_rdn0_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, 
                       const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights, long mv_wstride, int nspec, const int* host_a,
                       const int* host_b, const int32_t* ids_hc, int nids, const int64_t* counts, double norm, int leg_cols, int kappa_cols,
                       int leg_rows, int kappa_rows, int mrow, int64_t* n, double* S, double* C, void* stream);
+/* oa_mc_run_rdn0_mv_windowed: oa_mc_run_rdn0_mv's definition with ONE change -- s and s' are the WINDOWED triples: for z = 0, 1 the T, E, B
+ * that oa_mc_run_mv_windowed's source stage makes from the full-plane draw of streams 6 i + 3 z .. 6 i + 3 z + 2 (the very draws that entry
+ * makes for its realisations 2 i + z): T, E, B rotated to T, Q, U in the draw, C2R / Npix, x window_real, R2C, Q, U -> E, B on the leg
+ * band.  The arguments are oa_mc_run_rdn0_mv's plus window_real, rot_c, rot_s, which mean what they mean in oa_mc_run_mv_windowed: the
+ * window multiplies T, Q, U, not E, B, and rot_c / rot_s are the Q, U -> E, B planes.  The data legs are those of the unchanged
+ * oa_rdn0_set_data_mv: the data is the triple AS ANALYSED, already apodised by the caller.  A, B, the spectrum list, the tail, its fixed
+ * summation order and its bit-reproducibility are oa_mc_run_rdn0_mv's.  There is NO mean-field argument: s, s' and d are independent and
+ * zero-mean, so A and B carry no mean field (that of the data's own reconstructions is the caller's to subtract:
+ * mc.RDN0MonteCarloPol.data_bandpowers(mean_field=...)).
+ * Source stage per realisation (power-of-two plans), onto the leg band of the entry's six draw planes:
+ *   OA_OPT_WIN_FUSED = 1, OA_OPT_DRAW_FUSED = 1: FIVE launches for the six planes -- one inverse column pass-1 launch with both triples'
+ *     draws at its load (oa_grf_mix_icols, ntriples = 2: each Philox counter evaluated once per triple), one in-place pass 2, one fused
+ *     row launch over six planes (C2R / Npix -> x window -> R2C, the real maps in LDS only, compact row planes), one forward column launch
+ *     over six -- and the Q, U -> E, B rotation on the band, one launch per pair;
+ *   OA_OPT_DRAW_FUSED = 0: oa_mc_run_mv_windowed's fused sequence per triple (the T, Q, U draw into full planes, its batched inverse
+ *     columns + fused row launch, its forward column launch, the rotation);
+ *   OA_OPT_WIN_FUSED = 0: that entry's unfused flow per triple (oa_fft_c2r_windowed -> real map in HBM -> oa_fft_r2c on the band).
+ * The stage's planes (six full hc planes + six compact row planes) are entry-owned, shared with oa_mc_run_mv_windowed: nothing is allocated
+ * after the first call and oa_plan_release_pools frees them.
+ * Refused by name before anything is launched, n, S, C untouched: a NULL window (the message names oa_mc_run_rdn0_mv, the entry without
+ * one), a window without both rotation planes, and everything oa_mc_run_rdn0_mv refuses (a plan that is not power-of-two, no data, stale
+ * legs, nest, sources, tail tables); the messages name this entry, mc.RDN0MonteCarloPol and one_call=False. */
+int oa_mc_run_rdn0_mv_windowed(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest,
+                               const int* host_npieces, const double* host_signs, const void* const* host_FG, const void* const* host_FH,
+                               const int* host_swap, const int* host_xsrc, const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights,
+                               long mv_wstride, int nspec, const int* host_a, const int* host_b, const int32_t* ids_hc, int nids, const int64_t* counts,
+                               double norm, int leg_cols, int kappa_cols, int leg_rows, int kappa_rows, int mrow, const void* window_real,
+                               const void* rot_c, const void* rot_s, int64_t* n, double* S, double* C, void* stream);
 /* oa_mc_run_mv_windowed: oa_mc_run_mv with a real-space window on the T, Q, U maps of every realisation and with the mean-field stacks of the
  * estimator set.  The arguments are oa_mc_run_mv's, plus
  *   window_real     ny x nx reals of the plan's dtype (the apodisation every map is multiplied by before its transform), or NULL;
@@ -751,6 +785,20 @@ int oa_grf_mix(oa_plan* p, uint64_t seed, uint64_t stream_id0, int ncomp, const 
  * ncomp 1..3, NULL blocks are zero.  What oa_grf_hc_band is to oa_grf_hc. */
 int oa_grf_mix_band(oa_plan* p, uint64_t seed, uint64_t stream_id0, int ncomp, const void* const* covsqrt_hc, double scale,
                     void* const* hc_out, int width, int rband, void* stream);
+/* The mixed T, Q, U draw INSIDE the inverse column transform: plane 3 t + c (t < ntriples, c = 0 T, 1 Q, 2 U; planes zstride complex elements
+ * apart) of hc_out is bit for bit oa_fft_cols(inverse = 1, scale = 1, width = nx/2 + 1) of component c of
+ *     oa_grf_mix(p, seed, stream_id0 + 3 t, ncomp = 3, covsqrt_hc, rot_c = c, rot_s = -s, NULL, NULL, 1, ...)
+ * where rot_c = c, rot_s = s are the caller's Q, U -> E, B planes as oa_mc_run_mv_windowed takes them (the sine enters negated: E, B -> Q, U);
+ * both NULL = no rotation, the planes are T, E, B.  Same Philox counters ys * npair + x / 2 of streams stream_id0 + 3 t + k, same
+ * self-conjugate rules at columns 0 and nx/2, same 1 / sqrt 2, mixing order and rotation expressions as oa_grf_mix.  A workgroup of column
+ * pass 1 owns one column tile of one TRIPLE: it evaluates the three streams' normals ONCE (a lane pair shares each counter, as in
+ * oa_grf_hc_icols), keeps them in registers and takes the three planes through the pipeline one after the other; pass 2 is the in-place
+ * launch over all planes.  Columns beyond nx/2 are not written.  Power-of-two plans with ny >= 32, nx >= 4 only; other plans are refused
+ * by name, as are ntriples outside 1 <= 3 ntriples <= 65535, a zstride below one plane, one rotation plane without the other, and float64
+ * plans of 32768 rows and more (512-thread pass-1 workgroups: a triple's normals do not fit their registers without spilling; the entry
+ * oa_mc_run_rdn0_mv_windowed runs its per-triple sequence there). */
+int oa_grf_mix_icols(oa_plan* p, uint64_t seed, uint64_t stream_id0, int ntriples, const void* const* covsqrt_hc, const void* rot_c,
+                     const void* rot_s, void* hc_out, long zstride, void* stream);
 /* The band of oa_grf_mix_band written into the hc layout of an INNER grid of `my` rows and row pitch `out_pitch` (complex elements): Philox
  * counters, self-conjugate edge rules and the covsqrt planes are those of the plan's N grid at row y, the value goes to row y of the
  * output planes for y < rband and to row y - ny + my above (ky mod my: the band grid's layout), same column.  Bit-identical to

@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("ORPHICS_AMD_LIB", os.path.join(_HERE, "liborphics_amd
 
 OA_F32 = 0
 OA_F64 = 1
-ABI_VERSION = 413   # include/orphics_amd.h OA_ABI_VERSION: the signatures below are those of this version
+ABI_VERSION = 414   # include/orphics_amd.h OA_ABI_VERSION: the signatures below are those of this version
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
@@ -79,6 +79,9 @@ SIGNATURES = {
     "oa_rdn0_set_data_mv": (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
     "oa_mc_run_rdn0_mv": (c_int, [c_void_p, c_u64, c_long, c_long, c_void_p, c_int] + [c_void_p] * 9 + [c_long, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                   c_void_p, c_double] + [c_int] * 5 + [c_void_p] * 4),
+    # oa_mc_run_rdn0_mv's arguments + (window_real, rot_c, rot_s) behind mrow; power-of-two plans only
+    "oa_mc_run_rdn0_mv_windowed": (c_int, [c_void_p, c_u64, c_long, c_long, c_void_p, c_int] + [c_void_p] * 9 + [c_long, c_int, c_void_p, c_void_p,
+                                           c_void_p, c_int, c_void_p, c_double] + [c_int] * 5 + [c_void_p] * 7),
     "oa_mc_run_mv": (c_int, [c_void_p, c_u64, c_long, c_long, c_void_p, c_int] + [c_void_p] * 9 + [c_long, c_int, c_void_p, c_void_p, c_void_p, c_int,
                              c_void_p, c_double] + [c_int] * 5 + [c_void_p] * 4),
     # oa_mc_run_mv's arguments + (window_real, rot_c, rot_s) behind mrow and host_meanfield in front of the stream; power-of-two plans only
@@ -128,6 +131,7 @@ SIGNATURES = {
     "oa_grf_hc_band": (c_int, [c_void_p, c_u64, c_u64, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "oa_grf_mix": (c_int, [c_void_p, c_u64, c_u64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
     "oa_grf_mix_band": (c_int, [c_void_p, c_u64, c_u64, c_int, c_void_p, c_double, c_void_p, c_int, c_int, c_void_p]),
+    "oa_grf_mix_icols": (c_int, [c_void_p, c_u64, c_u64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
     "oa_grf_mix_band_inner": (c_int, [c_void_p, c_u64, c_u64, c_int, c_void_p, c_double, c_void_p, c_int, c_long, c_int, c_int, c_void_p]),
     "oa_randn": (c_int, [c_int, c_u64, c_u64, c_void_p, c_long, c_void_p]),
     "oa_moments_add": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -197,6 +197,11 @@ int qe_rows_chain_w(oa_plan* p, int nest, int total, const void* const* gx, cons
                     long pl, long pk, hipStream_t st, int my);
 // nreal full-plane draws (streams stream_id ...) straight into their inverse column transform: oa_grf_hc_icols without its checks (fft.hip)
 int grf_icols_w(oa_plan* p, uint64_t seed, uint64_t stream_id, int nreal, const void* cs, void* out, long zstride, hipStream_t st);
+// ntriples mixed T, Q, U draws (streams sid0 + 3 t + k) straight into their inverse column transform: oa_grf_mix_icols without its checks
+int grf_mix_icols_w(oa_plan* p, uint64_t seed, uint64_t sid0, int ntriples, const void* const* cs, const void* rc, const void* rs, void* out,
+                    long zstride, hipStream_t st);
+// the plans its kernel exists for: power of two, and not float64 with a pass-1 sub-length of 256 (ny >= 32768: fft.hip, col_mix)
+inline bool grf_mix_icols_serves(const oa_plan* p) { return p->pow2 && !(p->dtype != OA_F32 && p->logNy >= 15); }
 bool qe_rows_chain_ok(const oa_plan* p, int win, int wout, int mrow, int my);
 int grf_hc_band_batch(oa_plan* p, uint64_t seed, uint64_t stream_id, int nreal, const void* covsqrt_hc, void* hc_out, long zstride,
                       int width, int rband, hipStream_t stream);

@@ -219,6 +219,15 @@ __global__ __launch_bounds__(col_maxnt<SEQ>(), fused_col_waves_per_eu<T>()) void
     col_grf_body<T, SEQ>(c, a);
 }
 
+// the same pass with the mixed T, Q, U draw at its load (col_mix_body): a lane keeps the 96 normals of its sixteen points (three streams)
+// next to the pipeline's registers -- float32 gets the 256-register budget (two waves per SIMD); float64, whose radix-16 butterfly alone
+// holds ~140, gets the whole file (one wave per SIMD: the longer sub-lengths overflow into AGPRs, none into scratch memory)
+template <typename T, class SEQ>
+__global__ __launch_bounds__(col_maxnt<SEQ>(), (sizeof(T) == 8 ? 1 : 2)) void col_mix_kernel(MixColArgs<T> a) {
+    GpuCtx c{oa_dyn_smem};
+    col_mix_body<T, SEQ>(c, a);
+}
+
 // resident workgroups per CU of a persistent kernel, with its dynamic-LDS attribute set: asked of the runtime ONCE per (kernel,
 // workgroup size, LDS bytes) -- both are driver calls of several microseconds, more than a 4096^2 launch leaves the host
 static int resident_per_cu(const void* kern, int nt, size_t smem, std::string* err) {
@@ -599,6 +608,19 @@ struct HipLauncher {
             if constexpr (seq_logl<S>() <= 8) {
                 if (nt > col_maxnt<S>()) { if (!rc) rc = fail("fft: column workgroup size exceeds its launch bound"); return; }
                 go(col_grf_kernel<T, S>, dim3(gx, gy, nz), nt, smem, a);
+            } else if (!rc) rc = fail("fft: unsupported column sub-length");
+        });
+        if (!ok && !rc) rc = fail("fft: unsupported column length");
+    }
+    template <typename T>
+    void col_mix(int gx, int gy, int nt, size_t smem, const MixColArgs<T>& a, int nz) {
+        const bool ok = dispatch_seq(a.logL, [&](auto seq) {
+            using S = decltype(seq);
+            // (float64 sub-length 256 -- 32768 rows and more -- runs 512-thread workgroups, two waves per SIMD: the kept normals do not
+            // fit their 256 registers without spilling, so that kernel does not exist; grf_mix_icols_serves, oa_grf_mix_icols refuses)
+            if constexpr (seq_logl<S>() <= 8 && !(sizeof(T) == 8 && seq_logl<S>() == 8)) {
+                if (nt > col_maxnt<S>()) { if (!rc) rc = fail("fft: column workgroup size exceeds its launch bound"); return; }
+                go(col_mix_kernel<T, S>, dim3(gx, gy, nz), nt, smem, a);
             } else if (!rc) rc = fail("fft: unsupported column sub-length");
         });
         if (!ok && !rc) rc = fail("fft: unsupported column length");
@@ -1015,6 +1037,19 @@ int grf_icols_w(oa_plan* p, uint64_t seed, uint64_t stream_id, int nreal, const 
     return p->dtype == OA_F32 ? grf_icols_impl<float>(p, seed, stream_id, nreal, cs, out, zstride, st)
                               : grf_icols_impl<double>(p, seed, stream_id, nreal, cs, out, zstride, st);
 }
+// ntriples mixed T, Q, U draws (streams stream_id0 + 3 t + k) and their inverse column transform (oa_grf_mix_icols)
+template <typename T>
+static int grf_mix_icols_impl(oa_plan* p, uint64_t seed, uint64_t sid0, int ntriples, const void* const* cs, const void* rc, const void* rs,
+                              void* out, long zstride, hipStream_t st) {
+    HipLauncher q{st};
+    view<T>(p).grf_mix_icols(q, seed, sid0, ntriples, (const T* const*)cs, (const T*)rc, (const T*)rs, (cx<T>*)out, zstride);
+    return q.rc;
+}
+int grf_mix_icols_w(oa_plan* p, uint64_t seed, uint64_t sid0, int ntriples, const void* const* cs, const void* rc, const void* rs, void* out,
+                    long zstride, hipStream_t st) {
+    return p->dtype == OA_F32 ? grf_mix_icols_impl<float>(p, seed, sid0, ntriples, cs, rc, rs, out, zstride, st)
+                              : grf_mix_icols_impl<double>(p, seed, sid0, ntriples, cs, rc, rs, out, zstride, st);
+}
 // flat-sky Taylor lensing, FFT part (oa_lens_maps): nmaps real maps -> their transforms (k0: nmaps hc planes) -> the nd derivative
 // fields of each, inverse-transformed: ONE pass-1 launch with the derivative factor at the load, ONE pass-2 launch, ONE row C2R
 // launch per (map, y-derivative order) (hc_pool: one hc plane at least; real_pool: nmaps * nd real planes, 1 / Npix applied)
@@ -1270,6 +1305,22 @@ int oa_grf_hc_icols(oa_plan* p, uint64_t seed, uint64_t stream_id, int nreal, co
     OA_REQUIRE(nreal == 1 || zstride >= (long)p->ny * p->kp, "oa_grf_hc_icols: zstride must be at least one plane (ny * pitch elements)");
     OA_REQUIRE(p->ny >= 32 && p->nx >= 4, "oa_grf_hc_icols: needs ny >= 32 and nx >= 4");
     return oa::grf_icols_w(p, seed, stream_id, nreal, covsqrt_hc, hc_out, zstride, (hipStream_t)stream);
+}
+
+int oa_grf_mix_icols(oa_plan* p, uint64_t seed, uint64_t stream_id0, int ntriples, const void* const* covsqrt_hc, const void* rot_c,
+                     const void* rot_s, void* hc_out, long zstride, void* stream) {
+    OA_REQUIRE(p && covsqrt_hc, "oa_grf_mix_icols: NULL argument");
+    OA_REQUIRE(p->pow2, "oa_grf_mix_icols: the draw is fused into the power-of-two inverse column pass; this plan's sides are not powers of two "
+               "(run oa_grf_mix, then the plan's own column transform)");
+    OA_REQUIRE(ntriples >= 1 && 3L * ntriples <= 65535, "oa_grf_mix_icols: 1 <= 3 * ntriples <= 65535 (grid z of pass 2)");
+    OA_REQUIRE(hc_out, "oa_grf_mix_icols: NULL output");
+    OA_REQUIRE(zstride >= (long)p->ny * p->kp, "oa_grf_mix_icols: zstride must be at least one plane (ny * pitch elements)");
+    OA_REQUIRE((rot_c == nullptr) == (rot_s == nullptr), "oa_grf_mix_icols: rot_c and rot_s go together (both NULL: no rotation)");
+    OA_REQUIRE(p->ny >= 32 && p->nx >= 4, "oa_grf_mix_icols: needs ny >= 32 and nx >= 4");
+    OA_REQUIRE(oa::grf_mix_icols_serves(p), "oa_grf_mix_icols: float64 plans of 32768 rows and more are not served (their pass-1 workgroups run two "
+               "waves per SIMD, whose registers do not hold a triple's normals next to the column pipeline without spilling); run oa_grf_mix, then "
+               "oa_fft_cols");
+    return oa::grf_mix_icols_w(p, seed, stream_id0, ntriples, covsqrt_hc, rot_c, rot_s, hc_out, zstride, (hipStream_t)stream);
 }
 
 int oa_qe_rows(oa_plan* p, const void* gx, const void* gy, const void* h, void* px, void* py, double scale,

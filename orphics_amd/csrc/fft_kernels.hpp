@@ -2322,4 +2322,226 @@ OA_HD void col_grf_body(Ctx& ctx, const GrfColArgs<T>& a) {
     col_pipeline_from_regs<T, SEQ>(ctx, s, v, tid, CNT, CLC, twl, logL, st);
 }
 
+// ===========================================================================
+// The mixed T, Q, U draw INSIDE inverse column pass 1 (oa_grf_mix_icols): the analogue of col_grf_body for grf_mix_kernel's three-field
+// draw with the E, B -> Q, U rotation (rng.hip; grf_mix_teb_to_tqu).  A workgroup owns one column tile of one TRIPLE (grid z = triple t:
+// streams sid + 3 t + k, planes 3 t + c): the three streams' normals are evaluated ONCE (Philox / Box-Muller is the cost of the draw) and
+// stay in registers as floats -- 16 points x 3 streams x 2 normals per lane, the same count in float64 as in float32 -- while the three
+// planes go through the column pipeline one after the other; the mix and the rotation (a few multiplies and the amplitude loads) are formed
+// per plane from the kept normals.  Same counters, edge rules, 1 / sqrt 2, mixing order and rotation expressions as grf_mix_kernel: with
+// pass 2 behind it plane 3 t + c is bit for bit oa_fft_cols(inverse) of component c of that draw (-ffp-contract=off).
+// ===========================================================================
+template <typename T>
+struct MixColArgs {
+    uint64_t seed, sid;        // Philox key; grid z = triple t: streams sid + 3 t .. sid + 3 t + 2
+    const T* cs[9];            // oa_grf_mix's amplitude blocks [c * 3 + k] (row pitch `pitch`), nullptr = zero block
+    const T* rc; const T* rs;  // the Q, U -> E, B planes (the sine enters negated), or both nullptr: the planes are T, E, B
+    cx<T>* out;                // plane 3 t + c lies (3 t + c) * out_zstride elements behind `out`
+    long out_zstride, pitch;   // complex elements
+    int width, ny, nxh;        // width = nxh + 1 columns
+    int logL, NT;
+    const cx<T>* tw;           // master table of length 2^logTw (= Ny)
+    int logTw;
+    long in_ns, out_gs;        // N2, N1: input row of point n in group g = g + n N2, output row of bin k = g N1 + k
+    int twiddle;               // multiply bin k of group g by W_{Ny}^{g k}
+};
+
+template <typename T>
+struct MixColLoad {
+    uint64_t seed, sid;        // sid: the triple's first stream
+    const T* const* cs;
+    const T* rc; const T* rs;
+    long kp;
+    int ny, nxh, npair;
+    int y0, ystep;      // row of point n: y0 + n * ystep
+    int x0, ncols;      // first column and valid columns of this tile (x0 is even)
+    OA_HD int counter_row(int y, int x) const { return ((x == 0 || x == nxh) && y > ny / 2) ? ny - y : y; }
+    OA_HD void normals(int ys, int x, float (&n)[3][4]) const {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) normals4(seed, sid + (uint64_t)k, (uint64_t)ys * (uint64_t)npair + (uint64_t)(x >> 1), n[k]);
+    }
+    // row cc of the mixing table applied to the three white modes: terms w_k * cs[cc][k] formed and added in k order, NULL blocks skipped
+    template <typename U> OA_HD cx<U> mix(const cx<U> (&w)[3], long i, int cc) const {
+        cx<U> v = mk<U>((U)0, (U)0);
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (!cs[cc * 3 + k]) continue;
+            const U q = cs[cc * 3 + k][i];
+            const cx<U> term = mk<U>(w[k].x * q, w[k].y * q);
+            v = any ? v + term : term;
+            any = true;
+        }
+        return v;
+    }
+    // component c of the mode of (y, x) from the two normals n[k] = (re, im) each stream k holds for it (slots 2 j, 2 j + 1 of ITS counter,
+    // j = x & 1), as the inverse pass reads it (real and imaginary part swapped): grf_mix_kernel's expressions in its order
+    template <typename U> OA_HD cx<U> mode(const float (&n)[3][2], int y, int x, int c) const {
+        const U rs2 = (U)0.70710678118654752440;
+        const bool edgecol = (x == 0 || x == nxh);
+        const bool cj = edgecol && y > ny / 2;
+        const int ys = cj ? ny - y : y;
+        cx<U> w[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            U re = (U)n[k][0], im = (U)n[k][1];
+            if (edgecol && (ys == 0 || ys == ny / 2)) { im = (U)0; }
+            else { re *= rs2; im *= rs2; }
+            if (cj) im = -im;
+            w[k] = mk<U>(re, im);
+        }
+        const long i = (long)y * kp + x;
+        cx<U> r;
+        if (c == 0 || !rc) r = mix<U>(w, i, c);
+        else {
+            const cx<U> p = mix<U>(w, i, 1), q = mix<U>(w, i, 2);
+            const U cc = rc[i], ss = -rs[i];
+            r = c == 1 ? p * cc - q * ss : p * ss + q * cc;
+        }
+        return mk<U>(r.y, r.x);
+    }
+    // one element of plane c (the statement; the kernel evaluates a lane pair's counters once per triple: mix_col_normals / mix_col_fill)
+    template <typename U> OA_HD cx<U> get(int n, int c, int plane) const {
+        if (c >= ncols) return mk<U>((U)0, (U)0);
+        const int y = y0 + n * ystep, x = x0 + c, j = x & 1;
+        float nn[3][4];
+        normals(counter_row(y, x), x, nn);
+        const float own[3][2] = {{nn[0][2 * j], nn[0][2 * j + 1]}, {nn[1][2 * j], nn[1][2 * j + 1]}, {nn[2][2 * j], nn[2][2 * j + 1]}};
+        return mode<U>(own, y, x, plane);
+    }
+};
+
+// The normals behind a lane's sixteen points of ITS column, all three streams, each Philox counter evaluated ONCE per triple
+// (grf_col_fill's lane-pair split: one counter yields the modes of columns 2 p and 2 p + 1, the adjacent lanes tid, tid ^ 1 at the same
+// points; the even lane evaluates the counters of the first eight points, the odd lane those of the last eight, each keeps its own
+// column's two normals per stream and hands the other column's to its neighbour -- DPP; through the tile under the thread emulator, which
+// has no lanes).  own[slot][k] = (re, im) of stream k at first-stage slot `slot` (stage_in's mapping).  Where the even column is
+// self-conjugate (0 or nx/2) and the row lies above the middle, its normals come from the mirrored row's counter and the odd column's from
+// the row's own -- grf_mix_kernel's two evaluations for such a pair.
+// The stream loop stays ROLLED with the point loop unrolled inside it: eight independent Philox chains in flight, one copy of the
+// evaluation per point in the code (three would exceed what the compiler unrolls, and an array indexed by a loop counter lives in
+// scratch memory); the stream index is uniform, so the stores are selects on a scalar condition.
+template <typename T, int R, class Ctx>
+OA_HD void mix_col_normals(Ctx& ctx, cx<T>* s, float (&own)[EPT][3][2], int tid, int NT, int logL, const MixColLoad<T>& ld) {
+    constexpr int LR = Log2c<R>::v;
+    constexpr int logC = COL_LOGC;
+    constexpr int H = EPT / 2;
+    const int logLR = logL - LR;
+    const int odd = tid & 1;
+    int ys_[H], xe_[H];
+#pragma unroll
+    for (int i = 0; i < H; ++i) {
+        const int slot = i + odd * H, u = slot >> LR, t = slot & (R - 1);
+        const int b = tid + u * NT, c = b & ((1 << logC) - 1), j = b >> logC;
+        ys_[i] = ld.y0 + (j + (t << logLR)) * ld.ystep;
+        xe_[i] = ld.x0 + (c & ~1);
+    }
+    // (uniform over the workgroup: the tile holds column 0 or nx/2)
+    const bool edge_tile = ld.x0 == 0 || (ld.x0 <= ld.nxh && ld.nxh < ld.x0 + (1 << logC));
+#pragma nounroll
+    for (int k = 0; k < 3; ++k) {
+        float keep[H][2], send[H][2];
+#pragma unroll
+        for (int i = 0; i < H; ++i) {
+            float m[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (xe_[i] <= ld.nxh) normals4(ld.seed, ld.sid + (uint64_t)k, (uint64_t)ys_[i] * (uint64_t)ld.npair + (uint64_t)(xe_[i] >> 1), m);
+            keep[i][0] = odd ? m[2] : m[0]; keep[i][1] = odd ? m[3] : m[1];
+            send[i][0] = odd ? m[0] : m[2]; send[i][1] = odd ? m[1] : m[3];
+        }
+        if (edge_tile) {
+#pragma unroll
+            for (int i = 0; i < H; ++i) {
+                const int ys = ld.counter_row(ys_[i], xe_[i]);
+                if (xe_[i] > ld.nxh || ys == ys_[i]) continue;
+                float m[4];
+                normals4(ld.seed, ld.sid + (uint64_t)k, (uint64_t)ys * (uint64_t)ld.npair + (uint64_t)(xe_[i] >> 1), m);
+                if (odd) { send[i][0] = m[0]; send[i][1] = m[1]; }
+                else { keep[i][0] = m[0]; keep[i][1] = m[1]; }
+            }
+        }
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+        for (int i = 0; i < H; ++i) { send[i][0] = lane_swap1(send[i][0]); send[i][1] = lane_swap1(send[i][1]); }
+#else
+        float* const sf = reinterpret_cast<float*>(s);
+        for (int i = 0; i < H; ++i) { sf[(tid * H + i) * 2] = send[i][0]; sf[(tid * H + i) * 2 + 1] = send[i][1]; }
+        ctx.sync();
+        for (int i = 0; i < H; ++i) { send[i][0] = sf[((tid ^ 1) * H + i) * 2]; send[i][1] = sf[((tid ^ 1) * H + i) * 2 + 1]; }
+        ctx.sync();
+#endif
+#pragma unroll
+        for (int kk = 0; kk < 3; ++kk)
+            if (kk == k) {
+#pragma unroll
+                for (int i = 0; i < H; ++i) {
+                    own[i][kk][0] = odd ? send[i][0] : keep[i][0];         own[i][kk][1] = odd ? send[i][1] : keep[i][1];
+                    own[i + H][kk][0] = odd ? keep[i][0] : send[i][0];     own[i + H][kk][1] = odd ? keep[i][1] : send[i][1];
+                }
+            }
+    }
+}
+
+// v[u * R + t] = ld.get(j_u + t * L / R, c_u, plane) from the kept normals of the lane's own column
+template <typename T, int R>
+OA_HD void mix_col_fill(cx<T>* v, const float (&own)[EPT][3][2], int plane, int tid, int NT, int logL, const MixColLoad<T>& ld) {
+    constexpr int LR = Log2c<R>::v;
+    constexpr int logC = COL_LOGC;
+    const int logLR = logL - LR;
+#pragma unroll
+    for (int slot = 0; slot < EPT; ++slot) {
+        const int u = slot >> LR, t = slot & (R - 1);
+        const int b = tid + u * NT, c = b & ((1 << logC) - 1), j = b >> logC;
+        const int y = ld.y0 + (j + (t << logLR)) * ld.ystep;
+        v[slot] = c < ld.ncols ? ld.template mode<T>(own[slot], y, ld.x0 + c, plane) : mk<T>((T)0, (T)0);
+#if defined(__HIP_DEVICE_COMPILE__)
+        // the amplitude and rotation loads of four slots in flight at a time: hoisted all at once (sixteen slots x up to eleven planes) they
+        // would not fit the register file next to the kept normals
+        if ((slot & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+#endif
+    }
+}
+
+// plane C of the triple: its modes from the kept normals, then the column pipeline into plane 3 t + C
+template <typename T, class SEQ, int C, class Ctx>
+OA_HD void col_mix_plane(Ctx& ctx, const MixColArgs<T>& a, const MixColLoad<T>& ld, const float (&own)[EPT][3][2], cx<T>* s, const cx<T>* twl,
+                         const cx<T>* ti, int tid, long g, long t, int c0, int ncols) {
+    constexpr int CLC = COL_LOGC, logL = seq_total_log<SEQ>();
+    constexpr int CNT = ((1 << (logL + CLC)) / EPT) > 0 ? ((1 << (logL + CLC)) / EPT) : 1;
+    const ColStore<T> st{a.out + (3 * t + C) * a.out_zstride + g * a.out_gs * a.pitch + c0, (unsigned)a.pitch, ncols, true,
+                         a.twiddle ? ti : nullptr, (unsigned)g, (T)1, 0, 0, 0, 0};
+    cx<T> v[EPT];
+    mix_col_fill<T, SEQ::get(0)>(v, own, C, tid, CNT, logL, ld);
+    col_pipeline_from_regs<T, SEQ>(ctx, s, v, tid, CNT, CLC, twl, logL, st);
+}
+
+template <typename T, class SEQ, class Ctx>
+OA_HD void col_mix_body(Ctx& ctx, const MixColArgs<T>& a) {
+    cx<T>* s = reinterpret_cast<cx<T>*>(ctx.smem());
+    const int tid = ctx.tid();
+    constexpr int CLC = COL_LOGC;
+    constexpr int CNT = ((1 << (seq_total_log<SEQ>() + COL_LOGC)) / EPT) > 0 ? ((1 << (seq_total_log<SEQ>() + COL_LOGC)) / EPT) : 1;
+    const int c0 = ctx.bid_x() << CLC;
+    const long g = ctx.bid_y();
+    int ncols = a.width - c0;
+    if (ncols > (1 << CLC)) ncols = 1 << CLC;
+    constexpr int logL = seq_total_log<SEQ>();
+    cx<T>* twl = s + (1 << (logL + CLC));
+    cx<T>* ti = twl + tw_lds_size(logL);
+    tw_lds_fill<T>(ctx, twl, a.tw, a.logTw, logL, CNT);
+    if (a.twiddle)
+        for (int i = tid; i < (1 << logL); i += CNT) ti[i] = a.tw[(unsigned)g * (unsigned)i];
+    const long t = ctx.bid_z();
+    const MixColLoad<T> ld{a.seed, a.sid + 3 * (uint64_t)t, a.cs, a.rc, a.rs, a.pitch, a.ny, a.nxh, a.nxh / 2 + 1, (int)g, (int)a.in_ns, c0, ncols};
+    float own[EPT][3][2];
+    mix_col_normals<T, SEQ::get(0)>(ctx, s, own, tid, CNT, logL, ld);
+    ctx.sync();                                     // the twiddle tables are in LDS
+    // (three calls, not a loop: the kept normals stay in registers only when every index into them is a literal after inlining; the
+    // barriers between them: a plane's last stage has left the tile before the next plane's first stage writes it)
+    col_mix_plane<T, SEQ, 0>(ctx, a, ld, own, s, twl, ti, tid, g, t, c0, ncols);
+    ctx.sync();
+    col_mix_plane<T, SEQ, 1>(ctx, a, ld, own, s, twl, ti, tid, g, t, c0, ncols);
+    ctx.sync();
+    col_mix_plane<T, SEQ, 2>(ctx, a, ld, own, s, twl, ti, tid, g, t, c0, ncols);
+}
+
 }  // namespace oa

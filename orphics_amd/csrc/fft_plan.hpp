@@ -358,6 +358,24 @@ struct Fft2dPlan {
         cols(q, out, kp, out, kp, width, true, (T)1, 2, 1, nullptr, nullptr, 0, false, -1, nreal, zstride, zstride);
     }
 
+    // ---- ntriples mixed T, Q, U draws (streams sid + 3 t + k) straight into their inverse column transform (oa_grf_mix_icols): pass 1
+    //      evaluates a triple's normals once per workgroup and takes its three planes through the pipeline (col_mix_body), pass 2 is the
+    //      in-place launch of cols() over the 3 ntriples planes
+    template <class Launcher>
+    void grf_mix_icols(Launcher& q, uint64_t seed, uint64_t sid, int ntriples, const T* const* cs, const T* rc, const T* rs, cx<T>* out,
+                       long zstride) const {
+        const int logN1 = (logNy + 1) / 2, logN2 = logNy - logN1;
+        const long N1 = 1L << logN1, N2 = 1L << logN2;
+        const int C = 1 << COLC, width = nx / 2 + 1, tiles = (width + C - 1) / C;
+        MixColArgs<T> a{};
+        a.seed = seed; a.sid = sid; a.rc = rc; a.rs = rs; a.out = out; a.out_zstride = zstride; a.pitch = kp; a.width = width; a.ny = ny;
+        for (int i = 0; i < 9; ++i) a.cs[i] = cs[i];
+        a.nxh = nx / 2; a.logL = logN1; a.NT = (int)((N1 * C) / EPT); a.tw = tw_y; a.logTw = logNy; a.in_ns = N2; a.out_gs = N1;
+        a.twiddle = (logN2 > 0) ? 1 : 0;
+        q.col_mix(tiles, (int)N2, a.NT, ((size_t)N1 * C + tw_lds_size(logN1) + N1) * sizeof(cx<T>), a, ntriples);
+        cols(q, out, kp, out, kp, width, true, (T)1, 2, 1, nullptr, nullptr, 0, false, -1, 3 * ntriples, zstride, zstride);
+    }
+
     // (A) legs + inverse column transform of the three leg planes (outputs ready for rows_qe)
     template <class Launcher>
     void legs_cols(Launcher& q, const cx<T>* kX, const cx<T>* kY, const T* FG, const T* FH, const T* lxd, const T* lyd,

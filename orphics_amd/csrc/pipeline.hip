@@ -67,7 +67,8 @@ struct Pipeline {
     DevBuf mvmc;                      // oa_mc_run_mv: the three drawn hc planes | per-estimator kappa planes (only when the one-launch divergence
                                       // is not engaged) | oa_bin_power_multi's partials | its sums
     DevBuf mvwin;                     // oa_mc_run_mv_windowed: the three full-plane T, Q, U draws | one column temporary per plane (the real maps of
-                                      // the unfused flow) | the three compact row-transformed planes
+                                      // the unfused flow) | the three compact row-transformed planes; oa_mc_run_rdn0_mv_windowed's fused-draw
+                                      // arm: six full planes (T, Q, U of s, then of s') | six compact row-transformed planes
     // oa_rdn0_set_data / oa_mc_run_rdn0.  On a band grid the two buffers are the inner plan's, the key is the map's plan's
     DevBuf rdn0_legs;                 // the data map's three compact leg planes gx, gy, h, as the leg stage of oa_qe_tt(kX = d) leaves them
     DevBuf rdn0_pool;                 // 2 MC_BATCH_MAX drawn hc planes | 2 MC_BATCH_MAX kappa planes | the partial sums of the tail (rdn0.hpp)
@@ -1983,31 +1984,37 @@ static int mc_mv_pow2_loop(oa_plan* p, Pipeline* q, const McMvArgs& a, McMvLoop*
  * POWER OF TWO, fused: one fused row launch over the three planes (inverse columns, C2R / Npix -> x window -> R2C, the real maps in LDS only,
  * leg columns stored at the compact pitch), one batched forward column launch, Q, U -> E, B on the band.  Unfused (A/B): the window at
  * the C2R's store, the real map in HBM, the R2C on the leg band. */
-static int mv_window_source_pow2(oa_plan* p, Pipeline* q, const McMvArgs& a, bool fused, McMvLoop* L) {
+// ONE windowed triple (both entries' per-triple body): streams sid0 .. sid0 + 2 -> T, E, B on the leg band of dst[0..2] (full-pitch hc planes
+// one plane apart).  wb: 3 full T, Q, U planes | 3 column temporaries | 3 compact row planes
+static int mv_window_triple_pow2(oa_plan* p, const McMvArgs& a, bool fused, uint64_t sid0, char* wb, void* const* dst) {
     const size_t es = elem_bytes(p), pb = plane_bytes(p);
     const long pl = work_pitch(p, a.wl);
     const size_t lb = (size_t)pl * p->ny * es;
-    if (int rc = q->mvwin.reserve(6 * pb + 3 * lb)) return rc;
-    char* const wb = q->mvwin.at();
     char* const tmp = wb + 3 * pb;
     char* const rowT = wb + 6 * pb;
     const double inv = 1.0 / ((double)p->ny * p->nx);
-    void* const* const dst = L->draw;
-    L->source = [=](long i) -> int {
-        void* tqu[3] = {wb, wb + pb, wb + 2 * pb};
-        int rc = grf_mix_teb_to_tqu(p, a.base_seed, 3 * (uint64_t)i, a.covsqrt, a.rot_c, a.rot_s, tqu, a.st);
-        if (rc) return rc;
-        if (fused) {
-            if ((rc = qe_windowed_rows_w(p, wb, tmp, a.window, a.wl, pl, inv, a.st, rowT, 3, plane_elems(p), (long)(lb / es)))) return rc;
-            if ((rc = qe_fwd_cols_batch_w(p, rowT, pl, dst[0], 3, (long)(lb / es), plane_elems(p), a.wl, a.rl, a.st))) return rc;
-        } else {
-            for (int f = 0; f < 3; ++f) {
-                if ((rc = oa_fft_c2r_windowed(p, tqu[f], tmp + (size_t)f * pb, inv, a.window, a.st))) return rc;
-                if ((rc = oa_fft_r2c(p, tmp + (size_t)f * pb, dst[f], 1.0, a.wl, a.rl, a.st))) return rc;
-            }
+    void* tqu[3] = {wb, wb + pb, wb + 2 * pb};
+    int rc = grf_mix_teb_to_tqu(p, a.base_seed, sid0, a.covsqrt, a.rot_c, a.rot_s, tqu, a.st);
+    if (rc) return rc;
+    if (fused) {
+        if ((rc = qe_windowed_rows_w(p, wb, tmp, a.window, a.wl, pl, inv, a.st, rowT, 3, plane_elems(p), (long)(lb / es)))) return rc;
+        if ((rc = qe_fwd_cols_batch_w(p, rowT, pl, dst[0], 3, (long)(lb / es), plane_elems(p), a.wl, a.rl, a.st))) return rc;
+    } else {
+        for (int f = 0; f < 3; ++f) {
+            if ((rc = oa_fft_c2r_windowed(p, tqu[f], tmp + (size_t)f * pb, inv, a.window, a.st))) return rc;
+            if ((rc = oa_fft_r2c(p, tmp + (size_t)f * pb, dst[f], 1.0, a.wl, a.rl, a.st))) return rc;
         }
-        return band_rot2(p->dtype, a.rot_c, a.rot_s, dst[1], dst[2], p->ny, p->kp, a.wl, a.rl, a.st);
-    };
+    }
+    return band_rot2(p->dtype, a.rot_c, a.rot_s, dst[1], dst[2], p->ny, p->kp, a.wl, a.rl, a.st);
+}
+static size_t mv_window_triple_bytes(const oa_plan* p, int wl) {
+    return 6 * plane_bytes(p) + 3 * (size_t)work_pitch(p, wl) * p->ny * elem_bytes(p);
+}
+static int mv_window_source_pow2(oa_plan* p, Pipeline* q, const McMvArgs& a, bool fused, McMvLoop* L) {
+    if (int rc = q->mvwin.reserve(mv_window_triple_bytes(p, a.wl))) return rc;
+    char* const wb = q->mvwin.at();
+    void* const* const dst = L->draw;
+    L->source = [=](long i) -> int { return mv_window_triple_pow2(p, a, fused, 3 * (uint64_t)i, wb, dst); };
     return 0;
 }
 /* BAND GRID, fused: ONE batched inverse column launch over the three N-grid planes (in place), ONE fused row launch, the pruned column DFT
@@ -2496,6 +2503,70 @@ int oa_rdn0_set_data_mv(oa_plan* p, const void* const* host_kD, int nest, const 
     return 0;
 }
 
+// the default of OA_OPT_DRAW_FUSED for oa_mc_run_rdn0_mv_windowed (its own constant: the rule is the TT entry's, the kernel is another):
+// 1 only once oa_grf_mix_icols has measured faster per triple than grf_mix_teb_to_tqu + the batched inverse columns beyond both 10th - 90th
+// spreads at every measured geometry (tools/rdn0_pol_bench.py --windowed).  No such measurement is recorded yet, so the default
+// is the per-triple sequence; OA_OPT_DRAW_FUSED = 1 opts in, and the moments are bit-equal either way
+constexpr bool DRAW_FUSED_DEFAULT_RDN0_MV = false;
+/* The body of oa_mc_run_rdn0_mv and oa_mc_run_rdn0_mv_windowed: every refusal under the caller's name before the first launch, then one
+ * realisation at a time -- the source stage puts T, E, B of s and of s' on the leg band of the six planes of P.draw, then rdn0mv_one.
+ * No window: the two band draws (streams 6 i .. 6 i + 2 and 6 i + 3 .. 6 i + 5).  Window (a.window, a.rot_c, a.rot_s), on planes of
+ * q->mvwin (6 full hc planes | 6 compact row planes; the per-triple arms use mv_window_triple_pow2's layout inside it):
+ *   OA_OPT_WIN_FUSED = 1, OA_OPT_DRAW_FUSED = 1: ONE pass-1 launch with both triples' draws at its load + ONE in-place pass 2
+ *     (oa_grf_mix_icols, ntriples = 2), ONE fused row launch over the six planes, ONE forward column launch over six, Q, U -> E, B per pair;
+ *   OA_OPT_DRAW_FUSED = 0: oa_mc_run_mv_windowed's fused sequence per triple;   OA_OPT_WIN_FUSED = 0: its unfused flow per triple. */
+static int rdn0mv_shard(const std::string& who, oa_plan* p, const McMvArgs& a) {
+    const long sim_lo = a.sim_lo, sim_hi = a.sim_hi;
+    OA_REQUIRE(p && a.covsqrt && a.npieces && a.signs && a.FG && a.FH && a.xsrc && a.ysrc && a.Fn && a.ids && a.counts && a.n && a.S && a.C &&
+               a.sim_hi >= a.sim_lo, who + ": bad argument");
+    OA_REQUIRE(p->pow2, who + ": the one-call RDN0 of an estimator set runs on power-of-two map sides only (not on the band grid of sides 2^a 3^b 5^c "
+               "yet, nor on chirp-z sides)" + RDN0MV_HOW);
+    if (int rc = rdn0mv_set_check(who, p, a.nest, a.npieces, a.FG, a.FH, a.xsrc, a.ysrc, a.wl, a.wk, a.rl, a.rk)) return rc;
+    for (int e = 0; e < a.nest; ++e) OA_REQUIRE(a.Fn[e], who + ": NULL normalisation plane");
+    OA_REQUIRE(!a.w || a.wstride >= (long)p->ny * p->kp, who + ": weight planes closer than one hc-real plane");
+    if (int rc = rdn0mv_tail_check(who.c_str(), a.nest, a.w != nullptr, a.nspec, a.a, a.b, a.nids)) return rc;
+    Pipeline* q = pipe_of(p);
+    OA_REQUIRE(!q->rdn0mv_key.empty() && q->rdn0mv_legs.p, who + ": no data set: call oa_rdn0_set_data_mv with this estimator set first" + RDN0MV_HOW);
+    const Rdn0MvSlots SL = rdn0mv_slots(a.nest, a.npieces, a.FG, a.FH, a.swap, a.xsrc, a.ysrc);
+    const int band[5] = {a.wl, a.wk, a.rl, a.rk, a.mrow};
+    int my = 0;
+    if (int rc = resolve_my(p, a.mrow == 0 ? 0 : q->mcol, a.rl, a.rk, &my)) return rc;
+    OA_REQUIRE(SL.key() == q->rdn0mv_key && std::equal(band, band + 5, q->rdn0mv_band) && my == q->rdn0mv_my,
+               who + ": the data legs are stale -- the filter planes, the bands, the row grid or the column grid (oa_plan_set_col_grid) differ from those "
+               "of oa_rdn0_set_data_mv: call it again" + RDN0MV_HOW);
+    if (int rc = ensure_work(p, q)) return rc;     // (nothing to do after oa_rdn0_set_data_mv)
+    const size_t pb = plane_bytes(p), es = elem_bytes(p);
+    if (int rc = q->rdn0mv_pool.reserve((6 + 2 * (size_t)a.nest) * pb + rdn0mv_scratch_bytes(p->ny, a.rk, a.nspec, a.nids), true)) return rc;
+    if (int rc = ensure_pool(q, rdn0mv_split_bytes(p, SL, a.nest, a.wl, a.wk))) return rc;
+    const long pl = work_pitch(p, a.wl), pe = plane_elems(p);
+    const size_t lb = (size_t)pl * p->ny * es;
+    if (a.window)
+        if (int rc = q->mvwin.reserve(std::max(6 * pb + 6 * lb, mv_window_triple_bytes(p, a.wl)))) return rc;
+    const bool fused = q->opt_win_fused;
+    // (float64 plans of 32768 rows and more have no fused-draw kernel: the per-triple sequence, which is bit-equal)
+    const bool dfused = fused && grf_mix_icols_serves(p) && (q->opt_draw_fused < 0 ? DRAW_FUSED_DEFAULT_RDN0_MV : q->opt_draw_fused != 0);
+    const Rdn0MvPlanes P = rdn0mv_planes(p, q, SL, a.nest, a.wl, a.wk);
+    for (long i = sim_lo; i < sim_hi; ++i) {
+        if (a.window && dfused) {
+            char* const wb = q->mvwin.at();
+            char* const rowT = wb + 6 * pb;
+            if (int rc = grf_mix_icols_w(p, a.base_seed, 6 * (uint64_t)i, 2, a.covsqrt, a.rot_c, a.rot_s, wb, pe, a.st)) return rc;
+            if (int rc = qe_win_rows_w(p, wb, a.window, a.wl, pl, 1.0 / ((double)p->ny * p->nx), a.st, rowT, 6, pe, (long)(lb / es))) return rc;
+            if (int rc = qe_fwd_cols_batch_w(p, rowT, pl, P.draw, 6, (long)(lb / es), pe, a.wl, a.rl, a.st)) return rc;
+            for (int z = 0; z < 2; ++z)
+                if (int rc = band_rot2(p->dtype, a.rot_c, a.rot_s, P.draw + (3 * (size_t)z + 1) * pb, P.draw + (3 * (size_t)z + 2) * pb, p->ny, p->kp,
+                                       a.wl, a.rl, a.st)) return rc;
+        } else {
+            for (int z = 0; z < 2; ++z) {
+                void* const out[3] = {P.draw + 3 * (size_t)z * pb, P.draw + (3 * (size_t)z + 1) * pb, P.draw + (3 * (size_t)z + 2) * pb};
+                if (int rc = a.window ? mv_window_triple_pow2(p, a, fused, 6 * (uint64_t)i + 3 * z, q->mvwin.at(), out)
+                                      : oa_grf_mix_band(p, a.base_seed, 6 * (uint64_t)i + 3 * z, 3, a.covsqrt, 1.0, out, a.wl, a.rl, a.st)) return rc;
+            }
+        }
+        if (int rc = rdn0mv_one(p, q, a, SL, P, my)) return rc;
+    }
+    return 0;
+}
 /* oa_mc_run_rdn0_mv (include/orphics_amd.h): the RDN0 shard [sim_lo, sim_hi) of an estimator set, one realisation at a time (as mc_mv_loop):
  * the two band draws (streams 6 i .. 6 i + 2 and 6 i + 3 .. 6 i + 5) into entry-owned planes, then rdn0mv_one.  Everything is refused before
  * the first launch. */
@@ -2504,40 +2575,28 @@ int oa_mc_run_rdn0_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, 
                       const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights, long mv_wstride, int nspec, const int* host_a,
                       const int* host_b, const int32_t* ids_hc, int nids, const int64_t* counts, double norm, int leg_cols, int kappa_cols,
                       int leg_rows, int kappa_rows, int mrow, int64_t* n, double* S, double* C, void* stream) {
-    const std::string who = "oa_mc_run_rdn0_mv";
     const McMvArgs a{base_seed, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, host_FG, host_FH, host_swap, host_xsrc, host_ysrc,
                      host_Fnorm, mv_weights, mv_wstride, nspec, host_a, host_b, ids_hc, nids, counts, norm, leg_cols, kappa_cols, leg_rows,
                      kappa_rows, mrow, n, S, C, (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr};
-    OA_REQUIRE(p && a.covsqrt && a.npieces && a.signs && a.FG && a.FH && a.xsrc && a.ysrc && a.Fn && a.ids && a.counts && a.n && a.S && a.C &&
-               a.sim_hi >= a.sim_lo, who + ": bad argument");
-    OA_REQUIRE(p->pow2, who + ": the one-call RDN0 of an estimator set runs on power-of-two map sides only (not on the band grid of sides 2^a 3^b 5^c "
-               "yet, nor on chirp-z sides)" + RDN0MV_HOW);
-    if (int rc = rdn0mv_set_check(who, p, nest, host_npieces, host_FG, host_FH, host_xsrc, host_ysrc, leg_cols, kappa_cols, leg_rows, kappa_rows)) return rc;
-    for (int e = 0; e < nest; ++e) OA_REQUIRE(host_Fnorm[e], who + ": NULL normalisation plane");
-    OA_REQUIRE(!mv_weights || mv_wstride >= (long)p->ny * p->kp, who + ": weight planes closer than one hc-real plane");
-    if (int rc = rdn0mv_tail_check(who.c_str(), nest, mv_weights != nullptr, nspec, host_a, host_b, nids)) return rc;
-    Pipeline* q = pipe_of(p);
-    OA_REQUIRE(!q->rdn0mv_key.empty() && q->rdn0mv_legs.p, who + ": no data set: call oa_rdn0_set_data_mv with this estimator set first" + RDN0MV_HOW);
-    const Rdn0MvSlots SL = rdn0mv_slots(nest, host_npieces, host_FG, host_FH, host_swap, host_xsrc, host_ysrc);
-    const int band[5] = {leg_cols, kappa_cols, leg_rows, kappa_rows, mrow};
-    int my = 0;
-    if (int rc = resolve_my(p, mrow == 0 ? 0 : q->mcol, leg_rows, kappa_rows, &my)) return rc;
-    OA_REQUIRE(SL.key() == q->rdn0mv_key && std::equal(band, band + 5, q->rdn0mv_band) && my == q->rdn0mv_my,
-               who + ": the data legs are stale -- the filter planes, the bands, the row grid or the column grid (oa_plan_set_col_grid) differ from those "
-               "of oa_rdn0_set_data_mv: call it again" + RDN0MV_HOW);
-    if (int rc = ensure_work(p, q)) return rc;     // (nothing to do after oa_rdn0_set_data_mv)
-    const size_t pb = plane_bytes(p);
-    if (int rc = q->rdn0mv_pool.reserve((6 + 2 * (size_t)nest) * pb + rdn0mv_scratch_bytes(p->ny, kappa_rows, nspec, nids), true)) return rc;
-    if (int rc = ensure_pool(q, rdn0mv_split_bytes(p, SL, nest, leg_cols, kappa_cols))) return rc;
-    const Rdn0MvPlanes P = rdn0mv_planes(p, q, SL, nest, leg_cols, kappa_cols);
-    for (long i = sim_lo; i < sim_hi; ++i) {
-        for (int z = 0; z < 2; ++z) {
-            void* const out[3] = {P.draw + 3 * (size_t)z * pb, P.draw + (3 * (size_t)z + 1) * pb, P.draw + (3 * (size_t)z + 2) * pb};
-            if (int rc = oa_grf_mix_band(p, base_seed, 6 * (uint64_t)i + 3 * z, 3, host_covsqrt, 1.0, out, leg_cols, leg_rows, a.st)) return rc;
-        }
-        if (int rc = rdn0mv_one(p, q, a, SL, P, my)) return rc;
-    }
-    return 0;
+    return rdn0mv_shard("oa_mc_run_rdn0_mv", p, a);
+}
+
+/* oa_mc_run_rdn0_mv_windowed (include/orphics_amd.h): oa_mc_run_rdn0_mv whose s and s' are the windowed triples of oa_mc_run_mv_windowed's
+ * source stage (streams 6 i + 3 z .. + 2).  The window and its rotation planes are checked first, then rdn0mv_shard. */
+int oa_mc_run_rdn0_mv_windowed(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const void* const* host_covsqrt, int nest,
+                               const int* host_npieces, const double* host_signs, const void* const* host_FG, const void* const* host_FH,
+                               const int* host_swap, const int* host_xsrc, const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights,
+                               long mv_wstride, int nspec, const int* host_a, const int* host_b, const int32_t* ids_hc, int nids, const int64_t* counts,
+                               double norm, int leg_cols, int kappa_cols, int leg_rows, int kappa_rows, int mrow, const void* window_real,
+                               const void* rot_c, const void* rot_s, int64_t* n, double* S, double* C, void* stream) {
+    const std::string who = "oa_mc_run_rdn0_mv_windowed";
+    const McMvArgs a{base_seed, sim_lo, sim_hi, host_covsqrt, nest, host_npieces, host_signs, host_FG, host_FH, host_swap, host_xsrc, host_ysrc,
+                     host_Fnorm, mv_weights, mv_wstride, nspec, host_a, host_b, ids_hc, nids, counts, norm, leg_cols, kappa_cols, leg_rows,
+                     kappa_rows, mrow, n, S, C, (hipStream_t)stream, window_real, rot_c, rot_s, nullptr};
+    OA_REQUIRE(window_real, who + ": NULL window -- oa_mc_run_rdn0_mv is the entry without one" + RDN0MV_HOW);
+    OA_REQUIRE(rot_c && rot_s, who + ": a window acts on Q and U and needs both rotation planes rot_c, rot_s (cos / sin 2 phi_l on the half plane, "
+               "oa_mc_run_mv_windowed's convention: what mc.RDN0MonteCarloPol.set_window binds)" + RDN0MV_HOW);
+    return rdn0mv_shard(who, p, a);
 }
 
 /* Monte-Carlo shard with a REAL-SPACE WINDOW (the reference's analysis flow multiplies every map by its apodisation taper

@@ -680,6 +680,34 @@ class Engine(object):
                                   _ptr(rot[1]) if rot is not None else None, ins, _ptr(filt), float(scale), outs, _stream()))
         return list(out)
 
+    def grf_mix_icols(self, seed, covsqrt_hc, rot, stream_id0=0, ntriples=1, out=None):
+        """``oa_grf_mix_icols``: ``ntriples`` mixed T, Q, U draws (triple t: streams ``stream_id0 + 3 t`` .. ``+ 2``) evaluated inside the
+        load of the inverse column pass, each Philox counter once per triple.  ``covsqrt_hc``: :meth:`grf_mix`'s 3 x 3 table; ``rot`` =
+        (c, s), the Q, U -> E, B planes (``None``: no rotation, the planes are T, E, B).  Plane ``3 t + c`` of the ``(3 ntriples, Ny, kp)``
+        result is bit for bit ``fft_cols(grf_mix(seed, covsqrt_hc, rot=(c, -s), stream_id0=stream_id0 + 3 t)[c], inverse=True,
+        width=nx/2 + 1)``; the row padding is not written.  Power-of-two plans only."""
+        if len(covsqrt_hc) != 3 or any(len(r) != 3 for r in covsqrt_hc):
+            raise ValueError("grf_mix_icols: covsqrt_hc must be a 3 x 3 table")
+        for r in covsqrt_hc:
+            for c in r:
+                if c is not None:
+                    self._chk(c, "hcreal")
+        if rot is not None:
+            self._chk(rot[0], "hcreal"); self._chk(rot[1], "hcreal")
+        ntriples = int(ntriples)
+        shp = (3 * max(ntriples, 0), self.ny, self.kp)
+        if out is None:
+            out = torch.zeros(shp, dtype=self.cdt, device=self.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and tuple(out.shape) == shp and out.dtype == self.cdt and out.is_contiguous()):
+            raise ValueError("grf_mix_icols: out must be a contiguous %s CUDA tensor of shape %s" % (self.cdt, shp))
+        else:
+            _dirty(out)
+        cs = (ctypes.c_void_p * 9)(*[_ptr(covsqrt_hc[i][j]) for i in range(3) for j in range(3)])
+        check(self.lib.oa_grf_mix_icols(self.plan, int(seed), int(stream_id0), ntriples, cs, _ptr(rot[0]) if rot is not None else None,
+                                        _ptr(rot[1]) if rot is not None else None, _ptr(out) if out.numel() else None, self.ny * self.kp,
+                                        _stream()))
+        return out
+
     def grf_mix_band(self, seed, covsqrt_hc, out, width=0, rband=0, scale=1.0, stream_id0=0):
         """``oa_grf_mix_band``: the leg band (columns < width, rows |ky index| < rband; 0 = all) of :meth:`grf_mix`'s plain draw
         (no rotation, no inputs) -- the same values as the full draw there, the rest of the ``out`` planes untouched."""

@@ -293,6 +293,24 @@ def teb_covsqrt(total_power):
     return a, b, c, d
 
 
+def _windowed_teb(e, base_seed, cs, rot, window, draw, maps, stream_id0):
+    """The windowed T, E, B triple of Philox streams ``stream_id0 .. stream_id0 + 2`` through the existing entries (the host loop of the
+    windowed pol drivers and the reference of their one calls): T, E, B -> T, Q, U in the draw's pass (``Engine.grf_mix(rot=(c, -s))`` on
+    the full planes ``draw``), x window in real space (``Engine.irfft(window=...)`` into the real planes ``maps``), ``Engine.rfft`` back
+    into ``draw``, then Q, U -> E, B (``Engine.rot2``): the window multiplies Q and U.  ``rot`` = (c, s, -s).  Returns (kT, kE, kB)."""
+    c, s_, ms = rot
+    e.grf_mix(base_seed, cs, rot=(c, ms), out=draw, stream_id0=int(stream_id0))
+    for j in range(3):
+        if e.pow2 or e.mixed:
+            e.irfft(draw[j], out=maps[j], window=window)
+        else:
+            e.irfft(draw[j], out=maps[j])
+            maps[j].mul_(window)
+        e.rfft(maps[j], out=draw[j])
+    kE, kB = e.rot2(c, s_, draw[1], draw[2])
+    return draw[0], kE, kB
+
+
 class GaussianN0MonteCarloPol(object):
     """N0 Monte Carlo of an estimator set (TT, TE, EE, EB, TB) and its MV combination on Gaussian T, E, B fields with the observed
     total powers: per realisation the bandpowers of every estimator's auto spectrum, of the N0 cross spectra N0^{ab} and of the MV
@@ -494,17 +512,8 @@ class GaussianN0MonteCarloPol(object):
             f = {"T": draw[0], "E": draw[1], "B": draw[2]}
         else:
             # T, E, B -> T, Q, U in the draw's pass, x window in real space, back to T, E, B: the window multiplies Q and U
-            c, s_, ms = self.rot
-            e.grf_mix(self.base_seed, self.cs, rot=(c, ms), out=draw, stream_id0=3 * int(i))
-            for j in range(3):
-                if e.pow2 or e.mixed:
-                    e.irfft(draw[j], out=self.host_maps[j], window=self.window)
-                else:
-                    e.irfft(draw[j], out=self.host_maps[j])
-                    self.host_maps[j].mul_(self.window)
-                e.rfft(self.host_maps[j], out=draw[j])
-            kE, kB = e.rot2(c, s_, draw[1], draw[2])
-            f = {"T": draw[0], "E": kE, "B": kB}
+            kT, kE, kB = _windowed_teb(e, self.base_seed, self.cs, self.rot, self.window, draw, self.host_maps, 3 * int(i))
+            f = {"T": kT, "E": kE, "B": kB}
         fields = [q.reconstruct_hc(XY, f[XY[0]], f[XY[1]], out=outs[j]) for j, XY in enumerate(self.estimators)]
         if self.mv:
             kmv = self.w[0] * fields[0]
@@ -795,7 +804,7 @@ class RDN0MonteCarlo(object):
     ``one_call=False`` is the host loop on any side -- ``Engine.grf_hc`` (full plane) -> ``Engine.irfft`` ->
     x window -> ``Engine.rfft`` for both draws, then the sequence above; ``one_call=True`` raises where there is no one-call path.
     Without ``window`` the class behaves exactly as before it had the argument.  The polarisation / MV driver,
-    :class:`RDN0MonteCarloPol`, has no ``window`` argument yet."""
+    :class:`RDN0MonteCarloPol`, has no ``window`` argument: it takes its window through ``set_window``."""
 
     def __init__(self, qest, data, total_power_half, bin_edges, comm=None, base_seed=1234, one_call=None, window=None):
         torch = _torch()
@@ -998,8 +1007,21 @@ class RDN0MonteCarloPol(object):
     each pair with ``accumulate=True``), the weighted sums in torch, ``Engine.bin_power`` per spectrum for A and for B,
     ``Statistics.add``.  ``one_call=None`` (default): the one call on power-of-two sides, the host loop elsewhere.
 
-    There is no window: simulations that carry the data's apodisation taper (and the mean field that comes with it) are not part of
-    this driver yet, exactly as for :class:`RDN0MonteCarlo`."""
+    There is no window argument to the constructor: bind one with :meth:`set_window` (before any sample is accumulated).  ``s`` and
+    ``s'`` are then the WINDOWED triples :class:`GaussianN0MonteCarloPol` ``(window=...)`` makes for its realisations ``2 i`` and
+    ``2 i + 1``: the full-plane draw rotated E, B -> Q, U, inverse-transformed, multiplied by the window, transformed and rotated back
+    (the window multiplies T, Q, U, not E, B: a taper leaks E into B).  ``data`` is taken as given -- the triple as analysed, i.e.
+    ALREADY apodised by the caller.  ``window_moments`` = (mean w^2, mean w^4); :meth:`debiased` divides mean(w^4) out.  With a window
+    ``one_call=True`` runs ``oa_mc_run_rdn0_mv_windowed`` on power-of-two sides (the source stage of ``oa_mc_run_mv_windowed`` per triple,
+    or -- plan option ``draw_fused`` = 1 -- per realisation ONE inverse column pass-1 launch that evaluates both triples' draws at its
+    load, each Philox counter once per triple: ``oa_grf_mix_icols``, then one pass 2, one fused row launch C2R x window -> R2C and one
+    forward column launch over the six planes, the Q, U -> E, B rotation on the leg band; then the launches above).  ``one_call=None``
+    with a window is the host loop on every side until the one call has been timed against it (``ONE_CALL_WINDOWED_DEFAULT``).  The host loop and :meth:`sample_host` (the reference of the one call) are
+    then, per draw ``z``: ``Engine.grf_mix(rot=(c, -s), stream_id0=6 i + 3 z)`` on full planes, ``Engine.irfft(window=...)`` per field,
+    ``Engine.rfft``, ``Engine.rot2``, then the sequence above.  The data's own reconstructions carry the window's mean field; the
+    simulations' ``A`` and ``B`` carry none (``s``, ``s'``, ``d`` are independent and zero-mean): :meth:`data_bandpowers` takes the stacks
+    ``GaussianN0MonteCarloPol(window=..., mean_field=True)`` accumulates.  Without :meth:`set_window` every method behaves exactly as
+    before the method existed."""
 
     def __init__(self, qest, data, total_power_half, bin_edges, estimators=("TT", "TE", "EE", "EB", "TB"), cross=True, mv=True, comm=None,
                  base_seed=1234, one_call=None, qu=False, iau=False):
@@ -1022,7 +1044,45 @@ class RDN0MonteCarloPol(object):
         self.qu, self.iau = bool(qu), bool(iau)
         self.acc = Statistics(comm=self.comm if hasattr(self.comm, "dist") else None, device=e.device)
         self._host = None
+        self._hostw = None                    # (the real T, Q, U maps of the windowed host loop)
+        self._one_call_asked = one_call
+        self._nsamples = 0
+        self.window = None
+        self.window_moments = (1.0, 1.0)
+        self.rot = None
         self.set_data(data)
+
+    def set_window(self, window):
+        """Bind the data's apodisation window, an ``(Ny, Nx)`` real array (``None`` removes it): every SIMULATION is multiplied by it in
+        real space (T, Q, U) before its transform; the data is never touched.  Sets ``window``, ``window_moments`` = (mean w^2,
+        mean w^4) and the Q, U -> E, B rotation planes ``qest._qu_rot(False)``.  Windowed and unwindowed samples must not share a label:
+        raises once samples have been accumulated.  Returns ``self``."""
+        e = self.eng
+        if self._nsamples:
+            raise RuntimeError("RDN0MonteCarloPol.set_window: %d samples are already accumulated; windowed and unwindowed samples must not "
+                               "share a label -- bind the window before run / run_local, or build another driver" % self._nsamples)
+        if window is None:
+            self.window, self.window_moments, self.rot = None, (1.0, 1.0), None
+        else:
+            w = np.asarray(window, dtype=np.float64)
+            if w.shape != (e.ny, e.nx):
+                raise ValueError("window must be a (Ny, Nx) real-space array")
+            self.window = e.to_real(w)
+            self.window_moments = (float(np.mean(w ** 2)), float(np.mean(w ** 4)))
+            c, s_ = self.q._qu_rot(False)
+            self.rot = (c, s_, -s_)       # Q, U -> E, B planes (oa_rot2's combination) and the negated sine of the inverse rotation
+        self.one_call = self._default_one_call()
+        return self
+
+    def _default_one_call(self):
+        # one_call=None with a window on power-of-two sides: the one call only once it has measured faster than the host loop beyond both
+        # spreads at every measured geometry (tools/rdn0_pol_bench.py --windowed, DESIGN 5b); no such measurement is recorded yet, so the
+        # host loop stays the default there and one_call=True opts in -- ONE_CALL_WINDOWED_DEFAULT
+        if self._one_call_asked is None:
+            return bool(self.eng.pow2) and (self.window is None or self.ONE_CALL_WINDOWED_DEFAULT)
+        return bool(self._one_call_asked)
+
+    ONE_CALL_WINDOWED_DEFAULT = False
 
     def set_data(self, data):
         """Bind another data triple (hc transforms T, E, B, or real maps T, Q, U with ``qu=True``) on the same plan, bins and
@@ -1037,6 +1097,7 @@ class RDN0MonteCarloPol(object):
             self.kd = [e._chk(k.to(e.cdt).contiguous(), "hc") for k in data]
         self._dtoken = object()           # the plan's cached data legs (oa_rdn0_set_data_mv) belong to this token
         self._pd = None
+        self._pd_key = None
         return self
 
     # ---- results (after run / allreduce) ------------------------------------------------------------------------------------------
@@ -1061,26 +1122,61 @@ class RDN0MonteCarloPol(object):
         """D x D covariance of the sample vector (D = 2 * nspec * d: the rdn0 blocks, then the mcn0 blocks)."""
         return self.acc.cov("rdn0")
 
-    def data_bandpowers(self, a, b=None):
-        """``p(QE_a(d; d), QE_b(d; d))``: the bandpowers of the data's own reconstructions, with the driver's bins."""
-        if self._pd is None:
+    def _mean_field_planes(self, mean_field):
+        """label -> complex (Ny, kp) hc tensor of the engine's dtype, from complex tensors or (Ny, kp, 2) stack means"""
+        torch = _torch()
+        e = self.eng
+        labels = list(self.estimators) + (["MV"] if self.mv else [])
+        out = {}
+        for lab, m in mean_field.items():
+            if lab not in labels:
+                raise ValueError("mean_field: %r is not a field of this driver (%s)" % (lab, ", ".join(labels)))
+            m = m if isinstance(m, torch.Tensor) else torch.as_tensor(np.asarray(m))
+            m = m.to(e.device)
+            if not m.is_complex():
+                if tuple(m.shape) != (e.ny, e.kp, 2):
+                    raise ValueError("mean_field[%r] must be a complex (Ny, kp) hc tensor or a real (Ny, kp, 2) stack mean" % lab)
+                m = torch.view_as_complex(m.to(torch.float64).contiguous())
+            if tuple(m.shape) != (e.ny, e.kp):
+                raise ValueError("mean_field[%r] must be a complex (Ny, kp) hc tensor or a real (Ny, kp, 2) stack mean" % lab)
+            out[lab] = m.to(e.cdt)
+        return out
+
+    def data_bandpowers(self, a, b=None, mean_field=None):
+        """``p(QE_a(d; d) - m_a, QE_b(d; d) - m_b)``: the bandpowers of the data's own reconstructions, with the driver's bins.
+        ``mean_field``: a mapping from field label (``"TT"``, ..., ``"MV"``) to a complex hc tensor of kappa_hat's layout or the
+        ``(Ny, kp, 2)`` stack mean ``GaussianN0MonteCarloPol(window=..., mean_field=True)`` accumulates (``acc.stack_mean("mf_EB")``, ...);
+        a label that is absent subtracts nothing, except that the MV field without a ``"MV"`` entry is the weighted sum of the
+        estimators' fields AFTER their subtraction.  None subtracts nothing."""
+        key = None if mean_field is None else tuple(sorted((lab, id(m)) for lab, m in mean_field.items()))
+        if self._pd is None or self._pd_key != key:
             torch = _torch()
             e, q, g = self.eng, self.q, self._set
             f = dict(zip("TEB", self.kd))
+            mf = self._mean_field_planes(mean_field) if mean_field is not None else {}
             fields = [q.reconstruct_hc(XY, f[XY[0]], f[XY[1]]) for XY in self.estimators]
+            raw = list(fields)
+            for j, XY in enumerate(self.estimators):
+                if XY in mf:
+                    fields[j] = fields[j] - mf[XY]
             if self.mv:
-                kmv = g.w[0] * fields[0]
+                src = raw if "MV" in mf else fields
+                kmv = g.w[0] * src[0]
                 for j in range(1, len(self.estimators)):
-                    kmv += g.w[j] * fields[j]
+                    kmv += g.w[j] * src[j]
+                if "MV" in mf:
+                    kmv -= mf["MV"]
                 fields.append(kmv)
             cnt = g.counts[1:-1].double()
             self._pd = torch.cat([e.bin_power(fields[i], fields[j], self.norm, self.ids, self.nids, herm=True, active_cols=g.wk,
                                               active_rows=g.rk)[0][1:-1] / cnt for (i, j) in self.pairs]).cpu().numpy()
+            self._pd_key = key
+            self._pd_hold = None if mean_field is None else list(mean_field.values())     # (the key holds ids: keep the objects alive)
         return self._pd[self._set._slot(a, b)]
 
-    def debiased(self, a, b=None):
-        """``data_bandpowers(a, b) - rdn0(a, b)``."""
-        return self.data_bandpowers(a, b) - self.rdn0(a, b)
+    def debiased(self, a, b=None, mean_field=None):
+        """``(data_bandpowers(a, b, mean_field) - rdn0(a, b)) / window_moments[1]``; the divisor mean(w^4) is 1 without a window."""
+        return (self.data_bandpowers(a, b, mean_field) - self.rdn0(a, b)) / self.window_moments[1]
 
     @property
     def centers(self):
@@ -1097,8 +1193,15 @@ class RDN0MonteCarloPol(object):
             self._host = ([t[j] for j in range(3)], [t[3 + j] for j in range(3)], [q.new_output() for _ in range(2 * nE)],
                           g.counts[1:-1].double())
         s0, s1, outs, cnt = self._host
-        e.grf_mix(self.base_seed, g.cs, out=s0, stream_id0=6 * int(i))
-        e.grf_mix(self.base_seed, g.cs, out=s1, stream_id0=6 * int(i) + 3)
+        if self.window is None:
+            e.grf_mix(self.base_seed, g.cs, out=s0, stream_id0=6 * int(i))
+            e.grf_mix(self.base_seed, g.cs, out=s1, stream_id0=6 * int(i) + 3)
+        else:                                 # the windowed triples of GaussianN0MonteCarloPol(window=...)'s realisations 2 i, 2 i + 1
+            if self._hostw is None:
+                self._hostw = [e.real() for _ in range(3)]
+            s0 = list(_windowed_teb(e, self.base_seed, g.cs, self.rot, self.window, s0, self._hostw, 6 * int(i)))
+            s1 = list(_windowed_teb(e, self.base_seed, g.cs, self.rot, self.window, s1, self._hostw, 6 * int(i) + 3))
+            self.host_fields = (s0, s1)       # (the windowed T, E, B of the last sample_host call)
         idx = {"T": 0, "E": 1, "B": 2}
         sets = []
         for k, (X, Y) in enumerate(((self.kd, s0), (s0, s1))):        # A = (d, s) + (s, d); B = (s, s') + (s', s)
@@ -1138,6 +1241,13 @@ class RDN0MonteCarloPol(object):
                                             int(rl), int(rk), int(q.mrow), _stream()))
             e._rdn0mv_owner = own
         wstride = g.w[0].numel() if g.w is not None else 0
+        if self.window is not None:
+            check(e.lib.oa_mc_run_rdn0_mv_windowed(e.plan, self.base_seed, int(lo), int(hi), A["cs"], nE, A["npieces"], A["signs"], A["fgs"],
+                                                   A["fhs"], A["swaps"], A["xsrc"], A["ysrc"], A["fns"], _ptr(g.w), wstride, self.nspec, A["a"],
+                                                   A["b"], _ptr(self.ids), self.nids, _ptr(g.counts), float(self.norm), int(wl), int(wk), int(rl),
+                                                   int(rk), int(q.mrow), _ptr(self.window), _ptr(self.rot[0]), _ptr(self.rot[1]), _ptr(n), _ptr(S),
+                                                   _ptr(C), _stream()))
+            return
         check(e.lib.oa_mc_run_rdn0_mv(e.plan, self.base_seed, int(lo), int(hi), A["cs"], nE, A["npieces"], A["signs"], A["fgs"], A["fhs"], A["swaps"],
                                       A["xsrc"], A["ysrc"], A["fns"], _ptr(g.w), wstride, self.nspec, A["a"], A["b"], _ptr(self.ids), self.nids,
                                       _ptr(g.counts), float(self.norm), int(wl), int(wk), int(rl), int(rk), int(q.mrow), _ptr(n), _ptr(S), _ptr(C),
@@ -1145,10 +1255,12 @@ class RDN0MonteCarloPol(object):
 
     def run_local(self, sims):
         """Process the given global realisation indices on this rank's GPU: every contiguous block of indices is ONE
-        ``oa_mc_run_rdn0_mv`` call (one-call path), or one :meth:`sample_host` + ``Statistics.add`` per index (host loop)."""
+        ``oa_mc_run_rdn0_mv`` call (``oa_mc_run_rdn0_mv_windowed`` with a window; one-call path), or one :meth:`sample_host` +
+        ``Statistics.add`` per index (host loop)."""
         sims = [int(i) for i in sims]
         if not sims:
             return self
+        self._nsamples += len(sims)
         if not self.one_call:
             for i in sims:
                 self.acc.add("rdn0", self.sample_host(i))

@@ -11,7 +11,12 @@ least 7), in ms per realisation.  One JSON line per (geometry, precision), appen
 vectors of the timed realisations are compared as well (largest difference over the largest |mean|).
 --mode onecall N / --mode hostloop N: N realisations of one path and nothing else (the workload for a kernel trace).
 --geoms: comma-separated NYxNX@RES entries, RES in arcmin (default: 2048x2048@1 and 4096x4096@0.5).  Five estimators, their ten
-crosses, the MV auto; 19 bins."""
+crosses, the MV auto; 19 bins.
+--windowed: the same protocol for the windowed driver (RDN0MonteCarloPol.set_window(taper)), every path in one process on the same plan,
+    blocks of --iters (6) realisations alternated, 7 blocks per path: oa_mc_run_rdn0_mv_windowed with OA_OPT_DRAW_FUSED = 1 and = 0, the
+    windowed host loop (Engine.grf_mix(rot) -> irfft x window -> rfft -> rot2 for both triples, then the sequence above), and the
+    unwindowed oa_mc_run_rdn0_mv as the cost of everything behind the source stage.  Stand-alone, in microseconds per triple:
+    oa_grf_mix_icols (two triples per launch), oa_grf_mix(rot) + the batched inverse columns of its three planes, and that draw alone."""
 import argparse
 import json
 import os
@@ -52,6 +57,102 @@ def block_ms(drv, lo, iters):
     return a.elapsed_time(b) / iters
 
 
+def pct(t, nd=4):
+    return [round(float(np.percentile(t, 10)), nd), round(float(np.percentile(t, 90)), nd)]
+
+
+def events_us(fn, n):
+    import torch
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(n):
+        fn()
+    b.record()
+    b.synchronize()
+    return 1e3 * a.elapsed_time(b) / n
+
+
+def windowed(args, shape, res, q64, tot):
+    """one JSON line per precision: the windowed one call (draw_fused 1 / 0), the windowed host loop, the unwindowed one call; the draw
+    kernels alone"""
+    import ctypes
+    import torch
+    from orphics_amd import maps, mc
+    from orphics_amd._lib import check
+    from orphics_amd.engine import _ptr, _stream
+    edges = np.linspace(20, 3500, 20)
+    taper = np.asarray(maps.get_taper(shape, q64.geom, 12.0, 3.0)[0], dtype=np.float64)
+    it, reps = args.iters, args.reps
+    for prec in args.precs.split(","):
+        q = q64 if prec == "f64" else q64.astype("f32")
+        e = q.eng
+        mk = lambda one_call, win: mc.RDN0MonteCarloPol(q, [e.hc(), e.hc(), e.hc()], tot, edges, estimators=ESTS, base_seed=5, one_call=one_call)
+        one, host, plain = mk(True, True).set_window(taper), mk(False, True).set_window(taper), mk(True, False)
+        # the data as analysed: an apodised triple (the windowed draw of stream 10^6)
+        draw, real = [e.hc() for _ in range(3)], [e.real() for _ in range(3)]
+        data = [k.clone() for k in mc._windowed_teb(e, 17, one.cs, one.rot, one.window, draw, real, 10 ** 6)]
+        for drv in (one, host, plain):
+            drv.set_data(data)
+        paths = [("onecall_draw_fused1", one, 1), ("onecall_draw_fused0", one, 0), ("hostloop", host, -1), ("unwindowed_onecall", plain, -1)]
+        for _, drv, dfu in paths:                     # warm-up of each path: allocations, first-use tables, clocks
+            e.set_option("draw_fused", dfu)
+            drv.run_local(range(0, it))
+        torch.cuda.synchronize()
+        t = {name: [] for name, _, _ in paths}
+        for r in range(reps):                         # alternated block by block, the same realisations for every path
+            for name, drv, dfu in paths:
+                e.set_option("draw_fused", dfu)
+                t[name].append(block_ms(drv, (r + 1) * it, it))
+        e.set_option("draw_fused", -1)
+        one.acc.allreduce(); host.acc.allreduce()
+        m1, m0 = one.acc.mean("rdn0"), host.acc.mean("rdn0")
+        wl, wk, rl, rk = one._set._bands
+        line = dict(tool="rdn0_pol_bench", windowed=True, shape=list(shape), prec=prec, res_arcmin=float(res), estimators=list(ESTS),
+                    nspec=one.nspec, bins=int(one.d), iters=it, reps=reps, leg_band=[int(wl), int(rl)], kappa_band=[int(wk), int(rk)])
+        for name in t:
+            line[name + "_ms"] = round(float(np.median(t[name])), 4)
+            line[name + "_p10_p90"] = pct(t[name])
+        best = min(float(np.median(t[name])) for name in ("onecall_draw_fused1", "onecall_draw_fused0"))
+        line["speedup"] = round(float(np.median(t["hostloop"])) / best, 2)
+        line["source_stage_ms"] = {name: round(float(np.median(t[name]) - np.median(t["unwindowed_onecall"])), 4)
+                                   for name in ("onecall_draw_fused1", "onecall_draw_fused0")}
+        line["max_diff_mean_over_max_mean"] = float(np.max(np.abs(m1 - m0)) / np.max(np.abs(m0)))
+        # the draw kernels alone, microseconds per triple
+        w = e.nx // 2 + 1
+        rot = (one.rot[0], one.rot[2])
+        buf = torch.empty((6, e.ny, e.kp), dtype=e.cdt, device=e.device)
+        dr = torch.empty((3, e.ny, e.kp), dtype=e.cdt, device=e.device)
+        co = torch.empty((3, e.ny, e.kp), dtype=e.cdt, device=e.device)
+        drl = [dr[j] for j in range(3)]
+        fused = lambda: e.grf_mix_icols(5, one.cs, one.rot[:2], stream_id0=0, ntriples=2, out=buf)
+        def unfused():
+            for z in range(2):
+                e.grf_mix(5, one.cs, rot=rot, out=drl, stream_id0=3 * z)
+                for j in range(3):
+                    e.fft_cols(dr[j], inverse=True, out=co[j], width=w)
+        draw_only = lambda: (e.grf_mix(5, one.cs, rot=rot, out=drl, stream_id0=0), e.grf_mix(5, one.cs, rot=rot, out=drl, stream_id0=3))
+        k = {"mix_icols_us": [], "mix_then_cols_us": [], "mix_only_us": []}
+        for f in (fused, unfused, draw_only):
+            events_us(f, 5)
+        for r in range(reps):
+            k["mix_icols_us"].append(events_us(fused, 20) / 2)
+            k["mix_then_cols_us"].append(events_us(unfused, 20) / 2)
+            k["mix_only_us"].append(events_us(draw_only, 20) / 2)
+        for name in k:
+            line[name] = round(float(np.median(k[name])), 2)
+            line[name + "_p10_p90"] = pct(k[name], 2)
+        line["cols_launches_note"] = "mix_then_cols: one oa_fft_cols call per plane (the entry batches the three planes in one launch pair)"
+        del buf, dr, co, drl
+        txt = json.dumps(line)
+        print(txt, flush=True)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(txt + "\n")
+        del one, host, plain
+        e.release_pools()
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--mode", nargs="+", default=["compare"], help="compare | onecall N | hostloop N")
@@ -60,6 +161,7 @@ def main():
     ap.add_argument("--iters", type=int, default=6, help="realisations per timed block")
     ap.add_argument("--reps", type=int, default=7, help="timed blocks per path (>= 7)")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file")
+    ap.add_argument("--windowed", action="store_true", help="the windowed driver (see above)")
     args = ap.parse_args()
     import torch
     from orphics_amd import mc
@@ -71,6 +173,9 @@ def main():
         sides, res = spec.split("@")
         shape = tuple(int(s) for s in sides.split("x"))
         q64, tot = setup(shape, float(res))
+        if args.windowed:
+            windowed(args, shape, res, q64, tot)
+            continue
         for prec in args.precs.split(","):
             q = q64 if prec == "f64" else q64.astype("f32")
             e = q.eng
