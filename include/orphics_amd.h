@@ -43,7 +43,7 @@ typedef struct oa_plan oa_plan;
 const char* oa_last_error(void);
 /* ABI version = 100 x the build round that last changed a signature in this header; bindings must refuse a library
  * that reports less than the version they were written against (OA_ABI_VERSION) */
-#define OA_ABI_VERSION 414
+#define OA_ABI_VERSION 415
 int oa_version(void);
 /* number of HIP devices visible; <0 on error (no compute) */
 int oa_device_count(void);
@@ -170,8 +170,9 @@ int oa_qe_cols_div(oa_plan* p, const void* px_rows, const void* py_rows, const v
  *  oa_mc_run_rdn0_windowed : the same with s, s' multiplied by a real-space window (the simulations of an apodised data map).
  *  oa_rdn0_set_data_mv,
  *  oa_mc_run_rdn0_mv   : the same for an estimator SET (TT, TE, EE, EB, TB ...), its cross-spectra and its MV combination on
- *                        power-of-two plans: the data triple's distinct leg planes are cached, then per realisation two T, E, B
- *                        draws -> the 2 nest planes A_e, B_e -> one tail over all spectra (at their declarations below).
+ *                        power-of-two plans, and on the band grid of 2^a 3^b 5^c plans behind oa_qe_band_bind + oa_mc_mv_band_bind: the
+ *                        data triple's distinct leg planes are cached, then per realisation two T, E, B draws -> the 2 nest planes
+ *                        A_e, B_e -> one tail over all spectra (at their declarations below).
  *  BINDING: the plan keeps the POINTERS handed to oa_plan_set_filters / oa_plan_set_bins and may keep derived copies of what they
  *  point to (tile-major Fnorm / ids of the fused divergence launch; the (FG, FH) values of the R-split column stage in thread order).  Every call of either entry invalidates those copies -- also
  *  when the addresses are the ones bound before -- so a caller that changes the contents of a bound plane calls the entry again. */
@@ -466,7 +467,7 @@ int oa_mc_run_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const
                  const int* host_ysrc, const void* const* host_Fnorm, const void* mv_weights, long mv_wstride, int nspec, const int* host_a,
                  const int* host_b, const int32_t* ids_hc, int nids, const int64_t* counts, double norm, int leg_cols, int kappa_cols,
                  int leg_rows, int kappa_rows, int mrow, int64_t* n, double* S, double* C, void* stream);
-/* REALISATION-DEPENDENT N0 of an estimator SET and its MV combination (power-of-two plans): the RDN0 above for the estimators, crosses and MV
+/* REALISATION-DEPENDENT N0 of an estimator SET and its MV combination (power-of-two plans; 2^a 3^b 5^c plans on a band grid, below): the RDN0 above for the estimators, crosses and MV
  * field of oa_mc_run_mv.  The estimator set is oa_mc_run_mv's (nest <= 6, pieces flattened in estimator order: sign, FG, FH, swap; sources by
  * index 0 T, 1 E, 2 B; pure normalisations host_Fnorm; optional MV weights) and so are the spectrum list (field nest = MV), the bins, the
  * counts and the bands.  For field triples X = (X_T, X_E, X_B) and Y, QE_e(X; Y) is estimator e with kX = X[xsrc_e], kY = Y[ysrc_e].  With
@@ -492,11 +493,30 @@ int oa_mc_run_mv(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_hi, const
  *                        and the 3 launches of the tail (partial sums per fixed group of band rows with A_MV, B_MV formed in registers, the
  *                        fold to x_i, the moment update).  Every sum has an order fixed by the band, the bins and the spectrum list: the
  *                        moments are the same bit for bit on every run and however a range is cut into calls.
- * Refused by name before anything is launched, n, S, C untouched: a plan that is not power-of-two (band-grid and chirp-z sides: the
- * message names mc.RDN0MonteCarloPol and one_call=False); no data set; stale data legs (another filter-plane list, other bands or mrow, a
- * column grid changed by oa_plan_set_col_grid since oa_rdn0_set_data_mv); nest outside 1..6; a source index outside [0, 3); NULL planes;
- * a (nspec, nids) beyond the tail's tables: it holds nspec <= 28, 3 <= nids <= 1024, nspec nids <= 4096 -- every (nspec, nids >= 3)
- * oa_bin_power_multi accepts. */
+ * ON A BAND GRID (2^a 3^b 5^c plans).  Three set-up calls come first, in this order: oa_qe_band_bind with the set's distinct filter planes,
+ * its pure normalisations (in the order of host_Fnorm), the call's bands, mrow and column grid; oa_mc_mv_band_bind with the weights, the bin
+ * ids, nids and nspec_max >= nspec; then oa_rdn0_set_data_mv.  On such a plan oa_rdn0_set_data_mv looks the call's filter planes up in the
+ * oa_qe_band_bind binding, embeds the leg band of the data transforms into inner source planes, makes the data's distinct leg planes on the
+ * INNER plan with the inner filter copies and keeps them there; it also takes every plane a shard would otherwise allocate (the inner plan's
+ * leg pool for s, s' and the 2 nest chains, the six inner draw planes, the 2 nest inner kappa planes, the tail's scratch for the Monte-Carlo
+ * binding's nspec_max x nids, the device tables).  A shard then neither allocates nor synchronises.  Per realisation: ONE launch draws T, E, B
+ * of s and of s' into the inner layout (oa_grf_mix_band_inner_triples, ntriples = 2: the N grid's Philox counters, edge rules and covsqrt
+ * planes), then the launches above run on the inner plan with the inner copies of the filters, normalisations (they carry My Mx / (ny nx):
+ * kappa_hat per mode is the same on both grids), weights and bin ids, the binding's row grid and the inner column grid; the tail divides by
+ * the caller's counts, those of the whole N plane.  Since Mx >= 2 kappa_cols the inner Nyquist column is never visited: column 0 is the only
+ * visited one of Hermitian multiplicity 1, as on the N grid.  The moments are bit-reproducible and do not depend on how a range is cut into
+ * calls.  The data legs belong to the oa_qe_band_bind binding they were made on: EVERY later oa_qe_band_bind call (it rewrites the inner
+ * filter copies and may remake the inner plan) makes them stale, also one with the same planes.
+ * Refused there by name before anything is launched, n, S, C untouched, every message naming mc.RDN0MonteCarloPol and one_call=False: no
+ * oa_qe_band_bind binding (both entries: "bound first (oa_qe_band_bind, then oa_mc_mv_band_bind)"); bands or mrow other than the bound ones
+ * (both entries); a filter plane that is not bound (both entries), a normalisation plane that is not bound; no oa_mc_mv_band_bind binding on
+ * the current oa_qe_band_bind binding, or weights, stride, ids, nids or nest other than its, or nspec > its nspec_max; no data set; stale
+ * data legs (an oa_qe_band_bind call since oa_rdn0_set_data_mv, another filter-plane list, other bands, mrow or inner column grid).
+ * oa_mc_run_rdn0_mv_windowed is NOT on the band grid.
+ * Refused by name before anything is launched, n, S, C untouched: a chirp-z plan (the message names mc.RDN0MonteCarloPol and
+ * one_call=False); no data set; stale data legs (another filter-plane list, other bands or mrow, a column grid changed by
+ * oa_plan_set_col_grid since oa_rdn0_set_data_mv); nest outside 1..6; a source index outside [0, 3); NULL planes; a (nspec, nids) beyond the
+ * tail's tables: it holds nspec <= 28, 3 <= nids <= 1024, nspec nids <= 4096 -- every (nspec, nids >= 3) oa_bin_power_multi accepts. */
 int oa_rdn0_set_data_mv(oa_plan* p, const void* const* host_kD, int nest, const int* host_npieces, const void* const* host_FG,
                         const void* const* host_FH, const int* host_swap, const int* host_xsrc, const int* host_ysrc, int leg_cols, int kappa_cols,
                         int leg_rows, int kappa_rows, int mrow, void* stream);
@@ -807,6 +827,15 @@ int oa_grf_mix_icols(oa_plan* p, uint64_t seed, uint64_t stream_id0, int ntriple
  * output plane. */
 int oa_grf_mix_band_inner(oa_plan* p, uint64_t seed, uint64_t stream_id0, int ncomp, const void* const* covsqrt_hc, double scale,
                           void* const* hc_out, int my, long out_pitch, int width, int rband, void* stream);
+/* ntriples (1 or 2) T, E, B triples of oa_grf_mix_band_inner in ONE launch: hc_out holds 3 ntriples planes, and planes 3 z .. 3 z + 2 are
+ * bit for bit those of oa_grf_mix_band_inner(p, seed, stream_id0 + 3 z, ncomp = 3, covsqrt_hc, scale, hc_out + 3 z, my, out_pitch, width,
+ * rband, stream).  The triple is the grid's z index: a thread evaluates each Philox counter once for its triple; nothing outside the band of
+ * the output planes is written.  On an inner grid of 128^2 .. 512^2 points a draw launch is latency-bound, and a realisation of
+ * oa_mc_run_rdn0_mv needs s (streams 6 i ..) and s' (6 i + 3 ..): this is its source stage on a band grid.  Refused before any launch:
+ * ntriples outside 1..2, and what oa_grf_mix_band_inner refuses (a band that is not positive, 2 rband - 1 > min(ny, my),
+ * width > nx/2 + 1, 2 ceil(width / 2) > out_pitch, a NULL output plane). */
+int oa_grf_mix_band_inner_triples(oa_plan* p, uint64_t seed, uint64_t stream_id0, int ntriples, const void* const* covsqrt_hc, double scale,
+                                  void* const* hc_out, int my, long out_pitch, int width, int rband, void* stream);
 /* real white noise N(0,1) plane of n elements (enmap.rand_gauss) */
 int oa_randn(int dtype, uint64_t seed, uint64_t stream_id, void* out, long n, void* stream);
 

@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("ORPHICS_AMD_LIB", os.path.join(_HERE, "liborphics_amd
 
 OA_F32 = 0
 OA_F64 = 1
-ABI_VERSION = 414   # include/orphics_amd.h OA_ABI_VERSION: the signatures below are those of this version
+ABI_VERSION = 415   # include/orphics_amd.h OA_ABI_VERSION: the signatures below are those of this version
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
@@ -74,8 +74,8 @@ SIGNATURES = {
     "oa_mc_run_rdn0": (c_int, [c_void_p, c_u64, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "oa_plan_rdn0_batched": (c_int, [c_void_p]),
     "oa_mc_run_rdn0_windowed": (c_int, [c_void_p, c_u64, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    # ... of an estimator set and its MV combination (power-of-two plans): host_kD[3] + the set's description and bands, then oa_mc_run_mv's
-    # arguments; S: 2 nspec d, C: (2 nspec d)^2
+    # ... of an estimator set and its MV combination (power-of-two plans, and 2^a 3^b 5^c plans behind oa_qe_band_bind + oa_mc_mv_band_bind):
+    # host_kD[3] + the set's description and bands, then oa_mc_run_mv's arguments; S: 2 nspec d, C: (2 nspec d)^2
     "oa_rdn0_set_data_mv": (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
     "oa_mc_run_rdn0_mv": (c_int, [c_void_p, c_u64, c_long, c_long, c_void_p, c_int] + [c_void_p] * 9 + [c_long, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                   c_void_p, c_double] + [c_int] * 5 + [c_void_p] * 4),
@@ -133,6 +133,8 @@ SIGNATURES = {
     "oa_grf_mix_band": (c_int, [c_void_p, c_u64, c_u64, c_int, c_void_p, c_double, c_void_p, c_int, c_int, c_void_p]),
     "oa_grf_mix_icols": (c_int, [c_void_p, c_u64, c_u64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
     "oa_grf_mix_band_inner": (c_int, [c_void_p, c_u64, c_u64, c_int, c_void_p, c_double, c_void_p, c_int, c_long, c_int, c_int, c_void_p]),
+    # ... 1 or 2 T, E, B triples (streams stream_id0 + 3 z ..) in one launch: ntriples in the place of ncomp, 3 ntriples output planes
+    "oa_grf_mix_band_inner_triples": (c_int, [c_void_p, c_u64, c_u64, c_int, c_void_p, c_double, c_void_p, c_int, c_long, c_int, c_int, c_void_p]),
     "oa_randn": (c_int, [c_int, c_u64, c_u64, c_void_p, c_long, c_void_p]),
     "oa_moments_add": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "oa_moments_add_binned": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -75,12 +75,15 @@ struct Pipeline {
     unsigned long rdn0_gen = 0;       // bind_gen the data legs were made under (0: no data set) ...
     int rdn0_my = 0;                  // ... and the column grid
     int rdn0_ran_batched = 0;         // whether the last oa_mc_run_rdn0 / oa_mc_run_rdn0_windowed call ran a batch to its tail (oa_plan_rdn0_batched)
-    // oa_rdn0_set_data_mv / oa_mc_run_rdn0_mv (power-of-two plans; the estimator set comes with every call, so the key is its description)
+    // oa_rdn0_set_data_mv / oa_mc_run_rdn0_mv (the estimator set comes with every call, so the key is its description)
     DevBuf rdn0mv_legs;               // the data triple's distinct leg planes in Rdn0MvSlots' numbering
     DevBuf rdn0mv_pool;               // the 6 drawn hc planes (T, E, B of s, then of s') | the 2 nest kappa planes (A_e, then B_e) | the tail's scratch
     std::vector<const void*> rdn0mv_key;   // Rdn0MvSlots::key() the data legs were made for (empty: no data set) ...
     int rdn0mv_band[5] = {0, 0, 0, 0, 0};  // ... their leg_cols, kappa_cols, leg_rows, kappa_rows, mrow ...
     int rdn0mv_my = 0;                     // ... and their column grid
+    // on a band grid (oa_qe_band_bind + oa_mc_mv_band_bind first) the two buffers are those of the inner plan of the binding, the key, the
+    // bands and the (inner) column grid are kept here, on the map's plan, with ...
+    unsigned long rdn0mv_gen = 0;          // ... PolBind::gen of the binding the data legs were made on
     // tile-major copies of Fnorm and of the bin ids on the coarse grid of the fused divergence + binning launch (what they were
     // made from: rebuilt when the filters / bins / column grid change)
     // (one set per grid a plan can carry: [0] the column grid `my`, [1] the from-map grid `my3`)
@@ -131,6 +134,8 @@ struct Pipeline {
     // an estimator set) with inner-layout copies of the planes handed to oa_qe_band_bind, looked up by their N-grid address
     struct PolBind {
         bool bound = false;
+        unsigned long gen = 0;                 // bumped by every oa_qe_band_bind call: it rewrites the inner filter copies and may remake the
+                                               // inner plan, so whatever was made from them (the data legs of oa_rdn0_set_data_mv) is stale
         oa_plan* plan = nullptr;
         int my = 0, mx = 0;
         int wl = 0, wk = 0, rl = 0, rk = 0, mrow = -1;
@@ -657,6 +662,9 @@ int oa_plan_release_pools(oa_plan* p) {
     // ... the pool the split entries' inner call grew (regrown on demand), and the inner planes of oa_rdn0_set_data / oa_mc_run_rdn0
     if (q->band && q->band->pipe)
         for (DevBuf* b : {&((Pipeline*)q->band->pipe)->split_legs, &((Pipeline*)q->band->pipe)->rdn0_legs, &((Pipeline*)q->band->pipe)->rdn0_pool}) b->release();
+    // ... the inner planes of oa_rdn0_set_data_mv / oa_mc_run_rdn0_mv on the oa_qe_band_bind binding (its leg pool is the binding's: kept)
+    if (q->pb.plan && q->pb.plan->pipe)
+        for (DevBuf* b : {&((Pipeline*)q->pb.plan->pipe)->rdn0mv_legs, &((Pipeline*)q->pb.plan->pipe)->rdn0mv_pool}) b->release();
     // ... and the Monte-Carlo binding with its pool: oa_mc_mv_band_bind makes it again
     q->pb.mc.pool.release();
     q->pb.mc = Pipeline::PolBind::McBind();
@@ -1592,6 +1600,7 @@ static int pol_bind(oa_plan* p, Pipeline* q, int nf, const void* const* filters,
                     int mrow, int mcol, int max_leg_planes) {
     Pipeline::PolBind& B = q->pb;
     B.bound = false;
+    ++B.gen;
     B.mc.bound = false;                             // the Monte-Carlo binding belongs to the binding it was made on
     int my = 0, mx = 0;
     if (int rc = band_grid_rule(p, mrow, mcol, wl, wk, rl, rk, &my, &mx)) return rc;
@@ -1886,11 +1895,14 @@ struct MvShard {
     McMvLoop L;
 };
 // `who`: the entry's name.  `how_all`: every refusal ends with the way out (oa_mc_run_mv_windowed names the driver and one_call=False in
-// each of its refusals); oa_mc_run_mv's messages are as they were.
-static int mixed_mc_mv_lookup(const std::string& who, bool how_all, oa_plan* p, Pipeline* q, const McMvArgs& a, MvShard* out) {
-    static const char* const how = " -- bind the estimator set with oa_qe_band_bind, then oa_mc_mv_band_bind, or run the host loop of the "
-                                   "existing entries (mc.GaussianN0MonteCarloPol with one_call=False)";
-    const std::string tail = how_all ? how : "";
+// each of its refusals); oa_mc_run_mv's messages are as they were.  `how_rdn0` (oa_mc_run_rdn0_mv): that entry's way out in the place of `how`,
+// in every refusal; the inner plan's pool is then not checked here (oa_rdn0_set_data_mv grew it: the entry checks the data legs next).
+static int mixed_mc_mv_lookup(const std::string& who, bool how_all, oa_plan* p, Pipeline* q, const McMvArgs& a, MvShard* out,
+                              const char* how_rdn0 = nullptr) {
+    static const char* const how_mc = " -- bind the estimator set with oa_qe_band_bind, then oa_mc_mv_band_bind, or run the host loop of the "
+                                      "existing entries (mc.GaussianN0MonteCarloPol with one_call=False)";
+    const char* const how = how_rdn0 ? how_rdn0 : how_mc;
+    const std::string tail = (how_all || how_rdn0) ? how : "";
     Pipeline::PolBind& B = q->pb;
     const Pipeline::PolBind::McBind& M = B.mc;
     if (!B.bound) return fail(who + ": on map sides 2^a 3^b 5^c the filter and normalisation planes are bound first" + how);
@@ -1918,7 +1930,7 @@ static int mixed_mc_mv_lookup(const std::string& who, bool how_all, oa_plan* p, 
         iFn[e] = pol_inner(B.nkey, a.Fn[e], nbase, rb);
         if (!iFn[e]) return fail(who + ": a normalisation plane of this call is not bound (oa_qe_band_bind)" + tail);
     }
-    {                                               // the inner plan's leg pool: sized by oa_qe_band_bind, never grown here
+    if (!how_rdn0) {                                // the inner plan's leg pool: sized by oa_qe_band_bind, never grown here
         std::vector<std::pair<int, const void*>> grad, hpl;
         auto add = [](std::vector<std::pair<int, const void*>>& v, int s, const void* f) {
             for (auto& k : v) if (k.first == s && k.second == f) return;
@@ -2066,7 +2078,7 @@ static int mc_mv_shard(const std::string& who, bool how_all, oa_plan* p, const M
     return mc_mv_loop(L, a);
 }
 
-/* ---- oa_rdn0_set_data_mv / oa_mc_run_rdn0_mv: RDN0 of an estimator set (power-of-two plans) ----------------------------------------------
+/* ---- oa_rdn0_set_data_mv / oa_mc_run_rdn0_mv: RDN0 of an estimator set (a plan pointer: the map's power-of-two plan, or the inner plan of a band grid) ----------------------------------------------
  * SLOTS.  The distinct leg planes of a field triple X = (X_T, X_E, X_B) under an estimator set: one gradient pair per distinct
  * (source index, FG), one H plane per distinct (source index, FH) -- qe_mv_pow2's sharing rule with source INDICES in the place of source
  * pointers, so that the data triple d and the draws s, s' number their planes alike.  In a pool of compact planes gradient pair g sits at
@@ -2465,20 +2477,92 @@ int oa_mc_run_mv_windowed(oa_plan* p, uint64_t base_seed, long sim_lo, long sim_
 }
 
 /* oa_rdn0_set_data_mv (include/orphics_amd.h): the data triple's distinct leg planes (rdn0mv_slots) on the column grid of the set's bands,
- * transformed once and kept for oa_mc_run_rdn0_mv.  Set-up entry: may allocate and synchronise. */
+ * transformed once and kept for oa_mc_run_rdn0_mv.  Set-up entry: may allocate and synchronise.  On a 2^a 3^b 5^c plan: on the inner plan of
+ * the current oa_qe_band_bind binding (rdn0mv_set_data_band). */
 static const char* const RDN0MV_HOW = "; run the host loop of the existing entries (mc.RDN0MonteCarloPol with one_call=False)";
+static const char* const RDN0MV_CZT = ": map sides with a prime factor other than 2, 3 and 5 (chirp-z transforms) have no one-call path -- the one-call "
+                                      "RDN0 of an estimator set runs on power-of-two sides and on the band grid of sides 2^a 3^b 5^c";
+static const char* const RDN0MV_BIND = ": on map sides that are not power-of-two the estimator set is bound first (oa_qe_band_bind, then "
+                                       "oa_mc_mv_band_bind) and the entry runs on that binding's band grid";
+// ... on the band grid of the current oa_qe_band_bind binding (whose bands and row grid are the call's: checked by the caller)
+static int rdn0mv_set_data_band(const std::string& who, oa_plan* p, Pipeline* q, const void* const* host_kD, int nest, const int* host_npieces,
+                                const void* const* host_FG, const void* const* host_FH, const int* host_swap, const int* host_xsrc,
+                                const int* host_ysrc, int wl, int wk, int rl, int rk, int mrow, hipStream_t st) {
+    Pipeline::PolBind& B = q->pb;
+    oa_plan* b = B.plan;
+    Pipeline* qb = (Pipeline*)b->pipe;
+    band_options(q);
+    const size_t rb = band_real_bytes(b), cb = plane_bytes(b), es = elem_bytes(b);
+    char* const fbase = B.planes.at();
+    char* const sbase = fbase + (B.fkey.size() + B.nkey.size()) * rb;
+    int total = 0;
+    for (int e = 0; e < nest; ++e) total += host_npieces[e];
+    std::vector<const void*> iFG(total), iFH(total);
+    for (int i = 0; i < total; ++i) {
+        iFG[i] = pol_inner(B.fkey, host_FG[i], fbase, rb);
+        iFH[i] = pol_inner(B.fkey, host_FH[i], fbase, rb);
+        if (!iFG[i] || !iFH[i])
+            return fail(who + ": a filter plane of this call is not bound (oa_qe_band_bind binds every distinct plane)" + RDN0MV_HOW);
+    }
+    // the caller's planes number the slots and make the key; the inner copies (one per distinct bound plane) number alike
+    const Rdn0MvSlots S = rdn0mv_slots(nest, host_npieces, host_FG, host_FH, host_swap, host_xsrc, host_ysrc);
+    const Rdn0MvSlots Si = rdn0mv_slots(nest, host_npieces, iFG.data(), iFH.data(), host_swap, host_xsrc, host_ysrc);
+    OA_REQUIRE(Si.ng() == S.ng() && Si.nh() == S.nh(), who + ": a filter plane is bound twice (oa_qe_band_bind binds every DISTINCT plane)" + RDN0MV_HOW);
+    const void* any = nullptr;
+    for (const auto& g : S.grad) { OA_REQUIRE(host_kD[g.first], who + ": NULL data plane of a source an estimator reads"); any = host_kD[g.first]; }
+    for (const auto& h : S.hpl) OA_REQUIRE(host_kD[h.first], who + ": NULL data plane of a source an estimator reads");
+    int my = 0;
+    if (int rc = resolve_my(b, qb->mcol, rl, rk, &my)) return rc;                  // (pol_bind's resolution: the table exists)
+    const long pl = work_pitch(b, wl);
+    const size_t lb = (size_t)pl * b->ny * es;
+    // everything the shard would otherwise take: the leg planes of d, the pool of s, s' and the chains, the draw / kappa / tail planes
+    // (the tail's scratch for the Monte-Carlo binding's nspec_max x nids where that binding exists already), the device tables
+    if (int rc = qb->rdn0mv_legs.reserve((size_t)S.nplanes() * lb)) return rc;
+    if (int rc = ensure_pool(qb, rdn0mv_split_bytes(b, Si, nest, wl, wk))) return rc;
+    const Pipeline::PolBind::McBind& M = B.mc;
+    const size_t tail = M.bound ? rdn0mv_scratch_bytes(b->ny, rk, M.nspec_max, M.nids) : 0;     // (nspec_max <= 28, nids >= 3: checked by that entry)
+    if (int rc = qb->rdn0mv_pool.reserve((6 + 2 * (size_t)nest) * cb + tail, true)) return rc;
+    if (!qb->mv_ftab) OA_HIP(hipMalloc((void**)&qb->mv_ftab, 32 * sizeof(void*)));
+    if (!qb->mv_rtab) OA_HIP(hipMalloc(&qb->mv_rtab, MV_RTAB_BYTES));
+    // the leg band of the data transforms -> the binding's first three inner source planes (zero outside the band), source index = plane
+    std::vector<const void*> srcs(3);
+    for (int i = 0; i < 3; ++i) srcs[i] = host_kD[i] ? host_kD[i] : any;
+    if (int rc = mv_sources_embed(p, B, srcs, sbase, cb, wl, rl, st)) return rc;
+    const void* const isrc[3] = {sbase, sbase + cb, sbase + 2 * cb};
+    int done = 0;
+    if (int rc = rdn0mv_legs_of(b, qb, Si, isrc, qb->rdn0mv_legs.at(), lb, wl, rl, pl, my, st, &done)) return rc;
+    if (!done)
+        if (int rc = qe_legs_pass2_w(b, qb->rdn0mv_legs.p, Si.nplanes(), (long)(lb / es), wl, pl, st, my)) return rc;
+    q->rdn0mv_key = S.key();
+    const int band[5] = {wl, wk, rl, rk, mrow};
+    std::copy(band, band + 5, q->rdn0mv_band);
+    q->rdn0mv_my = my;
+    q->rdn0mv_gen = B.gen;
+    return 0;
+}
 int oa_rdn0_set_data_mv(oa_plan* p, const void* const* host_kD, int nest, const int* host_npieces, const void* const* host_FG,
                         const void* const* host_FH, const int* host_swap, const int* host_xsrc, const int* host_ysrc, int leg_cols, int kappa_cols,
                         int leg_rows, int kappa_rows, int mrow, void* stream) {
     const std::string who = "oa_rdn0_set_data_mv";
     OA_REQUIRE(p && host_kD && host_npieces && host_FG && host_FH && host_xsrc && host_ysrc, who + ": NULL argument");
-    OA_REQUIRE(p->pow2, who + ": the one-call RDN0 of an estimator set runs on power-of-two map sides only (not on the band grid of sides 2^a 3^b 5^c "
-               "yet, nor on chirp-z sides)" + RDN0MV_HOW);
+    OA_REQUIRE(p->pow2 || p->mixed, who + RDN0MV_CZT + RDN0MV_HOW);
+    if (p->mixed) {
+        Pipeline* q = pipe_of(p);
+        q->rdn0mv_key.clear();
+        OA_REQUIRE(q->pb.bound, who + RDN0MV_BIND + RDN0MV_HOW);
+    }
     if (int rc = rdn0mv_set_check(who, p, nest, host_npieces, host_FG, host_FH, host_xsrc, host_ysrc, leg_cols, kappa_cols, leg_rows, kappa_rows)) return rc;
     OA_REQUIRE(p->have_laxes, who + ": call oa_plan_set_laxes first");
     Pipeline* q = pipe_of(p);
     hipStream_t st = (hipStream_t)stream;
     q->rdn0mv_key.clear();
+    if (p->mixed) {
+        const Pipeline::PolBind& B = q->pb;
+        OA_REQUIRE(leg_cols == B.wl && kappa_cols == B.wk && leg_rows == B.rl && kappa_rows == B.rk && mrow == B.mrow,
+                   who + ": leg / kappa columns and rows or the row grid differ from the bound ones (call oa_qe_band_bind for this band)" + RDN0MV_HOW);
+        return rdn0mv_set_data_band(who, p, q, host_kD, nest, host_npieces, host_FG, host_FH, host_swap, host_xsrc, host_ysrc, leg_cols, kappa_cols,
+                                    leg_rows, kappa_rows, mrow, st);
+    }
     const Rdn0MvSlots S = rdn0mv_slots(nest, host_npieces, host_FG, host_FH, host_swap, host_xsrc, host_ysrc);
     for (const auto& g : S.grad) OA_REQUIRE(host_kD[g.first], who + ": NULL data plane of a source an estimator reads");
     for (const auto& h : S.hpl) OA_REQUIRE(host_kD[h.first], who + ": NULL data plane of a source an estimator reads");
@@ -2508,6 +2592,48 @@ int oa_rdn0_set_data_mv(oa_plan* p, const void* const* host_kD, int nest, const 
 // spreads at every measured geometry (tools/rdn0_pol_bench.py --windowed).  No such measurement is recorded yet, so the default
 // is the per-triple sequence; OA_OPT_DRAW_FUSED = 1 opts in, and the moments are bit-equal either way
 constexpr bool DRAW_FUSED_DEFAULT_RDN0_MV = false;
+/* oa_mc_run_rdn0_mv on a 2^a 3^b 5^c plan (the caller has checked the arguments and that oa_qe_band_bind bound the plan): every pointer of
+ * the call is looked up in the two bindings (mixed_mc_mv_lookup's checks under this entry's name), the data legs must be those of the current
+ * binding, and everything is refused before the first launch.  Then, per realisation, ONE draw launch puts T, E, B of s and of s' on the leg
+ * band of six contiguous inner planes (oa_grf_mix_band_inner_triples: the N grid's counters, edge rules and covsqrt) and rdn0mv_one runs on
+ * the inner plan with the inner filters, normalisations (they carry My Mx / (ny nx)), weights and ids, mrow and column grid as pol_bind
+ * resolved them, and the caller's counts, those of the N plane.  As in oa_mc_run_mv there, the tail's note holds: since Mx >= 2 kappa_cols the
+ * inner Nyquist column is never visited, so column 0 is the only visited one of Hermitian multiplicity 1, as on the N grid.  Nothing is
+ * allocated here after oa_rdn0_set_data_mv behind both bindings (the reservations below find their planes), nothing synchronises. */
+static int rdn0mv_shard_band(const std::string& who, oa_plan* p, const McMvArgs& a) {
+    static const std::string how = std::string(" -- bind the estimator set with oa_qe_band_bind, then oa_mc_mv_band_bind, then call oa_rdn0_set_data_mv") +
+                                   RDN0MV_HOW;
+    Pipeline* q = pipe_of(p);
+    MvShard c;
+    if (int rc = mixed_mc_mv_lookup(who, true, p, q, a, &c, how.c_str())) return rc;
+    Pipeline::PolBind& B = q->pb;
+    oa_plan* b = B.plan;
+    Pipeline* qb = (Pipeline*)b->pipe;
+    OA_REQUIRE(!q->rdn0mv_key.empty(), who + ": no data set: call oa_rdn0_set_data_mv with this estimator set first" + RDN0MV_HOW);
+    const Rdn0MvSlots SL = rdn0mv_slots(a.nest, a.npieces, a.FG, a.FH, a.swap, a.xsrc, a.ysrc);
+    const Rdn0MvSlots Si = rdn0mv_slots(a.nest, a.npieces, c.iFG.data(), c.iFH.data(), a.swap, a.xsrc, a.ysrc);
+    const int band[5] = {a.wl, a.wk, a.rl, a.rk, a.mrow};
+    int my = 0;
+    if (int rc = resolve_my(b, qb->mcol, a.rl, a.rk, &my)) return rc;
+    OA_REQUIRE(q->rdn0mv_gen == B.gen && qb->rdn0mv_legs.p && SL.key() == q->rdn0mv_key && Si.nplanes() == SL.nplanes() && std::equal(band, band + 5, q->rdn0mv_band) &&
+               my == q->rdn0mv_my,
+               who + ": the data legs are stale -- oa_qe_band_bind was called since they were made, or the filter planes, the bands, the row grid or "
+               "the inner column grid differ from those of oa_rdn0_set_data_mv: call oa_rdn0_set_data_mv again" + RDN0MV_HOW);
+    const size_t cb = plane_bytes(b);
+    if (int rc = qb->rdn0mv_pool.reserve((6 + 2 * (size_t)a.nest) * cb + rdn0mv_scratch_bytes(b->ny, a.rk, a.nspec, a.nids), true)) return rc;
+    if (int rc = ensure_pool(qb, rdn0mv_split_bytes(b, Si, a.nest, a.wl, a.wk))) return rc;
+    McMvArgs ai = a;                                // the call in the inner plan's layout
+    ai.FG = c.iFG.data(); ai.FH = c.iFH.data(); ai.Fn = c.iFn.data();
+    ai.w = c.L.w; ai.wstride = c.L.wstride; ai.ids = c.L.ids; ai.mrow = c.L.mrow;
+    const Rdn0MvPlanes P = rdn0mv_planes(b, qb, Si, a.nest, a.wl, a.wk);
+    void* out[6];
+    for (int i = 0; i < 6; ++i) out[i] = P.draw + (size_t)i * cb;
+    for (long i = a.sim_lo; i < a.sim_hi; ++i) {
+        if (int rc = oa_grf_mix_band_inner_triples(p, a.base_seed, 6 * (uint64_t)i, 2, a.covsqrt, 1.0, out, b->ny, b->kp, a.wl, a.rl, a.st)) return rc;
+        if (int rc = rdn0mv_one(b, qb, ai, Si, P, my)) return rc;
+    }
+    return 0;
+}
 /* The body of oa_mc_run_rdn0_mv and oa_mc_run_rdn0_mv_windowed: every refusal under the caller's name before the first launch, then one
  * realisation at a time -- the source stage puts T, E, B of s and of s' on the leg band of the six planes of P.draw, then rdn0mv_one.
  * No window: the two band draws (streams 6 i .. 6 i + 2 and 6 i + 3 .. 6 i + 5).  Window (a.window, a.rot_c, a.rot_s), on planes of
@@ -2519,12 +2645,17 @@ static int rdn0mv_shard(const std::string& who, oa_plan* p, const McMvArgs& a) {
     const long sim_lo = a.sim_lo, sim_hi = a.sim_hi;
     OA_REQUIRE(p && a.covsqrt && a.npieces && a.signs && a.FG && a.FH && a.xsrc && a.ysrc && a.Fn && a.ids && a.counts && a.n && a.S && a.C &&
                a.sim_hi >= a.sim_lo, who + ": bad argument");
-    OA_REQUIRE(p->pow2, who + ": the one-call RDN0 of an estimator set runs on power-of-two map sides only (not on the band grid of sides 2^a 3^b 5^c "
-               "yet, nor on chirp-z sides)" + RDN0MV_HOW);
+    // (the windowed entry is not on the band grid: its power-of-two form has not been timed against the host loop yet)
+    if (a.window)
+        OA_REQUIRE(p->pow2, who + ": the one-call RDN0 of an estimator set runs on power-of-two map sides only (not on the band grid of sides 2^a 3^b 5^c "
+                   "yet, nor on chirp-z sides)" + RDN0MV_HOW);
+    OA_REQUIRE(p->pow2 || p->mixed, who + RDN0MV_CZT + RDN0MV_HOW);
+    if (p->mixed) OA_REQUIRE(pipe_of(p)->pb.bound, who + RDN0MV_BIND + RDN0MV_HOW);
     if (int rc = rdn0mv_set_check(who, p, a.nest, a.npieces, a.FG, a.FH, a.xsrc, a.ysrc, a.wl, a.wk, a.rl, a.rk)) return rc;
     for (int e = 0; e < a.nest; ++e) OA_REQUIRE(a.Fn[e], who + ": NULL normalisation plane");
     OA_REQUIRE(!a.w || a.wstride >= (long)p->ny * p->kp, who + ": weight planes closer than one hc-real plane");
     if (int rc = rdn0mv_tail_check(who.c_str(), a.nest, a.w != nullptr, a.nspec, a.a, a.b, a.nids)) return rc;
+    if (p->mixed) return rdn0mv_shard_band(who, p, a);
     Pipeline* q = pipe_of(p);
     OA_REQUIRE(!q->rdn0mv_key.empty() && q->rdn0mv_legs.p, who + ": no data set: call oa_rdn0_set_data_mv with this estimator set first" + RDN0MV_HOW);
     const Rdn0MvSlots SL = rdn0mv_slots(a.nest, a.npieces, a.FG, a.FH, a.swap, a.xsrc, a.ysrc);

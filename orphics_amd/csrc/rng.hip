@@ -114,6 +114,7 @@ struct GrfMixArgs {
     const cx<T>* in[3];
     const T* filt;
     cx<T>* out[3];
+    cx<T>* out2[3];                // INNER launches with two triples (oa_grf_mix_band_inner_triples): the planes of triple 1 (grid z = 1)
     T scale;
     int ncomp, ny, nx;
     long kp;
@@ -155,7 +156,9 @@ OA_D void store_pair(E* p, long i0, bool second, const Pair<E>& v) {
 // its Philox counter and goes through the same expressions as the full draw: a bit-identical subset of it.
 // INNER (oa_grf_mix_band_inner; with BAND, a.rband >= 1): counters, edge rules and the cs loads are those of N-grid row y as before, the
 // stores go to row yo = ky mod a.my of (a.my, a.okp) planes -- the band in the hc layout of an inner grid (grf_band_inner_kernel's
-// mapping).  Only the store offset differs: the values are those of the BAND launch.
+// mapping).  Only the store offset differs: the values are those of the BAND launch.  Grid z = the TRIPLE of an INNER launch
+// (oa_grf_mix_band_inner_triples): workgroups of z = 1 draw streams sid0 + 3 .. into a.out2 -- the body, and with it every value, is that
+// of a launch of its own with those streams and planes; a thread still evaluates each Philox counter once for its triple.
 template <typename T, int NC, bool HAS_IN, bool VEC, bool BAND = false, bool INNER = false>
 __global__ __launch_bounds__(256) void grf_mix_kernel(GrfMixArgs<T> a) {
     static_assert(!INNER || (BAND && !VEC && !HAS_IN), "the inner layout is a BAND launch");
@@ -163,6 +166,10 @@ __global__ __launch_bounds__(256) void grf_mix_kernel(GrfMixArgs<T> a) {
     const int pr = blockIdx.x * blockDim.x + threadIdx.x;
     int y = blockIdx.y;
     [[maybe_unused]] int yo = y;
+    uint64_t sid0 = a.sid0;
+    if constexpr (INNER) {
+        if (blockIdx.z) sid0 += 3;
+    }
     if constexpr (BAND) {
         if (a.rband > 0 && y >= a.rband) {
             y += ny - (2 * a.rband - 1);
@@ -205,7 +212,7 @@ __global__ __launch_bounds__(256) void grf_mix_kernel(GrfMixArgs<T> a) {
         if (edgecol && y > ny / 2) { ys = ny - y; cj = true; }
         if (ys != cur_ys && x <= nxh) {
 #pragma unroll
-            for (int c = 0; c < NC; ++c) normals4(a.seed, a.sid0 + c, (uint64_t)ys * (uint64_t)npair + (uint64_t)pr, n[c]);
+            for (int c = 0; c < NC; ++c) normals4(a.seed, sid0 + c, (uint64_t)ys * (uint64_t)npair + (uint64_t)pr, n[c]);
             cur_ys = ys;
         }
 #pragma unroll
@@ -263,7 +270,7 @@ __global__ __launch_bounds__(256) void grf_mix_kernel(GrfMixArgs<T> a) {
     }
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-        if constexpr (INNER) store_pair<VEC>(a.out[c], (long)yo * a.okp + 2 * pr, second, o[c]);
+        if constexpr (INNER) store_pair<VEC>(blockIdx.z ? a.out2[c] : a.out[c], (long)yo * a.okp + 2 * pr, second, o[c]);
         else store_pair<VEC>(a.out[c], i0, second, o[c]);
     }
 }
@@ -316,7 +323,7 @@ static int grf_mix_launch(oa_plan* p, uint64_t seed, uint64_t sid0, int ncomp, c
     a.seed = seed; a.sid0 = sid0; a.rneg = rneg;
     for (int i = 0; i < 9; ++i) a.cs[i] = i < ncomp * ncomp ? (const T*)cs[i] : nullptr;
     a.rc = (const T*)rc; a.rs = (const T*)rs;
-    for (int i = 0; i < 3; ++i) { a.in[i] = (in && i < ncomp) ? (const cx<T>*)in[i] : nullptr; a.out[i] = i < ncomp ? (cx<T>*)out[i] : nullptr; }
+    for (int i = 0; i < 3; ++i) { a.in[i] = (in && i < ncomp) ? (const cx<T>*)in[i] : nullptr; a.out[i] = i < ncomp ? (cx<T>*)out[i] : nullptr; a.out2[i] = nullptr; }
     a.filt = (const T*)filt;
     a.scale = (T)scale;
     a.ncomp = ncomp; a.ny = p->ny; a.nx = p->nx; a.kp = p->kp;
@@ -351,7 +358,7 @@ static int grf_mix_band_launch(oa_plan* p, uint64_t seed, uint64_t sid0, int nco
     a.seed = seed; a.sid0 = sid0;
     for (int i = 0; i < 9; ++i) a.cs[i] = i < ncomp * ncomp ? (const T*)cs[i] : nullptr;
     a.rc = nullptr; a.rs = nullptr; a.filt = nullptr;
-    for (int i = 0; i < 3; ++i) { a.in[i] = nullptr; a.out[i] = i < ncomp ? (cx<T>*)out[i] : nullptr; }
+    for (int i = 0; i < 3; ++i) { a.in[i] = nullptr; a.out[i] = i < ncomp ? (cx<T>*)out[i] : nullptr; a.out2[i] = nullptr; }
     a.scale = (T)scale;
     a.ncomp = ncomp; a.ny = p->ny; a.nx = p->nx; a.kp = p->kp;
     const int hw = p->nx / 2 + 1;
@@ -368,21 +375,25 @@ static int grf_mix_band_launch(oa_plan* p, uint64_t seed, uint64_t sid0, int nco
     return 0;
 }
 
-// the same band into the hc layout of an inner (my, okp) grid (the caller has checked the band against both grids)
+// the same band into the hc layout of an inner (my, okp) grid (the caller has checked the band against both grids).  ntriples = 2 (ncomp = 3
+// only): `out` holds six planes and grid z = 1 draws streams sid0 + 3 .. sid0 + 5 into planes 3 .. 5, in the same launch
 template <typename T>
 static int grf_mix_band_inner_launch(oa_plan* p, uint64_t seed, uint64_t sid0, int ncomp, const void* const* cs, double scale, void* const* out,
-                                     int my, long okp, int width, int rband, hipStream_t st) {
+                                     int my, long okp, int width, int rband, hipStream_t st, int ntriples = 1) {
     GrfMixArgs<T> a;
     a.seed = seed; a.sid0 = sid0;
     for (int i = 0; i < 9; ++i) a.cs[i] = i < ncomp * ncomp ? (const T*)cs[i] : nullptr;
     a.rc = nullptr; a.rs = nullptr; a.filt = nullptr;
-    for (int i = 0; i < 3; ++i) { a.in[i] = nullptr; a.out[i] = i < ncomp ? (cx<T>*)out[i] : nullptr; }
+    for (int i = 0; i < 3; ++i) {
+        a.in[i] = nullptr; a.out[i] = i < ncomp ? (cx<T>*)out[i] : nullptr;
+        a.out2[i] = ntriples == 2 ? (cx<T>*)out[3 + i] : nullptr;
+    }
     a.scale = (T)scale;
     a.ncomp = ncomp; a.ny = p->ny; a.nx = p->nx; a.kp = p->kp;
     a.width = width; a.wpairs = (width + 1) / 2; a.rband = rband;
     a.my = my; a.okp = okp; a.rneg = 0;
     const int bs = a.wpairs >= 256 ? 256 : 64;
-    const dim3 grid((a.wpairs + bs - 1) / bs, 2 * rband - 1);
+    const dim3 grid((a.wpairs + bs - 1) / bs, 2 * rband - 1, ntriples);
     if (ncomp == 1) hipLaunchKernelGGL((grf_mix_kernel<T, 1, false, false, true, true>), grid, dim3(bs), 0, st, a);
     else if (ncomp == 2) hipLaunchKernelGGL((grf_mix_kernel<T, 2, false, false, true, true>), grid, dim3(bs), 0, st, a);
     else hipLaunchKernelGGL((grf_mix_kernel<T, 3, false, false, true, true>), grid, dim3(bs), 0, st, a);
@@ -451,6 +462,19 @@ int oa_grf_mix_band_inner(oa_plan* p, uint64_t seed, uint64_t stream_id0, int nc
     for (int i = 0; i < ncomp; ++i) OA_REQUIRE(hc_out[i], "oa_grf_mix_band_inner: NULL output plane");
     return p->dtype == OA_F32 ? grf_mix_band_inner_launch<float>(p, seed, stream_id0, ncomp, covsqrt_hc, scale, hc_out, my, out_pitch, width, rband, (hipStream_t)stream)
                               : grf_mix_band_inner_launch<double>(p, seed, stream_id0, ncomp, covsqrt_hc, scale, hc_out, my, out_pitch, width, rband, (hipStream_t)stream);
+}
+
+int oa_grf_mix_band_inner_triples(oa_plan* p, uint64_t seed, uint64_t stream_id0, int ntriples, const void* const* covsqrt_hc, double scale,
+                                  void* const* hc_out, int my, long out_pitch, int width, int rband, void* stream) {
+    OA_REQUIRE(p && covsqrt_hc && hc_out, "oa_grf_mix_band_inner_triples: NULL argument");
+    OA_REQUIRE(ntriples >= 1 && ntriples <= 2, "oa_grf_mix_band_inner_triples: bad argument (1 <= ntriples <= 2)");
+    OA_REQUIRE(my >= 1 && out_pitch >= 1 && width >= 1 && rband >= 1, "oa_grf_mix_band_inner_triples: the inner grid and the band must be positive");
+    OA_REQUIRE(2L * rband - 1 <= std::min(p->ny, my), "oa_grf_mix_band_inner_triples: row band beyond the rows of the map's or the inner grid (2 rband - 1 <= min(ny, my))");
+    OA_REQUIRE(width <= p->nx / 2 + 1, "oa_grf_mix_band_inner_triples: width beyond the hc columns (width <= nx/2 + 1)");
+    OA_REQUIRE(2L * ((width + 1) / 2) <= out_pitch, "oa_grf_mix_band_inner_triples: the band's column pairs do not fit the output row pitch");
+    for (int i = 0; i < 3 * ntriples; ++i) OA_REQUIRE(hc_out[i], "oa_grf_mix_band_inner_triples: NULL output plane");
+    return p->dtype == OA_F32 ? grf_mix_band_inner_launch<float>(p, seed, stream_id0, 3, covsqrt_hc, scale, hc_out, my, out_pitch, width, rband, (hipStream_t)stream, ntriples)
+                              : grf_mix_band_inner_launch<double>(p, seed, stream_id0, 3, covsqrt_hc, scale, hc_out, my, out_pitch, width, rband, (hipStream_t)stream, ntriples);
 }
 
 int oa_grf_hc_band(oa_plan* p, uint64_t seed, uint64_t stream_id, const void* covsqrt_hc, void* hc_out, int width, int rband,

@@ -746,6 +746,26 @@ class Engine(object):
                                              int(rband), _stream()))
         return list(out)
 
+    def grf_mix_band_inner_triples(self, seed, covsqrt_hc, out, my, pitch, width, rband, scale=1.0, stream_id0=0):
+        """``oa_grf_mix_band_inner_triples``: ``len(out) // 3`` (1 or 2) T, E, B triples of :meth:`grf_mix_band_inner` in ONE launch --
+        ``out``: 3 or 6 contiguous (my, pitch) complex planes, triple ``z`` (planes 3 z .. 3 z + 2) is the draw of streams
+        ``stream_id0 + 3 z ..``.  Bit for bit the values of one :meth:`grf_mix_band_inner` call per triple."""
+        if len(covsqrt_hc) != 3 or any(len(r) != 3 for r in covsqrt_hc) or len(out) % 3:
+            raise ValueError("grf_mix_band_inner_triples: covsqrt_hc must be a 3 x 3 table and out 3 planes per triple")
+        for r in covsqrt_hc:
+            for c in r:
+                if c is not None:
+                    self._chk(c, "hcreal")
+        for k in out:
+            if tuple(k.shape) != (int(my), int(pitch)) or k.dtype != self.cdt or not k.is_contiguous() or k.device != self.device:
+                raise ValueError("grf_mix_band_inner_triples: out planes must be contiguous (my, pitch) = (%d, %d) %s planes on %s"
+                                 % (int(my), int(pitch), self.cdt, self.device))
+        cs = (ctypes.c_void_p * 9)(*[_ptr(covsqrt_hc[i][j]) for i in range(3) for j in range(3)])
+        outs = (ctypes.c_void_p * max(len(out), 1))(*[_ptr(k) for k in out])
+        check(self.lib.oa_grf_mix_band_inner_triples(self.plan, int(seed), int(stream_id0), len(out) // 3, cs, float(scale), outs, int(my),
+                                                     int(pitch), int(width), int(rband), _stream()))
+        return list(out)
+
     def bin_power_multi(self, fields, pairs, norm, ids, nids, weights=None, active_cols=0, active_rows=0):
         """``oa_bin_power_multi``: the binned spectra Re(conj F_a F_b) * norm of the (nf, ny, kp) hc stack ``fields`` for every
         (a, b) of ``pairs`` in one pass; ``weights`` (nf, ny, kp) hc-real: index nf names sum_f w_f k_f.  Returns sums, a float64

@@ -1006,6 +1006,15 @@ class RDN0MonteCarloPol(object):
     any side with the same seeds and streams: ``Engine.grf_mix`` (twice), per estimator four ``reconstruct_hc`` calls (the second of
     each pair with ``accumulate=True``), the weighted sums in torch, ``Engine.bin_power`` per spectrum for A and for B,
     ``Statistics.add``.  ``one_call=None`` (default): the one call on power-of-two sides, the host loop elsewhere.
+    ``one_call="band"`` (:class:`GaussianN0MonteCarloPol`'s spelling and meaning) is the opt-in to the one call on sides 2^a 3^b 5^c: on
+    power-of-two sides it behaves as ``True``; elsewhere the shard runs on the band grid of the estimator set
+    (``qest.one_call_pol(estimators, ext_norm=True)``, bands ``qest._pol_bands(estimators, True)``: kappa's band is the kappa mask's
+    support) -- per block ``oa_qe_band_bind``, ``oa_mc_mv_band_bind`` and ``oa_rdn0_set_data_mv`` where the plan's bindings are not this
+    driver's current ones (a :meth:`sample_host` or :meth:`data_bandpowers` call in between re-binds the plan per estimator; the driver
+    then binds and sets the data again by itself), then ``oa_mc_run_rdn0_mv``: per realisation ONE draw launch for both triples
+    (``oa_grf_mix_band_inner_triples``) and the launches above on the inner grid.  It raises ``OrphicsAmdError`` naming
+    ``one_call=False`` where there is no band grid (chirp-z sides, unbounded filters, a grid not smaller than the map); any other string
+    is a ``ValueError``.  The windowed one call is not on the band grid: :meth:`set_window` raises there on a ``"band"`` driver.
 
     There is no window argument to the constructor: bind one with :meth:`set_window` (before any sample is accumulated).  ``s`` and
     ``s'`` are then the WINDOWED triples :class:`GaussianN0MonteCarloPol` ``(window=...)`` makes for its realisations ``2 i`` and
@@ -1025,6 +1034,9 @@ class RDN0MonteCarloPol(object):
 
     def __init__(self, qest, data, total_power_half, bin_edges, estimators=("TT", "TE", "EE", "EB", "TB"), cross=True, mv=True, comm=None,
                  base_seed=1234, one_call=None, qu=False, iau=False):
+        if isinstance(one_call, str) and one_call != "band":
+            raise ValueError("one_call must be None, True, False or \"band\", not %r" % (one_call,))
+        self.band_call = one_call == "band"   # True, and oa_mc_run_rdn0_mv on the band grid of sides 2^a 3^b 5^c as well
         # covsqrt, pure normalisations in one allocation, weights, bands, ids, counts: GaussianN0MonteCarloPol's set-up, host-loop flavour
         g = self._set = GaussianN0MonteCarloPol(qest, total_power_half, bin_edges, estimators=estimators, cross=cross, mv=mv, comm=comm,
                                                 base_seed=base_seed, one_call=False)
@@ -1035,17 +1047,26 @@ class RDN0MonteCarloPol(object):
         self.cs, self.w, self.counts = g.cs, g.w, g.counts
         self.nspec = len(self.spectra)
         self.D = 2 * self.nspec * self.d
-        if one_call and not e.pow2:
+        if one_call and not e.pow2 and not self.band_call:
             from ._lib import OrphicsAmdError
-            raise OrphicsAmdError("RDN0MonteCarloPol: the one call (oa_mc_run_rdn0_mv) runs on power-of-two map sides only; %d x %d: construct the "
-                                  "driver with one_call=False (host loop of the existing entries, any side) or leave one_call=None"
+            raise OrphicsAmdError("RDN0MonteCarloPol: with one_call=True the one call (oa_mc_run_rdn0_mv) runs on power-of-two map sides only; "
+                                  "%d x %d: construct the driver with one_call=False (host loop of the existing entries, any side), leave "
+                                  "one_call=None, or opt in to the call on the band grid of sides 2^a 3^b 5^c with one_call=\"band\""
                                   % (e.ny, e.nx))
+        self._bands = g._bands
+        if self.band_call and not e.pow2:
+            if not qest.one_call_pol(self.estimators, ext_norm=True):
+                from ._lib import OrphicsAmdError
+                raise OrphicsAmdError("RDN0MonteCarloPol: no one-call path on this %d x %d geometry (chirp-z sides, unbounded filters or a "
+                                      "band grid not smaller than the map): construct the driver with one_call=False" % (e.ny, e.nx))
+            # BAND GRID: kappa's band is the kappa mask's support, which also bounds the MV weights (what one_call_pol resolved)
+            self._bands = qest._pol_bands(self.estimators, True)
         self.one_call = bool(e.pow2) if one_call is None else bool(one_call)
         self.qu, self.iau = bool(qu), bool(iau)
         self.acc = Statistics(comm=self.comm if hasattr(self.comm, "dist") else None, device=e.device)
         self._host = None
         self._hostw = None                    # (the real T, Q, U maps of the windowed host loop)
-        self._one_call_asked = one_call
+        self._one_call_asked = True if self.band_call else one_call
         self._nsamples = 0
         self.window = None
         self.window_moments = (1.0, 1.0)
@@ -1064,6 +1085,11 @@ class RDN0MonteCarloPol(object):
         if window is None:
             self.window, self.window_moments, self.rot = None, (1.0, 1.0), None
         else:
+            if self.band_call and not e.pow2:
+                from ._lib import OrphicsAmdError
+                raise OrphicsAmdError("RDN0MonteCarloPol.set_window: the windowed one call (oa_mc_run_rdn0_mv_windowed) runs on power-of-two map "
+                                      "sides only, not on the band grid of a one_call=\"band\" driver; %d x %d: construct the driver with "
+                                      "one_call=False (host loop of the existing entries, any side)" % (e.ny, e.nx))
             w = np.asarray(window, dtype=np.float64)
             if w.shape != (e.ny, e.nx):
                 raise ValueError("window must be a (Ny, Nx) real-space array")
@@ -1228,19 +1254,38 @@ class RDN0MonteCarloPol(object):
         e, q, g = self.eng, self.q, self._set
         A = g._entry_args()
         e._ordered()
-        check(e.lib.oa_plan_set_col_grid(e.plan, int(q.mcol)))       # plans are shared per geometry: policy per call
-        if getattr(e, "_pipe_owner", None) is not q._token:
-            e._pipe_owner = None
         nE = len(self.estimators)
-        wl, wk, rl, rk = g._bands
+        wl, wk, rl, rk = self._bands
+        wstride = g.w[0].numel() if g.w is not None else 0
         own = (self._dtoken, int(q.mcol), int(q.mrow))
-        if getattr(e, "_rdn0mv_owner", None) != own:
+        if e.pow2:
+            check(e.lib.oa_plan_set_col_grid(e.plan, int(q.mcol)))       # plans are shared per geometry: policy per call
+            if getattr(e, "_pipe_owner", None) is not q._token:
+                e._pipe_owner = None
+        else:
+            # BAND GRID: the estimator set with its pure normalisations in order, then the weights and bin ids, on the plan's inner grid
+            # (GaussianN0MonteCarloPol._run_block's bindings); the data legs belong to the oa_qe_band_bind binding they were made on, so
+            # their owner carries the identity of the plan's current one: whatever bound the plan in between (sample_host's and
+            # data_bandpowers' reconstruct_hc do) makes this block bind and set the data again
+            q._pol_bind(self.estimators, [g.fn[i] for i in range(nE)], self._bands, split=False)
+            key = (g._token, g.w.data_ptr() if g.w is not None else 0, wstride, self.ids.data_ptr(), self.nids, nE, self.nspec)
+            mc = getattr(e, "_mc_owner", None)
+            if mc is None or mc[0] is not e._pol_owner or mc[1] != key:
+                e._mc_owner = None
+                check(e.lib.oa_mc_mv_band_bind(e.plan, _ptr(g.w), wstride, nE, _ptr(self.ids), self.nids, self.nspec))
+                e._mc_owner = (e._pol_owner, key)
+        cur = getattr(e, "_rdn0mv_owner", None)
+        if e.pow2:
+            fresh = cur == own
+        else:                                 # (identity, not equality: a re-made binding has an equal key)
+            fresh = isinstance(cur, tuple) and len(cur) == 2 and cur[0] is e._pol_owner and cur[1] == own
+            own = (e._pol_owner, own)
+        if not fresh:
             e._rdn0mv_owner = None
             kd = (ctypes.c_void_p * 3)(*[k.data_ptr() for k in self.kd])
             check(e.lib.oa_rdn0_set_data_mv(e.plan, kd, nE, A["npieces"], A["fgs"], A["fhs"], A["swaps"], A["xsrc"], A["ysrc"], int(wl), int(wk),
                                             int(rl), int(rk), int(q.mrow), _stream()))
             e._rdn0mv_owner = own
-        wstride = g.w[0].numel() if g.w is not None else 0
         if self.window is not None:
             check(e.lib.oa_mc_run_rdn0_mv_windowed(e.plan, self.base_seed, int(lo), int(hi), A["cs"], nE, A["npieces"], A["signs"], A["fgs"],
                                                    A["fhs"], A["swaps"], A["xsrc"], A["ysrc"], A["fns"], _ptr(g.w), wstride, self.nspec, A["a"],

@@ -16,7 +16,15 @@ crosses, the MV auto; 19 bins.
     blocks of --iters (6) realisations alternated, 7 blocks per path: oa_mc_run_rdn0_mv_windowed with OA_OPT_DRAW_FUSED = 1 and = 0, the
     windowed host loop (Engine.grf_mix(rot) -> irfft x window -> rfft -> rot2 for both triples, then the sequence above), and the
     unwindowed oa_mc_run_rdn0_mv as the cost of everything behind the source stage.  Stand-alone, in microseconds per triple:
-    oa_grf_mix_icols (two triples per launch), oa_grf_mix(rot) + the batched inverse columns of its three planes, and that draw alone."""
+    oa_grf_mix_icols (two triples per launch), oa_grf_mix(rot) + the batched inverse columns of its three planes, and that draw alone.
+--band: the same protocol on map sides 2^a 3^b 5^c (default --geoms 1200x1200@1,2400x2400@0.5): one_call="band" (oa_qe_band_bind,
+    oa_mc_mv_band_bind and oa_rdn0_set_data_mv once, then oa_mc_run_rdn0_mv on the band grid) against one_call=False on the same plan,
+    blocks alternated, the bindings of each path re-made by its own first block after the other's (that set-up is inside the block: it is
+    what alternating costs, and a production run pays it once); "onecall_steady" is the one call in blocks of its own with nothing in
+    between.
+    Stand-alone on the inner grid, in microseconds per realisation: the six planes of s and s' by ONE oa_grf_mix_band_inner_triples launch
+    and by TWO oa_grf_mix_band_inner launches; "onecall_two_draws_ms" is the one call's time with the difference added -- the
+    per-realisation time had the shard kept two single-triple launches (derived: the library has no switch for it)."""
 import argparse
 import json
 import os
@@ -153,16 +161,90 @@ def windowed(args, shape, res, q64, tot):
         torch.cuda.empty_cache()
 
 
+def band(args, shape, res, q64, tot):
+    """one JSON line per precision: one_call="band" against the host loop on the same plan; the two draw variants alone"""
+    import torch
+    from orphics_amd import mc
+    edges = np.linspace(20, 3500, 20)
+    it, reps = args.iters, args.reps
+    for prec in args.precs.split(","):
+        q = q64 if prec == "f64" else q64.astype("f32")
+        e = q.eng
+        one = mc.RDN0MonteCarloPol(q, [e.hc(), e.hc(), e.hc()], tot, edges, estimators=ESTS, base_seed=5, one_call="band")
+        data = e.grf_mix(17, one.cs, stream_id0=10 ** 6)
+        one.set_data(data)
+        host = mc.RDN0MonteCarloPol(q, data, tot, edges, estimators=ESTS, base_seed=5, one_call=False)
+        for drv in (one, host):                       # warm-up of each path: allocations, first-use tables, clocks
+            drv.run_local(range(0, it))
+        torch.cuda.synchronize()
+        t1, t0, ts = [], [], []
+        for r in range(reps):                         # alternated block by block, the same realisations for both
+            lo = (r + 1) * it
+            t1.append(block_ms(one, lo, it))          # (its first realisation re-binds the plan and sets the data again: the host loop
+            t0.append(block_ms(host, lo, it))         #  bound the plan per estimator in between)
+        # ... and the one call in blocks of its own, nothing in between: the steady state of a production shard
+        one.run_local(range((reps + 1) * it, (reps + 2) * it))
+        for r in range(reps):
+            ts.append(block_ms(one, (reps + 2 + r) * it, it))
+        one.acc.allreduce(); host.acc.allreduce()
+        wl, wk, rl, rk = one._bands
+        my, mx = q.pol_bound_grid
+        line = dict(tool="rdn0_pol_bench", band=True, shape=list(shape), prec=prec, res_arcmin=float(res), estimators=list(ESTS), nspec=one.nspec,
+                    bins=int(one.d), iters=it, reps=reps, band_grid=[int(my), int(mx)], leg_band=[int(wl), int(rl)], kappa_band=[int(wk), int(rk)],
+                    onecall_ms=round(float(np.median(t1)), 4), onecall_p10_p90=pct(t1),
+                    onecall_steady_ms=round(float(np.median(ts)), 4), onecall_steady_p10_p90=pct(ts),
+                    hostloop_ms=round(float(np.median(t0)), 4), hostloop_p10_p90=pct(t0),
+                    speedup=round(float(np.median(t0) / np.median(t1)), 2), speedup_steady=round(float(np.median(t0) / np.median(ts)), 2))
+        # same realisations in both paths up to (reps + 1) * it; the one call ran more after that, so compare the sample means loosely:
+        # the tests pin the equality, this is a sanity figure
+        m1, m0 = one.acc.mean("rdn0"), host.acc.mean("rdn0")
+        line["max_diff_mean_over_max_mean"] = float(np.max(np.abs(m1 - m0)) / np.max(np.abs(m0)))
+        line["mean_diff_note"] = "the one call accumulated %d more realisations than the host loop: a sanity figure, not an equality" % ((reps + 1) * it)
+        # the two draw variants alone, on the inner grid's planes
+        pitch = mx // 2 + 16
+        planes = torch.zeros((6, my, pitch), dtype=e.cdt, device=e.device)
+        pl = [planes[j] for j in range(6)]
+        both = lambda: e.grf_mix_band_inner_triples(5, one.cs, pl, my, pitch, wl, rl, stream_id0=0)
+        def twice():
+            e.grf_mix_band_inner(5, one.cs, pl[:3], my, pitch, wl, rl, stream_id0=0)
+            e.grf_mix_band_inner(5, one.cs, pl[3:], my, pitch, wl, rl, stream_id0=3)
+        k = {"draw_triples_us": [], "draw_two_singles_us": []}
+        for f in (both, twice):
+            events_us(f, 20)
+        for r in range(reps):
+            k["draw_triples_us"].append(events_us(both, 200))
+            k["draw_two_singles_us"].append(events_us(twice, 200))
+        for name in k:
+            line[name] = round(float(np.median(k[name])), 2)
+            line[name + "_p10_p90"] = pct(k[name], 2)
+        extra = (np.median(k["draw_two_singles_us"]) - np.median(k["draw_triples_us"])) / 1e3
+        line["onecall_two_draws_ms"] = round(float(np.median(ts) + extra), 4)
+        line["two_draws_note"] = ("derived: onecall_steady_ms + (draw_two_singles_us - draw_triples_us); the draws are timed through the Python "
+                                  "wrappers, back to back on one stream")
+        del planes, pl
+        txt = json.dumps(line)
+        print(txt, flush=True)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(txt + "\n")
+        del one, host
+        e.release_pools()
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--mode", nargs="+", default=["compare"], help="compare | onecall N | hostloop N")
-    ap.add_argument("--geoms", default="2048x2048@1,4096x4096@0.5")
+    ap.add_argument("--geoms", default=None, help="default: 2048x2048@1,4096x4096@0.5; with --band 1200x1200@1,2400x2400@0.5")
     ap.add_argument("--precs", default="f32,f64")
     ap.add_argument("--iters", type=int, default=6, help="realisations per timed block")
     ap.add_argument("--reps", type=int, default=7, help="timed blocks per path (>= 7)")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file")
     ap.add_argument("--windowed", action="store_true", help="the windowed driver (see above)")
+    ap.add_argument("--band", action="store_true", help="one_call=\"band\" on sides 2^a 3^b 5^c (see above)")
     args = ap.parse_args()
+    if args.geoms is None:
+        args.geoms = "1200x1200@1,2400x2400@0.5" if args.band else "2048x2048@1,4096x4096@0.5"
     import torch
     from orphics_amd import mc
     mode = args.mode[0]
@@ -175,6 +257,9 @@ def main():
         q64, tot = setup(shape, float(res))
         if args.windowed:
             windowed(args, shape, res, q64, tot)
+            continue
+        if args.band:
+            band(args, shape, res, q64, tot)
             continue
         for prec in args.precs.split(","):
             q = q64 if prec == "f64" else q64.astype("f32")
