@@ -43,7 +43,7 @@ typedef struct oa_plan oa_plan;
 const char* oa_last_error(void);
 /* ABI version = 100 x the build round that last changed a signature in this header; bindings must refuse a library
  * that reports less than the version they were written against (OA_ABI_VERSION) */
-#define OA_ABI_VERSION 415
+#define OA_ABI_VERSION 416
 int oa_version(void);
 /* number of HIP devices visible; <0 on error (no compute) */
 int oa_device_count(void);
@@ -711,6 +711,24 @@ int oa_lens_maps_hc(oa_plan* p, int nmaps, const void* hc_in, long hc_stride, do
                     const int32_t* shift_y, const void* dx, const void* dy, void* real_out, long out_stride, void* stream);
 int oa_plan_release_pools(oa_plan* p);
 
+/* ---- analytic N1 bias of the TT estimator: direct mode-pair sums (csrc/n1.hpp) ----
+ * For each of nL reconstructed modes L (full-plane indices host_Ly[i], host_Lx[i]; host arrays), with l2 = L - l1, l2' = L - l1',
+ *     g_L(l1, l2) = (L.l1) wg(l1) wh(l2),      f(a, b) = C_a (m.a) + C_b (m.b),   m = a + b,
+ *     S(L) = sum_{l1} sum_{l1'} g_L(l1, l2) g_L(l1', l2') [ Cpp(l1 - l1') f(l1, -l1') f(l2, -l2') + Cpp(l1 - l2') f(l1, -l2') f(l2, -l1') ]
+ * goes to S_out[i] (device, nL doubles);  N1_phi(L) = A_L^2 S(L) / Area^2,  N1_kappa(L) = [L (L + 1) / 2]^2 N1_phi(L).
+ * wg_hc, wh_hc (the DECONVOLVED leg weights), cr_hc (the response spectrum C) and cpp_hc (C^phiphi on the map's grid) are real hc-layout
+ * planes of a FLOAT64 plan; a mode with negative kx is read through its Hermitian partner (-ky mod ny, -kx).  The sums run over the modes
+ * |ky index| < leg_rows, |kx index| < leg_cols (the weights' band) in plain index arithmetic, float64 throughout; l vectors come from
+ * the plan's axes (oa_plan_set_laxes).  Any plan kind (power-of-two, 2^a 3^b 5^c, chirp-z): only the axes and the row pitch are used.
+ * Per L: a prologue launch (box-ordered mode table), pair launches bounded in their pair count (tiles of l1 in registers x chunks of l1'
+ * with their Cpp vector in LDS), one fold workgroup; per-workgroup partials in a plan-owned pool (taken on the first call, grown on
+ * demand -- that call may synchronise --, freed by oa_plan_release_pools), no atomics: S_out is the same bit for bit on every run and
+ * however a list of L is cut into calls.  Stream-ordered.
+ * Refused by name before anything is launched: a float32 plan; axes not set; legs not band-limited enough for all four modes of a
+ * pair to be un-aliased (needs 4 (leg_rows - 1) < ny and 4 (leg_cols - 1) < nx); nL < 1; an L index outside the plane. */
+int oa_n1_tt(oa_plan* p, const void* wg_hc, const void* wh_hc, const void* cr_hc, const void* cpp_hc, int leg_cols, int leg_rows, int nL,
+             const int32_t* host_Ly, const int32_t* host_Lx, double* S_out, void* stream);
+
 /* ---- radial binning (stats.bin2D, stats.py:782-811) ------------------------
  * oa_digitize : ids[i] = np.digitize(x[i], edges, right=True) (stats.py:786):
  *               e[id-1] < x <= e[id]; 0 = underflow, nedges = overflow. x, edges
@@ -854,6 +872,10 @@ int oa_stack_add(int dtype, const void* x, double* acc, long n, void* stream);
  * thread of the read probe). */
 int oa_probe_copy(void* dst, const void* src, size_t bytes, void* stream);
 int oa_probe_read(const void* src, size_t bytes, void* sink, void* stream);
+/* The attainable float64 vector rate, measured in the same run as the N1 pair kernel it prices (tools/n1_bench.py): `blocks` workgroups
+ * (<= 65536) of 256 threads, each thread `iters` (<= 2^24) steps of 8 independent x = fma(x, a, b) chains and nothing else;
+ * blocks x 256 x iters x 8 fused multiply-adds in all.  out: blocks 256 doubles (written once, so that the loop is kept). */
+int oa_probe_fma64(int blocks, long iters, double a, double b, double* out, void* stream);
 
 #ifdef __cplusplus
 }

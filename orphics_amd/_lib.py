@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("ORPHICS_AMD_LIB", os.path.join(_HERE, "liborphics_amd
 
 OA_F32 = 0
 OA_F64 = 1
-ABI_VERSION = 415   # include/orphics_amd.h OA_ABI_VERSION: the signatures below are those of this version
+ABI_VERSION = 416  # include/orphics_amd.h OA_ABI_VERSION: the signatures below are those of this version
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
@@ -113,6 +113,8 @@ SIGNATURES = {
     "oa_lens_maps": (c_int, [c_void_p, c_int, c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
     "oa_lens_maps_hc": (c_int, [c_void_p, c_int, c_void_p, c_long, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
     "oa_plan_release_pools": (c_int, [c_void_p]),
+    # analytic N1 sums of the TT estimator (float64 plans): wg, wh, cr, cpp hc planes, leg_cols, leg_rows, nL, host Ly / Lx (int32), S (device)
+    "oa_n1_tt": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "oa_lens_gather": (c_int, [c_void_p] * 6 + [c_int, c_int, c_double, c_void_p, c_int, c_void_p]),
     "oa_hc_derivs": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_long, c_void_p]),
     "oa_lens_taylor": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -141,6 +143,7 @@ SIGNATURES = {
     "oa_stack_add": (c_int, [c_int, c_void_p, c_void_p, c_long, c_void_p]),
     "oa_probe_copy": (c_int, [c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
     "oa_probe_read": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, c_void_p]),
+    "oa_probe_fma64": (c_int, [c_int, c_long, c_double, c_double, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -112,6 +112,8 @@ int mixed_cols_inverse(oa_plan* p, const void* hc_in, void* hc_out, hipStream_t 
 int mixed_lens_derivs(oa_plan* p, int nmaps, const void* real_in, long in_stride, void* k0, void* hc_pool, void* real_pool, int nd, hipStream_t st,
                       const void* hc_in, long hc_stride, double hc_scale);
 void pipeline_release(oa_plan* p);
+// oa_n1_tt (n1.hip): its plan-owned pool (pipeline.hip: grown on demand, oa_plan_release_pools frees it)
+int n1_pool_reserve(oa_plan* p, size_t bytes, char** out);
 // fused estimator passes on the plan's compact work planes (fft.hip)
 long work_pitch(const oa_plan* p, int w);
 int bin_power_moments(int dtype, const void* k, double norm, const int32_t* ids, long n, int nids, long hp, int nxh, double* sums,

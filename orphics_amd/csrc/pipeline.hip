@@ -78,6 +78,7 @@ struct Pipeline {
     // oa_rdn0_set_data_mv / oa_mc_run_rdn0_mv (the estimator set comes with every call, so the key is its description)
     DevBuf rdn0mv_legs;               // the data triple's distinct leg planes in Rdn0MvSlots' numbering
     DevBuf rdn0mv_pool;               // the 6 drawn hc planes (T, E, B of s, then of s') | the 2 nest kappa planes (A_e, then B_e) | the tail's scratch
+    DevBuf n1_pool;                   // oa_n1_tt (n1.hip): the box-ordered mode table and G of one L | the (tile, part) partial sums
     std::vector<const void*> rdn0mv_key;   // Rdn0MvSlots::key() the data legs were made for (empty: no data set) ...
     int rdn0mv_band[5] = {0, 0, 0, 0, 0};  // ... their leg_cols, kappa_cols, leg_rows, kappa_rows, mrow ...
     int rdn0mv_my = 0;                     // ... and their column grid
@@ -175,6 +176,13 @@ static Pipeline* pipe_of(oa_plan* p) {
     return (Pipeline*)p->pipe;
 }
 
+int n1_pool_reserve(oa_plan* p, size_t bytes, char** out) {
+    Pipeline* q = pipe_of(p);
+    if (int rc = q->n1_pool.reserve(bytes)) return rc;
+    *out = q->n1_pool.at();
+    return 0;
+}
+
 void pipeline_release(oa_plan* p) {
     if (!p || !p->pipe) return;
     Pipeline* q = (Pipeline*)p->pipe;
@@ -186,7 +194,7 @@ void pipeline_release(oa_plan* p) {
     if (q->ticket) (void)hipFree(q->ticket);
     if (q->mv_ftab) (void)hipFree(q->mv_ftab);
     if (q->mv_rtab) (void)hipFree(q->mv_rtab);
-    for (DevBuf* b : {&q->split_legs, &q->mc_src, &q->lens_pool, &q->mvmc, &q->mvwin, &q->rdn0_legs, &q->rdn0_pool, &q->rdn0mv_legs, &q->rdn0mv_pool, &q->dt[0].fn_t, &q->dt[0].ids_t,
+    for (DevBuf* b : {&q->split_legs, &q->mc_src, &q->lens_pool, &q->mvmc, &q->mvwin, &q->rdn0_legs, &q->rdn0_pool, &q->rdn0mv_legs, &q->rdn0mv_pool, &q->n1_pool, &q->dt[0].fn_t, &q->dt[0].ids_t,
                       &q->dt[1].fn_t, &q->dt[1].ids_t, &q->fb_t}) b->release();
     if (q->band) (void)oa_plan_destroy(q->band);
     q->release_band();
@@ -655,7 +663,7 @@ int oa_plan_release_pools(oa_plan* p) {
     // band grid: the split entries' inner source planes and kappa block (bsplit), the draw and row planes of oa_mc_run_windowed (bwin), the
     // map-side scratch of oa_qe_mv_maps (mrows) and the N-grid planes of oa_mc_run_mv_windowed (mwin): all retaken by the next call
     for (DevBuf* b : {&q->lens_pool, &q->split_legs, &q->mc_src, &q->mvmc, &q->mvwin, &q->bsplit, &q->bwin, &q->pb.mrows, &q->pb.mwin, &q->rdn0_legs,
-                      &q->rdn0_pool, &q->rdn0mv_legs, &q->rdn0mv_pool}) b->release();
+                      &q->rdn0_pool, &q->rdn0mv_legs, &q->rdn0mv_pool, &q->n1_pool}) b->release();
     q->bs_cap = 0;
     q->rdn0_gen = 0;                 // the data legs of oa_rdn0_set_data are gone: oa_mc_run_rdn0 asks for them again
     q->rdn0mv_key.clear();           // ... and those of oa_rdn0_set_data_mv

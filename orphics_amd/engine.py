@@ -86,6 +86,24 @@ def set_clean_region(t, region):
     return False
 
 
+def n1_check(ny, nx, leg_rows, leg_cols, Ly, Lx):
+    """Host-side argument check of ``Engine.n1_tt`` (no GPU needed): the legs' band must leave all four modes of a pair un-aliased
+    -- ``4 (leg_rows - 1) < ny`` and ``4 (leg_cols - 1) < nx``; a band of 0 means 'not band-limited' and is refused --, and the modes
+    are at least one pair of full-plane indices inside the plane.  Returns (Ly, Lx) as contiguous int32 arrays."""
+    leg_rows, leg_cols = int(leg_rows), int(leg_cols)
+    if leg_rows < 1 or leg_cols < 1 or 4 * (leg_rows - 1) >= ny or 4 * (leg_cols - 1) >= nx:
+        raise ValueError("n1_tt: the legs are not band-limited enough (leg_rows = %d, leg_cols = %d on a %d x %d plane): all four modes of "
+                         "a pair must be un-aliased, which needs 4 (leg_rows - 1) < ny and 4 (leg_cols - 1) < nx" % (leg_rows, leg_cols, ny, nx))
+    ya, xa = np.asarray(Ly), np.asarray(Lx)
+    if ya.ndim != 1 or ya.shape != xa.shape or ya.size < 1:
+        raise ValueError("n1_tt: Ly and Lx must be one-dimensional, of one length, with at least one mode")
+    if not (np.issubdtype(ya.dtype, np.integer) and np.issubdtype(xa.dtype, np.integer)):
+        raise TypeError("n1_tt: Ly and Lx are full-plane mode INDICES (integers)")
+    if ya.min() < 0 or ya.max() >= ny or xa.min() < 0 or xa.max() >= nx:
+        raise ValueError("n1_tt: an L index is outside the %d x %d plane" % (ny, nx))
+    return np.ascontiguousarray(ya, dtype=np.int32), np.ascontiguousarray(xa, dtype=np.int32)
+
+
 def cuda_device():
     _lib.require_gpu()
     if not torch.cuda.is_available():
@@ -512,7 +530,8 @@ class Engine(object):
         return my.value, mx.value
 
     def release_pools(self):
-        """free the plan-owned pools of the multi-map entries (oa_lens_maps, oa_qe_mv, oa_qe_tt_splits, oa_mc_run, oa_mc_run_mv, oa_mc_run_mv_windowed)"""
+        """free the plan-owned pools of the multi-map entries (oa_lens_maps, oa_qe_mv, oa_qe_tt_splits, oa_mc_run, oa_mc_run_mv, oa_mc_run_mv_windowed)
+        and of oa_n1_tt"""
         check(self.lib.oa_plan_release_pools(self.plan))
         self._mc_owner = None             # the Monte-Carlo binding of a band grid went with its pool (mc.GaussianN0MonteCarloPol binds again)
         self._rdn0_owner = None           # ... and the data legs of oa_rdn0_set_data (mc.RDN0MonteCarlo sets them again)
@@ -525,6 +544,27 @@ class Engine(object):
             raise ValueError("laxes must have shapes (ny,), (nx,)")
         check(self.lib.oa_plan_set_laxes(self.plan, ly.ctypes.data_as(ctypes.c_void_p), lx.ctypes.data_as(ctypes.c_void_p)))
         self._laxes = (ly, lx)
+
+    def n1_tt(self, wg, wh, cr, cpp, leg_cols, leg_rows, Ly, Lx, out=None):
+        """The N1 pair sums S(L) of the TT estimator (``oa_n1_tt``, include/orphics_amd.h) at the modes with full-plane indices
+        ``Ly``, ``Lx`` (integer sequences of one length): ``wg``, ``wh`` the deconvolved leg weights, ``cr`` the response spectrum and
+        ``cpp`` C^phiphi, all hcreal planes of this float64 engine; ``leg_cols`` / ``leg_rows`` the band of the weights.  Returns a
+        float64 device vector.  The arguments are checked on the host (:func:`n1_check`) before the library is called."""
+        if self.prec != "f64":
+            raise ValueError("n1_tt: needs a float64 engine (the pair sums are float64 throughout)")
+        if self._laxes is None:
+            raise RuntimeError("n1_tt: set_laxes first")
+        Ly, Lx = n1_check(self.ny, self.nx, leg_rows, leg_cols, Ly, Lx)
+        for t in (wg, wh, cr, cpp):
+            self._chk(t, "hcreal")
+        if out is None:
+            out = torch.empty(Ly.size, dtype=torch.float64, device=self.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == Ly.size):
+            raise ValueError("n1_tt: out must be a contiguous float64 CUDA vector with one entry per mode")
+        self._ordered()
+        check(self.lib.oa_n1_tt(self.plan, _ptr(wg), _ptr(wh), _ptr(cr), _ptr(cpp), int(leg_cols), int(leg_rows), int(Ly.size),
+                                Ly.ctypes.data_as(ctypes.c_void_p), Lx.ctypes.data_as(ctypes.c_void_p), _ptr(out), _stream()))
+        return out
 
     def qe_legs(self, kX, kY, FG, FH, phase_g=0, phase_h=0, h_times_i=False, out=None):
         self._chk(kX, "hc"); self._chk(kY, "hc"); self._chk(FG, "hcreal"); self._chk(FH, "hcreal")

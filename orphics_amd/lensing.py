@@ -111,6 +111,8 @@ class Estimator(object):
         self.cl_len = {"TT": np.where(ml >= 0, theory.lCl("TT", np.abs(ml)), 0.0)}
         self.AL, self.Nlkk, self._F, self._W, self._R = {}, {}, {}, {}, {}
         self._work = None
+        self.theory = theory
+        self.bigell = bigell
         self._setup_tt()
         if pol:
             for sp in ("EE", "BB", "TE"):
@@ -147,7 +149,8 @@ class Estimator(object):
         self.AL["TT"] = AL
         self.Nlkk["TT"] = (L * (L + 1.)) ** 2 / 4. * AL
         self.R_TT = R
-        self._F["TT"] = (self._hcreal(self.eng, Wg), self._hcreal(self.eng, Wh), self._hcreal(self.eng, Fnorm))
+        self.wg_tt, self.wh_tt = wg, wh                          # the deconvolved leg weights: what the N1 pair sums read (n1_sums)
+        self._F["TT"] =(self._hcreal(self.eng, Wg), self._hcreal(self.eng, Wh), self._hcreal(self.eng, Fnorm))
         self._W["TT"] = (self._support_cols(Wg, Wh), self._support_cols(Fnorm))
         self._R["TT"] = (self._support_rows(Wg, Wh), self._support_rows(Fnorm))
 
@@ -1107,6 +1110,79 @@ class Estimator(object):
     def N_kappa(self, XY="TT"):
         return self._full(self.Nlkk[XY])
 
+    # ---- analytic N1 bias of the TT estimator (oa_n1_tt, csrc/n1.hpp) -----------------------------------------
+    def n1_band(self):
+        """(leg_rows, leg_cols) of the deconvolved TT leg weights as ``_support_rows`` / ``_support_cols`` define them, computed
+        whatever ``prune`` is: 1 + the largest |ky index| / kx index at which ``wg`` or ``wh`` is non-zero."""
+        Ny = self.shape[-2]
+        nz = (self.wg_tt != 0) | (self.wh_tt != 0)
+        if not nz.any():
+            return 1, 1
+        y = np.nonzero(nz.any(axis=1))[0]
+        return int(np.minimum(y, Ny - y).max()) + 1, int(np.nonzero(nz.any(axis=0))[0].max()) + 1
+
+    def n1_clpp(self, clkk_half=None):
+        """C^phiphi on the half plane: ``4 Ckk(|l|) / (|l| (|l| + 1))^2``, 0 for |l| < 2 (the orphics kappa <-> phi rule);
+        ``Ckk`` defaults to ``theory.gCl('kk', |l|)``, the spectrum ``FlatLensingSims`` draws kappa from."""
+        L = self.modl_h
+        if clkk_half is None:
+            clkk_half = np.where(L <= self.bigell, self.theory.gCl("kk", L), 0.0)
+        clkk_half = np.asarray(clkk_half, dtype=np.float64)
+        if clkk_half.shape != L.shape:
+            raise ValueError("n1: a C^kk / C^phiphi plane must be a half plane of shape %s" % (L.shape,))
+        return np.where(L >= 2, _safe_div(4.0 * clkk_half, (L * (L + 1.0)) ** 2), 0.0)
+
+    def n1_sums(self, modes, clpp_half=None, cl_resp=None):
+        """The N1 pair sums S(L) of the TT estimator (definition: include/orphics_amd.h, ``oa_n1_tt``) as a NumPy array, one per mode.
+        ``modes``: a sequence of full-plane index pairs (Ly, Lx).  ``clpp_half``: C^phiphi on the half plane (default
+        :meth:`n1_clpp`); ``cl_resp``: the response spectrum C in f on the half plane (default ``cl_grad['TT']``, the one the
+        normalisation uses).  Runs on the float64 engine whatever the estimator's ``dtype``.  The legs must be band-limited with
+        ``4 (leg_rows - 1) < Ny`` and ``4 (leg_cols - 1) < Nx`` (all four modes of a pair un-aliased); refused by name otherwise."""
+        from .engine import n1_check
+        modes = np.asarray(modes)
+        if modes.ndim != 2 or modes.shape[1] != 2 or modes.shape[0] < 1:
+            raise ValueError("n1_sums: modes must be a sequence of (Ly, Lx) full-plane index pairs")
+        rows, cols = self.n1_band()
+        Ly, Lx = n1_check(self.shape[-2], self.shape[-1], rows, cols, modes[:, 0], modes[:, 1])
+        e = self.eng64
+        cr = self.cl_grad["TT"] if cl_resp is None else np.asarray(cl_resp, dtype=np.float64)
+        cpp = self.n1_clpp() if clpp_half is None else np.asarray(clpp_half, dtype=np.float64)
+        if cr.shape != self.modl_h.shape or cpp.shape != self.modl_h.shape:
+            raise ValueError("n1_sums: clpp_half and cl_resp must be half planes of shape %s" % (self.modl_h.shape,))
+        S = e.n1_tt(self._hcreal(e, self.wg_tt), self._hcreal(e, self.wh_tt), self._hcreal(e, cr), self._hcreal(e, cpp), cols, rows, Ly, Lx)
+        return S.cpu().numpy()
+
+    def N1_phi(self, modes, clpp_half=None, cl_resp=None):
+        """N1 of the reconstructed phi at the given modes: ``A_L^2 S(L) / Area^2`` (A_L = 1 / R(L), 0 where R = 0)."""
+        modes = np.asarray(modes)
+        S = self.n1_sums(modes, clpp_half=clpp_half, cl_resp=cl_resp)
+        AL = self._full(self.AL["TT"])[modes[:, 0], modes[:, 1]]
+        return AL ** 2 * S / self.geom.area ** 2
+
+    def N1_kappa(self, modes, clpp_half=None, cl_resp=None):
+        """N1 of the reconstructed kappa at the given modes: ``[L (L + 1) / 2]^2 N1_phi(L)`` -- the convention of ``Nlkk`` (no
+        ``kmask_K`` factor).  It is what the lensed-pair Monte Carlo of examples/n1_mc_check.py measures."""
+        modes = np.asarray(modes)
+        ly, lx = self.geom.laxes()
+        L = np.hypot(ly[modes[:, 0]], lx[modes[:, 1]])
+        return (L * (L + 1.0) / 2.0) ** 2 * self.N1_phi(modes, clpp_half=clpp_half, cl_resp=cl_resp)
+
+
+def n1_bin_modes(ly, lx, centers, per_bin=4):
+    """The modes ``NlGenerator.getN1`` samples: per bin centre ``c`` and j < per_bin the first-quadrant grid mode nearest to
+    ``|l| = c`` at the angle ``t_j = (j + 1/2) pi / (2 per_bin)``, i.e. ``(|ly|, |lx|)`` nearest to ``c (sin t_j, cos t_j)`` -- the first
+    quadrant of the INDEX plane: indices (Ly, Lx) with Ly <= Ny / 2, Lx <= Nx / 2, whatever the signs of the axes' steps.  Host only,
+    deterministic; returns an int array (nbins, per_bin, 2)."""
+    ly, lx = np.asarray(ly, dtype=np.float64), np.asarray(lx, dtype=np.float64)
+    if int(per_bin) < 1:
+        raise ValueError("getN1: per_bin must be >= 1")
+    dy, dx = abs(ly[1] - ly[0]), abs(lx[1] - lx[0])              # (a CAR geometry's x axis decreases: lx[1] < 0; the quadrant is one of indices)
+    t = (np.arange(int(per_bin)) + 0.5) * np.pi / (2 * int(per_bin))
+    c = np.asarray(centers, dtype=np.float64)[:, None]
+    iy = np.clip(np.rint(c * np.sin(t)[None, :] / dy), 0, ly.size // 2).astype(np.int64)
+    ix = np.clip(np.rint(c * np.cos(t)[None, :] / dx), 0, lx.size // 2).astype(np.int64)
+    return np.stack([iy, ix], axis=-1)
+
 
 def qest(shape, wcs, theory, **kwargs):
     """``lensing.qest(...)`` constructor name used by the reference notebooks (tutorials/tt_verification.ipynb cell 3)."""
@@ -1569,6 +1645,23 @@ class NlGenerator(object):
         self.N2d = self._N2d(polComb)
         cents, nl = self.binner.bin(self.N2d)
         return cents, nl
+
+    def getN1(self, polComb='TT', per_bin=4, clpp=None):
+        """Analytic N1 bias of the reconstructed kappa per bin: (bin centers, N1_kk).  A SAMPLED annulus, not a full-annulus
+        average: per bin the mean of ``Estimator.N1_kappa`` over ``per_bin`` grid modes of the first quadrant, those nearest to the
+        bin centre at the angles ``(j + 1/2) pi / (2 per_bin)`` (:func:`n1_bin_modes`).  The spectra are isotropic and the box is
+        symmetric, so one quadrant represents the annulus; each mode costs a double sum over the leg band (``oa_n1_tt``).  ``clpp``:
+        C^phiphi on the half plane (default: from ``theory.gCl('kk', .)``).  TT only: the polarisation estimators, cross-estimator
+        N1 and MV are a follow-up."""
+        if polComb != 'TT':
+            raise NotImplementedError("getN1: only 'TT' so far; N1 of the polarisation estimators, cross-estimator N1 and MV are a "
+                                      "follow-up (other (g, f) pair terms next to n1_pair_tt in csrc/n1.hpp)")
+        if self.q is None or self.binner is None:
+            raise RuntimeError("getN1: call updateNoise (and set bin_edges) first")
+        cents = 0.5 * (self.bin_edges[1:] + self.bin_edges[:-1])
+        modes = n1_bin_modes(*self.geom.laxes(), cents, per_bin)
+        n1 = self.q.N1_kappa(modes.reshape(-1, 2), clpp_half=clpp).reshape(modes.shape[:2])
+        return cents, n1.mean(axis=1)
 
     def getNlMV(self, polCombs):
         self.q.mv_weights(tuple(polCombs))
