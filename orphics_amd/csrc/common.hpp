@@ -44,6 +44,10 @@ struct DivBinFuse {
     const int32_t* ids_t;                 // tile-major copy on the coarse grid of the single-pass divergence launch, or nullptr
     const void* fn_t;                     // ... and of Fnorm (handed to ColDivArgs::Fn_t by the launcher)
     int tab_logc, tab_rows;               // tile shape the two copies were made for: log2 columns per tile, coarse rows
+    // run table of the same tile shape (divbin_runs.hpp), or run_ent == nullptr: this binding has none.  It was made for a band of
+    // run_w columns and run_rb rows (ColDivArgs::width / rband) and holds at most run_cap entries per tile
+    const unsigned long long* run_ent; const int32_t* run_off;
+    int run_w, run_rb, run_cap;
     double pnorm; int nids, nxh;
     double* part;                         // [maps][workgroups][nids] partial sums (capacity part_cap doubles)
     long part_cap;

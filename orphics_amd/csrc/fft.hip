@@ -1,4 +1,5 @@
 // HIP launchers for the LDS-staged 2-D FFT passes (K1) + oa_fft_* entry points.
+#include <algorithm>
 #include <cmath>
 #include <vector>
 #include "fft_launch.hpp"
@@ -180,11 +181,14 @@ __global__ __launch_bounds__((sizeof(T) == 8 ? 512 : 1024), (sizeof(T) == 8 ? 2 
     col_div_body<T, SEQ, GpuCtx, LOGC>(c, a);
 }
 
-// ... with the radial histogram of |kappa|^2 and the moment update in its tail (fft_divbin.hpp)
-template <typename T, class SEQ, int LOGC>
+// ... with the radial histogram of |kappa|^2 and the moment update in its tail (fft_divbin.hpp): RUNS: from the binding's run table
+// (DivRunTail), else from per-point ids (DivBinTail: bindings without a run table)
+// (both precisions take DivRunTail: in the job-level A/B of profiles/divbin_runs.txt the slowest new run lay above the fastest parent run for each)
+template <typename T, bool RUNS> using DivTailOf = std::conditional_t<RUNS, DivRunTail<T>, DivBinTail<T>>;
+template <typename T, class SEQ, int LOGC, bool RUNS>
 __global__ __launch_bounds__((sizeof(T) == 8 ? 512 : 1024), (sizeof(T) == 8 ? 2 : 4)) void col_div_sp_bin_kernel(ColDivArgs<T> a, DivBinFuse f) {
     GpuCtx c{oa_dyn_smem};
-    col_div_body<T, SEQ, GpuCtx, LOGC, DivBinTail<T>>(c, a, DivBinTail<T>{f});
+    col_div_body<T, SEQ, GpuCtx, LOGC, DivTailOf<T, RUNS>>(c, a, DivTailOf<T, RUNS>{f});
 }
 
 // the same two on column grids of 6 x 2^LOGQ rows (col_div3_body: 1536, 768): 96 KB tiles, six thread groups of Q C / 16 threads
@@ -193,10 +197,10 @@ __global__ __launch_bounds__((sizeof(T) == 8 ? 384 : 768), (sizeof(T) == 8 ? 2 :
     GpuCtx c{oa_dyn_smem};
     col_div3_body<T, LOGQ, LOGC>(c, a);
 }
-template <typename T, int LOGQ, int LOGC>
+template <typename T, int LOGQ, int LOGC, bool RUNS>
 __global__ __launch_bounds__((sizeof(T) == 8 ? 384 : 768), (sizeof(T) == 8 ? 2 : 3)) void col_div3_sp_bin_kernel(ColDivArgs<T> a, DivBinFuse f) {
     GpuCtx c{oa_dyn_smem};
-    col_div3_body<T, LOGQ, LOGC, GpuCtx, DivBinTail<T>>(c, a, DivBinTail<T>{f});
+    col_div3_body<T, LOGQ, LOGC, GpuCtx, DivTailOf<T, RUNS>>(c, a, DivTailOf<T, RUNS>{f});
 }
 
 template <typename T, class SEQ>
@@ -534,8 +538,14 @@ struct HipLauncher {
     // single pass: logL = whole column length (10 or 11), tile of 2^(14 - logL) columns, 1024 threads (f32) / 2^(13 - logL)
     // columns, 512 threads (f64): 128 KB of LDS either way
     DivBinFuse* fuse = nullptr;     // != nullptr: the caller wants binning + moments in the divergence launch (common.hpp)
+#define OA_GO_FUSED(K, ...) go_fused(K<__VA_ARGS__, false>, K<__VA_ARGS__, true>, gx, gz, nt, smem, a)
+    // kern_runs: the same kernel with DivRunTail -- taken when the binding's run table was made for this tile shape and band
     template <class K, typename T>
-    void go_fused(K kern, int gx, int gz, int nt, size_t smem, ColDivArgs<T> a) {
+    void go_fused(K kern_ids, K kern_runs, int gx, int gz, int nt, size_t smem, ColDivArgs<T> a) {
+        const bool tabs = fuse->tab_logc == a.logC && fuse->tab_rows == a.ny;
+        const bool runs = tabs && fuse->run_ent && fuse->run_w == a.width && fuse->run_rb == a.rband && fuse->run_cap <= 2 * nt;
+        const K kern = runs ? kern_runs : kern_ids;
+        if (runs) smem = std::max(smem, divrun_lds_bytes(a.ny, a.logC, nt, sizeof(T) == 8));     // (float32: P reaches a few KB past the tile)
         {
             const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), smem);
             if (e != hipSuccess) { rc = fail(std::string("hipFuncSetAttribute: ") + hipGetErrorString(e)); return; }
@@ -543,7 +553,6 @@ struct HipLauncher {
         fuse->gx = gx;
         if (!fuse->store) a.out = nullptr;
         // tile-major copies of Fn / ids (pipeline.hip) -- valid for THIS tile shape and one Fn for every map of the launch
-        const bool tabs = fuse->tab_logc == a.logC && fuse->tab_rows == a.ny;
         a.Fn_t = (tabs && a.fn_moff == 0) ? (const T*)fuse->fn_t : nullptr;
         if (!tabs) fuse->ids_t = nullptr;
         hipLaunchKernelGGL(kern, dim3(gx, 1, gz), dim3(nt), smem, st, a, *fuse);
@@ -560,11 +569,11 @@ struct HipLauncher {
         // (the wave-private histogram rows of the tail live in the column tile: waves x nids doubles must fit it)
         if (fuse && !a.accumulate && (long)gx * gz * fuse->nids <= fuse->part_cap && (logL == 10 || logL == 11 || (logL == 12 && !narrow)) &&
             (size_t)(nt / 64) * fuse->nids * sizeof(double) <= ((size_t)1 << lt) * sizeof(cx<T>)) {
-            if (logL == 12) go_fused(col_div_sp_bin_kernel<T, Seq<16, 16, 16>, lc11 - 1>, gx, gz, nt, smem, a);      // 4096-row column grids (the wide band at 8192^2)
-            else if (logL == 11 && !narrow) go_fused(col_div_sp_bin_kernel<T, Seq<16, 16, 8>, lc11>, gx, gz, nt, smem, a);
-            else if (logL == 10 && !narrow) go_fused(col_div_sp_bin_kernel<T, Seq<16, 16, 4>, lc10>, gx, gz, nt, smem, a);
-            else if (logL == 11) go_fused(col_div_sp_bin_kernel<T, Seq<16, 16, 8>, lc11 - 1>, gx, gz, nt, smem, a);
-            else go_fused(col_div_sp_bin_kernel<T, Seq<16, 16, 4>, lc10 - 1>, gx, gz, nt, smem, a);
+            if (logL == 12) OA_GO_FUSED(col_div_sp_bin_kernel, T, Seq<16, 16, 16>, lc11 - 1);      // 4096-row column grids (the wide band at 8192^2)
+            else if (logL == 11 && !narrow) OA_GO_FUSED(col_div_sp_bin_kernel, T, Seq<16, 16, 8>, lc11);
+            else if (logL == 10 && !narrow) OA_GO_FUSED(col_div_sp_bin_kernel, T, Seq<16, 16, 4>, lc10);
+            else if (logL == 11) OA_GO_FUSED(col_div_sp_bin_kernel, T, Seq<16, 16, 8>, lc11 - 1);
+            else OA_GO_FUSED(col_div_sp_bin_kernel, T, Seq<16, 16, 4>, lc10 - 1);
             return true;
         }
         if (logL == 12 && !narrow) { go(col_div_sp_kernel<T, Seq<16, 16, 16>, lc11 - 1>, dim3(gx, 1, gz), nt, smem, a); return true; }
@@ -583,8 +592,8 @@ struct HipLauncher {
         const int nt = a.NT;
         if (fuse && !a.accumulate && (long)gx * gz * fuse->nids <= fuse->part_cap &&
             (size_t)(nt / 64) * fuse->nids * sizeof(double) <= ((size_t)rows << a.logC) * sizeof(cx<T>)) {
-            if (rows == 1536) go_fused(col_div3_sp_bin_kernel<T, 8, lc>, gx, gz, nt, smem, a);
-            else go_fused(col_div3_sp_bin_kernel<T, 7, lc + 1>, gx, gz, nt, smem, a);
+            if (rows == 1536) OA_GO_FUSED(col_div3_sp_bin_kernel, T, 8, lc);
+            else OA_GO_FUSED(col_div3_sp_bin_kernel, T, 7, lc + 1);
             return;
         }
         if (rows == 1536) go(col_div3_sp_kernel<T, 8, lc>, dim3(gx, 1, gz), nt, smem, a);

@@ -40,13 +40,86 @@ __device__ __forceinline__ double wave_total_f64(double v) {
     return ((readlane_f64(v, 0) + readlane_f64(v, 16)) + readlane_f64(v, 32)) + readlane_f64(v, 48);
 }
 
+// What every tail ends with: this workgroup's partial of id i is partial(i) (a fixed-order sum in the tail's LDS, complete and
+// visible before the call); the partials go to memory, and the LAST workgroup (ticket) folds all of them in workgroup order,
+// divides by the mode counts and updates the moments.  red: LDS of at least blockDim.x + nids doubles that the tail no longer needs.
+template <class Partial>
+__device__ __forceinline__ void divbin_handover(const DivBinFuse& f, double* red, Partial partial) {
+    __shared__ int s_last;
+    const int t = threadIdx.x, nt = blockDim.x, nids = f.nids;
+    const long wg = (long)blockIdx.z * gridDim.x + blockIdx.x;
+    for (int i = t; i < nids; i += nt) {
+        const double s = partial(i);
+        __hip_atomic_store(f.part + wg * nids + i, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // write-through
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this thread's partials have been acknowledged
+    __syncthreads();
+    if (t == 0)
+        s_last = (__hip_atomic_fetch_add(f.ticket, 1u, OA_TICKET_ORDER, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x * gridDim.z - 1) ? 1 : 0;
+    __syncthreads();
+    if (!s_last) return;
+    // last workgroup: per map, in map order: sums[i] = the workgroups' partials in a fixed two-level order -- thread (g, i),
+    // i = t mod NI, g = t / NI, adds the partials of workgroups b = g, g + G, ... (four loads in flight), then the G group sums
+    // are added in group order; b = sums[1 .. nids-2] / mode counts; moments.  (One thread per id walking all workgroups was
+    // a chain of ~100 dependent L2-miss loads: 30-50 us.)
+    const int d = nids - 2;
+    int NI = 1;
+    while (NI < nids && NI < nt) NI <<= 1;
+    const int G = nt / NI > 0 ? nt / NI : 1, gi = t / NI, ii = t - gi * NI;
+    // red: [G][NI] group sums, then b in red[0 .. d) (the tail's own LDS is spent)
+    const int gx = (int)gridDim.x;
+    for (int z = 0; z < (int)gridDim.z; ++z) {
+        for (int i0 = 0; i0 < nids; i0 += NI) {          // (one round unless nids > workgroup size)
+            const int i = i0 + ii;
+            __syncthreads();
+            if (gi < G) {
+                double s = 0.0;
+                if (i < nids) {
+                    const double* pz = f.part + ((long)z * gx) * nids + i;
+                    int b = gi;
+                    for (; b + 3 * G < gx; b += 4 * G) {
+                        const double p0 = __hip_atomic_load(pz + (long)b * nids, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        const double p1 = __hip_atomic_load(pz + (long)(b + G) * nids, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        const double p2 = __hip_atomic_load(pz + (long)(b + 2 * G) * nids, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        const double p3 = __hip_atomic_load(pz + (long)(b + 3 * G) * nids, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        s += (p0 + p1) + (p2 + p3);
+                    }
+                    for (; b < gx; b += G) s += __hip_atomic_load(pz + (long)b * nids, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                red[gi * NI + ii] = s;
+            }
+            __syncthreads();
+            double tot = 0.0;
+            if (gi == 0 && i < nids) {
+                for (int k = 0; k < G; ++k) tot += red[k * NI + ii];
+                f.sums[(long)z * nids + i] = tot;
+            }
+            __syncthreads();
+            if (gi == 0 && i >= 1 && i <= d) red[G * NI + i - 1] = tot / (double)f.mcounts[i];     // b, behind the group sums
+        }
+        __syncthreads();
+        const double* bv = red + G * NI;
+        if (f.S) {
+            for (int a = t; a < d; a += nt) f.S[a] += bv[a];
+            for (long e = t; e < (long)d * d; e += nt) {
+                const int ra = (int)(e / d), cb = (int)(e - (long)ra * d);
+                f.C[e] += bv[ra] * bv[cb];
+            }
+        }
+    }
+    if (t == 0) {
+        if (f.n) f.n[0] += (int64_t)gridDim.z;
+        __hip_atomic_store(f.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next launch
+    }
+}
+
 template <typename T>
 struct DivBinTail {
-    static constexpr bool active = true;
+    static constexpr bool active = true, needs_ids = true;
     DivBinFuse f;
     double* rows = nullptr;     // LDS: [waves][nids]
 
-    __device__ __forceinline__ void begin(GpuCtx&, void* lds) {
+    __device__ __forceinline__ void begin(GpuCtx&, void* lds, int, int, int) {
         rows = reinterpret_cast<double*>(lds);
         const int nw = blockDim.x >> 6;
         for (int i = threadIdx.x; i < nw * f.nids; i += blockDim.x) rows[i] = 0.0;
@@ -57,7 +130,7 @@ struct DivBinTail {
     __device__ __forceinline__ bool packed_ids() const { return f.ids_t != nullptr; }
     __device__ __forceinline__ int id_at_t(long i) const { return f.ids_t[i]; }
     // id < 0: this lane has no value in this step; pw = re^2 + im^2 of kappa
-    __device__ __forceinline__ void add(GpuCtx&, int id, T pw, int col) {
+    __device__ __forceinline__ void add(GpuCtx&, int id, T pw, int col, int) {
         const int m = (col == 0 || col == f.nxh) ? 1 : (col < f.nxh ? 2 : 0);
         const bool ok = id >= 0 && id < f.nids && m > 0;
         const double v = ok ? (double)(pw * (T)f.pnorm) * (double)m : 0.0;
@@ -75,74 +148,103 @@ struct DivBinTail {
         }
     }
     __device__ __forceinline__ void finish(GpuCtx&) {
-        __shared__ int s_last;
-        const int t = threadIdx.x, nt = blockDim.x, nw = nt >> 6, nids = f.nids;
+        const int nw = blockDim.x >> 6, nids = f.nids;
+        const double* r = rows;
         __syncthreads();
-        const long wg = (long)blockIdx.z * gridDim.x + blockIdx.x;
-        for (int i = t; i < nids; i += nt) {
+        divbin_handover(f, rows, [=](int i) {
             double s = 0.0;
-            for (int k = 0; k < nw; ++k) s += rows[k * nids + i];
-            __hip_atomic_store(f.part + wg * nids + i, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // write-through
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this thread's partials have been acknowledged
+            for (int k = 0; k < nw; ++k) s += r[k * nids + i];
+            return s;
+        });
+    }
+};
+
+// The same tail without an id in sight (the one-call entries' choice whenever the binding has a run table: divbin_runs.hpp).  The bin
+// id of a mode is known when the bins are bound and is piecewise constant down a column, so the tile's runs (column, first row,
+// length, id), sorted by id, replace the id reads, the ballot / leader loop and the per-wave histogram rows:
+//   add:     v (DivBinTail's expression) goes to P[column][row] in the tile's LDS;
+//   finish:  thread e adds the values of run e in row order (R[e]); thread i adds R over the entries of id i in table order: the
+//            workgroup's partial of id i.  Then the shared hand-over.
+// Every sum has a fixed order that no wave timing enters: bit-reproducible; against DivBinTail only the order of the additions inside
+// a workgroup differs.
+// LDS: row y of a column sits at y + (y >> 6), columns divrun_col_stride() doubles apart.  The lanes of a wave in finish() mostly hold the
+// 64-row chunks of one long run, 64 rows apart: the skew puts them on consecutive banks (unskewed, in either layout, all of them hit one
+// bank: the float32 tail then took longer than DivBinTail's); the stride keeps the stores of add() -- C columns x 32 / C rows per half
+// wave -- apart.  P takes a little over half a float64 tile, R sits behind it; in float32 P is the tile and a few KB behind it
+// (divrun_lds_bytes: the launcher asks for them), and R lies over P's first entries, behind one more barrier.  The entries and
+// offsets of this thread are requested in begin(), ahead of the kernel's own Fnorm / axis loads: they have long arrived when finish()
+// looks at them.
+__host__ __device__ inline int divrun_col_stride(int rows, int logc) {
+    const int want = (32 >> logc) > 0 ? (32 >> logc) : 1;
+    const int s = rows + (rows >> 6) + 1;
+    return s + (((want - s) % 32) + 32) % 32;
+}
+// dynamic LDS the tail needs from the start of the tile: P, and in float64 R (two entries per thread) behind it
+inline size_t divrun_lds_bytes(int rows, int logc, int nt, bool f64) {
+    return ((size_t)divrun_col_stride(rows, logc) << logc) * sizeof(double) + (f64 ? (size_t)2 * nt * sizeof(double) : 0);
+}
+template <typename T>
+struct DivRunTail {
+    static constexpr bool active = true, needs_ids = false;
+    static constexpr bool r_behind = sizeof(T) == 8;
+    DivBinFuse f;
+    double* P = nullptr;
+    double* R = nullptr;
+    const int32_t* offp = nullptr;
+    int base = 0, cnt = 0, logc = 0, cs = 0, o0 = 0, o1 = 0;
+    unsigned e0 = 0, e1 = 0;      // this thread's entries (t, t + nt): their low words -- the id word is the builder's and the offsets' business
+
+    __device__ __forceinline__ void begin(GpuCtx&, void* lds, int tile, int logc_, int rows) {
+        P = reinterpret_cast<double*>(lds);
+        logc = logc_;
+        cs = divrun_col_stride(rows, logc);
+        R = r_behind ? P + ((long)cs << logc) : P;
+        const int t = threadIdx.x, nt = blockDim.x;
+        const int32_t* off = offp = f.run_off + (long)tile * (f.nids + 1);
+        base = off[0];
+        cnt = off[f.nids] - base;
+        if (cnt > 2 * nt) cnt = 2 * nt;                          // (the builder's cap; R holds no more)
+        const unsigned* ew = reinterpret_cast<const unsigned*>(f.run_ent + base);
+        e0 = t < cnt ? ew[2 * t] : 0u;
+        e1 = t + nt < cnt ? ew[2 * (t + nt)] : 0u;
+        if (t < f.nids) { o0 = off[t] - base; o1 = off[t + 1] - base; }
+    }
+    __device__ __forceinline__ int id_at(unsigned, int) const { return -1; }
+    __device__ __forceinline__ bool packed_ids() const { return false; }
+    __device__ __forceinline__ int id_at_t(long) const { return -1; }
+    // slot = coarse row * C + column in tile
+    __device__ __forceinline__ void add(GpuCtx&, int, T pw, int col, int slot) {
+        const int m = (col == 0 || col == f.nxh) ? 1 : (col < f.nxh ? 2 : 0);
+        const int y = slot >> logc, c = slot & ((1 << logc) - 1);
+        P[c * cs + y + (y >> 6)] = (double)(pw * (T)f.pnorm) * (double)m;
+    }
+    __device__ __forceinline__ double run_sum(unsigned w) const {
+        const int first = (int)(w & 0xffffu), len = (int)((w >> 16) & 0xffu), col = (int)(w >> 24);
+        const double* p = P + col * cs;
+        double s = 0.0;
+#pragma unroll 4
+        for (int y = first; y < first + len; ++y) s += p[y + (y >> 6)];
+        return s;
+    }
+    __device__ __forceinline__ void finish(GpuCtx&) {
+        const int t = threadIdx.x, nt = blockDim.x;
         __syncthreads();
-        if (t == 0)
-            s_last = (__hip_atomic_fetch_add(f.ticket, 1u, OA_TICKET_ORDER, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x * gridDim.z - 1) ? 1 : 0;
+        const double s0 = run_sum(e0), s1 = run_sum(e1);          // (no entry: length 0)
+        if (!r_behind) __syncthreads();                           // R lies over P: every run has been read
+        if (t < cnt) R[t] = s0;
+        if (t + nt < cnt) R[t + nt] = s1;
         __syncthreads();
-        if (!s_last) return;
-        // last workgroup: per map, in map order: sums[i] = the workgroups' partials in a fixed two-level order -- thread (g, i),
-        // i = t mod NI, g = t / NI, adds the partials of workgroups b = g, g + G, ... (four loads in flight), then the G group sums
-        // are added in group order; b = sums[1 .. nids-2] / mode counts; moments.  (One thread per id walking all workgroups was
-        // a chain of ~100 dependent L2-miss loads: 30-50 us.)
-        const int d = nids - 2;
-        int NI = 1;
-        while (NI < nids && NI < nt) NI <<= 1;
-        const int G = nt / NI > 0 ? nt / NI : 1, gi = t / NI, ii = t - gi * NI;
-        double* red = rows;                                  // [G][NI] group sums, then b in red[0 .. d) (the rows are spent)
-        const int gx = (int)gridDim.x;
-        for (int z = 0; z < (int)gridDim.z; ++z) {
-            for (int i0 = 0; i0 < nids; i0 += NI) {          // (one round unless nids > workgroup size)
-                const int i = i0 + ii;
-                __syncthreads();
-                if (gi < G) {
-                    double s = 0.0;
-                    if (i < nids) {
-                        const double* pz = f.part + ((long)z * gx) * nids + i;
-                        int b = gi;
-                        for (; b + 3 * G < gx; b += 4 * G) {
-                            const double p0 = __hip_atomic_load(pz + (long)b * nids, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            const double p1 = __hip_atomic_load(pz + (long)(b + G) * nids, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            const double p2 = __hip_atomic_load(pz + (long)(b + 2 * G) * nids, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            const double p3 = __hip_atomic_load(pz + (long)(b + 3 * G) * nids, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            s += (p0 + p1) + (p2 + p3);
-                        }
-                        for (; b < gx; b += G) s += __hip_atomic_load(pz + (long)b * nids, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                    red[gi * NI + ii] = s;
-                }
-                __syncthreads();
-                double tot = 0.0;
-                if (gi == 0 && i < nids) {
-                    for (int k = 0; k < G; ++k) tot += red[k * NI + ii];
-                    f.sums[(long)z * nids + i] = tot;
-                }
-                __syncthreads();
-                if (gi == 0 && i >= 1 && i <= d) red[G * NI + i - 1] = tot / (double)f.mcounts[i];     // b, behind the group sums
-            }
-            __syncthreads();
-            const double* bv = red + G * NI;
-            if (f.S) {
-                for (int a = t; a < d; a += nt) f.S[a] += bv[a];
-                for (long e = t; e < (long)d * d; e += nt) {
-                    const int ra = (int)(e / d), cb = (int)(e - (long)ra * d);
-                    f.C[e] += bv[ra] * bv[cb];
-                }
-            }
-        }
-        if (t == 0) {
-            if (f.n) f.n[0] += (int64_t)gridDim.z;
-            __hip_atomic_store(f.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next launch
-        }
+        const double* r = R;
+        const int32_t* off = offp;
+        const int a0 = o0, a1 = o1, b0 = base, n = cnt;
+        divbin_handover(f, P, [=](int i) {
+            int k = a0, k1 = a1;
+            if (i != t) { k = off[i] - b0; k1 = off[i + 1] - b0; }     // (more ids than threads)
+            if (k1 > n) k1 = n;
+            double s = 0.0;
+            for (; k < k1; ++k) s += r[k];
+            return s;
+        });
     }
 };
 

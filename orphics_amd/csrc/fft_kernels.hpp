@@ -1771,14 +1771,16 @@ struct ColDivArgs {
 // column transform + divergence: the product planes are read once, no pass-1 plane is written and read back.
 // Tail: what else happens to each kappa value while it is in registers.  NoDivTail: nothing.  DivBinTail (fft_divbin.hpp, GPU
 // only): the radial histogram of |kappa|^2 and the moment update of the one-call entries, so that the kappa plane is never
-// re-read (and need not be written at all: a.out == nullptr).
+// re-read (and need not be written at all: a.out == nullptr).  DivRunTail (same file): the same sums from a bind-time run table
+// instead of per-point ids (needs_ids = false: the kernel loads none); begin() gets the tile index, log2 of its width and its rows,
+// add() the value's place in the tile (coarse row * C + column).
 struct NoDivTail {
-    static constexpr bool active = false;
-    template <class Ctx> OA_HD void begin(Ctx&, void*) {}
+    static constexpr bool active = false, needs_ids = false;
+    template <class Ctx> OA_HD void begin(Ctx&, void*, int, int, int) {}
     OA_HD int id_at(unsigned, int) const { return -1; }
     OA_HD bool packed_ids() const { return false; }
     OA_HD int id_at_t(long) const { return -1; }
-    template <class Ctx, typename T> OA_HD void add(Ctx&, int, T, int) {}
+    template <class Ctx, typename T> OA_HD void add(Ctx&, int, T, int, int) {}
     template <class Ctx> OA_HD void finish(Ctx&) {}
 };
 
@@ -1838,7 +1840,7 @@ OA_HD void col_div_body(Ctx& ctx, const ColDivArgs<T>& a, Tail tail = Tail{}) {
     if constexpr (Tail::active) {
         // every lane takes part in every step of the tail (wave-level reductions): no early exits; the tile is free by now
         ctx.sync();
-        tail.begin(ctx, s);
+        tail.begin(ctx, s, tile, logC, 1 << logL);
         ctx.sync();
         // phase A, straight-line: every kappa value of this thread, its squared modulus and its bin id (loads batched by the
         // compiler: inside the wave-level steps of phase B each would be a dependent trip to memory)
@@ -1871,16 +1873,20 @@ OA_HD void col_div_body(Ctx& ctx, const ColDivArgs<T>& a, Tail tail = Tail{}) {
                         outb[i] = d;
                     }
                     pw[u * RL + t] = d.x * d.x + d.y * d.y;
-                    idv[u * RL + t] = tail.packed_ids() ? tail.id_at_t((((long)tile << logL) + k) * (1 << logC) + c) : tail.id_at(y + up, c0 + c);
+                    if constexpr (Tail::needs_ids)
+                        idv[u * RL + t] = tail.packed_ids() ? tail.id_at_t((((long)tile << logL) + k) * (1 << logC) + c) : tail.id_at(y + up, c0 + c);
+                    else tail.add(ctx, 0, d.x * d.x + d.y * d.y, c0 + c, (k << logC) + c);     // (no wave-level step: stored at once, at its place in the tile)
                 }
             }
         }
         // phase B: wave-level accumulation, every lane in every step
+        if constexpr (Tail::needs_ids) {
 #pragma unroll
-        for (int u = 0; u < NB; ++u) {
-            const int c = (tid + u * NT) & ((1 << logC) - 1);
+            for (int u = 0; u < NB; ++u) {
+                const int c = (tid + u * NT) & ((1 << logC) - 1);
 #pragma unroll
-            for (int t = 0; t < RL; ++t) tail.add(ctx, idv[u * RL + t], pw[u * RL + t], c0 + c);
+                for (int t = 0; t < RL; ++t) tail.add(ctx, idv[u * RL + t], pw[u * RL + t], c0 + c, -1);
+            }
         }
         tail.finish(ctx);
     } else {
@@ -1997,7 +2003,7 @@ OA_HD void col_div3_body(Ctx& ctx, const ColDivArgs<T>& a, Tail tail = Tail{}) {
     // bin y = k + Q q of position (k, c): row y + (y >= N / 2 ? yshift : 0) of Fn, ly, out
     if constexpr (Tail::active) {
         ctx.sync();                                          // the tile is free: the tail's histogram rows
-        tail.begin(ctx, s);
+        tail.begin(ctx, s, tile, logC, N);
         ctx.sync();
         T pw[NIT * 6];
         int idv[NIT * 6];
@@ -2023,14 +2029,17 @@ OA_HD void col_div3_body(Ctx& ctx, const ColDivArgs<T>& a, Tail tail = Tail{}) {
                         outb[i] = d;
                     }
                     pw[it * 6 + q] = d.x * d.x + d.y * d.y;
-                    idv[it * 6 + q] = tail.packed_ids() ? tail.id_at_t(ti_) : tail.id_at(y + up, c0 + c);
+                    if constexpr (Tail::needs_ids) idv[it * 6 + q] = tail.packed_ids() ? tail.id_at_t(ti_) : tail.id_at(y + up, c0 + c);
+                    else tail.add(ctx, 0, d.x * d.x + d.y * d.y, c0 + c, (int)(y << logC) + c);     // (stored at once, at its place in the tile)
                 }
             }
         }
+        if constexpr (Tail::needs_ids) {
 #pragma unroll
-        for (int it = 0; it < NIT; ++it) {
+            for (int it = 0; it < NIT; ++it) {
 #pragma unroll
-            for (int q = 0; q < 6; ++q) tail.add(ctx, idv[it * 6 + q], pw[it * 6 + q], c0 + pc[it]);
+                for (int q = 0; q < 6; ++q) tail.add(ctx, idv[it * 6 + q], pw[it * 6 + q], c0 + pc[it], -1);
+            }
         }
         tail.finish(ctx);
     } else {

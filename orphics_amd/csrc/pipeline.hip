@@ -12,6 +12,7 @@
 #include <vector>
 #include "common.hpp"
 #include "fft_plan.hpp"
+#include "divbin_runs.hpp"
 
 namespace oa {
 
@@ -92,6 +93,10 @@ struct Pipeline {
         DevBuf fn_t, ids_t;
         unsigned long tab_gen = 0;
         int tab_rows = 0, tab_logc = 0, tab_wk = 0;
+        // the run table of the ids (divbin_runs.hpp) on the same tiles, for kappa's band as the divergence launch clamps it
+        DevBuf run_ent, run_off;
+        bool has_runs = false;
+        int run_w = 0, run_rb = 0, run_cap = 0;
     } dt[2];
     DivTabs& tabs_of(int rows) { return (my3 && rows == my3) ? dt[1] : dt[0]; }
     const DivTabs& tabs_of(int rows) const { return (my3 && rows == my3) ? dt[1] : dt[0]; }
@@ -195,7 +200,7 @@ void pipeline_release(oa_plan* p) {
     if (q->mv_ftab) (void)hipFree(q->mv_ftab);
     if (q->mv_rtab) (void)hipFree(q->mv_rtab);
     for (DevBuf* b : {&q->split_legs, &q->mc_src, &q->lens_pool, &q->mvmc, &q->mvwin, &q->rdn0_legs, &q->rdn0_pool, &q->rdn0mv_legs, &q->rdn0mv_pool, &q->n1_pool, &q->dt[0].fn_t, &q->dt[0].ids_t,
-                      &q->dt[1].fn_t, &q->dt[1].ids_t, &q->fb_t}) b->release();
+                      &q->dt[1].fn_t, &q->dt[1].ids_t, &q->dt[0].run_ent, &q->dt[0].run_off, &q->dt[1].run_ent, &q->dt[1].run_off, &q->fb_t}) b->release();
     if (q->band) (void)oa_plan_destroy(q->band);
     q->release_band();
     q->brows.release();
@@ -484,7 +489,27 @@ const int64_t* oa_plan_bin_counts(oa_plan* p) { return (p && p->pipe) ? ((Pipeli
 static bool divbin_enabled(const Pipeline* q) { return q->opt_divbin; }
 // (re)build the tile-major copies of Fnorm / ids for the single-pass divergence launch on this plan's column grid.  Called where the
 // filters, the bins and the grid are known (oa_plan_set_bins, and again by make_fuse_tabs if any of them changed since): the first
-// build of a size allocates (one device synchronisation), later rebuilds are two small stream-ordered launches.
+// build of a size allocates (one device synchronisation), later rebuilds are two small launches -- and the run table of the ids
+// (divbin_runs.hpp), which is made on the host from the packed copy: one read-back and one upload per binding, the stream waited for.
+static int build_run_table(const oa_plan* p, Pipeline* q, Pipeline::DivTabs* t, int rows, int logc, long tiles, hipStream_t st) {
+    t->has_runs = false;
+    const int nxh = p->nx / 2;
+    const int w = q->wk > nxh + 1 ? nxh + 1 : q->wk;                            // Fft2dPlan::clampw / clampr on the coarse grid
+    const int rb = (q->rk <= 0 || 2L * q->rk - 1 >= rows) ? 0 : q->rk;
+    const int cap = 2 * ((rows << logc) / 16);                                  // two entries per thread of the launch
+    std::vector<int32_t> host((size_t)(tiles * rows) << logc);
+    OA_HIP(hipMemcpyAsync(host.data(), t->ids_t.p, host.size() * 4, hipMemcpyDeviceToHost, st));
+    OA_HIP(hipStreamSynchronize(st));
+    DivRunTable tab;
+    if (!divbin_build_runs(host.data(), (int)tiles, rows, logc, w, rb, q->nids, nxh, cap, &tab)) return 0;     // no run table: DivBinTail
+    if (int rc = t->run_ent.reserve((tab.ent.size() + 1) * 8)) return rc;
+    if (int rc = t->run_off.reserve(tab.off.size() * 4)) return rc;
+    OA_HIP(hipMemcpyAsync(t->run_ent.p, tab.ent.data(), tab.ent.size() * 8, hipMemcpyHostToDevice, st));
+    OA_HIP(hipMemcpyAsync(t->run_off.p, tab.off.data(), tab.off.size() * 4, hipMemcpyHostToDevice, st));
+    OA_HIP(hipStreamSynchronize(st));
+    t->has_runs = true; t->run_w = w; t->run_rb = rb; t->run_cap = cap;
+    return 0;
+}
 static int ensure_div_tables(oa_plan* p, Pipeline* q, hipStream_t st, int rows) {
     Pipeline::DivTabs* const t = &q->tabs_of(rows);
     if (!(q->Fn && q->ids && (rows == 1024 || rows == 2048 || rows == 4096 || (q->my3 && rows == q->my3)) && q->wk > 0)) { t->tab_rows = 0; return 0; }
@@ -496,6 +521,7 @@ static int ensure_div_tables(oa_plan* p, Pipeline* q, hipStream_t st, int rows) 
     if (int rc = t->ids_t.reserve((size_t)total * 4)) return rc;
     if (int rc = pack_tiles(p, q->Fn, t->fn_t.p, rows, logc, q->wk, (int)rs, st)) return rc;
     if (int rc = pack_tiles(p, q->ids, t->ids_t.p, rows, logc, q->wk, 4, st)) return rc;
+    if (int rc = build_run_table(p, q, t, rows, logc, tiles, st)) return rc;
     t->tab_gen = q->bind_gen; t->tab_rows = rows; t->tab_logc = logc; t->tab_wk = q->wk;
     return 0;
 }
@@ -523,6 +549,10 @@ static DivBinFuse make_fuse(const oa_plan* p, const Pipeline* q, int64_t* n, dou
     const Pipeline::DivTabs& t = q->tabs_of(rows);
     if (t.tab_rows && t.tab_gen == q->bind_gen && t.tab_rows == rows && t.tab_wk == q->wk) {
         f.ids_t = (const int32_t*)t.ids_t.p; f.fn_t = t.fn_t.p; f.tab_logc = t.tab_logc; f.tab_rows = t.tab_rows;
+        if (t.has_runs) {
+            f.run_ent = (const unsigned long long*)t.run_ent.p; f.run_off = (const int32_t*)t.run_off.p;
+            f.run_w = t.run_w; f.run_rb = t.run_rb; f.run_cap = t.run_cap;
+        }
     }
     f.ids = q->ids; f.ipitch = p->kp; f.pnorm = q->norm; f.nids = q->nids; f.nxh = p->nx / 2;
     f.part = (double*)q->bin_scratch; f.part_cap = (long)(oa_bin_scratch_bytes(q->nids) / (long)sizeof(double)) * MC_BATCH_MAX;
