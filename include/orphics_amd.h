@@ -249,7 +249,11 @@ int oa_plan_rsplit(const oa_plan* p);
 /* 1 when this plan's one-call moment entries (oa_qe_tt_moments, oa_qe_tt_moments2, oa_mc_run) bin |kappa_hat|^2 and update
  * n, S, C in the tail of the single-pass divergence launch (coarse grids of 1024 / 2048 / 4096 rows and from-map grids of 768 / 1536, bins bound) instead of two more
  * launches over the kappa plane; 0: the separate histogram launches.  Same per-mode arithmetic either way; the order of the
- * float64 sums differs (bandpowers agree to ~1e-15).  When fused, these entries do not write the plan-owned kappa plane
+ * float64 sums differs (bandpowers agree to ~1e-15).  The divergence workgroups store their bin partials and end; one single-workgroup
+ * launch (divbin_fold_kernel) behind it INSIDE THE SAME CALL, on the same stream, adds them in a fixed order and updates n, S, C per map
+ * in map order: n, S, C are complete, in stream order, when the call's work is, and calls issued back to back on one stream need no
+ * synchronisation between them (the partials buffer is the plan's; the next call's divergence launch is ordered behind this fold).
+ * When fused, these entries do not write the plan-owned kappa plane
  * (oa_plan_kappa) unless the mean-field stack of oa_mc_run needs it; oa_qe_tt always does.  oa_plan_set_option(p, OA_OPT_DIV_BIN, 0)
  * switches it off. */
 int oa_plan_div_fused(const oa_plan* p);

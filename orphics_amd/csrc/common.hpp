@@ -37,7 +37,7 @@ struct alignas(sizeof(T) * N > 16 ? 16 : sizeof(T) * N) Arr {
 };
 
 // Request to fold the radial histogram of |kappa|^2 and the moment update (n += maps, S += b, C += b b^T, b = sums / mode
-// counts) into the single-pass divergence launch (fft_divbin.hpp).  Filled by pipeline.hip, honoured by HipLauncher::col_div_sp
+// counts) into the single-pass divergence launch and the one-workgroup fold launched behind it (fft_divbin.hpp).  Filled by pipeline.hip, honoured by HipLauncher::col_div_sp
 // when the geometry runs that kernel (`done` set); otherwise the caller runs bin_power_moments as before.  Device pointers.
 struct DivBinFuse {
     const int32_t* ids; long ipitch;      // radial ids of the full-resolution half plane, row pitch
@@ -52,7 +52,6 @@ struct DivBinFuse {
     double* part;                         // [maps][workgroups][nids] partial sums (capacity part_cap doubles)
     long part_cap;
     double* sums;                         // [maps][nids]
-    unsigned* ticket;                     // zero before the launch; reset by the last workgroup
     const int64_t* mcounts; int64_t* n; double* S; double* C;
     int store;                            // != 0: kappa is also written to `out`
     int gx;                               // (set by the launcher) workgroups per map

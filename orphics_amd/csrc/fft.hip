@@ -557,6 +557,15 @@ struct HipLauncher {
         if (!tabs) fuse->ids_t = nullptr;
         hipLaunchKernelGGL(kern, dim3(gx, 1, gz), dim3(nt), smem, st, a, *fuse);
         hipError_t e = hipGetLastError();
+        if (e == hipSuccess) {
+            // the fold of the workgroups' partials and the moment update: one workgroup of the same size, behind the kernel boundary
+            const size_t fl = divbin_fold_lds_bytes(fuse->nids, nt, gz);
+            e = ensure_dyn_lds(reinterpret_cast<const void*>(divbin_fold_kernel), fl);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(divbin_fold_kernel, dim3(1), dim3(nt), fl, st, *fuse, gz);
+                e = hipGetLastError();
+            }
+        }
         if (e != hipSuccess) rc = fail(std::string("fft launch: ") + hipGetErrorString(e));
         fuse->done = true;
     }

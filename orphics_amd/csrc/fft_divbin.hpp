@@ -5,15 +5,11 @@
 // Per value the arithmetic is bin_kernel's: v = (double)((re^2 + im^2) * (T)pnorm) * multiplicity, multiplicity 1 on the columns
 // 0 and nx/2 of the half plane, 2 between.  Per wave-step the lanes that share an id are summed in a fixed order (DPP inside rows of 16 lanes, then the row totals) and the
 // lowest such lane adds the total to the wave's private LDS row (no atomics, fixed order); the rows are summed per workgroup
-// in wave order, the workgroups' partials by the LAST workgroup (ticket) in workgroup order: deterministic.
+// in wave order, the workgroups' partials by divbin_fold_kernel, the next launch on the stream, in workgroup order: deterministic.
 #pragma once
 #include "fft_launch.hpp"
 
 namespace oa {
-
-#if defined(__HIP_DEVICE_COMPILE__) && !(defined(__gfx942__) || defined(__gfx950__))
-#error "DivBinTail: the ticket hand-over relies on gfx942 / gfx950 behaviour (agent-scope relaxed atomic stores are sc1 write-through, stores count in vmcnt)"
-#endif
 
 // Sum of v over the 64 lanes, returned in every lane (wave-uniform): four DPP steps inside each row of 16 lanes (pairs, quads,
 // half-row mirror, row mirror: 2 v_mov_dpp + 1 v_add_f64 each -- float64 has no DPP add), then the four row totals in row
@@ -41,76 +37,94 @@ __device__ __forceinline__ double wave_total_f64(double v) {
 }
 
 // What every tail ends with: this workgroup's partial of id i is partial(i) (a fixed-order sum in the tail's LDS, complete and
-// visible before the call); the partials go to memory, and the LAST workgroup (ticket) folds all of them in workgroup order,
-// divides by the mode counts and updates the moments.  red: LDS of at least blockDim.x + nids doubles that the tail no longer needs.
+// visible before the call).  The partials go to f.part with plain vector stores and the workgroup ends: no acknowledge wait, no
+// barrier, no ticket.  divbin_fold_kernel, launched right behind the divergence kernel on the same stream (HipLauncher::go_fused),
+// folds them: the kernel boundary is the only ordering between the workgroups and the fold, on any target.  `part` belongs to the
+// plan: the next call's divergence launch on the same stream is ordered behind this call's fold, so back-to-back calls need nothing else.
 template <class Partial>
-__device__ __forceinline__ void divbin_handover(const DivBinFuse& f, double* red, Partial partial) {
-    __shared__ int s_last;
-    const int t = threadIdx.x, nt = blockDim.x, nids = f.nids;
-    const long wg = (long)blockIdx.z * gridDim.x + blockIdx.x;
-    for (int i = t; i < nids; i += nt) {
-        const double s = partial(i);
-        __hip_atomic_store(f.part + wg * nids + i, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // write-through
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this thread's partials have been acknowledged
-    __syncthreads();
-    if (t == 0)
-        s_last = (__hip_atomic_fetch_add(f.ticket, 1u, OA_TICKET_ORDER, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x * gridDim.z - 1) ? 1 : 0;
-    __syncthreads();
-    if (!s_last) return;
-    // last workgroup: per map, in map order: sums[i] = the workgroups' partials in a fixed two-level order -- thread (g, i),
-    // i = t mod NI, g = t / NI, adds the partials of workgroups b = g, g + G, ... (four loads in flight), then the G group sums
-    // are added in group order; b = sums[1 .. nids-2] / mode counts; moments.  (One thread per id walking all workgroups was
-    // a chain of ~100 dependent L2-miss loads: 30-50 us.)
-    const int d = nids - 2;
+__device__ __forceinline__ void divbin_handover(const DivBinFuse& f, Partial partial) {
+    const int nids = f.nids;
+    double* mine = f.part + ((long)blockIdx.z * gridDim.x + blockIdx.x) * nids;
+    for (int i = threadIdx.x; i < nids; i += blockDim.x) mine[i] = partial(i);
+}
+
+// LDS of the fold: [G][NI] group sums (G NI <= nt), then the nids - 2 bandpowers of every map behind them
+__host__ __device__ inline int divbin_fold_ni(int nids, int nt) {
     int NI = 1;
-    while (NI < nids && NI < nt) NI <<= 1;
-    const int G = nt / NI > 0 ? nt / NI : 1, gi = t / NI, ii = t - gi * NI;
-    // red: [G][NI] group sums, then b in red[0 .. d) (the tail's own LDS is spent)
-    const int gx = (int)gridDim.x;
-    for (int z = 0; z < (int)gridDim.z; ++z) {
-        for (int i0 = 0; i0 < nids; i0 += NI) {          // (one round unless nids > workgroup size)
+    while (NI < nids && 2 * NI <= nt) NI <<= 1;      // (a power of two of at most nt threads: 384- and 768-thread launches too)
+    return NI;
+}
+inline size_t divbin_fold_lds_bytes(int nids, int nt, int gz) { return ((size_t)nt + (size_t)gz * nids) * sizeof(double); }
+
+// The fold: ONE workgroup of as many threads as the divergence launch had (the order of the additions below depends on it), gx
+// workgroups' partials per map, gz maps.  Per map: sums[i] = the workgroups' partials in a fixed two-level order -- thread (g, i),
+// i = t mod NI, g = t / NI, adds the partials of workgroups b = g, g + G, ... in fours, (p0 + p1) + (p2 + p3), and what is left over
+// one by one; then the G group sums are added in group order; b = sums[1 .. nids-2] / mode counts.  Then the moments, every element
+// in map order.  It is a chain of memory round trips, so each trip carries all it can: sixteen partials of a thread are requested
+// together (133 workgroups at 19 bins: all of a thread's in one trip; the order of the additions is not the order of the loads), the
+// mode count of the id with them, and the thread's first elements of S, C and n before anything else; an element of S or C is read
+// and written once for all maps.  (One thread per id walking all workgroups was a chain of ~100 dependent L2-miss loads: 30-50 us.)
+__global__ __launch_bounds__(1024) void divbin_fold_kernel(DivBinFuse f, int gz) {
+    extern __shared__ double oa_fold_red[];
+    double* red = oa_fold_red;
+    const int t = threadIdx.x, nt = blockDim.x, nids = f.nids, d = nids - 2, gx = f.gx, dd = d * d;
+    const int NI = divbin_fold_ni(nids, nt);
+    const int G = nt / NI, gi = t / NI, ii = t - gi * NI;      // (threads behind G NI idle in the group sums)
+    double* bv = red + G * NI;                                 // [gz][d]
+    const bool mom = f.S != nullptr;
+    const double S0 = (mom && t < d) ? f.S[t] : 0.0, C0 = (mom && t < dd) ? f.C[t] : 0.0;
+    const int64_t n0 = (t == 0 && f.n) ? f.n[0] : 0;
+    for (int z = 0; z < gz; ++z) {
+        for (int i0 = 0; i0 < nids; i0 += NI) {          // (one round unless nids > NI)
             const int i = i0 + ii;
+            const bool isb = gi == 0 && i >= 1 && i <= d;
+            const int64_t mc = isb ? f.mcounts[i] : 1;
             __syncthreads();
             if (gi < G) {
                 double s = 0.0;
                 if (i < nids) {
                     const double* pz = f.part + ((long)z * gx) * nids + i;
-                    int b = gi;
-                    for (; b + 3 * G < gx; b += 4 * G) {
-                        const double p0 = __hip_atomic_load(pz + (long)b * nids, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        const double p1 = __hip_atomic_load(pz + (long)(b + G) * nids, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        const double p2 = __hip_atomic_load(pz + (long)(b + 2 * G) * nids, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        const double p3 = __hip_atomic_load(pz + (long)(b + 3 * G) * nids, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        s += (p0 + p1) + (p2 + p3);
+                    for (int b = gi; b < gx; b += 16 * G) {
+                        double p[16];
+#pragma unroll
+                        for (int k = 0; k < 16; ++k) p[k] = pz[(long)(b + k * G < gx ? b + k * G : gx - 1) * nids];     // (clamped: branch-free)
+#pragma unroll
+                        for (int j = 0; j < 16; j += 4) {
+                            if (b + (j + 3) * G < gx) s += (p[j] + p[j + 1]) + (p[j + 2] + p[j + 3]);
+                            else {
+#pragma unroll
+                                for (int k = j; k < j + 4; ++k)
+                                    if (b + k * G < gx) s += p[k];
+                            }
+                        }
                     }
-                    for (; b < gx; b += G) s += __hip_atomic_load(pz + (long)b * nids, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
                 red[gi * NI + ii] = s;
             }
             __syncthreads();
-            double tot = 0.0;
             if (gi == 0 && i < nids) {
+                double tot = 0.0;
                 for (int k = 0; k < G; ++k) tot += red[k * NI + ii];
                 f.sums[(long)z * nids + i] = tot;
-            }
-            __syncthreads();
-            if (gi == 0 && i >= 1 && i <= d) red[G * NI + i - 1] = tot / (double)f.mcounts[i];     // b, behind the group sums
-        }
-        __syncthreads();
-        const double* bv = red + G * NI;
-        if (f.S) {
-            for (int a = t; a < d; a += nt) f.S[a] += bv[a];
-            for (long e = t; e < (long)d * d; e += nt) {
-                const int ra = (int)(e / d), cb = (int)(e - (long)ra * d);
-                f.C[e] += bv[ra] * bv[cb];
+                if (isb) bv[z * d + i - 1] = tot / (double)mc;
             }
         }
     }
-    if (t == 0) {
-        if (f.n) f.n[0] += (int64_t)gridDim.z;
-        __hip_atomic_store(f.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next launch
+    __syncthreads();
+    if (mom) {
+        for (int a = t; a < d; a += nt) {
+            double s = a == t ? S0 : f.S[a];
+            for (int z = 0; z < gz; ++z) s += bv[z * d + a];
+            f.S[a] = s;
+        }
+        for (int e = t; e < dd; e += nt) {
+            const int ra = e / d, cb = e - ra * d;
+            double c = e == t ? C0 : f.C[e];
+            for (int z = 0; z < gz; ++z) c += bv[z * d + ra] * bv[z * d + cb];
+            f.C[e] = c;
+        }
     }
+    if (t == 0 && f.n) f.n[0] = n0 + (int64_t)gz;
 }
 
 template <typename T>
@@ -151,7 +165,7 @@ struct DivBinTail {
         const int nw = blockDim.x >> 6, nids = f.nids;
         const double* r = rows;
         __syncthreads();
-        divbin_handover(f, rows, [=](int i) {
+        divbin_handover(f, [=](int i) {
             double s = 0.0;
             for (int k = 0; k < nw; ++k) s += r[k * nids + i];
             return s;
@@ -237,7 +251,7 @@ struct DivRunTail {
         const double* r = R;
         const int32_t* off = offp;
         const int a0 = o0, a1 = o1, b0 = base, n = cnt;
-        divbin_handover(f, P, [=](int i) {
+        divbin_handover(f, [=](int i) {
             int k = a0, k1 = a1;
             if (i != t) { k = off[i] - b0; k1 = off[i + 1] - b0; }     // (more ids than threads)
             if (k1 > n) k1 = n;

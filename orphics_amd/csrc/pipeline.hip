@@ -556,7 +556,7 @@ static DivBinFuse make_fuse(const oa_plan* p, const Pipeline* q, int64_t* n, dou
     }
     f.ids = q->ids; f.ipitch = p->kp; f.pnorm = q->norm; f.nids = q->nids; f.nxh = p->nx / 2;
     f.part = (double*)q->bin_scratch; f.part_cap = (long)(oa_bin_scratch_bytes(q->nids) / (long)sizeof(double)) * MC_BATCH_MAX;
-    f.sums = q->sums; f.ticket = q->ticket; f.mcounts = q->counts_full; f.n = n; f.S = S; f.C = C; f.store = store; f.done = false;
+    f.sums = q->sums; f.mcounts = q->counts_full; f.n = n; f.S = S; f.C = C; f.store = store; f.done = false;
     return f;
 }
 

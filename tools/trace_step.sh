@@ -16,10 +16,12 @@ for f in glob.glob(O + '/p_trace/**/*kernel_trace.csv', recursive=True):
     rows += list(csv.DictReader(open(f)))
 rows.sort(key=lambda r: int(r['Start_Timestamp']))
 MARK = ('bin_final_kernel', 'col_div_sp_bin_kernel', 'col_div3_sp_bin_kernel')
+FOLD = 'divbin_fold_kernel'        # the one-workgroup launch behind a fused divergence launch closes that step
 steps, cur = [], []
-for r in rows:
+for k, r in enumerate(rows):
     cur.append(r)
-    if any(m in r['Kernel_Name'] for m in MARK):
+    nxt = rows[k + 1]['Kernel_Name'] if k + 1 < len(rows) else ''
+    if FOLD in r['Kernel_Name'] or (any(m in r['Kernel_Name'] for m in MARK) and FOLD not in nxt):
         steps.append(cur); cur = []
 w = {}
 for s in steps:
